@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Benchmark of the hot path: MSA-residues/s for the full 10-layer forward (emb + attention maps).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload configs2|configs3]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload configs2|configs3] [--dump-outputs DIR] [--full]
 
 With N > 1 and no launcher environment this process (which makes no GPU call) starts the N ranks itself, one per
 GPU, and exits with their status; under `python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...`
@@ -18,12 +18,16 @@ A step = the hot path (K0..K10 through rnamsm_forward) over the step's MSAs, inp
 HBM, plus (N > 1) the gather of every emb/atp pair to rank 0 with rnamsm.sharding.RoundGatherer (point-to-point RCCL,
 round k's transfers overlapping round k+1's forward) -- the same gather the CLI uses.
 
-Three separate loops: W warm-up steps; the HEADLINE loop of exactly K steps with the per-kernel timing hooks off
-(`value`, `ms_per_step`); then a ROOFLINE pass over the same work with HIP-event pairs around every launch on the
-launch stream (`roofline`, `kernel_ms_per_step`) -- the headline never pays for the instrumentation.
-`cpu_baseline` (N = 1) is the oracle (PyTorch-CPU restatement of the reference) on this host's cores at the best
-thread count of a sweep.  `fast_mode` / `bf16_mode` are extra measurements of the same workload with every
-contraction on the 16-bit matrix cores; they never replace `value`.
+A plain run does what the headline needs and nothing else: W warm-up steps, the HEADLINE loop of exactly K steps with the
+per-kernel timing hooks off (`value`, `ms_per_step` = milliseconds of one timed step), the outputs of the last timed step
+written to DIR (--dump-outputs), the result line.
+--full adds, after the headline: a ROOFLINE pass over the same work with HIP-event pairs around every launch on the launch
+stream (`roofline`, `kernel_ms_per_step`) -- the headline never pays for the instrumentation; (N > 1) the same steps without
+the gather (`compute_only_value`); (N = 1) `cpu_baseline`, the oracle (PyTorch-CPU restatement of the reference) on this
+host's cores at the best thread count of a sweep, and `torch_rocm_eager`; `fast_mode` / `bf16_mode` / `outputs_only_mode`,
+extra measurements of the same workload (16-bit matrix cores, the CLI's forward) that never replace `value`; the
+small-MSA batches and one forward per BASELINE config.  --no-cpu-baseline / --no-fast-mode / --no-per-config leave
+blocks of --full out.
 """
 import argparse
 import json
@@ -71,6 +75,14 @@ def parse_args(argv=None):
                          "compact <= 4 KB line.  Empty string: no file")
     ap.add_argument("--one-device", action="store_true", default=os.environ.get("RNAMSM_BENCH_ONE_DEVICE") == "1",
                     help="test hook: every rank on device 0 (exercises the N > 1 flow on a one-GPU box)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help=f"after the timed steps, write what the last timed step computed (rank 0's MSAs; {DUMP_MAX_MSAS} of them, "
+                         f"a seeded choice, when the step has more) as DIR/<name>.npy in float32 / float64, at most "
+                         f"{DUMP_LIMIT_BYTES // 10 ** 6} MB in all: an array too large for its share is written as a fixed seeded "
+                         f"sample of its elements (1-D)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beyond the headline: roofline pass, compute-only pass (N > 1), 16-bit and "
+                         "outputs-only modes, small-MSA batches, per-config block, CPU and PyTorch-eager baselines")
     args = ap.parse_args(argv)
     args.workload = WORKLOADS[args.workload]
     batch = args.workload == "configs3"
@@ -228,10 +240,63 @@ def host_cpu_info():
     return model, (len(cores) or logical), logical
 
 
+def usable_cpus():
+    """CPUs this process may keep busy: os.cpu_count(), narrowed by its affinity mask and by OMP_NUM_THREADS when that is set
+    (a host shared by several jobs gives each fewer CPUs than it has; a pool sized by the whole host only slows itself down)."""
+    n = os.cpu_count() or 1
+    try:
+        n = min(n, len(os.sched_getaffinity(0)))
+    except (AttributeError, OSError):
+        pass
+    omp = os.environ.get("OMP_NUM_THREADS", "").strip()
+    if omp.isdigit() and int(omp) > 0:
+        n = min(n, int(omp))
+    return max(1, n)
+
+
+DUMP_LIMIT_BYTES = 64 * 10 ** 6    # --dump-outputs: every file together
+DUMP_MAX_MSAS = 4                  # --dump-outputs: MSAs of the last step written (a seeded choice when the step has more)
+
+
+def dump_outputs(directory, items, limit=DUMP_LIMIT_BYTES):
+    """Write the outputs of `items` [(MSA index, {name: tensor})] as directory/<name>.npy (one MSA) or directory/msa<index>_<name>.npy,
+    floating tensors as float32, integer ones as float64.  All files together stay below `limit` bytes: the arrays are taken
+    smallest first, each may use an equal share of what is left; one larger than its share is written as a sample of its
+    elements -- 1-D, in flat-index order, the indices drawn by a generator seeded with the file name, so the same arguments
+    give the same sample in every run.  Returns {file name: (shape of the output, elements written)}."""
+    import zlib
+    import numpy as np
+    import torch
+    os.makedirs(directory, exist_ok=True)
+    arrays = []
+    for msa, out in items:
+        for key in sorted(out):
+            t = out[key].detach()
+            dtype = torch.float32 if t.is_floating_point() and t.element_size() <= 4 else torch.float64
+            arrays.append((key if len(items) == 1 else f"msa{msa}_{key}", t, dtype))
+    arrays.sort(key=lambda a: a[1].numel() * (4 if a[2] == torch.float32 else 8))
+    budget = limit - 128 * len(arrays)                                 # the .npy headers
+    written = {}
+    for left, (name, t, dtype) in zip(range(len(arrays), 0, -1), arrays):
+        size = 4 if dtype == torch.float32 else 8
+        share = budget // left
+        flat = t.reshape(-1)
+        if flat.numel() * size <= share:
+            arr = flat.to(dtype).cpu().numpy().reshape(tuple(t.shape))
+        else:
+            rng = np.random.default_rng(zlib.crc32(name.encode()))
+            idx = np.unique(rng.integers(0, flat.numel(), size=share // size))
+            arr = flat[torch.from_numpy(idx).to(flat.device)].to(dtype).cpu().numpy()
+        budget -= arr.nbytes
+        np.save(os.path.join(directory, name + ".npy"), arr)
+        written[name + ".npy"] = (tuple(t.shape), int(arr.size))
+    return written
+
+
 def cpu_baseline(M, L, state):
     """The oracle (port of the reference) on the host's cores, measured at the BENCHMARKED shape.
-    torch's intra-op pool is swept over {os.cpu_count(), physical cores, 1/2, 1/4, 1/8 of them} on ONE layer of the
-    M x L MSA of this bench (embedding and final LayerNorm included); at the fastest setting three more samples of that
+    torch's intra-op pool is swept over {usable_cpus(), physical cores, 1/2, 1/4, 1/8 of them}, none above usable_cpus(), on ONE
+    layer of the M x L MSA of this bench (embedding and final LayerNorm included); at the fastest setting three more samples of that
     layer (their median is the cross-check `per_layer_median_s`), then ONE COMPLETE 10-layer forward, timed whole:
     `value` = M L / `full_forward_s`, no extrapolation (the sweep has paged the weights in and spun the pool up: it is the
     warm-up).  RNAMSM_BENCH_CPU_FULL=0 falls back to the per-layer figure x 10 and says so."""
@@ -240,6 +305,7 @@ def cpu_baseline(M, L, state):
     from oracle import msm_oracle as O
     from rnamsm import synthetic
     model, physical, logical = host_cpu_info()
+    usable = usable_cpus()
     params = O.to_torch_params(state)
     toks = torch.from_numpy(synthetic.make_tokens(M, L, 0))
     chunk = 32768 if M * L > 32768 else None                          # FFN hidden formed 32 k tokens at a time (memory only)
@@ -251,8 +317,8 @@ def cpu_baseline(M, L, state):
 
     sweep = {}
     with torch.no_grad():
-        candidates = sorted({logical, physical, physical // 2, physical // 4, physical // 8}, reverse=True)
-        candidates = [n for n in candidates if 1 <= n <= logical]
+        candidates = sorted({usable, physical, physical // 2, physical // 4, physical // 8}, reverse=True)
+        candidates = [n for n in candidates if 1 <= n <= usable]
         torch.set_num_threads(candidates[min(1, len(candidates) - 1)])
         one_layer()                                                   # page the weights in, spin the pool up
         for n in candidates:
@@ -269,7 +335,7 @@ def cpu_baseline(M, L, state):
             full_s = time.perf_counter() - t0
     value = M * L / full_s if full_s else M * L / (10.0 * med)
     return {"value": value, "unit": "MSA-residues/s", "cores": best, "kind": "port",
-            "cpu_model": model, "physical_cores": physical, "logical_cpus": logical,
+            "cpu_model": model, "physical_cores": physical, "logical_cpus": logical, "usable_cpus": usable,
             "full_forward_s": None if full_s is None else round(full_s, 3),
             "extrapolation": None if full_s else "one of ten identical layers timed, x 10 (RNAMSM_BENCH_CPU_FULL=0)",
             "thread_sweep_at_bench_shape": {"shape": [M, L], "seconds_per_layer": {str(k): round(v, 4) for k, v in sweep.items()}},
@@ -327,8 +393,10 @@ def make_digest(result):
     def r(v, n=1):
         return None if v is None else round(float(v), n)
     d = {"value_k": r(result["value"] / 1e3), "ms": r(result["ms_per_step"], 2), "n_gpus": result["n_gpus"],
-         "dtype": result["dtype"].split(" ")[0], "gemm_frac_of_peak": r(result["roofline"]["frac"], 3),
-         "attn_frac_of_peak": r(result["attention_mfma"]["frac"], 3)}
+         "dtype": result["dtype"].split(" ")[0]}
+    if result.get("roofline"):                                         # --full only
+        d["gemm_frac_of_peak"] = r(result["roofline"]["frac"], 3)
+        d["attn_frac_of_peak"] = r(result["attention_mfma"]["frac"], 3)
     pc = result.get("per_config")
     if pc:
         d["cfg_cols"] = "ms, k_res_per_s, model_TF, frac_of_bounds"
@@ -389,9 +457,10 @@ def compact_line(result):
     line["config"] = dict(pick(cfg, ("workload",), 260), **pick(cfg, ("gather",), 200),
                           **pick(cfg, ("num_seqs", "seq_len", "msas_per_step", "world_size_initialised", "distinct_devices", "backend",
                                        "rccl_version", "devices")))
-    roof = result.get("roofline") or {}
-    line["roofline"] = pick(roof, ("bound", "kernel", "achieved", "peak", "unit", "frac", "avg_launch_ms", "launches", "flops_per_launch",
-                                   "traffic", "algorithmic_bytes_per_launch", "traffic_source", "traffic_replayed", "traffic_unit"), 120)
+    roof = result.get("roofline")
+    if roof:
+        line["roofline"] = pick(roof, ("bound", "kernel", "achieved", "peak", "unit", "frac", "avg_launch_ms", "launches", "flops_per_launch",
+                                       "traffic", "algorithmic_bytes_per_launch", "traffic_source", "traffic_replayed", "traffic_unit"), 120)
     if result.get("attention_mfma"):
         line["attention_mfma"] = pick(result["attention_mfma"], ("kernels", "achieved", "peak", "frac"), 60)
     for k in ("compute_only_value", "compute_only_ms_per_step", "outputs_finite", "err_word", "model_tflops"):
@@ -619,6 +688,8 @@ def run_rank(args) -> int:
     digest = torch.zeros((), dtype=torch.int64, device=dev)
     delivered = [0]
     last_gather = [None]
+    last_out = [None]              # this rank's last forward of the headline loop (outputs_finite / err_word of a plain run)
+    kept = []                      # --dump-outputs: (MSA index, outputs) of rank 0's MSAs in the last timed step
 
     def on_item(index, tensors):
         nonlocal digest
@@ -627,15 +698,24 @@ def run_rank(args) -> int:
             for t in tensors:
                 digest = digest + (index + 1) * t.contiguous().view(torch.int32).to(torch.int64).sum()
 
-    def run_steps(first_step, nsteps, items_of=None, use_gather=True):
+    def run_steps(first_step, nsteps, items_of=None, use_gather=True, headline=False):
         """`nsteps` steps: forward of this rank's MSAs, every output handed to ONE RoundGatherer that spans all the steps
         (global item index = step * items-per-step + position), so round k's transfers to rank 0 overlap the forwards of
-        round k+1 across step boundaries as well; finish() drains the last round inside the timed region."""
+        round k+1 across step boundaries as well; finish() drains the last round inside the timed region.
+        headline=True: keep the last forward in last_out and (--dump-outputs, rank 0) the outputs of the last step in `kept`."""
         per = [items_of(first_step + k) if items_of else step_items(first_step + k) for k in range(nsteps)]
         n_items = sum(len(it) for it in per)
         g = None
         if (gather and use_gather) or (args.digest and world == 1):
             g = sharding.RoundGatherer(n_items, on_item=on_item, tensors_per_item=2, dst=0, device=dev, group=gather_group)
+        keep = set()
+        if headline and args.dump_outputs and rank == 0 and per:
+            last_base = n_items - len(per[-1])
+            mine = [last_base + pos for pos, _ in per[-1] if sharding.owner_of(last_base + pos, world) == rank]
+            if len(mine) > DUMP_MAX_MSAS:
+                import numpy as _np
+                mine = _np.random.default_rng(0).choice(mine, DUMP_MAX_MSAS, replace=False).tolist()
+            keep = set(mine)
         base = 0
         for items in per:
             for pos, msa in items:
@@ -644,6 +724,10 @@ def run_rank(args) -> int:
                 out = model.forward_one(toks[msa], has_padding=False, need_repr=not args.outputs_only)
                 if g is not None:
                     g.submit(base + pos, (out["emb"], out["atp"]))
+                if headline:
+                    last_out[0] = out
+                    if base + pos in keep:
+                        kept.append((msa, out))
             base += len(items)
         if g is not None:
             g.finish()
@@ -671,15 +755,18 @@ def run_rank(args) -> int:
     delivered[0] = 0
     lib.rnamsm_timing_enable(0)
     t0 = time.perf_counter()
-    msas_timed = run_steps(0 if batch else args.warmup, args.steps)
+    msas_timed = run_steps(0 if batch else args.warmup, args.steps, headline=True)
     sync_all()
     elapsed = max_over_ranks(time.perf_counter() - t0)
     headline_digest = int(digest.item()) if args.digest else None
     headline_delivered = delivered[0]
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, kept)
+    del kept[:]
     # ---- N > 1: what the gather cost.  Per rank: bytes received, host seconds blocked on transfers, milliseconds the compute
     # stream stood waiting for the transfer stream (RoundGatherer.stats); and the same steps once more WITHOUT the gather
-    # (`compute_only_value`: max-over-ranks forward time only) so a first real multi-GPU run separates compute scaling from
-    # the gather's exposed time
+    # (`compute_only_value`: max-over-ranks forward time only, --full) so a first real multi-GPU run separates compute scaling
+    # from the gather's exposed time
     gather_stats = compute_only = None
     if world > 1:
         st = last_gather[0].stats() if (gather and last_gather[0] is not None) else {}
@@ -692,31 +779,33 @@ def run_rank(args) -> int:
                         "what": "RoundGatherer.stats() of the timed region: bytes into each rank (rank 0 is the sink), host seconds "
                                 "blocked in transfers, and ms the compute stream waited for the transfer stream (= the gather time "
                                 "NOT overlapped with the next forward)"}
-        sync_all()
-        tc = time.perf_counter()
-        run_steps(0 if batch else args.warmup, args.steps, use_gather=False)
-        sync_all()
-        compute_only = max_over_ranks(time.perf_counter() - tc)
+        if args.full:
+            sync_all()
+            tc = time.perf_counter()
+            run_steps(0 if batch else args.warmup, args.steps, use_gather=False)
+            sync_all()
+            compute_only = max_over_ranks(time.perf_counter() - tc)
 
-    # ---- roofline pass: the same work with HIP-event pairs around every launch (no gather: kernels only)
-    roof_steps = 1 if batch else args.steps
-    roof_of = (lambda k: step_items(0)[:max(world, min(per_step, 8 * world))]) if batch else None
-    sync_all()
-    lib.rnamsm_timing_reset()
-    lib.rnamsm_timing_enable(1)
-    t1 = time.perf_counter()
-    run_steps(0 if batch else args.warmup, roof_steps, items_of=roof_of, use_gather=False)
-    sync_all()
-    roof_elapsed = time.perf_counter() - t1
-    lib.rnamsm_timing_enable(0)
-    timings = _lib.kernel_timings()
-    roof_local = max(1, sum(1 for k in range(roof_steps) for pos, _ in (roof_of(k) if roof_of else step_items(0))
-                            if sharding.owner_of(pos, world) == rank))
+    # ---- roofline pass (--full): the same work with HIP-event pairs around every launch (no gather: kernels only)
+    if args.full:
+        roof_steps = 1 if batch else args.steps
+        roof_of = (lambda k: step_items(0)[:max(world, min(per_step, 8 * world))]) if batch else None
+        sync_all()
+        lib.rnamsm_timing_reset()
+        lib.rnamsm_timing_enable(1)
+        t1 = time.perf_counter()
+        run_steps(0 if batch else args.warmup, roof_steps, items_of=roof_of, use_gather=False)
+        sync_all()
+        roof_elapsed = time.perf_counter() - t1
+        lib.rnamsm_timing_enable(0)
+        timings = _lib.kernel_timings()
+        roof_local = max(1, sum(1 for k in range(roof_steps) for pos, _ in (roof_of(k) if roof_of else step_items(0))
+                                if sharding.owner_of(pos, world) == rank))
 
     # ---- extra modes (N = 1, default workload): every contraction on the 16-bit matrix cores
     fast = bf16_mode = outputs_only = small_batches = None
     first = toks[mine_all[0]]
-    if args.gemm_dtype == "f32" and not args.no_fast_mode and world == 1 and not batch:
+    if args.full and args.gemm_dtype == "f32" and not args.no_fast_mode and world == 1 and not batch:
         ref = model.forward_one(first)
         ref_emb, ref_atp = ref["emb"].clone(), ref["atp"].clone()
         # yardstick: the exact path against ITSELF when alignment rows 1.. are permuted (mathematically a no-op for row
@@ -827,7 +916,7 @@ def run_rank(args) -> int:
     # ---- every BASELINE config on the driver-run line (N = 1): one MSA of each shape, 1 warm-up + 2 timed forwards with the
     # hooks off, then one instrumented forward for the per-launch roofline sums
     per_config = None
-    if args.gemm_dtype == "f32" and not args.no_per_config and world == 1 and not batch:
+    if args.full and args.gemm_dtype == "f32" and not args.no_per_config and world == 1 and not batch:
         import numpy as _np
         per_config = {"what": "one forward per BASELINE config (complete forward, emb + atp + representation), inputs resident in "
                               "HBM: ms = mean of 2 timed forwards after 1 warm-up; model_tflops = SURVEY 8d flops / time; "
@@ -878,29 +967,31 @@ def run_rank(args) -> int:
         del cases, tk
         torch.cuda.empty_cache()
 
-    probe_out = model.forward_one(first)
+    # a plain run reads the headline loop's last forward; --full (as before) one more forward of the first MSA
+    probe_out = last_out[0] if (last_out[0] is not None and not args.full) else model.forward_one(first)
     finite = bool(torch.isfinite(probe_out["emb"]).all())
     err_word = int(probe_out["err"].item())       # 0: tokens in range (bit 0) and the folded LayerNorm's precondition held (bit 1)
     if rank == 0:
         residues = msas_timed * M * L
-        g = timings["gemm_f32"]
         mult = {"f32": 1.0, "bf16": 1.0, "f16x3": 3.0}[args.gemm_dtype]
         peak = FP32_MFMA_PEAK_TFLOPS if args.gemm_dtype == "f32" else F16_MFMA_PEAK_TFLOPS
         gemm_kernel = {"f32": "gemm_f32_kernel (nn.Linear, K2)",
                        "bf16": "gemm16_q16s_kernel (QKV, fc1, fc2) + gemm16_swp_kernel<split 1, bf16> (out_proj) (nn.Linear, K2)",
                        "f16x3": "gemm16_swp_kernel<split 3, fp16> (nn.Linear, K2)"}[args.gemm_dtype]
         flop_unit = "TFLOP/s" if mult == 1.0 else "TFLOP/s (executed MFMA flops = 3 x algorithmic)"
-        gemm_tflops = mult * g["flops"] / (g["ms"] * 1e-3) / 1e12 if g["ms"] > 0 else 0.0
-        attn_ms = sum(timings[k]["ms"] for k in ("row_logits", "row_apply", "col_attn"))
-        attn_fl = mult * sum(timings[k]["flops"] for k in ("row_logits", "row_apply", "col_attn"))
-        kern_ms = sum(v["ms"] for v in timings.values())
-        traffic, traffic_src = None, None
-        if (M, L) == (256, 512):                   # the shapes the committed PMC passes were collected on
-            traffic, traffic_src = {"f32": lambda: pmc_traffic_per_launch(),
-                                    "bf16": lambda: pmc_traffic_per_launch("rnamsm::gemm16_", "bf16_"),
-                                    "f16x3": lambda: pmc_traffic_per_launch("rnamsm::gemm16_", "f16x3_")}[args.gemm_dtype]()
-        elif (M, L) == (1024, 1024) and args.gemm_dtype == "bf16":     # BASELINE configs[4]
-            traffic, traffic_src = pmc_traffic_per_launch("rnamsm::gemm16_", "cfg4_bf16_")
+        if args.full:
+            g = timings["gemm_f32"]
+            gemm_tflops = mult * g["flops"] / (g["ms"] * 1e-3) / 1e12 if g["ms"] > 0 else 0.0
+            attn_ms = sum(timings[k]["ms"] for k in ("row_logits", "row_apply", "col_attn"))
+            attn_fl = mult * sum(timings[k]["flops"] for k in ("row_logits", "row_apply", "col_attn"))
+            kern_ms = sum(v["ms"] for v in timings.values())
+            traffic, traffic_src = None, None
+            if (M, L) == (256, 512):                   # the shapes the committed PMC passes were collected on
+                traffic, traffic_src = {"f32": lambda: pmc_traffic_per_launch(),
+                                        "bf16": lambda: pmc_traffic_per_launch("rnamsm::gemm16_", "bf16_"),
+                                        "f16x3": lambda: pmc_traffic_per_launch("rnamsm::gemm16_", "f16x3_")}[args.gemm_dtype]()
+            elif (M, L) == (1024, 1024) and args.gemm_dtype == "bf16":     # BASELINE configs[4]
+                traffic, traffic_src = pmc_traffic_per_launch("rnamsm::gemm16_", "cfg4_bf16_")
         if world == 1:
             gather_note = "none (single GPU)"
         elif not gather:
@@ -953,38 +1044,41 @@ def run_rank(args) -> int:
             "gather_stats": gather_stats,
             "outputs_finite": finite, "err_word": err_word,
             "model_tflops": flops_per_msa(M, L) * msas_timed / elapsed / 1e12,
-            "roofline": (dict(mode_roofline(timings, args.gemm_dtype, mult, roof_local), traffic=traffic,
-                              traffic_unit="bytes/launch of the GEMM kernels (HBM-side, PMC)", traffic_source=traffic_src,
-                              traffic_replayed=traffic is not None,
-                              algorithmic_bytes_per_launch=g["bytes"] / max(1, g["launches"]))
-                         if args.gemm_dtype != "f32" else None) or {"bound": "mfma", "kernel": gemm_kernel,
-                         "achieved": gemm_tflops, "peak": peak, "unit": flop_unit,
-                         "frac": gemm_tflops / peak,
-                         "avg_launch_ms": g["ms"] / max(1, g["launches"]), "launches": g["launches"],
-                         "flops_per_launch": g["flops"] / max(1, g["launches"]),
-                         "traffic": traffic, "traffic_unit": "bytes/launch (HBM-side, PMC)",
-                         "traffic_source": traffic_src,
-                         # counters cannot be collected inside a timed run: the figure is the committed PMC passes' (same workload,
-                         # same kernels, tools/prof_r06.sh), REPLAYED here -- not a measurement of this run
-                         "traffic_replayed": traffic is not None,
-                         "algorithmic_bytes_per_launch": g["bytes"] / max(1, g["launches"]),
-                         "measured_in": f"separate pass after the headline loop, HIP-event pairs on the launch stream, "
-                                        f"{roof_local} MSA(s) on rank 0 in {roof_elapsed:.3f} s",
-                         "note": ("flops counted = 2MNK of the Linear layers only; these launches also carry the three "
-                                  "LayerNorms of every layer (applied to the accumulators of the QKV / fc1 GEMMs, row statistics "
-                                  "left by the out_proj / fc2 epilogues: no LayerNorm launches) -- un-fused the same kernel "
-                                  "measures 0.900 and the step is 1.25 % slower (DESIGN 3.4b)")
-                                 if (args.gemm_dtype == "f32" and M * L >= 4096) else None},
-            "attention_mfma": {"kernels": "row_logits+row_apply+col_attn", "achieved": attn_fl / (attn_ms * 1e-3) / 1e12 if attn_ms else 0.0,
-                               "peak": peak, "unit": flop_unit,
-                               "frac": (attn_fl / (attn_ms * 1e-3) / 1e12 / peak) if attn_ms else 0.0},
-            "kernel_ms_per_msa": {k: v["ms"] / roof_local for k, v in timings.items()},
-            "per_kernel": per_kernel_bounds(timings, roof_local),
-            "kernel_time_share_of_roofline_pass": kern_ms / (1e3 * roof_elapsed),
         }
+        if args.full:
+            result.update({
+                "roofline": (dict(mode_roofline(timings, args.gemm_dtype, mult, roof_local), traffic=traffic,
+                                  traffic_unit="bytes/launch of the GEMM kernels (HBM-side, PMC)", traffic_source=traffic_src,
+                                  traffic_replayed=traffic is not None,
+                                  algorithmic_bytes_per_launch=g["bytes"] / max(1, g["launches"]))
+                             if args.gemm_dtype != "f32" else None) or {"bound": "mfma", "kernel": gemm_kernel,
+                             "achieved": gemm_tflops, "peak": peak, "unit": flop_unit,
+                             "frac": gemm_tflops / peak,
+                             "avg_launch_ms": g["ms"] / max(1, g["launches"]), "launches": g["launches"],
+                             "flops_per_launch": g["flops"] / max(1, g["launches"]),
+                             "traffic": traffic, "traffic_unit": "bytes/launch (HBM-side, PMC)",
+                             "traffic_source": traffic_src,
+                             # counters cannot be collected inside a timed run: the figure is the committed PMC passes' (same workload,
+                             # same kernels, tools/prof_r06.sh), REPLAYED here -- not a measurement of this run
+                             "traffic_replayed": traffic is not None,
+                             "algorithmic_bytes_per_launch": g["bytes"] / max(1, g["launches"]),
+                             "measured_in": f"separate pass after the headline loop, HIP-event pairs on the launch stream, "
+                                            f"{roof_local} MSA(s) on rank 0 in {roof_elapsed:.3f} s",
+                             "note": ("flops counted = 2MNK of the Linear layers only; these launches also carry the three "
+                                      "LayerNorms of every layer (applied to the accumulators of the QKV / fc1 GEMMs, row statistics "
+                                      "left by the out_proj / fc2 epilogues: no LayerNorm launches) -- un-fused the same kernel "
+                                      "measures 0.900 and the step is 1.25 % slower (DESIGN 3.4b)")
+                                     if (args.gemm_dtype == "f32" and M * L >= 4096) else None},
+                "attention_mfma": {"kernels": "row_logits+row_apply+col_attn", "achieved": attn_fl / (attn_ms * 1e-3) / 1e12 if attn_ms else 0.0,
+                                   "peak": peak, "unit": flop_unit,
+                                   "frac": (attn_fl / (attn_ms * 1e-3) / 1e12 / peak) if attn_ms else 0.0},
+                "kernel_ms_per_msa": {k: v["ms"] / roof_local for k, v in timings.items()},
+                "per_kernel": per_kernel_bounds(timings, roof_local),
+                "kernel_time_share_of_roofline_pass": kern_ms / (1e3 * roof_elapsed),
+            })
         tag = {"f32": "", "bf16": "bf16_", "f16x3": "f16x3_"}[args.gemm_dtype] if (M, L) == (256, 512) else (
             "cfg4_bf16_" if (M, L) == (1024, 1024) and args.gemm_dtype == "bf16" else None)
-        if tag is not None:
+        if args.full and tag is not None:
             result["gemm_traffic_by_kernel"] = pmc_traffic_by_kernel("rnamsm::gemm", tag)
         if args.digest:
             result["output_digest"] = {"value": headline_digest, "items": headline_delivered,
@@ -998,7 +1092,7 @@ def run_rank(args) -> int:
             result["small_msa_batches"] = small_batches
             result["fast_mode"] = fast
             result["bf16_mode"] = bf16_mode
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             result["torch_rocm_eager"] = torch_rocm_eager(M, L, state, dev)
             result["cpu_baseline"] = cpu_baseline(M, L, state)
         result["digest"] = make_digest(result)

@@ -2,7 +2,9 @@
 launch its own ranks, shard the configs[3] batch with rnamsm.sharding.shard_indices, gather every output to rank 0 with
 rnamsm.sharding.RoundGatherer and print one rank-0 JSON line -- and the gathered outputs must be the N=1 run's, bit for
 bit.  RCCL refuses two ranks on one device, so the N=2 run uses the bench's test hooks (--one-device, --backend gloo:
-same control flow, payloads staged through the host); the driver's 8-GPU run is the same code on backend nccl."""
+same control flow, payloads staged through the host); the driver's 8-GPU run is the same code on backend nccl.
+The roofline pass, the compute-only pass and the baselines run under --full only: the tests that read them pass it.  A plain
+run (the headline alone, --dump-outputs) has tests of its own at the end."""
 import json
 import os
 import subprocess
@@ -14,7 +16,7 @@ from conftest import ROOT
 
 pytestmark = pytest.mark.gpu
 COMMON = ["--workload", "configs3", "--num-msas", "6", "--num-seqs", "16", "--seq-len", "40", "--steps", "1",
-          "--warmup", "1", "--digest", "--no-cpu-baseline", "--no-fast-mode"]
+          "--warmup", "1", "--digest", "--no-cpu-baseline", "--no-fast-mode", "--full"]
 
 
 COMPACT_KEYS = ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline",
@@ -58,10 +60,10 @@ def _bench(extra, env=None, expect_rc=0):
 
 
 def test_the_default_flow_with_both_baselines_prints_one_compact_last_line():
-    """The driver's command shape (`bench.py --gpus 1 --steps K --warmup W`, every optional block ON: per-config block, 16-bit modes,
-    cpu_baseline, torch_rocm_eager) at a small alignment shape: stdout's LAST line is the one compact JSON line (<= 4096 bytes,
+    """The driver's command shape with --full (`bench.py --gpus 1 --steps K --warmup W --full`, every optional block ON: per-config
+    block, 16-bit modes, cpu_baseline, torch_rocm_eager) at a small alignment shape: stdout's LAST line is the one compact JSON line (<= 4096 bytes,
     _parse checks the keys) and it carries `roofline` and `cpu_baseline`; the detail file holds the blocks the line leaves out."""
-    res = _bench(["--gpus", "1", "--steps", "2", "--warmup", "1", "--num-seqs", "64", "--seq-len", "128"])
+    res = _bench(["--gpus", "1", "--steps", "2", "--warmup", "1", "--num-seqs", "64", "--seq-len", "128", "--full"])
     c = res["_compact"]
     assert c["steps"] == 2 and c["warmup"] == 1 and c["n_gpus"] == 1 and c["dtype"] == "f32" and c["vs_baseline"] is None
     assert c["roofline"]["bound"] == "mfma" and 0 < c["roofline"]["frac"] < 1 and c["roofline"]["launches"] > 0
@@ -98,7 +100,7 @@ def test_eight_ranks_on_one_device_gather_the_same_outputs_as_one_rank():
     bit-identical to the N = 1 run; per-rank gather statistics present; every rank's device identity on the line (here: eight
     ranks, ONE distinct device -- the field a real 8-GPU run must show 8 in)."""
     common = ["--workload", "configs3", "--num-msas", "16", "--num-seqs", "8", "--seq-len", "24", "--steps", "1", "--warmup", "1",
-              "--digest", "--no-cpu-baseline", "--no-fast-mode"]
+              "--digest", "--no-cpu-baseline", "--no-fast-mode", "--full"]
     one = _bench(["--gpus", "1"] + common)
     eight = _bench(["--gpus", "8", "--backend", "gloo", "--one-device"] + common)
     assert eight["n_gpus"] == 8 and eight["config"]["world_size_initialised"] == 8
@@ -116,7 +118,7 @@ def test_eight_ranks_on_one_device_gather_the_same_outputs_as_one_rank():
 
 def test_default_workload_runs_weak_scaling_through_the_same_gatherer():
     two = _bench(["--gpus", "2", "--backend", "gloo", "--one-device", "--num-seqs", "16", "--seq-len", "40", "--steps",
-                  "2", "--warmup", "1", "--no-cpu-baseline", "--no-fast-mode", "--digest"])
+                  "2", "--warmup", "1", "--no-cpu-baseline", "--no-fast-mode", "--digest", "--full"])
     assert two["scaling"] == "weak" and two["config"]["msas_per_step"] == 2 and two["output_digest"]["items"] == 4
 
 
@@ -298,3 +300,81 @@ sys.exit(0 if ok else 1)
     assert all(p.returncode == 0 for p in procs), [(p.returncode, o[-1500:], er[-3000:]) for p, (o, er) in zip(procs, outs)]
     res = [json.loads(t) for t in texts]
     assert all(r["ok"] for r in res) and any(r["rank"] == 0 and r["stats"]["bytes_received"] > 0 for r in res)
+
+
+def _plain(extra, tmp_path):
+    """bench.py without --full: returns (compact line, detail) after checking the line is the ONE JSON line and the last one."""
+    e = dict(os.environ)
+    for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
+        e.pop(k, None)
+    detail = tmp_path / "detail.json"
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--detail-out", str(detail)] + extra, capture_output=True,
+                       text=True, timeout=600, env=e, cwd=ROOT)
+    assert p.returncode == 0, (p.stdout[-2000:], p.stderr[-4000:])
+    out_lines = [ln for ln in p.stdout.splitlines() if ln.strip()]
+    assert sum(ln.startswith("{") for ln in out_lines) == 1 and out_lines[-1].startswith("{"), p.stdout
+    line = json.loads(out_lines[-1])
+    assert len(out_lines[-1].encode()) <= 4096 and list(line)[-1] == "digest"
+    return line, json.load(open(detail))
+
+
+def _model():
+    import torch
+    from rnamsm.model import MSATransformer
+    from truth import state
+    model = MSATransformer(num_layers=10)
+    model.load_state_dict({k: torch.from_numpy(v) for k, v in state().items()}, strict=True)
+    return model.eval().to("cuda:0")
+
+
+def test_a_plain_run_times_its_steps_and_dumps_what_the_last_step_computed(tmp_path):
+    """The command every change is measured with (`bench.py --gpus 1 --steps K --warmup W`, here at a small shape) does the
+    headline alone: ONE compact last line with the contract's keys, `ms_per_step` the milliseconds of one of the K timed steps,
+    none of --full's blocks in the line or the detail.  --dump-outputs writes what the last timed step computed: every array
+    forward_one returns for that step's MSA (make_tokens(M, L, W + K - 1)), bit for bit, in float32 / float64."""
+    import numpy as np
+    import torch
+    from rnamsm import synthetic
+    dump = tmp_path / "out"
+    c, detail = _plain(["--gpus", "1", "--steps", "3", "--warmup", "1", "--num-seqs", "16", "--seq-len", "40",
+                        "--dump-outputs", str(dump)], tmp_path)
+    for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "dtype", "config"):
+        assert k in c, k
+    assert c["steps"] == 3 and c["warmup"] == 1 and c["n_gpus"] == 1 and c["dtype"] == "f32" and c["higher_is_better"] is True
+    assert c["metric"].startswith("MSA-residues/sec") and c["unit"] == "MSA-residues/s" and c["outputs_finite"] and c["err_word"] == 0
+    assert abs(c["ms_per_step"] * c["steps"] * 1e-3 * c["value"] - 16 * 40 * 3) < 1e-3 * 16 * 40 * 3
+    for k in ("roofline", "attention_mfma", "cpu_baseline", "torch_rocm_eager", "per_config", "fast_mode", "bf16_mode",
+              "per_kernel", "kernel_ms_per_msa", "small_msa_batches"):
+        assert k not in c and k not in detail, k
+    files = sorted(os.listdir(dump))
+    assert files == ["atp.npy", "emb.npy", "err.npy", "repr.npy", "row_attn.npy"], files
+    out = _model().forward_one(torch.from_numpy(synthetic.make_tokens(16, 40, 1 + 3 - 1)).to("cuda:0"), has_padding=False)
+    for k, t in out.items():
+        a = np.load(dump / f"{k}.npy")
+        assert a.dtype == (np.float64 if k == "err" else np.float32) and a.shape == tuple(t.shape), (k, a.dtype, a.shape)
+        assert np.array_equal(a, t.cpu().numpy().astype(a.dtype)), k
+
+
+def test_a_plain_batch_run_dumps_a_seeded_choice_of_its_msas(tmp_path):
+    """configs3: a step is a pass over the whole batch, more MSAs than --dump-outputs writes (bench.DUMP_MAX_MSAS): a seeded choice
+    of them, the same in every run, each file named after its MSA and equal to that MSA's forward."""
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    from rnamsm import synthetic
+    runs = []
+    for tag in ("a", "b"):
+        c, _ = _plain(["--gpus", "1", "--workload", "configs3", "--num-msas", "6", "--num-seqs", "16", "--seq-len", "40",
+                       "--steps", "1", "--warmup", "1", "--dump-outputs", str(tmp_path / tag)], tmp_path)
+        assert c["steps"] == 1 and c["scaling"] == "strong" and abs(c["ms_per_step"] * 1e-3 * c["value"] - 6 * 16 * 40) < 1e-2 * 16 * 40
+        runs.append(sorted(os.listdir(tmp_path / tag)))
+    assert runs[0] == runs[1]
+    msas = sorted({int(f[3:].split("_")[0]) for f in runs[0]})
+    assert len(msas) == bench.DUMP_MAX_MSAS < 6 and len(runs[0]) == 5 * len(msas) and all(0 <= i < 6 for i in msas)
+    model = _model()
+    for i in msas:
+        out = model.forward_one(torch.from_numpy(synthetic.make_tokens(16, 40, i)).to("cuda:0"), has_padding=False)
+        for k in ("emb", "atp"):
+            a, b = np.load(tmp_path / "a" / f"msa{i}_{k}.npy"), np.load(tmp_path / "b" / f"msa{i}_{k}.npy")
+            assert np.array_equal(a, b) and np.array_equal(a, out[k].cpu().numpy()), (i, k)

@@ -316,6 +316,8 @@ def test_argument_validation_layer_under_address_and_ub_sanitizers():
         pytest.skip("hipcc not on PATH")
     if not os.path.exists(os.path.join(ROOT, "rna-msm_amd", "csrc", "asan.mk")):
         pytest.skip("asan.mk is not shipped to GPU boxes (sanitizers are a CPU-side tool on this pool)")
+    if os.path.exists("/dev/kfd"):          # a checkout on a GPU host has asan.mk too: the driver would open the device under ASan
+        pytest.skip("a GPU host (/dev/kfd present): the sanitizer build runs on GPU-less hosts only")
     p = subprocess.run(["make", "-C", os.path.join(ROOT, "rna-msm_amd", "csrc"), "-j8", "check-asan"], capture_output=True,
                        text=True, timeout=900)
     assert p.returncode == 0, p.stdout[-3000:] + p.stderr[-3000:]
@@ -336,6 +338,61 @@ def test_bench_launcher_fails_loudly_without_a_gpu():
                        capture_output=True, text=True, timeout=300, env=env)
     assert p.returncode != 0
     assert "no CPU path" in p.stderr and not any(ln.startswith("{") for ln in p.stdout.splitlines())
+
+
+def test_bench_dump_outputs_keeps_its_budget_and_draws_the_same_sample_every_time(tmp_path):
+    """bench.py --dump-outputs (bench.dump_outputs, CPU tensors here): arrays that fit their share of the budget are written whole in
+    their shape, floating as float32 and integer as float64; a larger one as a 1-D sample of its elements in flat-index order,
+    the same elements in every run; every file together within bench.DUMP_LIMIT_BYTES; more than one MSA: msa<index>_<name>.npy.
+    Also: a plain parse of the arguments leaves --full off and writes no outputs."""
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    a = bench.parse_args(["--gpus", "1", "--steps", "5", "--warmup", "2"])
+    assert a.full is False and a.dump_outputs is None and a.steps == 5 and a.warmup == 2
+    assert bench.parse_args(["--full", "--dump-outputs", "d"]).full and bench.parse_args(["--dump-outputs", "d"]).dump_outputs == "d"
+    out = {"big": torch.arange(20_000_000, dtype=torch.int64), "mid": torch.ones(3, 1000, 1000),
+           "small": torch.arange(12, dtype=torch.float32).view(3, 4), "err": torch.zeros(1, dtype=torch.int32)}
+    bench.dump_outputs(str(tmp_path / "a"), [(5, out)])
+    bench.dump_outputs(str(tmp_path / "b"), [(5, out)])
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert files == ["big.npy", "err.npy", "mid.npy", "small.npy"]
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in files) <= bench.DUMP_LIMIT_BYTES
+    got = {f[:-4]: np.load(tmp_path / "a" / f) for f in files}
+    for f in files:
+        assert np.array_equal(got[f[:-4]], np.load(tmp_path / "b" / f)), f
+    assert got["small"].dtype == np.float32 and np.array_equal(got["small"], np.arange(12, dtype=np.float32).reshape(3, 4))
+    assert got["err"].dtype == np.float64 and got["err"].shape == (1,) and got["mid"].shape == (3, 1000, 1000)
+    big = got["big"]                                    # sampled: the values are their own flat indices
+    assert big.dtype == np.float64 and big.ndim == 1 and 1_000_000 < big.size < 20_000_000
+    assert np.all(np.diff(big) > 0) and big[0] >= 0 and big[-1] < 20_000_000 and np.array_equal(big, np.round(big))
+    two = bench.dump_outputs(str(tmp_path / "c"), [(3, {"emb": torch.ones(4, 8)}), (7, {"emb": torch.zeros(4, 8)})])
+    assert sorted(two) == ["msa3_emb.npy", "msa7_emb.npy"] and np.load(tmp_path / "c" / "msa7_emb.npy").shape == (4, 8)
+
+
+def test_bench_compact_line_of_a_plain_run_has_the_contract_and_no_full_blocks():
+    """A plain run (no --full) has no roofline pass, baselines or side modes: the result line still carries every key of the bench
+    contract and the digest LAST, and neither the line nor the digest invents the blocks that were not measured."""
+    import json
+    sys.path.insert(0, ROOT)
+    import bench
+    res = json.loads(open(os.path.join(ROOT, "tests", "golden", "bench_detail_canned.json")).read().strip().splitlines()[-1])
+    for k in ("roofline", "attention_mfma", "kernel_ms_per_msa", "per_kernel", "kernel_time_share_of_roofline_pass", "per_config",
+              "fast_mode", "bf16_mode", "outputs_only_mode", "small_msa_batches", "cpu_baseline", "torch_rocm_eager",
+              "gemm_traffic_by_kernel", "digest"):
+        res.pop(k, None)
+    res["digest"] = bench.make_digest(res)
+    line = json.loads(json.dumps(bench.compact_line(res)))
+    for k in ("metric", "unit", "n_gpus", "steps", "warmup", "higher_is_better", "scaling", "dtype"):
+        assert line[k] == res[k], k
+    for k in ("value", "ms_per_step"):
+        assert abs(line[k] - res[k]) <= 1e-8 * res[k], k
+    assert line["config"]["workload"] == res["config"]["workload"]
+    assert list(line)[-1] == "digest" and line["digest"]["ms"] == round(res["ms_per_step"], 2)
+    for k in ("roofline", "attention_mfma", "cpu_baseline", "torch_rocm_eager"):
+        assert k not in line, k
+    assert "gemm_frac_of_peak" not in line["digest"] and "cfg" not in line["digest"] and "cpu_res_per_s" not in line["digest"]
 
 
 def test_bench_compact_line_fits_the_drivers_parser_whatever_the_run_measured():

@@ -6,7 +6,7 @@ export TMPDIR=/tmp
 R=$PWD
 O=$R/gpurun_out
 mkdir -p $O/prof $O/prof_bf16 $O/prof_f16x3
-run() { n=$1; shift; python3 bench.py --detail-out $O/$n.json "$@" > $O/$n.line.json 2>> $O/bench.err; }
+run() { n=$1; shift; python3 bench.py --full --detail-out $O/$n.json "$@" > $O/$n.line.json 2>> $O/bench.err; }
 run r06_bench
 tail -c 1400 $O/r06_bench.line.json
 run r06_bench_f16x3 --no-cpu-baseline --gemm-dtype f16x3
@@ -20,7 +20,7 @@ python3 tools/packed_batch_timing.py > $O/r06_packed_batch_timing.log 2>> $O/ben
 ( time python3 -m pytest tests -m gpu -q -x ) > $O/r06_gpu_suite.log 2>&1
 tail -3 $O/r06_gpu_suite.log
 cd /tmp
-B="python3 $R/bench.py --detail-out= --no-cpu-baseline --no-fast-mode --no-per-config"
+B="python3 $R/bench.py --full --detail-out= --no-cpu-baseline --no-fast-mode --no-per-config"
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -- $B --steps 4 --warmup 1 > $O/prof_run.log 2>&1
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_bf16 -- $B --steps 4 --warmup 1 --gemm-dtype bf16 > $O/prof_bf16_run.log 2>&1
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_f16x3 -- $B --steps 4 --warmup 1 --gemm-dtype f16x3 > $O/prof_f16x3_run.log 2>&1
