@@ -12,7 +12,15 @@ strided operand / output views (leading dimensions larger than the row), every e
                                   product of the PLANE VALUES
   * rnamsm_greedy_select / rnamsm_msa_weights   random alignments built from a few mutated founders (ties everywhere), both
                                   greedy schemes ("greedy_fused" 0 / 2), max and min: device rows == host rows, weights bit-equal
-Exit code 1 on any violation.     python tests/analysis/fuzz_kernels.py [cases [seed]]
+With --16 (run16: a separate case stream, so that run()'s seeds replay the cases they always did):
+  * rnamsm_row_logits16 + softmax_rows_planes + row_apply16, rnamsm_col_attn16(_prescaled)   R / C biased to the edges of
+                                  the dispatch thresholds (256x256 tiles, row_logits16q at C >= 384 with C % 8 == 0, the qb2
+                                  rounding rule on R, the slab caps) up to 1024, H 1..12, bf16 or f16x3, "attn16" 1 / 2 / 4 / 5,
+                                  "row16_max_rows" 0 / 32, padding masks, plane output, q / k / v as plane views with ld =
+                                  3 H 64 + 8 k into buffers whose unused columns and extra rows hold NaN bit patterns -- against
+                                  fp64 on the plane values and on the fp32 operands at tests/test_gpu_attn16.py's MODES bars; every
+                                  output finite (the kernels clamp tail reads to in-view rows: a NaN is an over-read)
+Exit code 1 on any violation.     python tests/analysis/fuzz_kernels.py [--16] [cases [seed]]
 """
 import math
 import os
@@ -256,7 +264,168 @@ def run(cases=40, seed=0, log=print):
     return bad
 
 
+# ---- 16-bit attention entry points (run16) ---------------------------------------------------------------------------
+R16 = [1, 3, 4, 5, 127, 128, 129, 255, 256, 257, 383, 384, 385, 511, 512, 513, 1024]
+C16 = [1, 63, 64, 65, 127, 128, 129, 255, 256, 257, 383, 384, 385, 1016, 1019, 1024]
+MODES16 = [(1, 0, 2e-6, 8e-3), (3, 1, 3e-6, 3e-6)]      # (split, fmt, bar vs the plane values, bar vs the fp32 operands): test_gpu_attn16.py
+BUDGET16 = 1 << 28                                       # R C H max(R, C): fp64 score tensors of <= 2 GB, a case in tens of ms
+NAN16 = {0: 0x7FC0, 1: 0x7E00}                           # quiet-NaN bit patterns of bf16 / fp16
+PS16 = 4096.0
+
+
+def _plane_buffer(x, split, fmt, ld, extra):
+    """fp32 [T, n] -> (hi, lo | None) plane views [T, n] with row stride ld into buffers of T + extra rows whose other
+    columns and rows hold NaN."""
+    T, n = x.shape
+    out = []
+    for p in ops.split_bf16(x, want_lo=split == 3, fmt=fmt):
+        if p is None:
+            out.append(None)
+            continue
+        buf = torch.full((T + extra, ld), NAN16[fmt], dtype=torch.int16, device=DEV)
+        buf[:T, :n] = p
+        out.append(buf[:T, :n])
+    return tuple(out)
+
+
+def _vals(pl, fmt):
+    ht = torch.float16 if fmt == 1 else torch.bfloat16
+    v = pl[0].contiguous().view(ht).double()
+    return v if pl[1] is None else v + pl[1].contiguous().view(ht).double()
+
+
+def _cut(pl, a, b):
+    return (pl[0][:, a:b], None if pl[1] is None else pl[1][:, a:b])
+
+
+def _draw16(rng, table):
+    return int(rng.choice(table)) if rng.random() < 0.7 else int(rng.integers(1, 1025))
+
+
+def fuzz_attention16(rng, gen):
+    while True:
+        R, C = _draw16(rng, R16), _draw16(rng, C16)
+        if rng.random() < 0.5 and C % 8 == 0 and C > 1:
+            C -= int(rng.integers(1, 8))                 # C % 8 != 0 half the time
+        hmax = min(12, BUDGET16 // (R * C * max(R, C)))
+        if hmax >= 1:
+            break
+    H = int(rng.integers(1, hmax + 1))
+    D = 64 * H
+    T = R * C
+    split, fmt, tol_e, tol_f = MODES16[int(rng.integers(0, 2))]
+    var, max_rows = int(rng.choice([1, 2, 4, 5])), int(rng.choice([0, 32]))
+    masked = rng.random() < 0.4
+    pre = split == 1 and not masked and rng.random() < 0.5
+    out_planes = rng.random() < 0.5
+    ld = 3 * D + 8 * int(rng.integers(0, 4))
+    extra = int(rng.integers(1, 65))
+    ops.set_param("attn16", var)
+    ops.set_param("row16_max_rows", max_rows)
+    qkv = torch.randn(T, 3 * D, device=DEV, generator=gen)
+    pl = _plane_buffer(qkv, split, fmt, ld, extra)
+    key_mask = pad = None
+    if masked:
+        key_mask = (torch.rand(C, device=DEV, generator=gen) < 0.2)
+        key_mask[0] = False
+        pad = (torch.rand(R, C, device=DEV, generator=gen) < 0.2)
+        pad[0] = False                                   # a column never loses all its keys in the reference's use
+    # tied row attention
+    scale = ops.row_scaling(R)
+    partial, nsplit = ops.row_logits16(_cut(pl, 0, D), _cut(pl, D, 2 * D), R, C, H, fmt=fmt, scale=scale)
+    probs, pp = ops.softmax_rows_planes(partial, split=split, fmt=fmt, plane_scale=PS16,
+                                        key_mask=None if key_mask is None else key_mask.to(torch.uint8))
+    ctx = ops.row_apply16(pp, _cut(pl, 2 * D, 3 * D), R, C, H, fmt=fmt, out_scale=1.0 / PS16)
+    e = _vals(pl, fmt).view(R, C, 3, H, 64)
+    f = qkv.double().view(R, C, 3, H, 64)
+    summed = partial.sum(0).double()
+    err_l = rel(summed, scale * torch.einsum("rihd,rjhd->hij", e[:, :, 0], e[:, :, 1]))
+    lf = scale * torch.einsum("rihd,rjhd->hij", f[:, :, 0], f[:, :, 1])
+    err_lf = rel(summed, lf)
+    if key_mask is not None:
+        summed = summed.masked_fill(key_mask[None, None, :], -10000.0)
+        lf = lf.masked_fill(key_mask[None, None, :], -10000.0)
+    err_p = float((probs.double() - torch.softmax(summed, -1)).abs().max())
+    p_eff = _vals(pp, fmt)[:, :C].reshape(H, C, C) / PS16
+    err_c = rel(ctx, torch.einsum("hij,rjhd->rihd", p_eff, e[:, :, 2]).reshape(T, D))
+    err_cf = rel(ctx, torch.einsum("hij,rjhd->rihd", torch.softmax(lf, -1), f[:, :, 2]).reshape(T, D))
+    # slabs of more than 32 rows ("row16_max_rows" = 0, or plain bf16, whose slabs are uncapped): fp32 chains of up to 64 R terms.
+    # There the logits bars and the context-vs-fp32 bar are at least twice what torch's fp32 arithmetic does on the same operands.
+    tol_l, tol_lf, tol_cf = tol_e, tol_f, tol_f
+    yl = yc = 0.0
+    if -(-R // nsplit) > 32:
+        f32 = qkv.view(R, C, 3, H, 64)
+        l32 = scale * torch.einsum("rihd,rjhd->hij", f32[:, :, 0], f32[:, :, 1])
+        c32 = torch.einsum("hij,rjhd->rihd", torch.softmax(l32.masked_fill(key_mask[None, None, :], -10000.0) if key_mask is not None
+                                                           else l32, -1), f32[:, :, 2]).reshape(T, D)
+        lf0 = scale * torch.einsum("rihd,rjhd->hij", f[:, :, 0], f[:, :, 1])
+        yl = rel(l32, lf0)
+        yc = rel(c32, torch.einsum("hij,rjhd->rihd", torch.softmax(lf, -1), f[:, :, 2]).reshape(T, D))
+        tol_l, tol_lf, tol_cf = max(tol_e, 2 * yl), max(tol_f, 2 * yl), max(tol_f, 2 * yc)
+        del f32, l32, c32, lf0
+    ldp = (C + 63) // 64 * 64
+    tail_ok = ldp == C or all(int(p[:, C:].abs().max()) == 0 for p in pp if p is not None)
+    finite = bool(torch.isfinite(partial).all()) and bool(torch.isfinite(probs).all()) and bool(torch.isfinite(ctx).all()) \
+        and bool(torch.isfinite(p_eff).all())
+    del partial, probs, pp, ctx, p_eff, summed, lf
+    # column attention
+    cpl = pl
+    if pre:
+        qs = qkv.clone()
+        qs[:, :D] *= 0.125 * 1.4426950408889634
+        cpl = _plane_buffer(qs, split, fmt, ld, extra)
+        del qs
+    args = (_cut(cpl, 0, D), _cut(cpl, D, 2 * D), _cut(cpl, 2 * D, 3 * D), R, C, H)
+    if pre:
+        got = ops.col_attn16(*args, fmt=fmt, prescaled=True, out_planes=out_planes)
+    else:
+        got = ops.col_attn16(*args, fmt=fmt, scale=0.125, pad_mask=None if pad is None else pad.to(torch.uint8),
+                             out_planes=out_planes)
+    got = _vals(got, fmt) if out_planes else got.double()
+    finite = finite and bool(torch.isfinite(got).all())
+
+    def col_ref(q, k, v):
+        s_ = torch.einsum("ichd,jchd->hcij", q, k)
+        if pad is not None:
+            s_ = s_.masked_fill(pad.t()[None, :, None, :], -10000.0)
+        return torch.einsum("hcij,jchd->ichd", torch.softmax(s_, -1), v).reshape(T, D)
+    ce = _vals(cpl, fmt).view(R, C, 3, H, 64) if pre else e
+    qe = ce[:, :, 0] * (0.6931471805599453 if pre else 0.125)
+    err_k = rel(got, col_ref(qe, ce[:, :, 1], ce[:, :, 2]))
+    err_kf = rel(got, col_ref(0.125 * f[:, :, 0], f[:, :, 1], f[:, :, 2]))
+    # P is rounded to the operand format inside the column kernel (3e-3 against the plane values in plain bf16); a plain-bf16
+    # plane output adds its own 2^-9 rounding (6e-3: the planes GEMM's plane-output bar above)
+    tk = (6e-3 if out_planes else 3e-3) if split == 1 else tol_e
+    tkf = tol_f if not (split == 1 and out_planes) else 1e-2
+    ok = (err_l < tol_l and err_lf < tol_lf and err_p < 2e-6 and err_c < tol_e and err_cf < tol_cf and err_k < tk and err_kf < tkf
+          and tail_ok and finite)
+    return ok, (f"attention16 R={R} C={C} H={H} ld={ld}+{extra} split={split} fmt={fmt} attn16={var} row16_max_rows={max_rows} "
+                f"nsplit={nsplit} masked={masked} prescaled={pre} planes={out_planes}: logits {err_l:.2e}/{err_lf:.2e} probs {err_p:.2e} "
+                f"row ctx {err_c:.2e}/{err_cf:.2e} col ctx {err_k:.2e}/{err_kf:.2e} tail0 {tail_ok} finite {finite}"
+                + (f" (torch fp32: logits {yl:.2e} ctx {yc:.2e})" if yl else ""))
+
+
+def run16(cases=40, seed=0, log=print):
+    rng = np.random.default_rng(seed)
+    gen = torch.Generator(device=DEV)
+    gen.manual_seed(seed)
+    bad = 0
+    defaults = {k_: ops.get_param(k_) for k_ in ("attn16", "row16_max_rows")}
+    try:
+        for case in range(cases):
+            ok, note = fuzz_attention16(rng, gen)
+            bad += not ok
+            log(f"{'ok ' if ok else 'BAD'} {case:3d} {note}")
+    finally:
+        for k_, v_ in defaults.items():
+            ops.set_param(k_, v_)
+        torch.cuda.empty_cache()
+    log(f"{cases} 16-bit attention cases, {bad} violations")
+    return bad
+
+
 if __name__ == "__main__":
-    n = run(int(sys.argv[1]) if len(sys.argv) > 1 else 40, int(sys.argv[2]) if len(sys.argv) > 2 else 0,
-            log=lambda line: print(line, flush=True))
+    argv = [a for a in sys.argv[1:] if a != "--16"]
+    fn = run16 if "--16" in sys.argv[1:] else run
+    n = fn(int(argv[0]) if argv else 40, int(argv[1]) if len(argv) > 1 else 0, log=lambda line: print(line, flush=True))
     sys.exit(1 if n else 0)

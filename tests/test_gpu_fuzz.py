@@ -47,3 +47,14 @@ def test_seeded_kernel_fuzz_has_no_violation(seed):
     lines = []
     bad = fuzz_kernels.run(cases=20, seed=seed, log=lines.append)
     assert bad == 0, "\n".join(line for line in lines if line.startswith("BAD"))
+
+
+@pytest.mark.parametrize("seed", [31, 32])
+def test_seeded_attention16_fuzz_has_no_violation(seed):
+    """16-bit attention entry points (row_logits16, softmax_rows_planes, row_apply16, col_attn16 and its prescaled entry) at
+    shapes biased to the dispatch thresholds up to 1024, every mode / knob / mask / plane-output combination, on plane views
+    inside NaN-filled buffers, vs fp64 (tests/analysis/fuzz_kernels.py run16)."""
+    import fuzz_kernels
+    lines = []
+    bad = fuzz_kernels.run16(cases=15, seed=seed, log=lines.append)
+    assert bad == 0, "\n".join(line for line in lines if line.startswith("BAD"))
