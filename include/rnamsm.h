@@ -339,6 +339,34 @@ size_t rnamsm_contact_head_workspace_bytes(int C, int nch);
 int rnamsm_contact_head(const float* row_attn, const float* weight, const float* bias, float* contacts,
                         void* workspace, size_t workspace_bytes, int C, int nch, void* stream);
 
+/* f4 -- RNA-MSM-SS secondary-structure head (_downstream_tasks/SS: predict.py, code/model.py ResNet._forward_impl with
+ * num_blocks BasicBlocks; renet_b16 = 16) on the attention maps of one alignment, exact fp32:
+ *   in[c, i, j] = onehot(seq[i])[c] (c < 4), onehot(seq[j])[c-4] (c < 8), atp[c-8, i, j] (c < 128)     i, j < L
+ *   x = conv3x3(in) + b;  per block x = x + conv5x5(relu(LN2(conv3x3(relu(LN1(x))))));  logits = fc1(relu(LN(x)))
+ *   probs = sigmoid(logits)                                                    logits / probs [L, L] row-major, i = row
+ * atp: plane p (= layer * 12 + head) at atp + p * atp_plane_stride, rows of L floats (the [120, L, L] of rnamsm_pack_outputs:
+ * stride L*L; a larger stride reads the planes of a wider buffer in place).  base_codes [L]: 0..3 = A, C, G, U; any other
+ * value is the all-zero one-hot vector (the reference encoder's handle_unknown='ignore').
+ * weights: RNAMSM_SS_GLOBAL_WEIGHTS + RNAMSM_SS_WEIGHTS_PER_BLOCK * num_blocks pointers in the reference's state_dict order:
+ *   [0] conv1.weight  [3][3][48 out][128 in]     [1] conv1.bias [48]     [2] bn1.weight [48]     [3] bn1.bias [48]
+ *   per block k, at 4 + 6k:  layer1.k.conv1.weight [3][3][48][48], layer1.k.bn1.weight, .bias [48],
+ *                            layer1.k.conv2.weight [5][5][48][48], layer1.k.bn2.weight, .bias [48]
+ *   last two: fc1.weight [48], fc1.bias [1]
+ * (bn1 is the LayerNorm after the blocks; conv weights are the torch [out][in][kh][kw] tensors repacked tap-major
+ * [kh][kw][out][in]); every weight pointer 16-byte aligned.  Either of logits / probs may be null, not both.
+ * workspace: rnamsm_ss_head_workspace_bytes(L) bytes (two [L*L, 48] fp32 images), 16-byte aligned; 0 for an L outside
+ * [1, RNAMSM_SS_MAX_L].  Refused (RNAMSM_ERR_INVALID): L outside [1, RNAMSM_SS_MAX_L], num_blocks outside
+ * [1, RNAMSM_SS_MAX_BLOCKS], atp_plane_stride < L*L, a null or misaligned pointer, a short workspace.
+ * No atomics: the same inputs give the same bits on every run. */
+#define RNAMSM_SS_MAX_L 1024
+#define RNAMSM_SS_MAX_BLOCKS 64
+#define RNAMSM_SS_GLOBAL_WEIGHTS 6
+#define RNAMSM_SS_WEIGHTS_PER_BLOCK 6
+size_t rnamsm_ss_head_workspace_bytes(int L);
+int rnamsm_ss_head(const float* atp, int64_t atp_plane_stride, const uint8_t* base_codes, int L, int num_blocks,
+                   const float* const* weights, float* logits, float* probs, void* workspace, size_t workspace_bytes,
+                   void* stream);
+
 /* a7 -- the residual add of NormalizedResidualBlock around a layer that is NOT one of this library's (modules.py:396,
  * `x = residual + x`; around the library's own layers the add is fused into the layer's last GEMM): out[i] = a[i] + b[i], fp32,
  * out may alias a or b. */

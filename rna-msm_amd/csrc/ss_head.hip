@@ -1,0 +1,299 @@
+// RNA-MSM-SS: the secondary-structure head on the attention maps (_downstream_tasks/SS/code/model.py, ResNet._forward_impl
+// :223-233 with BasicBlock.forward :67-85; renet_b16 = 16 blocks; input built by pre_processing/data_processing.py):
+//   x0      = conv1(in) + b                       3x3, 128 -> 48 channels; in[c, i, j] = onehot(seq[i])[c] (c < 4),
+//                                                 onehot(seq[j])[c - 4] (c < 8), atp[c - 8, i, j] (c < 128)
+//   x_{k+1} = x_k + conv5x5(relu(LN2(conv3x3(relu(LN1(x_k))))))     48 -> 48, no bias, zero padding of the conv INPUTS
+//   logits  = fc1(relu(LN(x_16))),  probs = sigmoid(logits)           [L, L]
+// Every convolution is an implicit GEMM on the exact-fp32 matrix cores (v_mfma_f32_16x16x4_f32): one 512-thread block per
+// 16 x 16 output pixels (M = 256), N = 48 = 3 MFMA columns, K = taps x input channels.  The block's input window (tile +
+// halo) is staged in LDS once, NHWC with a 52-float pixel stride; the LayerNorm + ReLU of the consuming conv is applied
+// while staging (per pixel, over its 48 staged channels) and out-of-image pixels are written as zeros AFTER it, as
+// nn.Conv2d pads relu(LN(x)).  Wave w owns output rows 2w, 2w+1 of the tile: 2 x 3 accumulators of 16 x 16.
+// One ds_read_b128 gives a lane the four k-steps {16q + 4g + j, j = 0..3} of its lane group g = lane >> 4 (A: the
+// pixel's channels, B: the weight row's input channels, permuted identically) -- a fixed order, so results are the same
+// bits run to run; nothing is reduced across threads, no atomics.  The weights of the next tap are loaded into
+// registers while the current tap's 72 MFMAs run (straight from L2: 9 KB per tap, read by every block).
+// Activations live in the caller's workspace as two NHWC [L*L][48] fp32 images: the residual stream x and the block's
+// middle t.  The 5x5 conv adds x in its epilogue and writes x in place (each output element is read and then written
+// by the one lane that owns it).
+#include "common.h"
+
+namespace rnamsm {
+namespace {
+
+constexpr int SS_CH = 48;                      // trunk channels
+constexpr int SS_TILE = 16;                    // output tile: 16 x 16 pixels
+constexpr int SS_THREADS = 512;                // 8 waves, 2 output rows each
+constexpr int SS_LDC = SS_CH + 4;              // LDS pixel stride (floats) of the trunk's staged window
+constexpr int SS_STEM_CK = 32;                 // stem: input channels per staged chunk (4 chunks of the 128)
+constexpr int SS_STEM_LDC = SS_STEM_CK + 4;
+constexpr int SS_STEM_SW = SS_TILE + 2;
+constexpr float SS_LN_EPS = 1e-5f;             // nn.LayerNorm default
+
+constexpr size_t ss_trunk_lds_bytes(int ks) {
+    return (size_t)(SS_TILE + ks - 1) * (SS_TILE + ks - 1) * SS_LDC * sizeof(float);
+}
+constexpr size_t SS_STEM_LDS_BYTES = (size_t)SS_STEM_SW * SS_STEM_SW * SS_STEM_LDC * sizeof(float);
+
+__device__ __forceinline__ f32x4 mfma16(float a, float b, f32x4 c) {
+    return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
+}
+
+// B fragments of one tap: b[q][nt] = W[n = 16 nt + r][c0 + 16 q + 4 g .. +3] of a [48][cin] weight slab
+template <int NQ>
+__device__ __forceinline__ void load_b(const float* __restrict__ wt, int cin, int c0, f32x4 (&b)[NQ][3]) {
+    const int lane = threadIdx.x & 63, r = lane & 15, g = lane >> 4;
+#pragma unroll
+    for (int q = 0; q < NQ; ++q)
+#pragma unroll
+        for (int nt = 0; nt < 3; ++nt)
+            b[q][nt] = *reinterpret_cast<const f32x4*>(wt + (size_t)(16 * nt + r) * cin + c0 + 16 * q + 4 * g);
+}
+
+// acc[mt][nt] += window pixel (row 2w + mt + dy, col r + dx), channels [0, 16 NQ) . b
+template <int NQ>
+__device__ __forceinline__ void tap_mma(const float* S, int sw, int ldc, int dy, int dx, const f32x4 (&b)[NQ][3],
+                                        f32x4 (&acc)[2][3]) {
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, r = lane & 15, g = lane >> 4;
+#pragma unroll
+    for (int q = 0; q < NQ; ++q) {
+        f32x4 a[2];
+#pragma unroll
+        for (int mt = 0; mt < 2; ++mt)
+            a[mt] = *reinterpret_cast<const f32x4*>(S + ((2 * w + mt + dy) * sw + r + dx) * ldc + 16 * q + 4 * g);
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+#pragma unroll
+            for (int mt = 0; mt < 2; ++mt)
+#pragma unroll
+                for (int nt = 0; nt < 3; ++nt) acc[mt][nt] = mfma16(a[mt][j], b[q][nt][j], acc[mt][nt]);
+    }
+}
+
+// The taps of one staged window: weights [taps][48][cin], this window holds input channels [c0, c0 + 16 NQ).
+template <int KS, int NQ>
+__device__ __forceinline__ void window_mma(const float* S, int sw, int ldc, const float* __restrict__ w, int cin, int c0,
+                                           f32x4 (&acc)[2][3]) {
+    f32x4 b[NQ][3], bn[NQ][3];
+    load_b<NQ>(w, cin, c0, b);
+#pragma unroll 1
+    for (int tap = 0; tap < KS * KS; ++tap) {
+        if (tap + 1 < KS * KS) load_b<NQ>(w + (size_t)(tap + 1) * SS_CH * cin, cin, c0, bn);
+        tap_mma<NQ>(S, sw, ldc, tap / KS, tap % KS, b, acc);
+#pragma unroll
+        for (int q = 0; q < NQ; ++q)
+#pragma unroll
+            for (int nt = 0; nt < 3; ++nt) b[q][nt] = bn[q][nt];
+    }
+}
+
+__device__ __forceinline__ void zero_acc16(f32x4 (&acc)[2][3]) {
+#pragma unroll
+    for (int mt = 0; mt < 2; ++mt)
+#pragma unroll
+        for (int nt = 0; nt < 3; ++nt) acc[mt][nt] = f32x4{0.f, 0.f, 0.f, 0.f};
+}
+
+// relu(LayerNorm(v)) of one pixel's 48 channels, in place (biased variance, two passes)
+__device__ __forceinline__ void ln_relu48(f32x4 (&v)[12], const float* __restrict__ gamma, const float* __restrict__ beta) {
+    float s = 0.f;
+#pragma unroll
+    for (int i = 0; i < 12; ++i) s += (v[i][0] + v[i][1]) + (v[i][2] + v[i][3]);
+    const float mean = s * (1.f / SS_CH);
+    float s2 = 0.f;
+#pragma unroll
+    for (int i = 0; i < 12; ++i)
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const float d = v[i][k] - mean;
+            s2 = fmaf(d, d, s2);
+        }
+    const float rstd = 1.f / sqrtf(s2 * (1.f / SS_CH) + SS_LN_EPS);
+#pragma unroll
+    for (int i = 0; i < 12; ++i) {
+        const f32x4 gm = *reinterpret_cast<const f32x4*>(gamma + 4 * i), bt = *reinterpret_cast<const f32x4*>(beta + 4 * i);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) v[i][k] = fmaxf(fmaf((v[i][k] - mean) * rstd, gm[k], bt[k]), 0.f);
+    }
+}
+
+// Epilogue: lane (r, g) holds D[pixel col 4g + t][channel 16 nt + r] of output row 2w + mt.
+// bias: per-channel bias (stem) or null; RESIDUAL: out += (in place: out is the residual stream).
+template <bool RESIDUAL>
+__device__ __forceinline__ void store_tile(const f32x4 (&acc)[2][3], const float* __restrict__ bias, float* out, int y0,
+                                           int x0, int L) {
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, r = lane & 15, g = lane >> 4;
+#pragma unroll
+    for (int mt = 0; mt < 2; ++mt) {
+        const int oy = y0 + 2 * w + mt;
+        if (oy >= L) continue;
+#pragma unroll
+        for (int t = 0; t < 4; ++t) {
+            const int ox = x0 + 4 * g + t;
+            if (ox >= L) continue;
+            float* o = out + ((size_t)oy * L + ox) * SS_CH + r;
+#pragma unroll
+            for (int nt = 0; nt < 3; ++nt) {
+                float v = acc[mt][nt][t];
+                if (bias) v += bias[16 * nt + r];
+                if (RESIDUAL) v = v + o[16 * nt];
+                o[16 * nt] = v;
+            }
+        }
+    }
+}
+
+// Stem: 3x3, 128 -> 48 with bias.  The input planes are built while staging: one-hot channels from the base codes
+// (0..3 = A, C, G, U; any other value = the all-zero vector of OneHotEncoder(handle_unknown='ignore')), the 120 maps read
+// in place from atp (plane c - 8 at c_plane_stride * (c - 8), rows of L floats).  Four chunks of 32 channels.
+__global__ __launch_bounds__(SS_THREADS) void ss_stem_kernel(const float* __restrict__ atp, int64_t plane_stride,
+                                                             const uint8_t* __restrict__ codes, const float* __restrict__ w,
+                                                             const float* __restrict__ bias, float* __restrict__ out, int L) {
+    extern __shared__ f32x4 ss_smem[];
+    float* S = reinterpret_cast<float*>(ss_smem);
+    const int y0 = blockIdx.y * SS_TILE, x0 = blockIdx.x * SS_TILE;
+    constexpr int NPIX = SS_STEM_SW * SS_STEM_SW;
+    f32x4 acc[2][3];
+    zero_acc16(acc);
+#pragma unroll 1
+    for (int chunk = 0; chunk < 128 / SS_STEM_CK; ++chunk) {
+        if (chunk) __syncthreads();                       // every wave is done with the previous chunk's window
+        for (int e = threadIdx.x; e < SS_STEM_CK * NPIX; e += SS_THREADS) {
+            const int c = e / NPIX, p = e - c * NPIX;
+            const int sy = p / SS_STEM_SW, sx = p - sy * SS_STEM_SW;
+            const int iy = y0 - 1 + sy, ix = x0 - 1 + sx, ch = chunk * SS_STEM_CK + c;
+            float v = 0.f;
+            if (iy >= 0 && iy < L && ix >= 0 && ix < L) {
+                if (ch < 4) v = codes[iy] == ch ? 1.f : 0.f;
+                else if (ch < 8) v = codes[ix] == ch - 4 ? 1.f : 0.f;
+                else v = atp[(int64_t)(ch - 8) * plane_stride + (int64_t)iy * L + ix];
+            }
+            S[p * SS_STEM_LDC + c] = v;
+        }
+        __syncthreads();
+        window_mma<3, SS_STEM_CK / 16>(S, SS_STEM_SW, SS_STEM_LDC, w, 128, chunk * SS_STEM_CK, acc);
+    }
+    store_tile<false>(acc, bias, out, y0, x0, L);
+}
+
+// Trunk conv: out (+)= conv_KS(relu(LN(x))), 48 -> 48, no bias.  RESIDUAL: out is the residual stream, updated in place.
+template <int KS, bool RESIDUAL>
+__global__ __launch_bounds__(SS_THREADS) void ss_conv_kernel(const float* __restrict__ x, const float* __restrict__ gamma,
+                                                             const float* __restrict__ beta, const float* __restrict__ w,
+                                                             float* out, int L) {
+    extern __shared__ f32x4 ss_smem[];
+    float* S = reinterpret_cast<float*>(ss_smem);
+    constexpr int P = KS / 2, SW = SS_TILE + 2 * P;
+    const int y0 = blockIdx.y * SS_TILE, x0 = blockIdx.x * SS_TILE;
+    for (int p = threadIdx.x; p < SW * SW; p += SS_THREADS) {
+        const int sy = p / SW, sx = p - sy * SW, iy = y0 - P + sy, ix = x0 - P + sx;
+        f32x4* dst = reinterpret_cast<f32x4*>(S + p * SS_LDC);
+        if (iy >= 0 && iy < L && ix >= 0 && ix < L) {
+            const f32x4* src = reinterpret_cast<const f32x4*>(x + ((size_t)iy * L + ix) * SS_CH);
+            f32x4 v[12];
+#pragma unroll
+            for (int i = 0; i < 12; ++i) v[i] = src[i];
+            ln_relu48(v, gamma, beta);
+#pragma unroll
+            for (int i = 0; i < 12; ++i) dst[i] = v[i];
+        } else {                                          // zero padding of the conv input relu(LN(x)), not relu(LN(0))
+#pragma unroll
+            for (int i = 0; i < 12; ++i) dst[i] = f32x4{0.f, 0.f, 0.f, 0.f};
+        }
+    }
+    __syncthreads();
+    f32x4 acc[2][3];
+    zero_acc16(acc);
+    window_mma<KS, 3>(S, SW, SS_LDC, w, SS_CH, 0, acc);
+    store_tile<RESIDUAL>(acc, nullptr, out, y0, x0, L);
+}
+
+// Head: logits = fc1(relu(LN(x))) (fc1: Linear(48, 1)), probs = sigmoid(logits); one thread per pixel.
+__global__ __launch_bounds__(256) void ss_out_kernel(const float* __restrict__ x, const float* __restrict__ gamma,
+                                                     const float* __restrict__ beta, const float* __restrict__ fw,
+                                                     const float* __restrict__ fb, float* __restrict__ logits,
+                                                     float* __restrict__ probs, int64_t n) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const f32x4* src = reinterpret_cast<const f32x4*>(x + i * SS_CH);
+    f32x4 v[12];
+#pragma unroll
+    for (int k = 0; k < 12; ++k) v[k] = src[k];
+    ln_relu48(v, gamma, beta);
+    float z = 0.f;
+#pragma unroll
+    for (int k = 0; k < 12; ++k)
+#pragma unroll
+        for (int t = 0; t < 4; ++t) z = fmaf(v[k][t], fw[4 * k + t], z);
+    z += fb[0];
+    if (logits) logits[i] = z;
+    if (probs) probs[i] = 1.f / (1.f + expf(-z));
+}
+
+template <class K>
+int allow_lds(K kernel, size_t bytes, DeviceOnce& once) {
+    if (once.pending()) {
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+        if (e != hipSuccess) return fail(RNAMSM_ERR_HIP, "ss_head: hipFuncSetAttribute: %s", hipGetErrorString(e));
+        once.mark();
+    }
+    return RNAMSM_OK;
+}
+
+}  // namespace
+}  // namespace rnamsm
+
+using namespace rnamsm;
+
+extern "C" size_t rnamsm_ss_head_workspace_bytes(int L) {
+    if (L < 1 || L > RNAMSM_SS_MAX_L) return 0;
+    return 2 * (size_t)L * L * SS_CH * sizeof(float);
+}
+
+extern "C" int rnamsm_ss_head(const float* atp, int64_t atp_plane_stride, const uint8_t* base_codes, int L, int num_blocks,
+                              const float* const* weights, float* logits, float* probs, void* workspace, size_t workspace_bytes,
+                              void* stream) {
+    RNAMSM_CHECK_ARG(atp && base_codes && weights && workspace, "ss_head: null pointer");
+    RNAMSM_CHECK_ARG(logits || probs, "ss_head: neither logits nor probs given");
+    RNAMSM_CHECK_ARG(L >= 1 && L <= RNAMSM_SS_MAX_L, "ss_head: L=%d outside [1, %d]", L, RNAMSM_SS_MAX_L);
+    RNAMSM_CHECK_ARG(num_blocks >= 1 && num_blocks <= RNAMSM_SS_MAX_BLOCKS, "ss_head: num_blocks=%d outside [1, %d]", num_blocks,
+                     RNAMSM_SS_MAX_BLOCKS);
+    RNAMSM_CHECK_ARG(atp_plane_stride >= (int64_t)L * L, "ss_head: atp plane stride %lld < L*L", (long long)atp_plane_stride);
+    RNAMSM_CHECK_ARG(workspace_bytes >= rnamsm_ss_head_workspace_bytes(L), "ss_head: workspace too small");
+    RNAMSM_CHECK_ARG(aligned16(workspace), "ss_head: 16-byte alignment of the workspace");
+    const int nw = RNAMSM_SS_GLOBAL_WEIGHTS + RNAMSM_SS_WEIGHTS_PER_BLOCK * num_blocks;
+    for (int i = 0; i < nw; ++i) {
+        RNAMSM_CHECK_ARG(weights[i], "ss_head: weight pointer %d is null", i);
+        RNAMSM_CHECK_ARG(aligned16(weights[i]), "ss_head: weight pointer %d is not 16-byte aligned", i);
+    }
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    float* xs = static_cast<float*>(workspace);
+    float* ts = xs + (size_t)L * L * SS_CH;
+    static DeviceOnce once_stem, once3, once5;
+    int rc;
+    if ((rc = allow_lds(ss_stem_kernel, SS_STEM_LDS_BYTES, once_stem)) != RNAMSM_OK) return rc;
+    if ((rc = allow_lds(ss_conv_kernel<3, false>, ss_trunk_lds_bytes(3), once3)) != RNAMSM_OK) return rc;
+    if ((rc = allow_lds(ss_conv_kernel<5, true>, ss_trunk_lds_bytes(5), once5)) != RNAMSM_OK) return rc;
+    const unsigned tiles = (unsigned)((L + SS_TILE - 1) / SS_TILE);
+    const dim3 grid(tiles, tiles);
+    // weight table: conv1.weight, conv1.bias, bn1.weight, bn1.bias, then per block conv1.weight, bn1.weight, bn1.bias,
+    // conv2.weight, bn2.weight, bn2.bias, then fc1.weight, fc1.bias (include/rnamsm.h)
+    hipLaunchKernelGGL(ss_stem_kernel, grid, dim3(SS_THREADS), SS_STEM_LDS_BYTES, s, atp, atp_plane_stride, base_codes, weights[0],
+                       weights[1], xs, L);
+    RNAMSM_CHECK_LAUNCH("ss_stem");
+    for (int k = 0; k < num_blocks; ++k) {
+        const float* const* bw = weights + 4 + RNAMSM_SS_WEIGHTS_PER_BLOCK * k;
+        hipLaunchKernelGGL((ss_conv_kernel<3, false>), grid, dim3(SS_THREADS), ss_trunk_lds_bytes(3), s, xs, bw[1], bw[2], bw[0],
+                           ts, L);
+        RNAMSM_CHECK_LAUNCH("ss_conv3x3");
+        hipLaunchKernelGGL((ss_conv_kernel<5, true>), grid, dim3(SS_THREADS), ss_trunk_lds_bytes(5), s, ts, bw[4], bw[5], bw[3],
+                           xs, L);
+        RNAMSM_CHECK_LAUNCH("ss_conv5x5");
+    }
+    const float* const* hw = weights + 4 + RNAMSM_SS_WEIGHTS_PER_BLOCK * num_blocks;
+    const int64_t n = (int64_t)L * L;
+    hipLaunchKernelGGL(ss_out_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, xs, weights[2], weights[3], hw[0], hw[1],
+                       logits, probs, n);
+    RNAMSM_CHECK_LAUNCH("ss_out");
+    return RNAMSM_OK;
+}

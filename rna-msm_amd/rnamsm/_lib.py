@@ -26,6 +26,12 @@ W_LAYER = ("row_ln_g", "row_ln_b", "row_wqkv", "row_bqkv", "row_wo", "row_bo",
            "col_ln_g", "col_ln_b", "col_wqkv", "col_bqkv", "col_wo", "col_bo",
            "ffn_ln_g", "ffn_ln_b", "fc1_w", "fc1_b", "fc2_w", "fc2_b")
 
+# index tables of rnamsm_ss_head's weight-pointer array (include/rnamsm.h): the reference state_dict's order
+W_SS_STEM = ("conv1.weight", "conv1.bias", "bn1.weight", "bn1.bias")
+W_SS_BLOCK = ("conv1.weight", "bn1.weight", "bn1.bias", "conv2.weight", "bn2.weight", "bn2.bias")
+W_SS_HEAD = ("fc1.weight", "fc1.bias")
+SS_MAX_L = 1024
+
 
 class ModelDims(ctypes.Structure):
     _fields_ = [("num_layers", c_int), ("embed_dim", c_int), ("num_heads", c_int), ("ffn_dim", c_int),
@@ -84,6 +90,9 @@ _SIGNATURES = {
     "rnamsm_pack_outputs": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
     "rnamsm_contact_head_workspace_bytes": (c_size_t, [c_int, c_int]),
     "rnamsm_contact_head": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_int, c_int, c_void_p]),
+    "rnamsm_ss_head_workspace_bytes": (c_size_t, [c_int]),
+    "rnamsm_ss_head": (c_int, [c_void_p, c_int64, c_void_p, c_int, c_int, POINTER(c_void_p), c_void_p, c_void_p, c_void_p, c_size_t,
+                               c_void_p]),
     "rnamsm_greedy_select_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
     "rnamsm_greedy_select": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
     "rnamsm_msa_weights": (c_int, [c_void_p, c_int, c_int, c_double, c_void_p, c_void_p]),

@@ -38,6 +38,11 @@ class DataConfig:                       # RNA_MSM_Inference.py:20-32
     # layers on the 16-bit matrix cores, attention on the exact kernels), a lone small alignment as a packed batch of one, so an
     # alignment's files depend on its company at fp32-accumulation rounding at most (which GEMM tile the batch's token count selects)
     pack_small_msas: bool = True
+    # extra (not in the reference): "" = off; else the RNA-MSM-SS weights (the reference's model/rna-msm_attention.pt): the
+    # secondary-structure head (rnamsm.ss) then runs on every alignment's attention maps where they lie on the device, and
+    # SS_result/<id>.{ct,bpseq,prob} are written next to the .npy files (_downstream_tasks/SS/predict.py's files; the sequence
+    # is row 0 of the tokens the forward ran on, so a T of the alignment reads as U there)
+    ss_model_path: str = ""
 
 
 @dataclass

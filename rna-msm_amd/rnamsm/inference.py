@@ -18,7 +18,7 @@ from typing import Dict, List, Optional
 import numpy as np
 import torch
 
-from . import ops, sharding
+from . import ops, sharding, ss
 from .alphabet import RNAAlphabet
 from .config import Config
 from .model import MSATransformer
@@ -83,13 +83,17 @@ class _AsyncNpyWriter:
                 if self._err is None:
                     event.synchronize()
                     for path, host in jobs:
-                        np.save(path, host.numpy())
+                        if callable(path):                  # a host-side consumer (the SS text files) instead of a .npy
+                            path(host.numpy())
+                        else:
+                            np.save(path, host.numpy())
                     done()
             except BaseException as e:                  # noqa: BLE001  (reported by close())
                 self._err = e
 
     def submit(self, jobs, done, after: Optional[torch.cuda.Event] = None) -> None:
-        """jobs: [(path, device tensor)], written in this order; done(): called by the worker after the last file.
+        """jobs: [(path, device tensor)], written in this order (a callable in place of the path is called with the host array);
+        done(): called by the worker after the last file.
         after: an event recorded behind the kernels that produced the tensors -- the copies then wait for THAT point of the compute
         stream only, not for what was enqueued since (the next packed group's forward: the CLI's pipelined pool); None = for
         everything enqueued so far."""
@@ -330,6 +334,22 @@ def extract_feat(cfg: Config, model: Optional[MSATransformer] = None, gather_to_
 
     save_dir = root / cfg.data.MSA_path
     save_dir.mkdir(parents=True, exist_ok=True)
+    # data.ss_model_path: the secondary-structure head on each alignment's device-resident maps (rnamsm.ss)
+    ss_model = ss.load_predictor(cfg.data.ss_model_path, device) if getattr(cfg.data, "ss_model_path", "") else None
+    if ss_model is not None:
+        ss_lut = torch.full((len(alphabet.all_toks),), 255, dtype=torch.uint8)
+        for code, ch in enumerate("ACGU"):
+            ss_lut[alphabet.tok_to_idx[ch]] = code
+        ss_lut = ss_lut.to(device)
+
+    def ss_text_jobs(rna_id: str, probs, tok_row) -> list:
+        """Writer jobs of SS_result/<id>.*: the query's tokens first (turned into its letters), then the probabilities."""
+        seq = []
+
+        def letters(toks: np.ndarray) -> None:
+            seq.append("".join(alphabet.all_toks[int(t)] for t in toks))
+
+        return [(letters, tok_row), (lambda prob: ss.write_ss_files(prob, seq[0], rna_id, save_dir), probs)]
     rng = np.random.RandomState(42)
     mine = sharding.shard_indices(len(ids), rank, world)
     written: List[str] = []
@@ -356,11 +376,15 @@ def extract_feat(cfg: Config, model: Optional[MSATransformer] = None, gather_to_
     writer = _AsyncNpyWriter(device) if async_io and (not gathering or rank == 0) else None
     reader = ThreadPoolExecutor(1, thread_name_prefix="rnamsm-msa-reader") if async_io else None
 
-    def emit(rna_id: str, emb: torch.Tensor, atp: torch.Tensor, after: Optional[torch.cuda.Event] = None) -> None:
+    def emit(rna_id: str, emb: torch.Tensor, atp: torch.Tensor, after: Optional[torch.cuda.Event] = None, ss_out=None) -> None:
+        """ss_out: (probabilities [L, L], query tokens [L]) on the device when data.ss_model_path is set."""
+        extra = ss_text_jobs(rna_id, *ss_out) if ss_out is not None else []
         if writer is not None:
-            writer.submit([(save_dir / f"{rna_id}_atp.npy", atp), (save_dir / f"{rna_id}_emb.npy", emb)],
+            writer.submit([(save_dir / f"{rna_id}_atp.npy", atp), (save_dir / f"{rna_id}_emb.npy", emb)] + extra,
                           lambda r=rna_id: written.append(r), after=after)
         else:
+            for fn, t in extra:
+                fn(t.cpu().numpy())
             write(rna_id, emb.cpu().numpy(), atp.cpu().numpy())
 
     # gather_to_rank0: outputs travel to rank 0 one ROUND (one MSA per rank) at a time, round k's RCCL transfers
@@ -376,16 +400,25 @@ def extract_feat(cfg: Config, model: Optional[MSATransformer] = None, gather_to_
                                f"(every rank then writes its own files)")
         if label != "primary" and rank == 0:
             print(f"gather to rank 0: {label}")
-    gatherer = sharding.RoundGatherer(len(ids), on_item=lambda i, ts: emit(ids[i], ts[0], ts[1]), tensors_per_item=2,
+    gatherer = sharding.RoundGatherer(len(ids), on_item=lambda i, ts: emit(ids[i], ts[0], ts[1], ss_out=ts[2:] or None),
+                                      tensors_per_item=2 if ss_model is None else 4,
                                       dst=0, device=device, group=gather_group) if gathering else None
     try:
         with torch.no_grad():
             pending = reader.submit(read, mine[0]) if reader and len(mine) else None
-            def deliver(idx: int, emb: torch.Tensor, atp: torch.Tensor, after: Optional[torch.cuda.Event] = None) -> None:
+            def deliver(idx: int, emb: torch.Tensor, atp: torch.Tensor, after: Optional[torch.cuda.Event] = None,
+                        toks: Optional[torch.Tensor] = None) -> None:
+                ss_out = None
+                if ss_model is not None:          # the head reads atp where it lies (a packed group's slice included)
+                    tok_row = toks[0, 1:]
+                    ss_out = (ss_model.predict(atp, ss_lut[tok_row]), tok_row)
+                    if after is not None:         # the copies wait for the head too
+                        after = torch.cuda.Event()
+                        after.record(torch.cuda.current_stream())
                 if gatherer is not None:
-                    gatherer.submit(idx, (emb, atp))
+                    gatherer.submit(idx, (emb, atp) + (ss_out or ()))
                 else:
-                    emit(ids[idx], emb, atp, after)
+                    emit(ids[idx], emb, atp, after, ss_out)
 
             # data.batch_small_msas: small alignments go through ONE launch set per group (forward_ragged: padded into one
             # frame, every MSA scaled by its own depth); a lone forward of a few hundred tokens costs 5.5 ms on a mostly
@@ -420,14 +453,14 @@ def extract_feat(cfg: Config, model: Optional[MSATransformer] = None, gather_to_
                     outs, ev = [alone(i, t) for i, t in members_], None
                 if not all(o["emb"].is_contiguous() and o["atp"].is_contiguous() for o in outs):
                     ev = None                                     # .contiguous() below would launch copies on the compute stream
-                for (i, _), out in zip(members_, outs):
-                    deliver(i, out["emb"].contiguous(), out["atp"].contiguous(), ev)
+                for (i, t), out in zip(members_, outs):
+                    deliver(i, out["emb"].contiguous(), out["atp"].contiguous(), ev, t)
 
             def finish_one(entry) -> None:
                 """Second half of a pipelined lone forward (the one-by-one loop of alignments too large to wait for company)."""
                 _, idx_, t_dev, has_pad, out, ev = entry
                 done = model.finish_forward_one(t_dev, out, has_pad, need_repr=False, what=ids[idx_], after=ev)
-                deliver(idx_, done["emb"], done["atp"], ev if done is out else None)
+                deliver(idx_, done["emb"], done["atp"], ev if done is out else None, t_dev)
 
             def finish_any(entry) -> None:
                 (finish_one if entry[0] == "one" else finish_packed)(entry)
@@ -496,14 +529,14 @@ def extract_feat(cfg: Config, model: Optional[MSATransformer] = None, gather_to_
                 if len(group) == 1:
                     idx0, t0 = group[0]
                     out = alone(idx0, t0)
-                    deliver(idx0, out["emb"].contiguous(), out["atp"].contiguous())
+                    deliver(idx0, out["emb"].contiguous(), out["atp"].contiguous(), toks=t0)
                 elif group:
                     try:
                         outs = model.forward_ragged([t for _, t in group], packed=packing)
                     except IndexError:                                # name the offending alignment: one by one
                         outs = [alone(i, t) for i, t in group]
-                    for (i, _), out in zip(group, outs):
-                        deliver(i, out["emb"].contiguous(), out["atp"].contiguous())
+                    for (i, t), out in zip(group, outs):
+                        deliver(i, out["emb"].contiguous(), out["atp"].contiguous(), toks=t)
                 group.clear()
 
             def read_and_run() -> None:
@@ -532,7 +565,7 @@ def extract_feat(cfg: Config, model: Optional[MSATransformer] = None, gather_to_
                     if gatherer is not None:       # (the gather orders its transfers behind the compute stream: one by one there, as before)
                         settle()
                         out = model.checked_forward_one(t_dev, has_pad, need_repr=False, what=rna_id)   # emb + atp are all that is written
-                        deliver(idx, out["emb"], out["atp"])
+                        deliver(idx, out["emb"], out["atp"], toks=t_dev)
                         continue
                     # PIPELINED (round 6): this forward is enqueued BEFORE the previous one's error word and outputs are read -- the ~3 ms
                     # of host work per alignment (weight-table check, ~140 launches, delivery) no longer idle the GPU between forwards

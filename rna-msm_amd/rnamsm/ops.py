@@ -557,6 +557,31 @@ def contact_head(row_attn: torch.Tensor, weight: torch.Tensor, bias: torch.Tenso
 
 
 @_on_operand_device
+def ss_head(atp: torch.Tensor, base_codes: torch.Tensor, ptrs, num_blocks: int, want: str = "probs") -> torch.Tensor:
+    """RNA-MSM-SS head (rnamsm_ss_head): atp [120, L, L] fp32 (planes may lie further apart than L*L: a slice of a wider
+    buffer is read in place), base_codes uint8 [L] (0..3 = A, C, G, U, other = no base), ptrs: the packed weight table
+    (ctypes c_void_p array, rnamsm.ss.SSPredictor) -> [L, L] fp32 probabilities (want="probs") or logits (want="logits")."""
+    if want not in ("probs", "logits"):
+        raise ValueError(f"ss_head: want must be 'probs' or 'logits', got {want!r}")
+    if atp.dim() != 3 or atp.shape[0] != 120 or atp.shape[1] != atp.shape[2]:
+        raise ValueError(f"ss_head: atp must be [120, L, L], got {tuple(atp.shape)}")
+    L = atp.shape[-1]
+    if atp.stride(2) != 1 or atp.stride(1) != L:
+        atp = atp.contiguous()
+    if base_codes.dim() != 1 or base_codes.shape[0] != L:
+        raise ValueError(f"ss_head: {base_codes.shape[0] if base_codes.dim() == 1 else tuple(base_codes.shape)} base codes "
+                         f"for atp of L = {L}")
+    lib = _lib.load()
+    ws = torch.empty(max(lib.rnamsm_ss_head_workspace_bytes(L), 16), dtype=torch.uint8, device=atp.device)
+    out = torch.empty(L, L, device=atp.device, dtype=torch.float32)
+    ptr = _dev(out, want)
+    _lib.check(lib.rnamsm_ss_head(_dev(atp, "atp"), atp.stride(0), _dev(base_codes.contiguous(), "base_codes", torch.uint8), L,
+                                  num_blocks, ptrs, ptr if want == "logits" else None, ptr if want == "probs" else None,
+                                  ws.data_ptr(), ws.numel(), _stream()))
+    return out
+
+
+@_on_operand_device
 def greedy_select(msa_u8: torch.Tensor, num_seqs: int, mode: str = "max") -> torch.Tensor:
     """msa uint8 [N, L] on the device -> int32 [num_seqs] ascending row indices (utils/align.py:128-148)."""
     if mode not in ("max", "min"):

@@ -1,0 +1,190 @@
+"""RNA-MSM-SS: secondary structure from the attention maps (the reference's _downstream_tasks/SS).
+
+`SSPredictor` carries the parameters of the reference's `renet_b16()` under the same names and shapes, so its
+`rna-msm_attention.pt` state_dict loads with strict=True; its arithmetic is one HIP entry point (rnamsm_ss_head, exact fp32
+on the matrix cores) that reads the [120, L, L] maps where they lie on the device.  `write_ss_files` is the reference's
+post-processing (code/post_processing/processing_output.py: prob_to_secondary_structure without the VARNA plots): the
+same `.ct`, `.bpseq` and `.prob` files, byte for byte.
+"""
+from __future__ import annotations
+
+import ctypes
+import os
+from pathlib import Path
+from typing import List, Tuple, Union
+
+import numpy as np
+import torch
+from torch import nn
+
+from . import _lib, ops
+
+NUM_MAPS = 120                  # layers x heads of the MSA transformer
+IN_PLANES = 8 + NUM_MAPS        # outer one-hot of the sequence + the maps
+CHANNELS = 48
+THRESHOLD = 0.516               # pairing threshold of the reference's post-processing
+_CODE = np.full(256, 255, dtype=np.uint8)
+for _i, _ch in enumerate("ACGU"):     # sklearn OneHotEncoder fitted on A, C, G, U (categories sorted), handle_unknown='ignore'
+    _CODE[ord(_ch)] = _i
+
+
+def base_codes(seq: str) -> np.ndarray:
+    """uint8 [L]: 0..3 for A, C, G, U; 255 (the all-zero one-hot vector) for anything else, lowercase and T included."""
+    raw = np.frombuffer(seq.encode("latin-1", errors="replace"), dtype=np.uint8)
+    return _CODE[raw]
+
+
+class _Block(nn.Module):
+    """Parameters of the reference's BasicBlock (code/model.py:32-85)."""
+
+    def __init__(self):
+        super().__init__()
+        self.conv1 = nn.Conv2d(CHANNELS, CHANNELS, 3, padding=1, bias=False)
+        self.bn1 = nn.LayerNorm(CHANNELS)
+        self.conv2 = nn.Conv2d(CHANNELS, CHANNELS, 5, padding=2, bias=False)
+        self.bn2 = nn.LayerNorm(CHANNELS)
+
+
+class SSPredictor(nn.Module):
+    """The reference's ResNet(128, BasicBlock, [num_blocks]) (renet_b16: 16 blocks) as parameters; the forward is the HIP head.
+
+    predict(atp, seq) -> [L, L] base-pair probabilities (sigmoid of the head, what predict.py hands to the post-processing);
+    logits(atp, seq) -> the pre-sigmoid values.  atp: the [120, L, L] fp32 maps on the HIP device (a view whose planes lie
+    further apart is read in place); seq: the query sequence (str) or its base codes (uint8 [L], see base_codes)."""
+
+    def __init__(self, num_blocks: int = 16):
+        super().__init__()
+        if not 1 <= num_blocks <= 64:
+            raise ValueError(f"num_blocks must be in [1, 64], got {num_blocks}")
+        self.num_blocks = num_blocks
+        self.conv1 = nn.Conv2d(IN_PLANES, CHANNELS, 3, padding=1)
+        self.bn1 = nn.LayerNorm(CHANNELS)
+        self.layer1 = nn.Sequential(*[_Block() for _ in range(num_blocks)])
+        self.fc1 = nn.Linear(CHANNELS, 1)
+        self._pack_key = None
+        self._pack = None
+
+    # ------------------------------------------------------------------ weight table of rnamsm_ss_head
+    def _packed_weights(self):
+        """The weight-pointer table in the kernel layout (conv weights tap-major [kh][kw][out][in]), rebuilt when a parameter was
+        replaced or written in place since (its data_ptr or version counter moved) -- the MSATransformer._packed_weights rule."""
+        params = list(self.parameters())
+        key = tuple((p.data_ptr(), p._version, p.device) for p in params)
+        if key == self._pack_key:
+            return self._pack
+        if self.conv1.weight.device.type != "cuda":
+            raise _lib.RnamsmError("SSPredictor must be moved to the HIP device (.to('cuda')): no CPU path exists")
+        keep: List[torch.Tensor] = []
+
+        def conv(w: torch.Tensor) -> torch.Tensor:
+            t = w.detach().to(torch.float32).permute(2, 3, 0, 1).contiguous()
+            keep.append(t)
+            return t
+
+        def vec(w: torch.Tensor) -> torch.Tensor:
+            t = w.detach().to(torch.float32).reshape(-1).contiguous().clone()
+            keep.append(t)
+            return t
+
+        table = [conv(self.conv1.weight), vec(self.conv1.bias), vec(self.bn1.weight), vec(self.bn1.bias)]
+        for blk in self.layer1:
+            table += [conv(blk.conv1.weight), vec(blk.bn1.weight), vec(blk.bn1.bias),
+                      conv(blk.conv2.weight), vec(blk.bn2.weight), vec(blk.bn2.bias)]
+        table += [vec(self.fc1.weight), vec(self.fc1.bias)]
+        assert len(table) == len(_lib.W_SS_STEM) + self.num_blocks * len(_lib.W_SS_BLOCK) + len(_lib.W_SS_HEAD)
+        ptrs = (ctypes.c_void_p * len(table))(*[t.data_ptr() for t in table])
+        self._pack = (ptrs, keep)
+        self._pack_key = key
+        return self._pack
+
+    def _apply(self, fn, *args, **kwargs):
+        self._pack_key = None
+        return super()._apply(fn, *args, **kwargs)
+
+    def _run(self, atp: torch.Tensor, seq: Union[str, np.ndarray, torch.Tensor], want: str) -> torch.Tensor:
+        if not isinstance(atp, torch.Tensor) or not atp.is_cuda:
+            raise _lib.RnamsmError("SSPredictor: atp must be a tensor on the HIP device (no CPU path exists)")
+        if atp.dim() != 3 or atp.shape[0] != NUM_MAPS or atp.shape[1] != atp.shape[2]:
+            raise ValueError(f"SSPredictor: atp must be [{NUM_MAPS}, L, L], got {tuple(atp.shape)}")
+        L = atp.shape[-1]
+        if L > _lib.SS_MAX_L:
+            raise ValueError(f"SSPredictor: L = {L} exceeds the head's limit of {_lib.SS_MAX_L}")
+        if isinstance(seq, str):
+            seq = base_codes(seq)
+        codes = torch.as_tensor(seq).to(device=atp.device, dtype=torch.uint8).reshape(-1)
+        if codes.numel() != L:
+            raise ValueError(f"SSPredictor: sequence of length {codes.numel()} for attention maps of L = {L}")
+        ptrs, _ = self._packed_weights()
+        return ops.ss_head(atp, codes, ptrs, self.num_blocks, want)
+
+    def predict(self, atp: torch.Tensor, seq) -> torch.Tensor:
+        return self._run(atp, seq, "probs")
+
+    def logits(self, atp: torch.Tensor, seq) -> torch.Tensor:
+        return self._run(atp, seq, "logits")
+
+    forward = predict
+
+
+def load_predictor(path: Union[str, Path], device, num_blocks: int = 16) -> SSPredictor:
+    """`rna-msm_attention.pt` (a plain state_dict) -> an SSPredictor on `device`, loaded strictly."""
+    state = torch.load(path, map_location="cpu")
+    model = SSPredictor(num_blocks)
+    model.load_state_dict(state, strict=True)
+    return model.eval().to(device)
+
+
+# ---------------------------------------------------------------------- post-processing (processing_output.py)
+def _multiplet_free(pairs: List[Tuple[int, int]], prob: np.ndarray) -> List[Tuple[int, int]]:
+    """multiplets_free_bp: while some base is in two or more pairs, drop -- for every such base, in ascending base order,
+    among its pairs in list order -- the first pair of lowest probability, all of one round's choices at once."""
+    while True:
+        count = {}
+        for i, j in pairs:
+            count[i] = count.get(i, 0) + 1
+            count[j] = count.get(j, 0) + 1
+        multi = sorted(b for b, n in count.items() if n > 1)
+        if not multi:
+            return pairs
+        drop = set()
+        for b in multi:
+            group = [p for p in pairs if b in p]
+            vals = [prob[p[0], p[1]] for p in group]
+            drop.add(group[vals.index(min(vals))])
+        pairs = [p for p in pairs if p not in drop]
+
+
+def secondary_structure(prob: np.ndarray) -> List[Tuple[int, int]]:
+    """Base pairs (i < j, 0-based) of an [L, L] probability matrix: the upper triangle above THRESHOLD in np.triu_indices
+    order, then made multiplet-free.  Only i < j is read: the matrix is not symmetric."""
+    prob = np.asarray(prob)
+    ii, jj = np.triu_indices(prob.shape[0], k=1)
+    keep = prob[ii, jj] > THRESHOLD
+    pairs = [(int(i), int(j)) for i, j in zip(ii[keep], jj[keep])]
+    return _multiplet_free(pairs, prob)
+
+
+def write_ss_files(prob: np.ndarray, seq: str, name: str, output_dir: Union[str, Path]) -> List[Tuple[int, int]]:
+    """`<output_dir>/SS_result/<name>.{ct,bpseq,prob}` as the reference writes them; returns the pairs."""
+    prob = np.asarray(prob, dtype=np.float32)
+    L = len(seq)
+    if prob.shape != (L, L):
+        raise ValueError(f"write_ss_files: probabilities of shape {prob.shape} for a sequence of length {L}")
+    pairs = secondary_structure(prob)
+    out = os.path.join(str(output_dir), "SS_result")
+    os.makedirs(out, exist_ok=True)
+    partner = np.zeros(L, dtype=int)
+    for i, j in pairs:
+        partner[i] = j + 1
+        partner[j] = i + 1
+    idx = np.arange(1, L + 1)
+    bases = np.array(list(seq))
+    fmt_int = lambda a: np.char.mod("%d", a)          # noqa: E731
+    ct = np.vstack((fmt_int(idx), bases, fmt_int(idx - 1), fmt_int(np.append(idx[1:], [0])), fmt_int(partner),
+                    fmt_int(idx))).T
+    np.savetxt(os.path.join(out, name + ".ct"), ct, delimiter="\t\t", fmt="%s",
+               header=f"{L}\t\t{name}\t\tRNAMSM_SS output\n", comments="")
+    bp = np.vstack((fmt_int(idx), bases, fmt_int(partner))).T
+    np.savetxt(os.path.join(out, name + ".bpseq"), bp, delimiter=" ", fmt="%s", header="#" + name, comments="")
+    np.savetxt(os.path.join(out, name + ".prob"), prob, delimiter="\t")
+    return pairs
