@@ -8,18 +8,49 @@ import torch.nn.functional as F
 from rnamsm import ss
 
 
-def features(atp: np.ndarray, seq: str) -> np.ndarray:
-    """[128, L, L]: outer one-hot of the sequence (channels 0-3: base i, 4-7: base j) and the 120 maps."""
-    L = atp.shape[-1]
-    codes = ss.base_codes(seq)
-    oh = np.zeros((L, 4))
-    ok = codes < 4
-    oh[np.nonzero(ok)[0], codes[ok]] = 1.0
-    x = np.zeros((128, L, L))
-    x[0:4] = oh.T[:, :, None]
-    x[4:8] = oh.T[:, None, :]
+def features(atp: np.ndarray, seq, rows=None, cols=None) -> np.ndarray:
+    """[128, R, C]: outer one-hot of the sequence (channels 0-3: base i, 4-7: base j) and the 120 maps, on the crop
+    rows [r0, r1) x cols [c0, c1) of the [L, L] image (default: the whole image); atp is that crop, [120, R, C].
+    seq: the whole query (str) or its base codes (uint8 [L], ss.base_codes)."""
+    codes = ss.base_codes(seq) if isinstance(seq, str) else np.asarray(seq, dtype=np.uint8).reshape(-1)
+    r0, r1 = rows if rows is not None else (0, atp.shape[-2])
+    c0, c1 = cols if cols is not None else (0, atp.shape[-1])
+    assert atp.shape[-2:] == (r1 - r0, c1 - c0), (atp.shape, rows, cols)
+
+    def onehot(c):
+        oh = np.zeros((len(c), 4))
+        ok = c < 4
+        oh[np.nonzero(ok)[0], c[ok]] = 1.0
+        return oh
+
+    x = np.zeros((128, r1 - r0, c1 - c0))
+    x[0:4] = onehot(codes[r0:r1]).T[:, :, None]
+    x[4:8] = onehot(codes[c0:c1]).T[:, None, :]
     x[8:] = atp
     return x
+
+
+def receptive_margin(num_blocks: int) -> int:
+    """An output pixel depends on inputs within this many pixels: 1 for the stem's 3x3, then 1 + 2 per block."""
+    return 1 + 3 * num_blocks
+
+
+def logits_window(atp, seq, state: dict, rows, cols, dtype=torch.float64, device="cpu", margin=None) -> np.ndarray:
+    """The block rows [r0, r1) x cols [c0, c1) of logits(features(atp, seq), state), computed on a crop that reaches
+    `margin` pixels beyond the block (default: the receptive margin, which gives the full map's result exactly), clipped
+    at the image border, where the crop's zero padding is the image's own.  atp: [120, L, L], a host array or a device
+    tensor; only the crop is copied."""
+    nb = sum(1 for k in state if k.endswith(".conv2.weight"))
+    m = receptive_margin(nb) if margin is None else margin
+    L = atp.shape[-1]
+    (r0, r1), (c0, c1) = rows, cols
+    assert 0 <= r0 < r1 <= L and 0 <= c0 < c1 <= L, (rows, cols, L)
+    R0, R1, C0, C1 = max(0, r0 - m), min(L, r1 + m), max(0, c0 - m), min(L, c1 + m)
+    crop = atp[:, R0:R1, C0:C1]
+    if isinstance(crop, torch.Tensor):
+        crop = crop.detach().to("cpu", torch.float64).numpy()
+    y = logits(features(crop, seq, (R0, R1), (C0, C1)), state, dtype, device)
+    return y[r0 - R0:r1 - R0, c0 - C0:c1 - C0]
 
 
 def make_state(num_blocks: int, seed: int, beta_scale: float = 0.3) -> dict:
@@ -52,16 +83,71 @@ def _ln_relu(x, sd, name):
     return torch.relu(y.permute(2, 0, 1))
 
 
+def _conv(x, w, b=None):
+    """nn.Conv2d(padding=k // 2) on [C, H, W], as a sum over the k x k taps of [O, C] x [C, H, W] products.
+    Every output element is then summed in an order that does not depend on H or W (F.conv2d's single GEMM over C k k
+    is split by the CPU BLAS differently for different image sizes), which makes logits_window exact."""
+    k = w.shape[-1]
+    p = k // 2
+    H, W = x.shape[-2:]
+    xp = F.pad(x, (p, p, p, p))
+    out = torch.zeros(w.shape[0], H, W, dtype=x.dtype, device=x.device)
+    for dy in range(k):
+        for dx in range(k):
+            out += torch.einsum("oc,chw->ohw", w[:, :, dy, dx], xp[:, dy:dy + H, dx:dx + W])
+    return out if b is None else out + b[:, None, None]
+
+
 def logits(x: np.ndarray, state: dict, dtype=torch.float64, device="cpu") -> np.ndarray:
     """[L, L] pre-sigmoid output of the head on features x [128, L, L]."""
     sd = {k: (v if isinstance(v, torch.Tensor) else torch.as_tensor(np.asarray(v))).to(device=device, dtype=dtype)
           for k, v in state.items()}
     nb = sum(1 for k in sd if k.endswith(".conv2.weight"))
-    h = torch.as_tensor(x).to(device=device, dtype=dtype)[None]
-    h = F.conv2d(h, sd["conv1.weight"], sd["conv1.bias"], padding=1)[0]
+    # fp64: the tap-wise sum (exact windows); any other dtype: F.conv2d, the reference network's own arithmetic (nn.Conv2d) --
+    # the fp32 restatement is the yardstick of the GPU tests' bars and stays what those bars were measured against
+    conv = _conv if dtype == torch.float64 else (lambda v, w, b=None: F.conv2d(v[None], w, b, padding=w.shape[-1] // 2)[0])
+    h = torch.as_tensor(x).to(device=device, dtype=dtype)
+    h = conv(h, sd["conv1.weight"], sd["conv1.bias"])
     for k in range(nb):
         p = f"layer1.{k}"
-        t = F.conv2d(_ln_relu(h, sd, p + ".bn1")[None], sd[p + ".conv1.weight"], padding=1)[0]
-        h = F.conv2d(_ln_relu(t, sd, p + ".bn2")[None], sd[p + ".conv2.weight"], padding=2)[0] + h
+        t = conv(_ln_relu(h, sd, p + ".bn1"), sd[p + ".conv1.weight"])
+        h = conv(_ln_relu(t, sd, p + ".bn2"), sd[p + ".conv2.weight"]) + h
     y = _ln_relu(h, sd, "bn1").permute(1, 2, 0) @ sd["fc1.weight"][0] + sd["fc1.bias"][0]
     return y.cpu().numpy()
+
+
+# element-wise bar of the GPU tests: max-abs vs fp64 within EW_MULT x the fp32 restatement's max-abs on the same pixels
+# (floor: EW_FLOOR x the largest |logit|); the rel-L2 bar is _check's, 2 x the restatement's (tests/analysis/README.md)
+EW_MULT, EW_FLOOR = 4.0, 1e-7
+L2_MULT, L2_FLOOR = 2.0, 1e-7
+
+
+def compare(got, t64, t32, label: str = "", seams: bool = False, floor: float = None, l2_mult: float = L2_MULT) -> float:
+    """Assert that the HIP logits `got` are as close to the fp64 truth `t64` as the fp32 restatement `t32` is, on the same
+    pixels: by rel-L2 and element-wise.  seams=True (`got` a whole [L, L] map): also report the worst error on the border
+    pixels (rows / columns 0, 1, L - 2, L - 1) and on the tile-seam pixels (index mod 16 in {0, 15}).  floor: one relative
+    floor for both bars in place of L2_FLOOR / EW_FLOOR (a single pixel, where the restatement's error is one rounding sample
+    and can be any fraction of an ulp).  l2_mult: the rel-L2 multiple, where the tolerance table records a finding.
+    Returns the max-abs."""
+    got, t64, t32 = (np.asarray(a, dtype=np.float64) for a in (got, t64, t32))
+    assert got.shape == t64.shape == t32.shape and np.isfinite(got).all(), label
+    d, d32 = np.abs(got - t64), np.abs(t32 - t64)
+    err, drift = float(np.linalg.norm(got - t64)), float(np.linalg.norm(t32 - t64))
+    norm = max(float(np.linalg.norm(t64)), 1e-30)
+    err, drift = err / norm, drift / norm
+    l2_floor, ew_floor = (L2_FLOOR, EW_FLOOR) if floor is None else (floor, floor)
+    ew_bar = EW_MULT * max(float(d32.max()), ew_floor * float(np.abs(t64).max()))
+    msg = (f"{label}: rel-L2 {err:.2e} (fp32 restatement {drift:.2e}), max-abs {d.max():.2e} (restatement {d32.max():.2e}, "
+           f"bar {ew_bar:.2e}, ratio {d.max() / ew_bar:.2f})")
+    if seams:
+        L = got.shape[0]
+        idx = np.arange(L)
+        edge = np.isin(idx, [0, 1, L - 2, L - 1])
+        seam = np.isin(idx % 16, [0, 15])
+        worst = lambda m: float(d[m].max()) if m.any() else 0.0        # noqa: E731
+        msg += (f"; worst border {worst(edge[:, None] | edge[None, :]):.2e}, "
+                f"worst seam {worst(seam[:, None] | seam[None, :]):.2e}")
+    print(msg)
+    assert err <= l2_mult * max(drift, l2_floor), msg
+    assert d.max() <= ew_bar, msg
+    return float(d.max())

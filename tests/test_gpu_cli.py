@@ -12,6 +12,7 @@ import torch
 from conftest import GOLDEN, ROOT, golden, rel_l2
 from oracle import msm_oracle as O
 from rnamsm import synthetic
+import ss_truth
 
 pytestmark = pytest.mark.gpu
 
@@ -75,7 +76,7 @@ def test_async_io_pipeline_writes_the_same_files(tmp_path):
     assert emb.shape == (35, 768) and emb.dtype == np.float32
 
 
-def _gather_worker(rank, world, port, root):
+def _gather_worker(rank, world, port, root, ss_model_path=""):
     """One rank of the CLI loop with gather_to_rank0 (both ranks on device 0, gloo: payloads staged through the host)."""
     import torch.distributed as dist
     os.environ["MASTER_ADDR"], os.environ["MASTER_PORT"] = "127.0.0.1", str(port)
@@ -93,16 +94,16 @@ def _gather_worker(rank, world, port, root):
         cfg.data.root_path, cfg.data.MSA_path, cfg.data.MSA_list = str(root), "results", "rna_id.txt"
         cfg.data.sample_method, cfg.data.max_seqs_per_msa, cfg.data.device = "first", 64, "cuda:0"
         cfg.data.batch_small_msas = False     # byte-identity across DIFFERENT shardings needs the one-by-one loop (see below)
+        cfg.data.ss_model_path = ss_model_path    # set: the SS head's probabilities and tokens travel with the maps (4 per item)
         written = extract_feat(cfg, model=model, gather_to_rank0=True)
         assert (len(written) == 5) if rank == 0 else (written == [])     # only rank 0 writes
     finally:
         dist.destroy_process_group()
 
 
-def test_cli_gather_to_rank0_streams_rounds_and_writes_the_same_files(tmp_path):
-    """ADVICE r01: with gather_to_rank0 the outputs travel to rank 0 one ROUND at a time (RoundGatherer) and leave through
-    the async writer as they arrive -- five ids over two ranks (three rounds, the last with an item-less rank), files
-    byte-identical to the single-process loop."""
+def _gather_and_single(tmp_path, ss_pt=""):
+    """Five ids over two ranks with gather_to_rank0 and the same ids in one process, both one by one; ss_pt: the
+    data.ss_model_path of both runs ("" = unset).  Asserts the .npy files byte-identical; returns both result roots."""
     import socket
     import torch.multiprocessing as mp
     from rnamsm.config import Config
@@ -128,16 +129,38 @@ def test_cli_gather_to_rank0_streams_rounds_and_writes_the_same_files(tmp_path):
     # sharding, and a frame's members agree with their lone forwards to fp32 rounding only -- the byte comparison below is
     # about the gather, so both sides run one by one
     cfg.data.batch_small_msas = False
+    cfg.data.ss_model_path = ss_pt
     extract_feat(cfg, model=model)
     with socket.socket() as s:
         s.bind(("127.0.0.1", 0))
         port = s.getsockname()[1]
-    mp.spawn(_gather_worker, args=(2, port, roots["gathered"]), nprocs=2, join=True)
+    mp.spawn(_gather_worker, args=(2, port, roots["gathered"], ss_pt), nprocs=2, join=True)
     a = {f.name: f.read_bytes() for f in sorted((roots["single"] / "results").glob("*.npy"))}
     b = {f.name: f.read_bytes() for f in sorted((roots["gathered"] / "results").glob("*.npy"))}
     assert len(a) == 10 and a.keys() == b.keys()
     for name in a:
         assert a[name] == b[name], name
+    return roots
+
+
+def test_cli_gather_to_rank0_streams_rounds_and_writes_the_same_files(tmp_path):
+    """ADVICE r01: with gather_to_rank0 the outputs travel to rank 0 one ROUND at a time (RoundGatherer) and leave through
+    the async writer as they arrive -- five ids over two ranks (three rounds, the last with an item-less rank), files
+    byte-identical to the single-process loop."""
+    roots = _gather_and_single(tmp_path)
+    assert not any((r / "results" / "SS_result").exists() for r in roots.values())
+
+
+def test_cli_gather_to_rank0_writes_the_same_ss_results(tmp_path):
+    """data.ss_model_path set: each item's SS probabilities and query tokens travel to rank 0 with its maps (4 tensors per
+    item in the RoundGatherer); the gathered SS_result files are the single-process run's, byte for byte."""
+    ss_pt = str(tmp_path / "rna-msm_attention.pt")
+    torch.save({k: torch.from_numpy(v) for k, v in ss_truth.make_state(16, seed=5).items()}, ss_pt)
+    roots = _gather_and_single(tmp_path, ss_pt)
+    ss_files = {r: {f.name: f.read_bytes() for f in sorted((roots[r] / "results" / "SS_result").glob("*"))} for r in roots}
+    assert len(ss_files["single"]) == 15 and ss_files["single"].keys() == ss_files["gathered"].keys()
+    for name, data in ss_files["single"].items():
+        assert ss_files["gathered"][name] == data, name
 
 
 @pytest.mark.parametrize("packing", [True, "split", False])

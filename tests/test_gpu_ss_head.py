@@ -43,11 +43,8 @@ def _check(L, state, num_blocks, seed, device="cpu"):
     x = ss_truth.features(atp, seq)
     t64 = ss_truth.logits(x, state, torch.float64, device)
     t32 = ss_truth.logits(x, state, torch.float32, device).astype(np.float64)
-    drift = rel_l2(t32, t64)
-    err = rel_l2(got, t64)
-    print(f"L={L}: HIP rel-L2 vs fp64 {err:.2e}, fp32 restatement {drift:.2e}, max-abs {np.abs(got - t64).max():.2e}")
-    assert got.shape == (L, L) and np.isfinite(got).all()
-    assert err <= 2 * max(drift, 1e-7), (err, drift)
+    assert got.shape == (L, L)
+    ss_truth.compare(got, t64, t32, f"L={L}", seams=True)      # rel-L2 <= 2 x the restatement's, and element-wise
     return got
 
 
@@ -180,6 +177,50 @@ def test_cli_key_writes_ss_results_equal_to_ss_predict(tmp_path, batching):
         assert r.returncode == 0, r.stderr[-2000:]
         for ext in ("prob", "bpseq", "ct"):
             assert (feat / "SS_result" / f"{i}.{ext}").read_bytes() == (outs[True] / "SS_result" / f"{i}.{ext}").read_bytes(), ext
+
+
+def test_cli_key_pairs_every_alignment_with_its_own_maps_and_tokens(tmp_path):
+    """Three alignments whose L and query differ pairwise (35, 12 with T, X and - in its query, 50 random): in the packed
+    loop (one group) and the one-by-one loop, every SS_result file is what write_ss_files writes from SSPredictor.predict on
+    that alignment's own _atp.npy and the letters of its own query tokens (a T of the alignment reads as U), so a swap of
+    maps, tokens or ids between members fails."""
+    sys.path.insert(0, ROOT)
+    import RNA_MSM_Inference as cli
+    from conftest import _LETTER
+    state = synthetic.make_state_dict(seed=0)
+    ckpt = tmp_path / "model.ckpt"
+    torch.save({"state_dict": {k: torch.from_numpy(v) for k, v in state.items()}}, ckpt)
+    ss_pt = _ss_state_file(tmp_path)
+    rng = np.random.RandomState(81)
+    rand_rows = ["".join(rng.choice(list("ACGU"), 50)) for _ in range(6)]
+    sources = {"rnaP": (open(os.path.join(GOLDEN, "2DRB_1_first64.a2m_msa2")).read(), "tokens_2DRB_1_first64.npz"),
+               "rnaQ": (open(os.path.join(GOLDEN, "synthetic_chars.a2m_msa2")).read(), "tokens_synthetic_chars.npz"),
+               "rnaR": ("".join(f">r{i}\n{row}\n" for i, row in enumerate(rand_rows)), None)}
+    seqs = {i: ("".join(_LETTER[int(t)] for t in golden(tok)["tokens"][0, 1:]) if tok else rand_rows[0])
+            for i, (_, tok) in sources.items()}
+    assert [len(s) for s in seqs.values()] == [35, 12, 50] and seqs["rnaQ"] == "ACGU-XACGUUU"
+    ids = list(sources)
+    outs = {}
+    for batching in (True, False):
+        res = tmp_path / f"batch_{batching}"
+        res.mkdir()
+        for i, (text, _) in sources.items():
+            (res / f"{i}.a2m_msa2").write_text(text)
+        (tmp_path / "rna_id.txt").write_text("\n".join(ids) + "\n")
+        cli.main([f"data.root_path={tmp_path}", f"data.MSA_path={res.name}", f"data.model_path={ckpt}", "data.MSA_list=rna_id.txt",
+                  "data.max_seqs_per_msa=32", "data.sample_method=first", f"data.batch_small_msas={batching}",
+                  f"data.ss_model_path={ss_pt}"])
+        outs[batching] = res
+    head = ss.load_predictor(ss_pt, DEV)
+    for i in ids:
+        atp = np.load(outs[False] / f"{i}_atp.npy")
+        assert atp.shape == (120, len(seqs[i]), len(seqs[i]))
+        want_dir = tmp_path / f"want_{i}"
+        ss.write_ss_files(head.predict(torch.from_numpy(atp).to(DEV), seqs[i]).cpu().numpy(), seqs[i], i, want_dir)
+        for ext in ("ct", "bpseq", "prob"):
+            want = (want_dir / "SS_result" / f"{i}.{ext}").read_bytes()
+            for batching, res in outs.items():
+                assert (res / "SS_result" / f"{i}.{ext}").read_bytes() == want, (i, ext, batching)
 
 
 def test_refusals(tmp_path):
