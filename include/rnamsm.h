@@ -566,7 +566,8 @@ void rnamsm_timing_reset(void);
  *   "row_narrow"  fp32 rnamsm_row_logits / rnamsm_row_apply at C <= 64: 1 (default) = the LDS-free narrow kernels, 0 = the
  *                 128x128 tile kernels.  Speed only, results bit-identical.
  *   "col_small"   fp32 rnamsm_col_attn_fused at R <= 16: 1 (default) = one wave per (column, head) on v_mfma_f32_16x16x4_f32,
- *                 no LDS; 0 = the 128-query-block kernels.  Results agree to fp32 rounding.
+ *                 no LDS; 0 = the 128-query-block kernels.  Results agree to fp32 rounding.  Plane output (ctx_hi) comes from the
+ *                 same kernel as the fp32 context under either value: the planes are the split of exactly those fp32 values.
  *   "col_fast"    rnamsm_col_attn_fused_prescaled: 1 (default) = first pass without a running maximum, the online softmax as the
  *                 fallback of a block whose row sums leave [2^-64, 2^100]; 0 = the online softmax only (results agree to rounding).
  *   "col_dma"     fp32 rnamsm_col_attn_fused: 1 = K/V chunks staged by LDS-DMA, 32-key chunks, three blocks per CU;

@@ -587,13 +587,17 @@ namespace rnamsm {
 // 12 sixteen-byte loads per lane straight from global memory (L1/L2-served), 32 MFMAs of 32 cycles, ~45 registers: 8 waves
 // per SIMD hide the latency.  Same arithmetic as the big kernels up to the summation order.  q_rows < R: only those query
 // rows are stored (rnamsm_col_attn_fused_queries), bit-identical to the full launch's.
-template <bool MASKED>
+// OUT: 0 = fp32 context; 1 / 2 = bf16 / fp16 hi (+ lo if ctx_lo) planes of the SAME fp32 values (the plane output of a shallow
+// alignment used to come from the 128-query-block kernel, whose summation order differs: planes and fp32 context of one
+// entry point then disagreed by several fp32 ulps -- tests/test_gpu_planes.py).
+template <bool MASKED, int OUT = 0>
 __global__ __launch_bounds__(256) void col_attn_small_kernel(const float* __restrict__ q, const float* __restrict__ k,
                                                              const float* __restrict__ v, int64_t ld, float* __restrict__ ctx,
                                                              int64_t ldc, int R, int C, int H,
                                                              const uint8_t* __restrict__ pad_mask, int q_rows,
                                                              int64_t qkv_bstride, int64_t ctx_bstride,
-                                                             const PackedMsa* __restrict__ pk, int log2_domain) {
+                                                             const PackedMsa* __restrict__ pk, int log2_domain,
+                                                             uint16_t* __restrict__ ctx_hi, uint16_t* __restrict__ ctx_lo) {
     typedef float f32x4s __attribute__((ext_vector_type(4)));
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int prob = blockIdx.x * 4 + wave;
@@ -663,10 +667,26 @@ __global__ __launch_bounds__(256) void col_attn_small_kernel(const float* __rest
         for (int s = 0; s < 4; ++s) o[tile] = __builtin_amdgcn_mfma_f32_16x16x4f32(v4[s][tile], p[s], o[tile], 0, 0, 0);
     }
     if (fr < q_rows) {                                           // register t of the four tiles = head dims 16 fq + 4 t + 0..3 of query fr
-        float* orow = ctx + ((int64_t)fr * C + c) * ldc + h * CA_HD + 16 * fq;
+        const int64_t ooff = ((int64_t)fr * C + c) * ldc + h * CA_HD + 16 * fq;
 #pragma unroll
-        for (int t = 0; t < 4; ++t)
-            *reinterpret_cast<f32x4s*>(orow + 4 * t) = f32x4s{o[0][t], o[1][t], o[2][t], o[3][t]} * inv;
+        for (int t = 0; t < 4; ++t) {
+            const f32x4s ov = f32x4s{o[0][t], o[1][t], o[2][t], o[3][t]} * inv;
+            if (OUT == 0) {
+                *reinterpret_cast<f32x4s*>(ctx + ooff + 4 * t) = ov;
+            } else {
+                typedef typename Half16<(OUT > 0 ? OUT - 1 : 0)>::T Hh;
+                typedef Hh Hh4 __attribute__((ext_vector_type(4)));
+                Hh4 hv, lv;
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    const float x = pinned(ov[e]);
+                    hv[e] = (Hh)x;
+                    lv[e] = (Hh)(x - (float)hv[e]);
+                }
+                *reinterpret_cast<Hh4*>(ctx_hi + ooff + 4 * t) = hv;
+                if (ctx_lo) *reinterpret_cast<Hh4*>(ctx_lo + ooff + 4 * t) = lv;
+            }
+        }
     }
 }
 }  // namespace rnamsm
@@ -691,12 +711,16 @@ static int col_attn_launch(const float* q, const float* k, const float* v, int64
     const unsigned grid = xcd_panel_grid((unsigned)C * H, iblocks);
     KernelTimer timer(TC_COL_ATTN, 4.0 * batch * C * H * (double)q_rows * R * CA_HD, 4.0 * batch * (2.0 * R + 2.0 * q_rows) * C * H * CA_HD, s);
     // shallow alignments: one wave per (column, head), no LDS ("col_small" = 0 keeps the 128-query blocks: A/B)
-    if (R <= 16 && !ctx_hi && tuning().col_small != 0) {
+    if (R <= 16 && tuning().col_small != 0) {
         const dim3 sgrid(((unsigned)C * H + 3) / 4, batch);
-        if (pad_mask)
-            hipLaunchKernelGGL(col_attn_small_kernel<true>, sgrid, dim3(256), 0, s, q, k, v, ld, ctx, ldc, R, C, H, pad_mask, q_rows, qkv_bstride, ctx_bstride, (const PackedMsa*)nullptr, prescaled ? 1 : 0);
-        else
-            hipLaunchKernelGGL(col_attn_small_kernel<false>, sgrid, dim3(256), 0, s, q, k, v, ld, ctx, ldc, R, C, H, pad_mask, q_rows, qkv_bstride, ctx_bstride, (const PackedMsa*)nullptr, prescaled ? 1 : 0);
+#define CS_GO(M_, OUT_)                                                                                                        \
+    hipLaunchKernelGGL((col_attn_small_kernel<M_, OUT_>), sgrid, dim3(256), 0, s, q, k, v, ld, ctx, ldc, R, C, H, pad_mask, q_rows, \
+                       qkv_bstride, ctx_bstride, (const PackedMsa*)nullptr, prescaled ? 1 : 0, ctx_hi, ctx_lo)
+        if (pad_mask) CS_GO(true, 0);                    // (plane output has no masked variant: refused above)
+        else if (!ctx_hi) CS_GO(false, 0);
+        else if (plane_fmt == 0) CS_GO(false, 1);
+        else CS_GO(false, 2);
+#undef CS_GO
         RNAMSM_CHECK_LAUNCH("col_attn_small");
         return RNAMSM_OK;
     }
@@ -803,7 +827,7 @@ int col_attn_packed(const float* q, const float* k, const float* v, int64_t ld, 
     }
     if (sgrid) {
         hipLaunchKernelGGL(col_attn_small_kernel<false>, dim3(sgrid, B), dim3(256), 0, s, q, k, v, ld, ctx, ldc, 0, 0, H,
-                           (const uint8_t*)nullptr, 0, (int64_t)0, (int64_t)0, pk, prescaled ? 1 : 0);
+                           (const uint8_t*)nullptr, 0, (int64_t)0, (int64_t)0, pk, prescaled ? 1 : 0, (uint16_t*)nullptr, (uint16_t*)nullptr);
         RNAMSM_CHECK_LAUNCH("col_attn_small (packed)");
     }
     return RNAMSM_OK;

@@ -193,6 +193,35 @@ __device__ __forceinline__ float wave_max(float v) {
     return v;
 }
 
+// LayerNorm of one row held as up to four float4 per lane (D <= 1024), biased variance, two passes like ATen's CPU kernel.
+// ONE arithmetic for every kernel that normalises a row (layernorm_kernel, embed_ln_kernel, layernorm_split_kernel): the
+// fused steps are written as fmaf and nothing else has the a * b + c shape, so -ffp-contract=fast has no choice to make and two
+// kernels that call these compute the same bits.  (Found by tests/test_gpu_planes.py: with `ss += d * d` and
+// `(x - mean) * rstd * g + b` left to the compiler, the fp32 kernel got a mix of packed multiply + add and fused steps and the
+// plane-writing kernel an fmac chain; rstd then differed in its last bit and the two outputs by 2-3 fp32 ulps.)
+struct LnStats {
+    float mean, rstd;
+};
+__device__ __forceinline__ LnStats ln_row_stats(const f32x4 (&x)[4], int nvec, int lane, int D, float eps) {
+    float s = 0.f;
+#pragma unroll
+    for (int e = 0; e < 4; ++e)
+        if (lane + 64 * e < nvec) s += (x[e][0] + x[e][1]) + (x[e][2] + x[e][3]);
+    const float mean = wave_sum(s) / (float)D;
+    float ss = 0.f;
+#pragma unroll
+    for (int e = 0; e < 4; ++e)
+        if (lane + 64 * e < nvec) {
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const float d = x[e][i] - mean;
+                ss = fmaf(d, d, ss);
+            }
+        }
+    return LnStats{mean, rsqrtf(wave_sum(ss) / (float)D + eps)};
+}
+__device__ __forceinline__ float ln_value(float x, LnStats st, float g, float b) { return fmaf((x - st.mean) * st.rstd, g, b); }
+
 // Exact-fp32 matrix core step: D(32x32) += A(32x2) * B(2x32).
 // Lane l supplies A[row = l&31][k = l>>5] and B[k = l>>5][col = l&31]; accumulator register t of lane l is
 // D[row = (t&3) + 8*(t>>2) + 4*(l>>5)][col = l&31]  (cdna_hip_programming.md §3).

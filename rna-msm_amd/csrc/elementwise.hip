@@ -13,22 +13,8 @@ constexpr int LN_MAX_VEC = 4;     // float4 per lane -> D <= 1024
 __device__ __forceinline__ void ln_row(f32x4 (&x)[LN_MAX_VEC], int nvec, int lane, int D, float eps,
                                        const float* __restrict__ gamma, const float* __restrict__ beta,
                                        float* __restrict__ out_row) {
-    float s = 0.f;
-#pragma unroll
-    for (int e = 0; e < LN_MAX_VEC; ++e)
-        if (lane + 64 * e < nvec) s += (x[e][0] + x[e][1]) + (x[e][2] + x[e][3]);
-    const float mean = wave_sum(s) / (float)D;
-    float ss = 0.f;
-#pragma unroll
-    for (int e = 0; e < LN_MAX_VEC; ++e)
-        if (lane + 64 * e < nvec) {
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const float d = x[e][i] - mean;
-                ss += d * d;
-            }
-        }
-    const float rstd = rsqrtf(wave_sum(ss) / (float)D + eps);
+    static_assert(LN_MAX_VEC == 4, "ln_row_stats holds four float4 per lane");
+    const LnStats st = ln_row_stats(x, nvec, lane, D, eps);
 #pragma unroll
     for (int e = 0; e < LN_MAX_VEC; ++e) {
         const int vi = lane + 64 * e;
@@ -37,7 +23,7 @@ __device__ __forceinline__ void ln_row(f32x4 (&x)[LN_MAX_VEC], int nvec, int lan
             const f32x4 b = *reinterpret_cast<const f32x4*>(beta + 4 * vi);
             f32x4 y;
 #pragma unroll
-            for (int i = 0; i < 4; ++i) y[i] = (x[e][i] - mean) * rstd * g[i] + b[i];
+            for (int i = 0; i < 4; ++i) y[i] = ln_value(x[e][i], st, g[i], b[i]);
             *reinterpret_cast<f32x4*>(out_row + 4 * vi) = y;
         }
     }

@@ -1047,7 +1047,7 @@ static int launch_hq(const uint16_t* Whi, const float* bias, const float* residu
 }
 
 // LayerNorm whose output goes straight into 16-bit hi/lo planes (the A operand of the following matrix-core GEMM):
-// same arithmetic as layernorm_kernel (elementwise.hip), only the store differs.
+// the arithmetic of layernorm_kernel (elementwise.hip) by construction (ln_row_stats / ln_value, common.h), only the store differs.
 template <int FMT>
 __global__ __launch_bounds__(256) void layernorm_split_kernel(const float* __restrict__ x, const float* __restrict__ gamma,
                                                               const float* __restrict__ beta, uint16_t* __restrict__ hi,
@@ -1058,25 +1058,10 @@ __global__ __launch_bounds__(256) void layernorm_split_kernel(const float* __res
     const int64_t stride = (int64_t)gridDim.x * 4;
     for (int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); row < T; row += stride) {
         f32x4 v[4];
-        float s = 0.f;
 #pragma unroll
         for (int e = 0; e < 4; ++e)
-            if (lane + 64 * e < nvec) {
-                v[e] = *reinterpret_cast<const f32x4*>(x + row * D + 4 * (lane + 64 * e));
-                s += (v[e][0] + v[e][1]) + (v[e][2] + v[e][3]);
-            }
-        const float mean = wave_sum(s) / (float)D;
-        float ss = 0.f;
-#pragma unroll
-        for (int e = 0; e < 4; ++e)
-            if (lane + 64 * e < nvec) {
-#pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    const float d = v[e][i] - mean;
-                    ss += d * d;
-                }
-            }
-        const float rstd = rsqrtf(wave_sum(ss) / (float)D + eps);
+            if (lane + 64 * e < nvec) v[e] = *reinterpret_cast<const f32x4*>(x + row * D + 4 * (lane + 64 * e));
+        const LnStats st = ln_row_stats(v, nvec, lane, D, eps);
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
             const int vi = lane + 64 * e;
@@ -1086,7 +1071,7 @@ __global__ __launch_bounds__(256) void layernorm_split_kernel(const float* __res
                 H4 h, l;
 #pragma unroll
                 for (int i = 0; i < 4; ++i) {
-                    const float y = pinned((v[e][i] - mean) * rstd * g[i] + b[i]);
+                    const float y = pinned(ln_value(v[e][i], st, g[i], b[i]));
                     h[i] = (H)y;
                     l[i] = (H)(y - (float)h[i]);
                 }
