@@ -367,6 +367,45 @@ int rnamsm_ss_head(const float* atp, int64_t atp_plane_stride, const uint8_t* ba
                    const float* const* weights, float* logits, float* probs, void* workspace, size_t workspace_bytes,
                    void* stream);
 
+/* f5 -- RNA-MSM RSA (relative solvent accessibility) predictor (_downstream_tasks/RSA: predict.py, model/_0811/model_entry.py
+ * FrameModel(Cin, 1, planes 64, depth 1, BatchNorm1d)) for an ensemble of n_models members in one set of four launches, exact fp32:
+ *   x[c, p]  = (onehot(code[p])[c] - mu_oh[c]) / std_oh[c]  (c < 4, only with use_onehot),
+ *              (emb[p, e] - mu_emb[e]) / std_emb[e]  (the next 768 channels), 1 (the last channel: the mask)      p < L
+ *              and 0 in every channel outside [0, L): the convolutions pad the NORMALISED input, mask channel included
+ *   h = relu(BN1(conv1_k3(x)));  h = relu(BN2(conv2_k3(h)));  w = sigmoid(fc2(relu(fc1(mean_p h))))
+ *   y = relu(h * w + BNs(shortcut_k1(x)));  y += proj(softmax(Q K^T / sqrt 8) V) on LN1(y), 8 heads of 8;
+ *   y += W2 gelu_erf(W1 LN2(y));  logits = final(y);  probs = sigmoid(logits)              probs / logits [n_models, L]
+ * emb: row p at emb + p * emb_row_stride, 768 floats (stride 768: the [L, 768] of rnamsm_pack_outputs; a larger stride reads rows
+ * of a wider buffer in place, e.g. row 0, columns 1..L of the final representation).  base_codes [L] as for rnamsm_ss_head.
+ * Cin = 773 with use_onehot, 769 without.  The normalisation repeats the reference's numpy arithmetic on its shipped statistics:
+ * float32 subtraction and division for the embedding, float64 (rounded once) for the one-hot columns.
+ * weights: RNAMSM_RSA_GLOBAL_WEIGHTS + RNAMSM_RSA_WEIGHTS_PER_MODEL * n_models pointers (a host array), 16-byte aligned each:
+ *   [0] mu_emb  [1] std_emb  (float [768])       [2] mu_oh  [3] std_oh  (double [4]; not read and may be null without use_onehot)
+ *   per member k, at 4 + 26k, fp32 (names of the reference's state_dict; BN folded in float64 into scale = weight / sqrt(var + 1e-5),
+ *   shift = bias - mean * scale; every matrix transposed to [in][out] so that a wave reads consecutive outputs):
+ *    +0 stem [4][800][64]: slabs 0..2 = net.0.0.conv1.weight taps, slab 3 = net.0.0.shortcut.0.weight; rows >= Cin are zero
+ *    +1 bn1 scale  +2 bn1 shift  +3 shortcut.1 scale  +4 shortcut.1 shift  [64]
+ *    +5 conv2.weight [3 taps][64 in][64 out]   +6 bn2 scale  +7 bn2 shift [64]
+ *    +8 fc1.weight [4][64]  +9 fc1.bias [4]  +10 fc2.weight [64][4]  +11 fc2.bias [64]           (squeeze-excite, as stored)
+ *    +12 net.1.0.ln1.weight  +13 ln1.bias [64]
+ *    +14 attn.{query,key,value}.weight [3][64 in][64 out]   +15 their biases [3][64]
+ *    +16 attn.proj.weight [64 in][64 out]  +17 attn.proj.bias [64]   +18 ln2.weight  +19 ln2.bias [64]
+ *    +20 mlp.0.weight [64 in][256 out]  +21 mlp.0.bias [256]  +22 mlp.2.weight [256 in][64 out]  +23 mlp.2.bias [64]
+ *    +24 final.weight [64]  +25 final.bias [1]
+ * Either of probs / logits may be null, not both.  workspace: rnamsm_rsa_head_workspace_bytes(L, n_models) bytes, 16-byte aligned,
+ * caller-owned (nothing is allocated inside); 0 for L or n_models outside their limits.
+ * Refused (RNAMSM_ERR_INVALID) before anything is launched: L outside [1, RNAMSM_RSA_MAX_L], n_models outside
+ * [1, RNAMSM_RSA_MAX_MODELS], emb_row_stride < 768, a null or misaligned pointer, a short workspace.
+ * No atomics, one fixed summation order: the same bits on every run, and member k's row does not depend on the other members. */
+#define RNAMSM_RSA_MAX_L 1024
+#define RNAMSM_RSA_MAX_MODELS 8
+#define RNAMSM_RSA_GLOBAL_WEIGHTS 4
+#define RNAMSM_RSA_WEIGHTS_PER_MODEL 26
+size_t rnamsm_rsa_head_workspace_bytes(int L, int n_models);
+int rnamsm_rsa_head(const float* emb, int64_t emb_row_stride, const uint8_t* base_codes, int L, int n_models, int use_onehot,
+                    const void* const* weights, float* probs, float* logits, void* workspace, size_t workspace_bytes,
+                    void* stream);
+
 /* a7 -- the residual add of NormalizedResidualBlock around a layer that is NOT one of this library's (modules.py:396,
  * `x = residual + x`; around the library's own layers the add is fused into the layer's last GEMM): out[i] = a[i] + b[i], fp32,
  * out may alias a or b. */

@@ -32,6 +32,16 @@ W_SS_BLOCK = ("conv1.weight", "bn1.weight", "bn1.bias", "conv2.weight", "bn2.wei
 W_SS_HEAD = ("fc1.weight", "fc1.bias")
 SS_MAX_L = 1024
 
+# index tables of rnamsm_rsa_head's weight-pointer array (include/rnamsm.h): four statistics, then 26 packed entries per member
+W_RSA_GLOBAL = ("mu_emb", "std_emb", "mu_oh", "std_oh")
+W_RSA_MODEL = ("stem", "bn1.scale", "bn1.shift", "shortcut.1.scale", "shortcut.1.shift", "conv2.weight", "bn2.scale", "bn2.shift",
+               "fc1.weight", "fc1.bias", "fc2.weight", "fc2.bias", "ln1.weight", "ln1.bias", "attn.qkv.weight", "attn.qkv.bias",
+               "attn.proj.weight", "attn.proj.bias", "ln2.weight", "ln2.bias", "mlp.0.weight", "mlp.0.bias", "mlp.2.weight",
+               "mlp.2.bias", "final.weight", "final.bias")
+RSA_MAX_L = 1024
+RSA_MAX_MODELS = 8
+RSA_CIN_PAD = 800
+
 
 class ModelDims(ctypes.Structure):
     _fields_ = [("num_layers", c_int), ("embed_dim", c_int), ("num_heads", c_int), ("ffn_dim", c_int),
@@ -93,6 +103,9 @@ _SIGNATURES = {
     "rnamsm_ss_head_workspace_bytes": (c_size_t, [c_int]),
     "rnamsm_ss_head": (c_int, [c_void_p, c_int64, c_void_p, c_int, c_int, POINTER(c_void_p), c_void_p, c_void_p, c_void_p, c_size_t,
                                c_void_p]),
+    "rnamsm_rsa_head_workspace_bytes": (c_size_t, [c_int, c_int]),
+    "rnamsm_rsa_head": (c_int, [c_void_p, c_int64, c_void_p, c_int, c_int, c_int, POINTER(c_void_p), c_void_p, c_void_p, c_void_p,
+                                c_size_t, c_void_p]),
     "rnamsm_greedy_select_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
     "rnamsm_greedy_select": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
     "rnamsm_msa_weights": (c_int, [c_void_p, c_int, c_int, c_double, c_void_p, c_void_p]),

@@ -10,6 +10,7 @@ from __future__ import annotations
 
 import os
 import queue
+import random
 import threading
 from concurrent.futures import ThreadPoolExecutor
 from pathlib import Path
@@ -18,7 +19,7 @@ from typing import Dict, List, Optional
 import numpy as np
 import torch
 
-from . import ops, sharding, ss
+from . import ops, rsa, sharding, ss
 from .alphabet import RNAAlphabet
 from .config import Config
 from .model import MSATransformer
@@ -350,6 +351,34 @@ def extract_feat(cfg: Config, model: Optional[MSATransformer] = None, gather_to_
             seq.append("".join(alphabet.all_toks[int(t)] for t in toks))
 
         return [(letters, tok_row), (lambda prob: ss.write_ss_files(prob, seq[0], rna_id, save_dir), probs)]
+    # data.rsa_model_dir: the solvent-accessibility ensemble on each alignment's device-resident embedding (rnamsm.rsa)
+    rsa_model = rsa.load_ensemble(cfg.data.rsa_model_dir, device) if getattr(cfg.data, "rsa_model_dir", "") else None
+    if rsa_model is not None:
+        rsa_lut = torch.full((len(alphabet.all_toks),), 255, dtype=torch.uint8)
+        for code, ch in enumerate("ACGU"):
+            rsa_lut[alphabet.tok_to_idx[ch]] = code
+        rsa_lut = rsa_lut.to(device)
+        rsa_rng = random.Random(2022)         # the reference program's seed; drawn from on the writer thread, in delivery order
+
+    def rsa_text_jobs(rna_id: str, values, tok_row) -> list:
+        """Writer jobs of RSA_result/<id>_*/<id>.txt: the query's tokens first (turned into its letters), then the members' RSA."""
+        seq = []
+
+        def letters(toks: np.ndarray) -> None:
+            seq.append("".join(alphabet.all_toks[int(t)] for t in toks))
+
+        return [(letters, tok_row), (lambda v: rsa.write_rsa_files(v, seq[0], rna_id, save_dir, rsa_model.model_names, rsa_rng), values)]
+
+    def head_jobs(rna_id: str, heads) -> list:
+        """heads: the tensors deliver() appended for the heads that are on -- (probabilities, tokens) of SS, then (RSA, tokens)."""
+        heads = list(heads or ())
+        jobs = []
+        if ss_model is not None and heads:
+            jobs += ss_text_jobs(rna_id, heads[0], heads[1])
+            heads = heads[2:]
+        if rsa_model is not None and heads:
+            jobs += rsa_text_jobs(rna_id, heads[0], heads[1])
+        return jobs
     rng = np.random.RandomState(42)
     mine = sharding.shard_indices(len(ids), rank, world)
     written: List[str] = []
@@ -377,8 +406,9 @@ def extract_feat(cfg: Config, model: Optional[MSATransformer] = None, gather_to_
     reader = ThreadPoolExecutor(1, thread_name_prefix="rnamsm-msa-reader") if async_io else None
 
     def emit(rna_id: str, emb: torch.Tensor, atp: torch.Tensor, after: Optional[torch.cuda.Event] = None, ss_out=None) -> None:
-        """ss_out: (probabilities [L, L], query tokens [L]) on the device when data.ss_model_path is set."""
-        extra = ss_text_jobs(rna_id, *ss_out) if ss_out is not None else []
+        """ss_out: the heads' device tensors -- (probabilities [L, L], query tokens [L]) when data.ss_model_path is set, then
+        (RSA [K, L], query tokens [L]) when data.rsa_model_dir is set."""
+        extra = head_jobs(rna_id, ss_out)
         if writer is not None:
             writer.submit([(save_dir / f"{rna_id}_atp.npy", atp), (save_dir / f"{rna_id}_emb.npy", emb)] + extra,
                           lambda r=rna_id: written.append(r), after=after)
@@ -401,7 +431,7 @@ def extract_feat(cfg: Config, model: Optional[MSATransformer] = None, gather_to_
         if label != "primary" and rank == 0:
             print(f"gather to rank 0: {label}")
     gatherer = sharding.RoundGatherer(len(ids), on_item=lambda i, ts: emit(ids[i], ts[0], ts[1], ss_out=ts[2:] or None),
-                                      tensors_per_item=2 if ss_model is None else 4,
+                                      tensors_per_item=2 + 2 * (ss_model is not None) + 2 * (rsa_model is not None),
                                       dst=0, device=device, group=gather_group) if gathering else None
     try:
         with torch.no_grad():
@@ -412,9 +442,12 @@ def extract_feat(cfg: Config, model: Optional[MSATransformer] = None, gather_to_
                 if ss_model is not None:          # the head reads atp where it lies (a packed group's slice included)
                     tok_row = toks[0, 1:]
                     ss_out = (ss_model.predict(atp, ss_lut[tok_row]), tok_row)
-                    if after is not None:         # the copies wait for the head too
-                        after = torch.cuda.Event()
-                        after.record(torch.cuda.current_stream())
+                if rsa_model is not None:         # the ensemble reads emb where it lies
+                    tok_row = toks[0, 1:]
+                    ss_out = (ss_out or ()) + (rsa_model.predict(emb, rsa_lut[tok_row]), tok_row)
+                if ss_out is not None and after is not None:         # the copies wait for the heads too
+                    after = torch.cuda.Event()
+                    after.record(torch.cuda.current_stream())
                 if gatherer is not None:
                     gatherer.submit(idx, (emb, atp) + (ss_out or ()))
                 else:

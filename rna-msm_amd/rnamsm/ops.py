@@ -582,6 +582,33 @@ def ss_head(atp: torch.Tensor, base_codes: torch.Tensor, ptrs, num_blocks: int, 
 
 
 @_on_operand_device
+def rsa_head(emb: torch.Tensor, base_codes: torch.Tensor, ptrs, n_models: int, use_onehot: bool, want: str = "probs") -> torch.Tensor:
+    """RNA-MSM RSA ensemble (rnamsm_rsa_head): emb [L, 768] fp32 (rows may lie further apart than 768 floats: a slice of the
+    final representation is read in place), base_codes uint8 [L], ptrs: the packed weight table of the n_models members
+    (rnamsm.rsa.RSAEnsemble) -> [n_models, L] fp32 RSA (want="probs") or the pre-sigmoid values (want="logits")."""
+    if want not in ("probs", "logits"):
+        raise ValueError(f"rsa_head: want must be 'probs' or 'logits', got {want!r}")
+    if not isinstance(emb, torch.Tensor) or not emb.is_cuda:
+        raise _lib.RnamsmError("rsa_head: emb: expected a tensor on the HIP device (no CPU path exists)")
+    if emb.dim() != 2 or emb.shape[1] != 768:
+        raise ValueError(f"rsa_head: emb must be [L, 768], got {tuple(emb.shape)}")
+    L = emb.shape[0]
+    if emb.stride(1) != 1 or (L > 1 and emb.stride(0) < 768) or emb.data_ptr() % 16:
+        emb = emb.contiguous()
+    if base_codes.dim() != 1 or base_codes.shape[0] != L:
+        raise ValueError(f"rsa_head: {tuple(base_codes.shape)} base codes for an embedding of L = {L}")
+    lib = _lib.load()
+    ws = torch.empty(max(lib.rnamsm_rsa_head_workspace_bytes(L, n_models), 16), dtype=torch.uint8, device=emb.device)
+    out = torch.empty(n_models, L, device=emb.device, dtype=torch.float32)
+    ptr = _dev(out, want)
+    _lib.check(lib.rnamsm_rsa_head(_dev(emb, "emb"), emb.stride(0) if L > 1 else 768,
+                                   _dev(base_codes.contiguous(), "base_codes", torch.uint8), L, n_models, 1 if use_onehot else 0, ptrs,
+                                   ptr if want == "probs" else None, ptr if want == "logits" else None, ws.data_ptr(), ws.numel(),
+                                   _stream()))
+    return out
+
+
+@_on_operand_device
 def greedy_select(msa_u8: torch.Tensor, num_seqs: int, mode: str = "max") -> torch.Tensor:
     """msa uint8 [N, L] on the device -> int32 [num_seqs] ascending row indices (utils/align.py:128-148)."""
     if mode not in ("max", "min"):

@@ -1,0 +1,347 @@
+"""RNA-MSM RSA: relative solvent accessibility from the embedding (the reference's _downstream_tasks/RSA).
+
+`RSAPredictor` carries the parameters of one of the reference's `FrameModel(Cin, 1, planes=64, depth=1)` networks under the same
+names and shapes, so a state_dict taken from an upstream model loads with strict=True; `RSAEnsemble` holds K of them and the
+normalisation statistics, and its arithmetic is one HIP entry point (rnamsm_rsa_head: all members in four launches, exact fp32)
+that reads the [L, 768] embedding where it lies on the device.  `load_ensemble` reads an upstream model directory -- its `.pt`
+files are pickled whole modules and are opened with no upstream code importable -- and `write_rsa_files` is the reference's
+host arithmetic and text format (predict.py: doSavePredict_single, per model and for the ensemble), byte for byte.
+"""
+from __future__ import annotations
+
+import ctypes
+import glob
+import os
+import pickle
+import re
+import types
+from pathlib import Path
+from typing import Dict, List, Optional, Sequence, Tuple, Union
+
+import numpy as np
+import torch
+from torch import nn
+
+from . import _lib, ops
+from .ss import base_codes
+
+EMBED_DIM = 768
+PLANES = 64
+HEADS = 8
+BN_EPS = 1e-5
+ASA_SCALE = {"A": 400, "U": 350, "C": 350, "G": 400}       # predict.py: BASES 'AUCG', asa_std
+_BASES = "AUCG"
+
+
+class _BasicBlock(nn.Module):
+    """Parameters of the reference's squeeze-excite BasicBlock (model/_0713/resnet.py)."""
+
+    def __init__(self, cin: int):
+        super().__init__()
+        self.conv1 = nn.Conv1d(cin, PLANES, 3, padding=1, bias=False)
+        self.bn1 = nn.BatchNorm1d(PLANES)
+        self.conv2 = nn.Conv1d(PLANES, PLANES, 3, padding=1, bias=False)
+        self.bn2 = nn.BatchNorm1d(PLANES)
+        self.shortcut = nn.Sequential(nn.Conv1d(cin, PLANES, 1, bias=False), nn.BatchNorm1d(PLANES))
+        self.fc1 = nn.Conv1d(PLANES, PLANES // 16, 1)
+        self.fc2 = nn.Conv1d(PLANES // 16, PLANES, 1)
+
+
+class _SelfAttention(nn.Module):
+    def __init__(self):
+        super().__init__()
+        self.key = nn.Linear(PLANES, PLANES)
+        self.query = nn.Linear(PLANES, PLANES)
+        self.value = nn.Linear(PLANES, PLANES)
+        self.proj = nn.Linear(PLANES, PLANES)
+
+
+class _Block(nn.Module):
+    """Parameters of the reference's minGPT Block (model/_0713/mingpt.py)."""
+
+    def __init__(self):
+        super().__init__()
+        self.ln1 = nn.LayerNorm(PLANES)
+        self.ln2 = nn.LayerNorm(PLANES)
+        self.attn = _SelfAttention()
+        self.mlp = nn.Sequential(nn.Linear(PLANES, 4 * PLANES), nn.GELU(), nn.Linear(4 * PLANES, PLANES), nn.Dropout(0.1))
+
+
+class RSAPredictor(nn.Module):
+    """One member: the reference's FrameModel(Cin, 1, planes=64, depth=1, norm_layer_type='BATCHNORM1D') as parameters and
+    BatchNorm running statistics (state_dict names `net.0.0.conv1.weight` ... `net.1.0.mlp.2.bias`, `final.*`).
+    Cin = 773 (one-hot + embedding + mask) or 769 (embedding + mask).  The arithmetic lives in RSAEnsemble."""
+
+    def __init__(self, cin: int = 4 + EMBED_DIM + 1):
+        super().__init__()
+        if cin not in (EMBED_DIM + 1, 4 + EMBED_DIM + 1):
+            raise ValueError(f"RSAPredictor: {cin} input channels; the network takes {4 + EMBED_DIM + 1} (one-hot + embedding + mask) "
+                             f"or {EMBED_DIM + 1} (embedding + mask)")
+        self.cin = cin
+        self.net = nn.Sequential(nn.Sequential(_BasicBlock(cin)), nn.Sequential(_Block()))
+        self.final = nn.Linear(PLANES, 1)
+
+    @property
+    def use_onehot(self) -> bool:
+        return self.cin == 4 + EMBED_DIM + 1
+
+    @classmethod
+    def from_state_dict(cls, state: Dict[str, torch.Tensor]) -> "RSAPredictor":
+        """Cin is read off net.0.0.conv1.weight; everything is loaded strictly."""
+        w = state.get("net.0.0.conv1.weight")
+        if w is None or w.dim() != 3:
+            raise _lib.RnamsmError("RSAPredictor: the state has no net.0.0.conv1.weight [64, Cin, 3]")
+        model = cls(int(w.shape[1]))
+        model.load_state_dict({k: torch.as_tensor(v) for k, v in state.items()}, strict=True)
+        return model.eval()
+
+    def packed(self) -> List[torch.Tensor]:
+        """The member's 26 table entries in the kernel layout (include/rnamsm.h): BatchNorm folded in float64 into scale / shift,
+        matrices transposed to [in][out], the stem's three conv taps and the shortcut as four zero-padded [800][64] slabs."""
+        blk, gpt = self.net[0][0], self.net[1][0]
+        dev = blk.conv1.weight.device
+
+        def f32(t: torch.Tensor) -> torch.Tensor:
+            return t.detach().to(torch.float32).contiguous().clone()
+
+        def bn(m: nn.BatchNorm1d) -> Tuple[torch.Tensor, torch.Tensor]:
+            scale = m.weight.detach().double() / torch.sqrt(m.running_var.detach().double() + m.eps)
+            shift = m.bias.detach().double() - m.running_mean.detach().double() * scale
+            return f32(scale), f32(shift)
+
+        stem = torch.zeros(4, _lib.RSA_CIN_PAD, PLANES, dtype=torch.float32, device=dev)
+        stem[:3, :self.cin] = blk.conv1.weight.detach().to(torch.float32).permute(2, 1, 0)
+        stem[3, :self.cin] = blk.shortcut[0].weight.detach().to(torch.float32)[:, :, 0].t()
+        att = gpt.attn
+        qkv_w = torch.stack([f32(m.weight).t() for m in (att.query, att.key, att.value)])
+        qkv_b = torch.stack([f32(m.bias) for m in (att.query, att.key, att.value)])
+        table = [stem, *bn(blk.bn1), *bn(blk.shortcut[1]), f32(blk.conv2.weight.permute(2, 1, 0)), *bn(blk.bn2),
+                 f32(blk.fc1.weight[:, :, 0]), f32(blk.fc1.bias), f32(blk.fc2.weight[:, :, 0]), f32(blk.fc2.bias),
+                 f32(gpt.ln1.weight), f32(gpt.ln1.bias), f32(qkv_w), f32(qkv_b), f32(att.proj.weight.t()), f32(att.proj.bias),
+                 f32(gpt.ln2.weight), f32(gpt.ln2.bias), f32(gpt.mlp[0].weight.t()), f32(gpt.mlp[0].bias),
+                 f32(gpt.mlp[2].weight.t()), f32(gpt.mlp[2].bias), f32(self.final.weight.reshape(-1)), f32(self.final.bias)]
+        assert len(table) == len(_lib.W_RSA_MODEL)
+        return table
+
+
+class RSAEnsemble(nn.Module):
+    """K RSAPredictors of one kind and their normalisation statistics; the forward is the HIP head.
+
+    predict(emb, seq) -> [K, L] RSA of every member (what predict.py hands to doSavePredict_single); logits(emb, seq) -> the
+    pre-sigmoid values.  emb: the [L, 768] fp32 embedding on the HIP device (a view whose rows lie further apart is read in
+    place); seq: the sequence (str) or its base codes (uint8 [L], rnamsm.ss.base_codes).
+    stats: {"emb": (mu, std)} and, for the one-hot kind, {"oh": (mu, std)}.  The embedding statistics are held in float32 and the
+    one-hot statistics in float64, as the reference ships them: numpy's arithmetic on them is what the kernel repeats."""
+
+    def __init__(self, members: Sequence[RSAPredictor], stats: Dict[str, Tuple[np.ndarray, np.ndarray]],
+                 names: Optional[Sequence[str]] = None):
+        super().__init__()
+        members = list(members)
+        if not 1 <= len(members) <= _lib.RSA_MAX_MODELS:
+            raise ValueError(f"RSAEnsemble: {len(members)} members; the head takes 1 to {_lib.RSA_MAX_MODELS}")
+        if len({m.cin for m in members}) != 1:
+            raise ValueError("RSAEnsemble: members of both kinds (773 and 769 input channels) in one ensemble")
+        self.members = nn.ModuleList(members)
+        self.use_onehot = members[0].use_onehot
+        self.model_names = list(names) if names is not None else [f"model_{i}" for i in range(len(members))]
+        if len(self.model_names) != len(members):
+            raise ValueError("RSAEnsemble: one name per member")
+        if "emb" not in stats or (self.use_onehot and "oh" not in stats):
+            raise _lib.RnamsmError("RSAEnsemble: statistics missing ('emb', and 'oh' for the one-hot kind)")
+        mu, std = (np.asarray(a).reshape(-1) for a in stats["emb"])
+        if mu.shape != (EMBED_DIM,) or std.shape != (EMBED_DIM,):
+            raise ValueError(f"RSAEnsemble: embedding statistics of shapes {mu.shape}, {std.shape}, expected ({EMBED_DIM},)")
+        self.register_buffer("mu_emb", torch.from_numpy(mu.astype(np.float32)))
+        self.register_buffer("std_emb", torch.from_numpy(std.astype(np.float32)))
+        if self.use_onehot:
+            mu, std = (np.asarray(a, dtype=np.float64).reshape(-1) for a in stats["oh"])
+            if mu.shape != (4,) or std.shape != (4,):
+                raise ValueError(f"RSAEnsemble: one-hot statistics of shapes {mu.shape}, {std.shape}, expected (4,)")
+            self.register_buffer("mu_oh", torch.from_numpy(mu.copy()))
+            self.register_buffer("std_oh", torch.from_numpy(std.copy()))
+        self._pack_key = None
+        self._pack = None
+
+    def __len__(self) -> int:
+        return len(self.members)
+
+    # ------------------------------------------------------------------ weight table of rnamsm_rsa_head
+    def _packed_weights(self):
+        """The weight-pointer table (statistics, then every member's packed entries), rebuilt when a parameter or buffer was
+        replaced or written in place since (its data_ptr or version counter moved) -- the SSPredictor._packed_weights rule."""
+        tensors = list(self.parameters()) + list(self.buffers())
+        key = tuple((p.data_ptr(), p._version, p.device) for p in tensors)
+        if key == self._pack_key:
+            return self._pack
+        if self.mu_emb.device.type != "cuda":
+            raise _lib.RnamsmError("RSAEnsemble must be moved to the HIP device (.to('cuda')): no CPU path exists")
+        keep: List[torch.Tensor] = [self.mu_emb.to(torch.float32).contiguous().clone(), self.std_emb.to(torch.float32).contiguous().clone()]
+        if self.use_onehot:       # (nn.Module.to(dtype) would have narrowed them with everything else: held in float64 whatever happened)
+            keep += [self.mu_oh.to(torch.float64).contiguous().clone(), self.std_oh.to(torch.float64).contiguous().clone()]
+            head = [t.data_ptr() for t in keep]
+        else:
+            head = [t.data_ptr() for t in keep] + [None, None]
+        table = []
+        for m in self.members:
+            table += m.packed()
+        keep += table
+        assert len(head) == len(_lib.W_RSA_GLOBAL)
+        ptrs = (ctypes.c_void_p * (len(head) + len(table)))(*(head + [t.data_ptr() for t in table]))
+        self._pack = (ptrs, keep)
+        self._pack_key = key
+        return self._pack
+
+    def _apply(self, fn, *args, **kwargs):
+        self._pack_key = None
+        return super()._apply(fn, *args, **kwargs)
+
+    def _run(self, emb: torch.Tensor, seq: Union[str, np.ndarray, torch.Tensor], want: str) -> torch.Tensor:
+        if not isinstance(emb, torch.Tensor) or not emb.is_cuda:
+            raise _lib.RnamsmError("RSAEnsemble: emb must be a tensor on the HIP device (no CPU path exists)")
+        if emb.dim() != 2 or emb.shape[1] != EMBED_DIM:
+            raise ValueError(f"RSAEnsemble: emb must be [L, {EMBED_DIM}], got {tuple(emb.shape)}")
+        L = emb.shape[0]
+        if not 1 <= L <= _lib.RSA_MAX_L:
+            raise ValueError(f"RSAEnsemble: L = {L} outside the head's range [1, {_lib.RSA_MAX_L}]")
+        if isinstance(seq, str):
+            seq = base_codes(seq)
+        codes = torch.as_tensor(seq).to(device=emb.device, dtype=torch.uint8).reshape(-1)
+        if codes.numel() != L:
+            raise ValueError(f"RSAEnsemble: sequence of length {codes.numel()} for an embedding of L = {L}")
+        ptrs, _ = self._packed_weights()
+        return ops.rsa_head(emb, codes, ptrs, len(self.members), self.use_onehot, want)
+
+    def predict(self, emb: torch.Tensor, seq) -> torch.Tensor:
+        return self._run(emb, seq, "probs")
+
+    def logits(self, emb: torch.Tensor, seq) -> torch.Tensor:
+        return self._run(emb, seq, "logits")
+
+    forward = predict
+
+
+# ---------------------------------------------------------------------- loading an upstream model directory
+class _Inert(nn.Module):
+    """Stand-in for an upstream module class inside a pickled whole model: it receives the pickled attributes (parameters,
+    buffers, submodules) and nothing else; no upstream code runs.  Only state_dict() is ever called on it."""
+
+
+_STANDINS = {("model._0811.model_entry", "FrameModel"), ("model._0811.model_entry", "WrapLayers"),
+             ("model._0713.resnet", "BasicBlock"), ("model._0713.mingpt", "Block"), ("model._0713.mingpt", "SelfAttention")}
+_TORCH_PREFIXES = ("torch._utils", "torch.nn.", "torch._tensor", "torch.storage", "torch.serialization")
+
+
+class _RestrictedUnpickler(pickle.Unpickler):
+    """Admits the five upstream classes (as inert stand-ins), torch's own tensor / storage / nn.Module names and
+    collections.OrderedDict; any other global is refused before it is looked up."""
+
+    def find_class(self, module: str, name: str):
+        if (module, name) in _STANDINS:
+            return _Inert
+        if (module, name) in (("collections", "OrderedDict"), ("builtins", "set"), ("__builtin__", "set")):
+            return super().find_class(module, name)
+        if module == "torch" or module.startswith(_TORCH_PREFIXES):
+            return super().find_class(module, name)
+        raise pickle.UnpicklingError(f"refused global {module}.{name}: an RSA checkpoint may name only torch / collections "
+                                     f"classes and the reference's five model classes")
+
+
+def _restricted_load(f, **kwargs):
+    return _RestrictedUnpickler(f, **kwargs).load()
+
+
+_pickle_module = types.ModuleType("rnamsm._rsa_restricted_pickle")
+_pickle_module.Unpickler = _RestrictedUnpickler
+_pickle_module.load = _restricted_load
+_pickle_module.UnpicklingError = pickle.UnpicklingError
+
+
+def load_state(path: Union[str, Path]) -> Dict[str, torch.Tensor]:
+    """One `model_pcc_*.pt`: a plain state_dict, or upstream's pickled whole FrameModel (opened with the restricted unpickler:
+    only its state is taken)."""
+    try:
+        obj = torch.load(str(path), map_location="cpu", pickle_module=_pickle_module, weights_only=False)
+    except pickle.UnpicklingError as e:
+        raise _lib.RnamsmError(f"{path}: {e}") from None
+    if isinstance(obj, nn.Module):
+        obj = obj.state_dict()
+    if not isinstance(obj, dict) or not all(isinstance(v, torch.Tensor) for v in obj.values()):
+        raise _lib.RnamsmError(f"{path}: neither a state_dict nor a pickled model")
+    return {k: v.detach() for k, v in obj.items()}
+
+
+def _load_stats(path: str) -> Tuple[np.ndarray, np.ndarray]:
+    """statistic_dict*.pickle: a dict of numpy arrays / scalars; 'mu' and 'std' are taken.  numpy's array reconstruction is all
+    the pickle may name."""
+
+    class _NumpyOnly(pickle.Unpickler):
+        def find_class(self, module: str, name: str):
+            if module.split(".")[0] == "numpy" and name in ("_reconstruct", "ndarray", "dtype", "scalar", "_frombuffer"):
+                return super().find_class(module, name)
+            raise pickle.UnpicklingError(f"refused global {module}.{name} in {path}")
+
+    with open(path, "rb") as f:
+        try:
+            d = _NumpyOnly(f).load()
+        except pickle.UnpicklingError as e:
+            raise _lib.RnamsmError(str(e)) from None
+    return np.asarray(d["mu"]), np.asarray(d["std"])
+
+
+def load_ensemble(model_dir: Union[str, Path], device) -> RSAEnsemble:
+    """An upstream model directory (models/OH+RNA-MSM_Emb or models/RNA-MSM_Emb) -> an RSAEnsemble on `device`:
+    `model_pcc_*.pt` in SORTED order (the reference takes glob's order, which the file system decides), statistics from
+    statistic_dict_oh.pickle + statistic_dict_emb.pickle, or statistic_dict.pickle (embedding only)."""
+    model_dir = str(model_dir)
+    paths = sorted(glob.glob(os.path.join(glob.escape(model_dir), "model_pcc_*.pt")))
+    if not paths:
+        raise _lib.RnamsmError(f"{model_dir}: no model_pcc_*.pt")
+    members = [RSAPredictor.from_state_dict(load_state(p)) for p in paths]
+    stats = {}
+    for key, fname in (("oh", "statistic_dict_oh.pickle"), ("emb", "statistic_dict_emb.pickle"), ("emb", "statistic_dict.pickle")):
+        p = os.path.join(model_dir, fname)
+        if os.path.isfile(p) and key not in stats:
+            stats[key] = _load_stats(p)
+    ens = RSAEnsemble(members, stats, names=[os.path.basename(p) for p in paths])
+    return ens.eval().to(device)
+
+
+# ---------------------------------------------------------------------- host arithmetic and text files (predict.py)
+def _save_single(name: str, seq: str, rsa: Optional[np.ndarray], out_dir: str, des: str, rng, asa: Optional[np.ndarray] = None):
+    """doSavePredict_single: ASA = RSA x the per-base scale in float64 (or RSA = ASA / scale when the ASA is given), one text file."""
+    os.makedirs(out_dir, exist_ok=True)
+    sequence = re.sub(r"[T]", "U", "".join(seq))
+    sequence = re.sub(r"[^AGCU]", _BASES[rng.randint(0, 3)], sequence)        # ONE draw per call, whether or not anything matches
+    scale = np.array([ASA_SCALE[c] for c in sequence])
+    if asa is None:
+        asa = np.multiply(rsa, scale).T
+    else:
+        rsa = asa / scale
+    if len(asa[asa == 0]):
+        raise _lib.RnamsmError(f"error in predict\t {name},{seq}")
+    idx = np.array([i + 1 for i in range(len(seq))])[None, :]
+    nts = np.array([c for c in seq])[None, :]
+    rows = np.vstack((np.char.mod("%d", idx), nts, np.char.mod("%.2f", asa), np.char.mod("%.3f", rsa))).T
+    np.savetxt(os.path.join(out_dir, f"{name}.txt"), rows, delimiter="\t\t", fmt="%s",
+               header=f"#{des}\n#index\t\tnt\t\tASA\t\tRSA\n", comments="")
+    return asa, rsa
+
+
+def write_rsa_files(rsa_k: np.ndarray, seq: str, name: str, output_dir: Union[str, Path], model_names: Sequence[str],
+                    rng) -> Tuple[np.ndarray, np.ndarray]:
+    """`<output_dir>/RSA_result/<name>_<i>/<name>.txt` for every member and `.../<name>_ensemble/<name>.txt`, as the reference
+    writes them (ensemble: mean of the members' ASA, RSA = ASA / scale); returns the ensemble's (ASA, RSA), float64 [L].
+    rsa_k: [K, L] float32, the members' RSA.  rng: `random` (the module, seeded 2022 by the reference's program) or a
+    random.Random: K + 1 draws are taken from it.  An ASA of exactly 0 raises RnamsmError where the reference exits."""
+    rsa_k = np.asarray(rsa_k, dtype=np.float32)
+    seq = str(seq)
+    if rsa_k.ndim != 2 or rsa_k.shape[1] != len(seq) or rsa_k.shape[0] != len(model_names):
+        raise ValueError(f"write_rsa_files: RSA of shape {rsa_k.shape} for {len(model_names)} models and a sequence of length {len(seq)}")
+    out = os.path.join(str(output_dir), "RSA_result")
+    os.makedirs(out, exist_ok=True)
+    asas = []
+    for i, model_name in enumerate(model_names):
+        asa, _ = _save_single(name, seq, rsa_k[i], os.path.join(out, f"{name}_{i}"), f"{name} predict by {model_name}\n", rng)
+        asas.append(asa)
+    mean = np.array(asas).mean(0)
+    return _save_single(name, seq, None, os.path.join(out, f"{name}_ensemble"), f"{name} predict by ensemble model\n", rng, asa=mean)

@@ -1,0 +1,178 @@
+"""fp64 truth for the RNA-MSM RSA head (rnamsm.rsa): the reference's network (_downstream_tasks/RSA: model/_0811/model_entry.py
+FrameModel, model/_0713/resnet.py BasicBlock, model/_0713/mingpt.py Block) restated in torch functional form, at any dtype.
+Test infrastructure only: tests/test_rsa_truth.py ties it to the reference's own outputs (tests/golden/rsa/); the GPU tests then
+check the HIP head against it at every size."""
+import math
+import os
+
+import numpy as np
+import torch
+import torch.nn.functional as F
+
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "rsa")
+EMB, PLANES, HEADS = 768, 64, 8
+
+
+def onehot(seq) -> np.ndarray:
+    """float64 [L, 4] over ACGU in that order; anything else (T, lowercase, N, -) is the zero vector.  seq: str or base codes."""
+    if isinstance(seq, str):
+        codes = np.array(["ACGU".find(c) if c in "ACGU" else 255 for c in seq], dtype=np.int64)
+    else:
+        codes = np.asarray(seq).astype(np.int64).reshape(-1)
+    oh = np.zeros((len(codes), 4))
+    ok = codes < 4
+    oh[np.nonzero(ok)[0], codes[ok]] = 1.0
+    return oh
+
+
+def features(emb: np.ndarray, seq, stats: dict, use_onehot: bool = True) -> np.ndarray:
+    """The reference's input [Cin, L] float32 (predict.py:131-141) in numpy's own arithmetic: the embedding is normalised in
+    the dtype of its statistics (float32 as shipped), the one-hot columns in float64, the mask is 1, all rounded to float32."""
+    emb = np.asarray(emb, dtype=np.float32)
+    cols = [(emb - stats["emb_mu"]) / stats["emb_std"], np.ones((emb.shape[0], 1))]
+    if use_onehot:
+        cols.insert(0, (onehot(seq) - stats["oh_mu"]) / stats["oh_std"])
+    return np.concatenate(cols, axis=1).T.astype(np.float32)
+
+
+def make_state(seed: int, cin: int = 773) -> dict:
+    """Random parameters and running statistics of every kind (variances in [0.5, 2], non-trivial biases and affines), float32
+    numpy under the reference's names."""
+    rng = np.random.RandomState(seed)
+    sd = {}
+
+    def mat(name, *shape):
+        sd[name] = (rng.standard_normal(shape) / np.sqrt(np.prod(shape[1:]))).astype(np.float32)
+
+    def vec(name, n, scale=0.3, centre=0.0):
+        sd[name] = (centre + scale * rng.standard_normal(n)).astype(np.float32)
+
+    def bn(name):
+        vec(name + ".weight", PLANES, centre=1.0)
+        vec(name + ".bias", PLANES)
+        vec(name + ".running_mean", PLANES)
+        sd[name + ".running_var"] = rng.uniform(0.5, 2.0, PLANES).astype(np.float32)
+        sd[name + ".num_batches_tracked"] = np.array(3, dtype=np.int64)
+
+    b = "net.0.0."
+    mat(b + "conv1.weight", PLANES, cin, 3)
+    bn(b + "bn1")
+    mat(b + "conv2.weight", PLANES, PLANES, 3)
+    bn(b + "bn2")
+    mat(b + "shortcut.0.weight", PLANES, cin, 1)
+    bn(b + "shortcut.1")
+    mat(b + "fc1.weight", PLANES // 16, PLANES, 1)
+    vec(b + "fc1.bias", PLANES // 16)
+    mat(b + "fc2.weight", PLANES, PLANES // 16, 1)
+    vec(b + "fc2.bias", PLANES)
+    g = "net.1.0."
+    for ln in ("ln1", "ln2"):
+        vec(g + ln + ".weight", PLANES, centre=1.0)
+        vec(g + ln + ".bias", PLANES)
+    for lin in ("key", "query", "value", "proj"):
+        mat(g + f"attn.{lin}.weight", PLANES, PLANES)
+        vec(g + f"attn.{lin}.bias", PLANES)
+    mat(g + "mlp.0.weight", 4 * PLANES, PLANES)
+    vec(g + "mlp.0.bias", 4 * PLANES)
+    mat(g + "mlp.2.weight", PLANES, 4 * PLANES)
+    vec(g + "mlp.2.bias", PLANES)
+    mat("final.weight", 1, PLANES)
+    vec("final.bias", 1)
+    return sd
+
+
+def logits(x: np.ndarray, state: dict, dtype=torch.float64, pad=None) -> np.ndarray:
+    """[L] pre-sigmoid output of the network on its input x [Cin, L] (features()).
+    pad: None = the reference (Conv1d pads the normalised input, mask channel included, with zeros); a [Cin] vector = a WRONG
+    network whose stem sees that column at positions -1 and L (what padding the raw embedding, or a mask of ones, would give)."""
+    sd = {k: torch.as_tensor(np.asarray(v)).to(dtype) for k, v in state.items() if not k.endswith("num_batches_tracked")}
+    col = None if pad is None else torch.as_tensor(np.asarray(pad)).to(dtype)
+    return logits_torch(torch.as_tensor(np.asarray(x)).to(dtype), sd, col).numpy()
+
+
+def logits_torch(x: torch.Tensor, sd: dict, pad=None) -> torch.Tensor:
+    """The same on tensors that already share a dtype and a device (the eager-PyTorch side of tools/rsa_head_timing.py)."""
+    x = x[None]
+    b = "net.0.0."
+
+    def bn(h, name):
+        return F.batch_norm(h, sd[name + ".running_mean"], sd[name + ".running_var"], sd[name + ".weight"], sd[name + ".bias"],
+                            training=False, eps=1e-5)
+
+    if pad is None:
+        c1 = F.conv1d(x, sd[b + "conv1.weight"], padding=1)
+    else:
+        col = pad[None, :, None]
+        c1 = F.conv1d(torch.cat([col, x, col], dim=2), sd[b + "conv1.weight"])
+    h = torch.relu(bn(c1, b + "bn1"))
+    h = torch.relu(bn(F.conv1d(h, sd[b + "conv2.weight"], padding=1), b + "bn2"))
+    w = h.mean(dim=2, keepdim=True)
+    w = torch.relu(F.conv1d(w, sd[b + "fc1.weight"], sd[b + "fc1.bias"]))
+    w = torch.sigmoid(F.conv1d(w, sd[b + "fc2.weight"], sd[b + "fc2.bias"]))
+    y = torch.relu(h * w + bn(F.conv1d(x, sd[b + "shortcut.0.weight"]), b + "shortcut.1"))
+    y = y[0].t()                                                             # [L, 64]
+    g = "net.1.0."
+    L = y.shape[0]
+    t = F.layer_norm(y, (PLANES,), sd[g + "ln1.weight"], sd[g + "ln1.bias"], eps=1e-5)
+
+    def heads(name):
+        return F.linear(t, sd[g + f"attn.{name}.weight"], sd[g + f"attn.{name}.bias"]).view(L, HEADS, PLANES // HEADS).transpose(0, 1)
+
+    q, k, v = heads("query"), heads("key"), heads("value")
+    att = torch.softmax((q @ k.transpose(-2, -1)) * (1.0 / math.sqrt(PLANES // HEADS)), dim=-1)
+    ctx = (att @ v).transpose(0, 1).contiguous().view(L, PLANES)
+    y = y + F.linear(ctx, sd[g + "attn.proj.weight"], sd[g + "attn.proj.bias"])
+    t = F.layer_norm(y, (PLANES,), sd[g + "ln2.weight"], sd[g + "ln2.bias"], eps=1e-5)
+    t = F.linear(F.gelu(F.linear(t, sd[g + "mlp.0.weight"], sd[g + "mlp.0.bias"])), sd[g + "mlp.2.weight"], sd[g + "mlp.2.bias"])
+    y = y + t
+    return F.linear(y, sd["final.weight"], sd["final.bias"])[:, 0]
+
+
+def load_state(name: str) -> dict:
+    """A fixture state (state_oh_0 ...): the arrays under the reference's names."""
+    with np.load(os.path.join(GOLDEN, name + ".npz")) as z:
+        return {k: z[k] for k in z.files if k != "__file__"}
+
+
+def load_random_state() -> dict:
+    sd = {}
+    for f in ("rsa_ref_random.npz", "rsa_ref_random_conv1.npz"):
+        with np.load(os.path.join(GOLDEN, f)) as z:
+            sd.update({k[3:]: z[k] for k in z.files if k.startswith("sd/")})
+    return sd
+
+
+def load_stats(kind: str = "oh") -> dict:
+    with np.load(os.path.join(GOLDEN, "stats.npz")) as z:
+        if kind == "oh":
+            return {k: z[k] for k in ("oh_mu", "oh_std", "emb_mu", "emb_std")}
+        return {"emb_mu": z["embonly_mu"], "emb_std": z["embonly_std"]}
+
+
+# The project's rule for heads (ss_truth.compare), with the multiples the RSA head's issue sets: rel-L2 to fp64 within
+# L2_MULT x the fp32 CPU restatement's on the same input (floor L2_FLOOR, the rule's own: one or three logits at L = 1 are single
+# rounding samples and the restatement's error can be any fraction of an ulp, 0 included); element-wise max-abs within
+# EW_MULT x the restatement's max-abs plus EW_ULPS fp32 ulps of the largest |logit|.
+# L2_MULT_SHORT: at L <= 3 the rel-L2 of a lone member is a ratio of two samples of one to three roundings, not of two
+# distributions: with make_state weights (769 channels) at L = 2 the head measured 5.8e-7 against the restatement's 2.3e-7 (ratio
+# 2.5) while its max-abs, 1.3e-6, is what both sides show at every longer L (1.1e-6 .. 1.8e-6 against 2.0e-6 .. 2.5e-6).  The
+# issue's provision for a shape that cannot meet 2 x -- at most 4 x, ratios recorded in DESIGN 3.9 -- is used for L <= 3 only.
+L2_MULT, L2_FLOOR = 2.0, 1e-7
+L2_MULT_SHORT = 4.0
+EW_MULT, EW_ULPS = 2.0, 4.0
+
+
+def compare(got, t64, t32, label: str = "", l2_mult: float = L2_MULT) -> float:
+    got, t64, t32 = (np.asarray(a, dtype=np.float64) for a in (got, t64, t32))
+    assert got.shape == t64.shape == t32.shape and np.isfinite(got).all(), label
+    norm = max(float(np.linalg.norm(t64)), 1e-30)
+    err, drift = float(np.linalg.norm(got - t64)) / norm, float(np.linalg.norm(t32 - t64)) / norm
+    d, d32 = float(np.abs(got - t64).max()), float(np.abs(t32 - t64).max())
+    ulp = float(np.spacing(np.float32(np.abs(t64).max())))
+    ew_bar = EW_MULT * d32 + EW_ULPS * ulp
+    msg = (f"{label}: rel-L2 {err:.2e} (fp32 restatement {drift:.2e}, ratio {err / max(drift, 1e-30):.2f}), max-abs {d:.2e} "
+           f"(restatement {d32:.2e}, bar {ew_bar:.2e}, ratio to restatement {d / max(d32, 1e-30):.2f})")
+    print(msg)
+    assert err <= l2_mult * max(drift, L2_FLOOR), msg
+    assert d <= ew_bar, msg
+    return d
