@@ -367,6 +367,37 @@ int rnamsm_ss_head(const float* atp, int64_t atp_plane_stride, const uint8_t* ba
                    const float* const* weights, float* logits, float* probs, void* workspace, size_t workspace_bytes,
                    void* stream);
 
+/* f4, several structures per launch -- rnamsm_ss_head over B structures of unlike length in ONE set of launches (stem,
+ * num_blocks x (3x3 + 5x5), output pass).  Every launch covers sum_b ceil(L_b / 16)^2 blocks -- each member's own tiles,
+ * never B x the largest member's -- and a block finds its member in a device descriptor table.  A tile's arithmetic is the lone
+ * call's (the same device functions on the member's own image and L), so every member's logits / probs are BIT-IDENTICAL to
+ * rnamsm_ss_head on that member alone, whatever its company and its place in the batch.
+ * items: a HOST array of B entries, read during the call and free to go afterwards (the descriptors travel as kernel
+ * arguments on `stream`).  Per member: atp / atp_plane_stride / base_codes / L / logits / probs as for rnamsm_ss_head; the
+ * members' maps may be slices of one buffer (the atp of rnamsm_forward_packed), their outputs must not overlap.
+ * weights, num_blocks: exactly those of rnamsm_ss_head.
+ * workspace: rnamsm_ss_head_packed_workspace_bytes(B, Ls) bytes, 16-byte aligned, caller-owned (nothing is allocated inside):
+ * the descriptor table (64 bytes per member, rounded up to 256), then the two NHWC [sum L_b^2, 48] fp32 images; member b's
+ * image starts at pixel sum_{a<b} L_a^2.  The size is 0 for B outside [1, RNAMSM_SS_MAX_BATCH], a null Ls or an L outside
+ * [1, RNAMSM_SS_MAX_L].
+ * Refused (RNAMSM_ERR_INVALID) before anything is enqueued, rnamsm_last_error naming the member where one is at fault: B or
+ * num_blocks out of range, a member's L out of range, a null pointer (items, weights, workspace, a member's atp or
+ * base_codes, a weight), a member with neither logits nor probs, a float pointer that is not 4-byte aligned, a weight pointer
+ * or workspace that is not 16-byte aligned, atp_plane_stride < L*L, a short workspace.
+ * No atomics: the same inputs give the same bits on every run. */
+typedef struct {                 /* one structure of the batch */
+    const float*   atp;          /* device: plane p at atp + p * atp_plane_stride, rows of L floats */
+    int64_t        atp_plane_stride;   /* >= L*L */
+    const uint8_t* base_codes;   /* device, [L] */
+    int32_t        L;            /* 1 .. RNAMSM_SS_MAX_L */
+    float*         logits;       /* device [L, L] or null */
+    float*         probs;        /* device [L, L] or null; not both null */
+} rnamsm_ss_item;
+#define RNAMSM_SS_MAX_BATCH 1024
+size_t rnamsm_ss_head_packed_workspace_bytes(int B, const int* Ls);
+int rnamsm_ss_head_packed(const rnamsm_ss_item* items, int B, int num_blocks, const float* const* weights,
+                          void* workspace, size_t workspace_bytes, void* stream);
+
 /* f5 -- RNA-MSM RSA (relative solvent accessibility) predictor (_downstream_tasks/RSA: predict.py, model/_0811/model_entry.py
  * FrameModel(Cin, 1, planes 64, depth 1, BatchNorm1d)) for an ensemble of n_models members in one set of four launches, exact fp32:
  *   x[c, p]  = (onehot(code[p])[c] - mu_oh[c]) / std_oh[c]  (c < 4, only with use_onehot),

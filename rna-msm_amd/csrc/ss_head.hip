@@ -146,12 +146,11 @@ __device__ __forceinline__ void store_tile(const f32x4 (&acc)[2][3], const float
 // Stem: 3x3, 128 -> 48 with bias.  The input planes are built while staging: one-hot channels from the base codes
 // (0..3 = A, C, G, U; any other value = the all-zero vector of OneHotEncoder(handle_unknown='ignore')), the 120 maps read
 // in place from atp (plane c - 8 at c_plane_stride * (c - 8), rows of L floats).  Four chunks of 32 channels.
-__global__ __launch_bounds__(SS_THREADS) void ss_stem_kernel(const float* __restrict__ atp, int64_t plane_stride,
-                                                             const uint8_t* __restrict__ codes, const float* __restrict__ w,
-                                                             const float* __restrict__ bias, float* __restrict__ out, int L) {
-    extern __shared__ f32x4 ss_smem[];
-    float* S = reinterpret_cast<float*>(ss_smem);
-    const int y0 = blockIdx.y * SS_TILE, x0 = blockIdx.x * SS_TILE;
+// The body is shared by the lone kernel (tile from blockIdx, one image) and the packed one (tile and image from a descriptor):
+// one arithmetic, so a structure's bits do not depend on which of the two ran it.
+__device__ __forceinline__ void ss_stem_body(float* S, const float* __restrict__ atp, int64_t plane_stride,
+                                             const uint8_t* __restrict__ codes, const float* __restrict__ w,
+                                             const float* __restrict__ bias, float* __restrict__ out, int L, int y0, int x0) {
     constexpr int NPIX = SS_STEM_SW * SS_STEM_SW;
     f32x4 acc[2][3];
     zero_acc16(acc);
@@ -175,16 +174,22 @@ __global__ __launch_bounds__(SS_THREADS) void ss_stem_kernel(const float* __rest
     }
     store_tile<false>(acc, bias, out, y0, x0, L);
 }
+__global__ __launch_bounds__(SS_THREADS) void ss_stem_kernel(const float* __restrict__ atp, int64_t plane_stride,
+                                                             const uint8_t* __restrict__ codes, const float* __restrict__ w,
+                                                             const float* __restrict__ bias, float* __restrict__ out, int L) {
+    extern __shared__ f32x4 ss_smem[];
+    ss_stem_body(reinterpret_cast<float*>(ss_smem), atp, plane_stride, codes, w, bias, out, L, blockIdx.y * SS_TILE,
+                 blockIdx.x * SS_TILE);
+}
 
 // Trunk conv: out (+)= conv_KS(relu(LN(x))), 48 -> 48, no bias.  RESIDUAL: out is the residual stream, updated in place.
+// The bounds tests are those of the IMAGE (iy < L), never of the buffer it lies in: in a packed batch the rows before and after
+// an image are its neighbours' pixels, and a halo read there must give the zero padding all the same.
 template <int KS, bool RESIDUAL>
-__global__ __launch_bounds__(SS_THREADS) void ss_conv_kernel(const float* __restrict__ x, const float* __restrict__ gamma,
-                                                             const float* __restrict__ beta, const float* __restrict__ w,
-                                                             float* out, int L) {
-    extern __shared__ f32x4 ss_smem[];
-    float* S = reinterpret_cast<float*>(ss_smem);
+__device__ __forceinline__ void ss_conv_body(float* S, const float* __restrict__ x, const float* __restrict__ gamma,
+                                             const float* __restrict__ beta, const float* __restrict__ w, float* out, int L,
+                                             int y0, int x0) {
     constexpr int P = KS / 2, SW = SS_TILE + 2 * P;
-    const int y0 = blockIdx.y * SS_TILE, x0 = blockIdx.x * SS_TILE;
     for (int p = threadIdx.x; p < SW * SW; p += SS_THREADS) {
         const int sy = p / SW, sx = p - sy * SW, iy = y0 - P + sy, ix = x0 - P + sx;
         f32x4* dst = reinterpret_cast<f32x4*>(S + p * SS_LDC);
@@ -207,15 +212,22 @@ __global__ __launch_bounds__(SS_THREADS) void ss_conv_kernel(const float* __rest
     window_mma<KS, 3>(S, SW, SS_LDC, w, SS_CH, 0, acc);
     store_tile<RESIDUAL>(acc, nullptr, out, y0, x0, L);
 }
+template <int KS, bool RESIDUAL>
+__global__ __launch_bounds__(SS_THREADS) void ss_conv_kernel(const float* __restrict__ x, const float* __restrict__ gamma,
+                                                             const float* __restrict__ beta, const float* __restrict__ w,
+                                                             float* out, int L) {
+    extern __shared__ f32x4 ss_smem[];
+    ss_conv_body<KS, RESIDUAL>(reinterpret_cast<float*>(ss_smem), x, gamma, beta, w, out, L, blockIdx.y * SS_TILE,
+                               blockIdx.x * SS_TILE);
+}
 
 // Head: logits = fc1(relu(LN(x))) (fc1: Linear(48, 1)), probs = sigmoid(logits); one thread per pixel.
-__global__ __launch_bounds__(256) void ss_out_kernel(const float* __restrict__ x, const float* __restrict__ gamma,
-                                                     const float* __restrict__ beta, const float* __restrict__ fw,
-                                                     const float* __restrict__ fb, float* __restrict__ logits,
-                                                     float* __restrict__ probs, int64_t n) {
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= n) return;
-    const f32x4* src = reinterpret_cast<const f32x4*>(x + i * SS_CH);
+// pixel: the 48 channels of the pixel; i: its index inside its own [L, L] outputs
+__device__ __forceinline__ void ss_out_body(const float* __restrict__ pixel, const float* __restrict__ gamma,
+                                            const float* __restrict__ beta, const float* __restrict__ fw,
+                                            const float* __restrict__ fb, float* __restrict__ logits, float* __restrict__ probs,
+                                            int64_t i) {
+    const f32x4* src = reinterpret_cast<const f32x4*>(pixel);
     f32x4 v[12];
 #pragma unroll
     for (int k = 0; k < 12; ++k) v[k] = src[k];
@@ -229,6 +241,93 @@ __global__ __launch_bounds__(256) void ss_out_kernel(const float* __restrict__ x
     if (logits) logits[i] = z;
     if (probs) probs[i] = 1.f / (1.f + expf(-z));
 }
+__global__ __launch_bounds__(256) void ss_out_kernel(const float* __restrict__ x, const float* __restrict__ gamma,
+                                                     const float* __restrict__ beta, const float* __restrict__ fw,
+                                                     const float* __restrict__ fb, float* __restrict__ logits,
+                                                     float* __restrict__ probs, int64_t n) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    ss_out_body(x + i * SS_CH, gamma, beta, fw, fb, logits, probs, i);
+}
+
+// ---- several structures per launch (rnamsm_ss_head_packed) ---------------------------------------------------------------------
+// The images of a batch lie back to back in the two workspace images (member b's first pixel is pixel pix0 of the buffer); a
+// launch has the SUM of the members' tiles as a flat grid, and a block finds its member by a binary search over the tile prefix
+// sums of this descriptor table (B <= 1024: at most ten wave-uniform loads of a table that stays in L2).  From there on it runs
+// the lone kernel's body on the member's own (image, L, tile): the same bits.
+struct SsMember {            // 64 bytes
+    const float* atp;
+    int64_t plane_stride;
+    const uint8_t* codes;
+    float* logits;
+    float* probs;
+    int64_t pix0;            // pixels of the members before it
+    int32_t L, tiles;        // tiles = ceil(L / 16): its launches' share is tiles x tiles blocks
+    int32_t tile0;           // blocks of the members before it
+    int32_t pad_;
+};
+static_assert(sizeof(SsMember) == 64, "SsMember layout");
+
+__device__ __forceinline__ int ss_member_of_tile(const SsMember* __restrict__ mem, int B, int tile) {
+    int lo = 0, hi = B;      // mem[lo].tile0 <= tile < mem[hi].tile0 (mem[B].tile0 = the grid)
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (mem[mid].tile0 <= tile) lo = mid;
+        else hi = mid;
+    }
+    return lo;
+}
+__device__ __forceinline__ int ss_member_of_pixel(const SsMember* __restrict__ mem, int B, int64_t pixel) {
+    int lo = 0, hi = B;
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (mem[mid].pix0 <= pixel) lo = mid;
+        else hi = mid;
+    }
+    return lo;
+}
+
+__global__ __launch_bounds__(SS_THREADS) void ss_stem_packed_kernel(const SsMember* __restrict__ mem, int B,
+                                                                    const float* __restrict__ w, const float* __restrict__ bias,
+                                                                    float* __restrict__ out) {
+    extern __shared__ f32x4 ss_smem[];
+    const SsMember m = mem[ss_member_of_tile(mem, B, (int)blockIdx.x)];
+    const int t = (int)blockIdx.x - m.tile0, ty = t / m.tiles, tx = t - ty * m.tiles;
+    ss_stem_body(reinterpret_cast<float*>(ss_smem), m.atp, m.plane_stride, m.codes, w, bias, out + (size_t)m.pix0 * SS_CH, m.L,
+                 ty * SS_TILE, tx * SS_TILE);
+}
+
+template <int KS, bool RESIDUAL>
+__global__ __launch_bounds__(SS_THREADS) void ss_conv_packed_kernel(const SsMember* __restrict__ mem, int B,
+                                                                    const float* __restrict__ x, const float* __restrict__ gamma,
+                                                                    const float* __restrict__ beta, const float* __restrict__ w,
+                                                                    float* out) {
+    extern __shared__ f32x4 ss_smem[];
+    const SsMember* m = mem + ss_member_of_tile(mem, B, (int)blockIdx.x);
+    const int L = m->L, tiles = m->tiles, t = (int)blockIdx.x - m->tile0, ty = t / tiles, tx = t - ty * tiles;
+    const size_t off = (size_t)m->pix0 * SS_CH;
+    ss_conv_body<KS, RESIDUAL>(reinterpret_cast<float*>(ss_smem), x + off, gamma, beta, w, out + off, L, ty * SS_TILE,
+                               tx * SS_TILE);
+}
+
+__global__ __launch_bounds__(256) void ss_out_packed_kernel(const SsMember* __restrict__ mem, int B, const float* __restrict__ x,
+                                                            const float* __restrict__ gamma, const float* __restrict__ beta,
+                                                            const float* __restrict__ fw, const float* __restrict__ fb,
+                                                            int64_t n) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const SsMember* m = mem + ss_member_of_pixel(mem, B, i);
+    ss_out_body(x + i * SS_CH, gamma, beta, fw, fb, m->logits, m->probs, i - m->pix0);
+}
+
+// The descriptors travel as kernel arguments, 32 (2 KB) per launch, on the caller's stream: no host buffer has to outlive the call
+// (packed_descriptors_upload does the same for PackedMsa).
+struct SsMemberChunk { SsMember m[32]; };
+__global__ void ss_members_kernel(SsMemberChunk chunk, int n, SsMember* __restrict__ dev) {
+    if ((int)threadIdx.x < n) dev[threadIdx.x] = chunk.m[threadIdx.x];
+}
+
+constexpr size_t ss_members_bytes(int B) { return ((size_t)B * sizeof(SsMember) + 255) & ~(size_t)255; }
 
 template <class K>
 int allow_lds(K kernel, size_t bytes, DeviceOnce& once) {
@@ -295,5 +394,100 @@ extern "C" int rnamsm_ss_head(const float* atp, int64_t atp_plane_stride, const 
     hipLaunchKernelGGL(ss_out_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, xs, weights[2], weights[3], hw[0], hw[1],
                        logits, probs, n);
     RNAMSM_CHECK_LAUNCH("ss_out");
+    return RNAMSM_OK;
+}
+
+extern "C" size_t rnamsm_ss_head_packed_workspace_bytes(int B, const int* Ls) {
+    if (B < 1 || B > RNAMSM_SS_MAX_BATCH || !Ls) return 0;
+    size_t pixels = 0;
+    for (int b = 0; b < B; ++b) {
+        if (Ls[b] < 1 || Ls[b] > RNAMSM_SS_MAX_L) return 0;
+        pixels += (size_t)Ls[b] * Ls[b];
+    }
+    return ss_members_bytes(B) + 2 * pixels * SS_CH * sizeof(float);
+}
+
+extern "C" int rnamsm_ss_head_packed(const rnamsm_ss_item* items, int B, int num_blocks, const float* const* weights, void* workspace,
+                                     size_t workspace_bytes, void* stream) {
+    // every refusal comes before the first launch: a refused call leaves the stream and the outputs untouched
+    RNAMSM_CHECK_ARG(items && weights && workspace, "ss_head_packed: null pointer");
+    RNAMSM_CHECK_ARG(B >= 1 && B <= RNAMSM_SS_MAX_BATCH, "ss_head_packed: B=%d outside [1, %d]", B, RNAMSM_SS_MAX_BATCH);
+    RNAMSM_CHECK_ARG(num_blocks >= 1 && num_blocks <= RNAMSM_SS_MAX_BLOCKS, "ss_head_packed: num_blocks=%d outside [1, %d]", num_blocks,
+                     RNAMSM_SS_MAX_BLOCKS);
+    int64_t pixels = 0, tiles_total = 0;
+    for (int b = 0; b < B; ++b) {
+        const rnamsm_ss_item& it = items[b];
+        RNAMSM_CHECK_ARG(it.L >= 1 && it.L <= RNAMSM_SS_MAX_L, "ss_head_packed: member %d: L=%d outside [1, %d]", b, it.L, RNAMSM_SS_MAX_L);
+        RNAMSM_CHECK_ARG(it.atp && it.base_codes, "ss_head_packed: member %d: null pointer", b);
+        RNAMSM_CHECK_ARG(it.logits || it.probs, "ss_head_packed: member %d: neither logits nor probs given", b);
+        RNAMSM_CHECK_ARG(((uintptr_t)it.atp & 3u) == 0 && ((uintptr_t)it.logits & 3u) == 0 && ((uintptr_t)it.probs & 3u) == 0,
+                         "ss_head_packed: member %d: a float pointer is not 4-byte aligned", b);
+        RNAMSM_CHECK_ARG(it.atp_plane_stride >= (int64_t)it.L * it.L, "ss_head_packed: member %d: atp plane stride %lld < L*L", b,
+                         (long long)it.atp_plane_stride);
+        const int64_t t = (it.L + SS_TILE - 1) / SS_TILE;
+        pixels += (int64_t)it.L * it.L;
+        tiles_total += t * t;
+    }
+    RNAMSM_CHECK_ARG(aligned16(workspace), "ss_head_packed: 16-byte alignment of the workspace");
+    RNAMSM_CHECK_ARG(workspace_bytes >= ss_members_bytes(B) + 2 * (size_t)pixels * SS_CH * sizeof(float),
+                     "ss_head_packed: workspace too small");
+    const int nw = RNAMSM_SS_GLOBAL_WEIGHTS + RNAMSM_SS_WEIGHTS_PER_BLOCK * num_blocks;
+    for (int i = 0; i < nw; ++i) {
+        RNAMSM_CHECK_ARG(weights[i], "ss_head_packed: weight pointer %d is null", i);
+        RNAMSM_CHECK_ARG(aligned16(weights[i]), "ss_head_packed: weight pointer %d is not 16-byte aligned", i);
+    }
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    SsMember* mem = static_cast<SsMember*>(workspace);
+    float* xs = reinterpret_cast<float*>(static_cast<char*>(workspace) + ss_members_bytes(B));
+    float* ts = xs + (size_t)pixels * SS_CH;
+    static DeviceOnce once_stem, once3, once5;
+    int rc;
+    if ((rc = allow_lds(ss_stem_packed_kernel, SS_STEM_LDS_BYTES, once_stem)) != RNAMSM_OK) return rc;
+    if ((rc = allow_lds(ss_conv_packed_kernel<3, false>, ss_trunk_lds_bytes(3), once3)) != RNAMSM_OK) return rc;
+    if ((rc = allow_lds(ss_conv_packed_kernel<5, true>, ss_trunk_lds_bytes(5), once5)) != RNAMSM_OK) return rc;
+    int64_t pix0 = 0;
+    int32_t tile0 = 0;
+    for (int b0 = 0; b0 < B; b0 += 32) {
+        SsMemberChunk chunk;
+        const int n = B - b0 < 32 ? B - b0 : 32;
+        for (int i = 0; i < 32; ++i) {
+            SsMember& m = chunk.m[i];
+            if (i >= n) {
+                m = chunk.m[0];
+                continue;
+            }
+            const rnamsm_ss_item& it = items[b0 + i];
+            m.atp = it.atp;
+            m.plane_stride = it.atp_plane_stride;
+            m.codes = it.base_codes;
+            m.logits = it.logits;
+            m.probs = it.probs;
+            m.pix0 = pix0;
+            m.L = it.L;
+            m.tiles = (it.L + SS_TILE - 1) / SS_TILE;
+            m.tile0 = tile0;
+            m.pad_ = 0;
+            pix0 += (int64_t)it.L * it.L;
+            tile0 += m.tiles * m.tiles;
+        }
+        hipLaunchKernelGGL(ss_members_kernel, dim3(1), dim3(32), 0, s, chunk, n, mem + b0);
+        RNAMSM_CHECK_LAUNCH("ss_members");
+    }
+    const dim3 grid((unsigned)tiles_total);          // the members' own tiles, nothing for a small member beside a large one
+    hipLaunchKernelGGL(ss_stem_packed_kernel, grid, dim3(SS_THREADS), SS_STEM_LDS_BYTES, s, mem, B, weights[0], weights[1], xs);
+    RNAMSM_CHECK_LAUNCH("ss_stem (packed)");
+    for (int k = 0; k < num_blocks; ++k) {
+        const float* const* bw = weights + 4 + RNAMSM_SS_WEIGHTS_PER_BLOCK * k;
+        hipLaunchKernelGGL((ss_conv_packed_kernel<3, false>), grid, dim3(SS_THREADS), ss_trunk_lds_bytes(3), s, mem, B, xs, bw[1], bw[2],
+                           bw[0], ts);
+        RNAMSM_CHECK_LAUNCH("ss_conv3x3 (packed)");
+        hipLaunchKernelGGL((ss_conv_packed_kernel<5, true>), grid, dim3(SS_THREADS), ss_trunk_lds_bytes(5), s, mem, B, ts, bw[4], bw[5],
+                           bw[3], xs);
+        RNAMSM_CHECK_LAUNCH("ss_conv5x5 (packed)");
+    }
+    const float* const* hw = weights + 4 + RNAMSM_SS_WEIGHTS_PER_BLOCK * num_blocks;
+    hipLaunchKernelGGL(ss_out_packed_kernel, dim3((unsigned)((pixels + 255) / 256)), dim3(256), 0, s, mem, B, xs, weights[2], weights[3],
+                       hw[0], hw[1], pixels);
+    RNAMSM_CHECK_LAUNCH("ss_out (packed)");
     return RNAMSM_OK;
 }

@@ -31,6 +31,7 @@ W_SS_STEM = ("conv1.weight", "conv1.bias", "bn1.weight", "bn1.bias")
 W_SS_BLOCK = ("conv1.weight", "bn1.weight", "bn1.bias", "conv2.weight", "bn2.weight", "bn2.bias")
 W_SS_HEAD = ("fc1.weight", "fc1.bias")
 SS_MAX_L = 1024
+SS_MAX_BATCH = 1024
 
 # index tables of rnamsm_rsa_head's weight-pointer array (include/rnamsm.h): four statistics, then 26 packed entries per member
 W_RSA_GLOBAL = ("mu_emb", "std_emb", "mu_oh", "std_oh")
@@ -47,6 +48,12 @@ class ModelDims(ctypes.Structure):
     _fields_ = [("num_layers", c_int), ("embed_dim", c_int), ("num_heads", c_int), ("ffn_dim", c_int),
                 ("vocab", c_int), ("num_positions", c_int), ("pad_idx", c_int), ("ln_eps", c_float),
                 ("row_pos_dim", c_int)]          # 0 / 1: scalar per alignment row; embed_dim: the msm/ variant's per-channel rows
+
+
+class SsItem(ctypes.Structure):
+    """rnamsm_ss_item: one structure of an rnamsm_ss_head_packed batch (device pointers as integers)."""
+    _fields_ = [("atp", c_void_p), ("atp_plane_stride", c_int64), ("base_codes", c_void_p), ("L", ctypes.c_int32),
+                ("logits", c_void_p), ("probs", c_void_p)]
 
 
 _SIGNATURES = {
@@ -103,6 +110,8 @@ _SIGNATURES = {
     "rnamsm_ss_head_workspace_bytes": (c_size_t, [c_int]),
     "rnamsm_ss_head": (c_int, [c_void_p, c_int64, c_void_p, c_int, c_int, POINTER(c_void_p), c_void_p, c_void_p, c_void_p, c_size_t,
                                c_void_p]),
+    "rnamsm_ss_head_packed_workspace_bytes": (c_size_t, [c_int, POINTER(c_int)]),
+    "rnamsm_ss_head_packed": (c_int, [POINTER(SsItem), c_int, c_int, POINTER(c_void_p), c_void_p, c_size_t, c_void_p]),
     "rnamsm_rsa_head_workspace_bytes": (c_size_t, [c_int, c_int]),
     "rnamsm_rsa_head": (c_int, [c_void_p, c_int64, c_void_p, c_int, c_int, c_int, POINTER(c_void_p), c_void_p, c_void_p, c_void_p,
                                 c_size_t, c_void_p]),

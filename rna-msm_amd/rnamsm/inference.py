@@ -437,11 +437,13 @@ def extract_feat(cfg: Config, model: Optional[MSATransformer] = None, gather_to_
         with torch.no_grad():
             pending = reader.submit(read, mine[0]) if reader and len(mine) else None
             def deliver(idx: int, emb: torch.Tensor, atp: torch.Tensor, after: Optional[torch.cuda.Event] = None,
-                        toks: Optional[torch.Tensor] = None) -> None:
+                        toks: Optional[torch.Tensor] = None, ss_probs: Optional[torch.Tensor] = None) -> None:
+                """ss_probs: this alignment's base-pair probabilities where its group's batched head (ss_group) has already computed
+                them; absent, the lone head runs here."""
                 ss_out = None
                 if ss_model is not None:          # the head reads atp where it lies (a packed group's slice included)
                     tok_row = toks[0, 1:]
-                    ss_out = (ss_model.predict(atp, ss_lut[tok_row]), tok_row)
+                    ss_out = (ss_probs if ss_probs is not None else ss_model.predict(atp, ss_lut[tok_row]), tok_row)
                 if rsa_model is not None:         # the ensemble reads emb where it lies
                     tok_row = toks[0, 1:]
                     ss_out = (ss_out or ()) + (rsa_model.predict(emb, rsa_lut[tok_row]), tok_row)
@@ -452,6 +454,22 @@ def extract_feat(cfg: Config, model: Optional[MSATransformer] = None, gather_to_
                     gatherer.submit(idx, (emb, atp) + (ss_out or ()))
                 else:
                     emit(ids[idx], emb, atp, after, ss_out)
+
+            def ss_group(atps: List[torch.Tensor], toks_: List[torch.Tensor]) -> List[Optional[torch.Tensor]]:
+                """The SS head of a whole group in one launch set (SSPredictor.predict_many: every launch covers all the members'
+                tiles, each member's probabilities are the lone head's bits); a list of None when the head is off."""
+                if ss_model is None:
+                    return [None] * len(atps)
+                return ss_model.predict_many(atps, [ss_lut[t[0, 1:]] for t in toks_])
+
+            def deliver_group(members_, outs, ev: Optional[torch.cuda.Event] = None) -> None:
+                embs, atps = [o["emb"].contiguous() for o in outs], [o["atp"].contiguous() for o in outs]
+                probs = ss_group(atps, [t for _, t in members_])
+                if ss_model is not None and ev is not None:           # the copies wait for the batched head too
+                    ev = torch.cuda.Event()
+                    ev.record(torch.cuda.current_stream())
+                for (i, t), emb, atp, p in zip(members_, embs, atps, probs):
+                    deliver(i, emb, atp, ev, t, ss_probs=p)
 
             # data.batch_small_msas: small alignments go through ONE launch set per group (forward_ragged: padded into one
             # frame, every MSA scaled by its own depth); a lone forward of a few hundred tokens costs 5.5 ms on a mostly
@@ -486,8 +504,7 @@ def extract_feat(cfg: Config, model: Optional[MSATransformer] = None, gather_to_
                     outs, ev = [alone(i, t) for i, t in members_], None
                 if not all(o["emb"].is_contiguous() and o["atp"].is_contiguous() for o in outs):
                     ev = None                                     # .contiguous() below would launch copies on the compute stream
-                for (i, t), out in zip(members_, outs):
-                    deliver(i, out["emb"].contiguous(), out["atp"].contiguous(), ev, t)
+                deliver_group(members_, outs, ev)
 
             def finish_one(entry) -> None:
                 """Second half of a pipelined lone forward (the one-by-one loop of alignments too large to wait for company)."""
@@ -561,15 +578,13 @@ def extract_feat(cfg: Config, model: Optional[MSATransformer] = None, gather_to_
             def flush() -> None:
                 if len(group) == 1:
                     idx0, t0 = group[0]
-                    out = alone(idx0, t0)
-                    deliver(idx0, out["emb"].contiguous(), out["atp"].contiguous(), toks=t0)
+                    deliver_group(group, [alone(idx0, t0)])
                 elif group:
                     try:
                         outs = model.forward_ragged([t for _, t in group], packed=packing)
                     except IndexError:                                # name the offending alignment: one by one
                         outs = [alone(i, t) for i, t in group]
-                    for (i, t), out in zip(group, outs):
-                        deliver(i, out["emb"].contiguous(), out["atp"].contiguous(), toks=t)
+                    deliver_group(group, outs)
                 group.clear()
 
             def read_and_run() -> None:

@@ -8,7 +8,7 @@ from __future__ import annotations
 
 import functools
 import math
-from typing import Optional, Tuple
+from typing import List, Optional, Sequence, Tuple
 
 import torch
 
@@ -579,6 +579,56 @@ def ss_head(atp: torch.Tensor, base_codes: torch.Tensor, ptrs, num_blocks: int, 
                                   num_blocks, ptrs, ptr if want == "logits" else None, ptr if want == "probs" else None,
                                   ws.data_ptr(), ws.numel(), _stream()))
     return out
+
+
+@_on_operand_device
+def ss_head_packed(atps: Sequence[torch.Tensor], codes: Sequence[torch.Tensor], ptrs, num_blocks: int,
+                   want: str = "probs") -> List[torch.Tensor]:
+    """RNA-MSM-SS head over several structures in one set of launches (rnamsm_ss_head_packed): atps[b] [120, L_b, L_b] fp32,
+    codes[b] uint8 [L_b], the operand rules of ss_head per member (slices of one wider buffer are read in place) -> a list of
+    [L_b, L_b] tensors, each bit-identical to ss_head on that member alone.  One workspace and one output allocation per call:
+    the returned tensors are views of one buffer."""
+    if want not in ("probs", "logits"):
+        raise ValueError(f"ss_head_packed: want must be 'probs' or 'logits', got {want!r}")
+    atps, codes = list(atps), list(codes)
+    if len(atps) != len(codes):
+        raise ValueError(f"ss_head_packed: {len(atps)} maps for {len(codes)} base-code rows")
+    if not atps:
+        return []
+    B = len(atps)
+    if B > _lib.SS_MAX_BATCH:
+        raise ValueError(f"ss_head_packed: {B} structures exceed the limit of {_lib.SS_MAX_BATCH} per call")
+    device = atps[0].device if isinstance(atps[0], torch.Tensor) else None
+    for b in range(B):
+        atp, bc = atps[b], codes[b]
+        _dev(atp, f"atp[{b}]")
+        if atp.dim() != 3 or atp.shape[0] != 120 or atp.shape[1] != atp.shape[2]:
+            raise ValueError(f"ss_head_packed: atp[{b}] must be [120, L, L], got {tuple(atp.shape)}")
+        if atp.device != device:
+            raise ValueError(f"ss_head_packed: atp[{b}] lies on {atp.device}, atp[0] on {device}")
+        L = atp.shape[-1]
+        if not 1 <= L <= _lib.SS_MAX_L:
+            raise ValueError(f"ss_head_packed: atp[{b}]: L = {L} outside [1, {_lib.SS_MAX_L}]")
+        if atp.stride(2) != 1 or atp.stride(1) != L or atp.stride(0) < L * L:
+            atps[b] = atp.contiguous()
+        _dev(bc, f"base_codes[{b}]", torch.uint8)
+        if bc.dim() != 1 or bc.shape[0] != L:
+            raise ValueError(f"ss_head_packed: {bc.shape[0] if bc.dim() == 1 else tuple(bc.shape)} base codes for atp[{b}] of L = {L}")
+        codes[b] = bc.contiguous()
+    lib = _lib.load()
+    Ls = [int(a.shape[-1]) for a in atps]
+    ws = torch.empty(lib.rnamsm_ss_head_packed_workspace_bytes(B, (_lib.c_int * B)(*Ls)), dtype=torch.uint8, device=device)
+    out = torch.empty(sum(L * L for L in Ls), device=device, dtype=torch.float32)
+    items = (_lib.SsItem * B)()
+    outs, off = [], 0
+    for b, L in enumerate(Ls):
+        o = out[off:off + L * L].view(L, L)
+        off += L * L
+        outs.append(o)
+        items[b] = _lib.SsItem(atps[b].data_ptr(), atps[b].stride(0), codes[b].data_ptr(), L, o.data_ptr() if want == "logits" else None,
+                               o.data_ptr() if want == "probs" else None)
+    _lib.check(lib.rnamsm_ss_head_packed(items, B, num_blocks, ptrs, ws.data_ptr(), ws.numel(), _stream()))
+    return outs
 
 
 @_on_operand_device

@@ -11,7 +11,7 @@ from __future__ import annotations
 import ctypes
 import os
 from pathlib import Path
-from typing import List, Tuple, Union
+from typing import List, Sequence, Tuple, Union
 
 import numpy as np
 import torch
@@ -32,6 +32,27 @@ def base_codes(seq: str) -> np.ndarray:
     """uint8 [L]: 0..3 for A, C, G, U; 255 (the all-zero one-hot vector) for anything else, lowercase and T included."""
     raw = np.frombuffer(seq.encode("latin-1", errors="replace"), dtype=np.uint8)
     return _CODE[raw]
+
+
+SS_CHUNK_PIXELS = 1024 * 1024   # pixels of one packed call: the workspace of one lone L = 1024 call (403 MB)
+
+
+def plan_ss_chunks(Ls: Sequence[int], max_pixels: int = SS_CHUNK_PIXELS, max_batch: int = _lib.SS_MAX_BATCH) -> List[List[int]]:
+    """Indices of `Ls` split into consecutive calls of rnamsm_ss_head_packed, in list order: a chunk takes the next structure
+    as long as its sum of L^2 stays within max_pixels and its length within max_batch (greedy, so no two neighbouring chunks
+    could have been one).  A structure larger than the budget by itself -- impossible at the default, L <= 1024 -- is a chunk of
+    its own."""
+    chunks: List[List[int]] = []
+    pixels = 0
+    for i, L in enumerate(Ls):
+        n = int(L) * int(L)
+        if chunks and pixels + n <= max_pixels and len(chunks[-1]) < max_batch:
+            chunks[-1].append(i)
+            pixels += n
+        else:
+            chunks.append([i])
+            pixels = n
+    return chunks
 
 
 class _Block(nn.Module):
@@ -124,6 +145,43 @@ class SSPredictor(nn.Module):
         return self._run(atp, seq, "logits")
 
     forward = predict
+
+    def _run_many(self, atps: Sequence[torch.Tensor], seqs: Sequence, want: str) -> List[torch.Tensor]:
+        atps, seqs = list(atps), list(seqs)
+        if len(atps) != len(seqs):
+            raise ValueError(f"SSPredictor: {len(atps)} attention maps for {len(seqs)} sequences")
+        codes = []
+        for b, (atp, seq) in enumerate(zip(atps, seqs)):       # shapes and lengths first: they are wrong on any device
+            if not isinstance(atp, torch.Tensor):
+                raise _lib.RnamsmError(f"SSPredictor: atps[{b}] must be a tensor on the HIP device (no CPU path exists)")
+            if atp.dim() != 3 or atp.shape[0] != NUM_MAPS or atp.shape[1] != atp.shape[2]:
+                raise ValueError(f"SSPredictor: atps[{b}] must be [{NUM_MAPS}, L, L], got {tuple(atp.shape)}")
+            L = atp.shape[-1]
+            if L > _lib.SS_MAX_L:
+                raise ValueError(f"SSPredictor: atps[{b}]: L = {L} exceeds the head's limit of {_lib.SS_MAX_L}")
+            if isinstance(seq, str):
+                seq = base_codes(seq)
+            c = torch.as_tensor(seq).reshape(-1)
+            if c.numel() != L:
+                raise ValueError(f"SSPredictor: seqs[{b}] has length {c.numel()} for attention maps of L = {L}")
+            codes.append(c)
+        for b, atp in enumerate(atps):
+            if not atp.is_cuda:
+                raise _lib.RnamsmError(f"SSPredictor: atps[{b}] must be a tensor on the HIP device (no CPU path exists)")
+        codes = [c.to(device=a.device, dtype=torch.uint8) for c, a in zip(codes, atps)]
+        ptrs, _ = self._packed_weights()
+        out: List[torch.Tensor] = []
+        for chunk in plan_ss_chunks([a.shape[-1] for a in atps]):
+            out += ops.ss_head_packed([atps[i] for i in chunk], [codes[i] for i in chunk], ptrs, self.num_blocks, want)
+        return out
+
+    def predict_many(self, atps: Sequence[torch.Tensor], seqs: Sequence) -> List[torch.Tensor]:
+        """predict() of every (atps[b], seqs[b]) in as few launch sets as plan_ss_chunks allows (rnamsm_ss_head_packed: all the
+        structures of a call share each launch); every result is bit-identical to predict() on that structure alone."""
+        return self._run_many(atps, seqs, "probs")
+
+    def logits_many(self, atps: Sequence[torch.Tensor], seqs: Sequence) -> List[torch.Tensor]:
+        return self._run_many(atps, seqs, "logits")
 
 
 def load_predictor(path: Union[str, Path], device, num_blocks: int = 16) -> SSPredictor:

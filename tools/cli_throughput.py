@@ -23,9 +23,15 @@ if os.environ.get("PACKED_SMALL"):                       # A/B of the size up to
     inference.PACKED_SMALL_TOKENS = int(os.environ["PACKED_SMALL"])
 if os.environ.get("PACKED_SMALL_16"):
     inference.PACKED_SMALL_TOKENS_16BIT = {k: int(os.environ["PACKED_SMALL_16"]) for k in inference.PACKED_SMALL_TOKENS_16BIT}
+SS_MODEL = ""
+if os.environ.get("SS_BLOCKS"):                          # the SS key on (data.ss_model_path): a random head of that many blocks (16 = renet_b16)
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import ss_truth
+    SS_MODEL = os.path.join(tempfile.mkdtemp(prefix="rnamsm_cli_ss_", dir=os.environ.get("SCRATCH", "/tmp")), "rna-msm_attention.pt")
+    torch.save({k: torch.from_numpy(v) for k, v in ss_truth.make_state(int(os.environ["SS_BLOCKS"]), seed=0).items()}, SS_MODEL)
 rng = np.random.RandomState(0)
 letters = np.array(list("ACGU-"))
-for mode in (False, True, False, True):
+for mode in (False, True, False, True) if N else ():     # N=0: the small-alignment lists alone
     root = tempfile.mkdtemp(prefix="rnamsm_cli_", dir=os.environ.get("SCRATCH", "/tmp"))
     os.makedirs(os.path.join(root, "results"))
     ids = [f"rna{i:03d}" for i in range(N)]
@@ -39,6 +45,7 @@ for mode in (False, True, False, True):
     cfg.model.gemm_dtype = MODE
     cfg.data.root_path, cfg.data.MSA_path, cfg.data.MSA_list = root, "results", "rna_id.txt"
     cfg.data.sample_method, cfg.data.max_seqs_per_msa = "first", M
+    cfg.data.ss_model_path = SS_MODEL
     torch.cuda.synchronize(); t0 = time.perf_counter()
     extract_feat(cfg, model=model, async_io=mode)
     torch.cuda.synchronize(); dt = time.perf_counter() - t0
@@ -74,6 +81,7 @@ for label, (dlo, dhi), (llo, lhi) in (("tiny", (2, 13), (40, 81)), ("small", (4,
             cfg.data.root_path, cfg.data.MSA_path, cfg.data.MSA_list = root, "results", "rna_id.txt"
             cfg.data.sample_method, cfg.data.max_seqs_per_msa, cfg.data.batch_small_msas = "first", 64, bool(batching)
             cfg.data.pack_small_msas = batching is True
+            cfg.data.ss_model_path = SS_MODEL
             torch.cuda.synchronize(); t0 = time.perf_counter()
             extract_feat(cfg, model=model)
             torch.cuda.synchronize(); dt = time.perf_counter() - t0
