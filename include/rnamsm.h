@@ -437,6 +437,39 @@ int rnamsm_rsa_head(const float* emb, int64_t emb_row_stride, const uint8_t* bas
                     const void* const* weights, float* probs, float* logits, void* workspace, size_t workspace_bytes,
                     void* stream);
 
+/* f5, several alignments per launch -- rnamsm_rsa_head over B embeddings of unlike length in ONE set of four launches.  Every
+ * launch covers sum_b ceil(L_b / 32) x n_models blocks -- each member's own tiles, never B x the longest member's -- and a block
+ * finds its member in a device descriptor table.  A tile's arithmetic is the lone call's (the same device functions on the
+ * member's own embedding, L and workspace slab; its squeeze mean and attention keys are its own), so every member's
+ * [n_models, L_b] probs / logits are BIT-IDENTICAL to rnamsm_rsa_head on that member alone, whatever its company, its place in
+ * the batch and its embedding's row stride.
+ * items: a HOST array of B entries, read during the call and free to go afterwards (the descriptors travel as kernel arguments
+ * on `stream`).  Per member: emb / emb_row_stride / base_codes / L / probs / logits as for rnamsm_rsa_head; the members'
+ * embeddings may be slices of one buffer, their outputs must not overlap.
+ * weights, n_models, use_onehot: exactly those of rnamsm_rsa_head.
+ * workspace: rnamsm_rsa_head_packed_workspace_bytes(B, Ls, n_models) bytes, 16-byte aligned, caller-owned (nothing is allocated
+ * inside): the descriptor table (64 bytes per member, rounded up to 256), then the members' slabs in order -- member b's is the
+ * lone call's workspace, rnamsm_rsa_head_workspace_bytes(L_b, n_models) bytes, at the sum of the slabs before it.  The size is 0
+ * for B outside [1, RNAMSM_RSA_MAX_BATCH], a null Ls, an L outside [1, RNAMSM_RSA_MAX_L] or n_models outside
+ * [1, RNAMSM_RSA_MAX_MODELS].
+ * Refused (RNAMSM_ERR_INVALID) before anything is enqueued, rnamsm_last_error naming the member where one is at fault: B or
+ * n_models out of range, a member's L out of range, a null pointer (items, weights, workspace, a member's emb or base_codes, a
+ * weight), a member with neither probs nor logits, emb_row_stride < 768, an embedding, weight pointer or workspace that is not
+ * 16-byte aligned, an output that is not 4-byte aligned, a short workspace.
+ * No atomics: the same inputs give the same bits on every run. */
+typedef struct {                 /* one alignment of the batch */
+    const float*   emb;          /* device: row p at emb + p * emb_row_stride, 768 floats; 16-byte aligned */
+    int64_t        emb_row_stride;     /* >= 768 */
+    const uint8_t* base_codes;   /* device, [L] */
+    int32_t        L;            /* 1 .. RNAMSM_RSA_MAX_L */
+    float*         probs;        /* device [n_models, L] or null */
+    float*         logits;       /* device [n_models, L] or null; not both null */
+} rnamsm_rsa_item;
+#define RNAMSM_RSA_MAX_BATCH 1024
+size_t rnamsm_rsa_head_packed_workspace_bytes(int B, const int* Ls, int n_models);
+int rnamsm_rsa_head_packed(const rnamsm_rsa_item* items, int B, int n_models, int use_onehot, const void* const* weights,
+                           void* workspace, size_t workspace_bytes, void* stream);
+
 /* a7 -- the residual add of NormalizedResidualBlock around a layer that is NOT one of this library's (modules.py:396,
  * `x = residual + x`; around the library's own layers the add is fused into the layer's last GEMM): out[i] = a[i] + b[i], fp32,
  * out may alias a or b. */

@@ -56,14 +56,16 @@ static_assert(W_OUT_B + 1 == RNAMSM_RSA_WEIGHTS_PER_MODEL, "weight table layout"
 // (half, quarter) multiplies its 8 channels of the step into four 32 x 32 accumulators (conv taps 0..2 and the shortcut, which is
 // the centre tap of the same staged input against a second weight slab) for output channels half*32 ..+32.  The four quarters are
 // then summed in fixed order through LDS.
-__global__ __launch_bounds__(RSA_STEM_THREADS) void rsa_stem_kernel(const float* __restrict__ emb, int64_t emb_stride,
-                                                                    const uint8_t* __restrict__ codes, int L, int use_onehot,
-                                                                    const RsaTable table, float* __restrict__ ws) {
-    __shared__ float Xs[RSA_KC * RSA_XP];
-    __shared__ float Red[3 * 2 * 2 * 16 * 64];
+// The four bodies are shared by the lone kernels (tile from blockIdx, one sequence) and the packed ones (tile and sequence from a
+// descriptor): one arithmetic on the member's own (embedding, L, workspace base, tile), so a member's bits do not depend on which
+// of the two ran it.  ws is the MEMBER's base (its K model slabs); LDS is the calling kernel's.
+constexpr int RSA_STEM_XS = RSA_KC * RSA_XP;
+constexpr int RSA_STEM_RED = 3 * 2 * 2 * 16 * 64;
+__device__ __forceinline__ void rsa_stem_body(float* Xs, float* Red, const float* __restrict__ emb, int64_t emb_stride,
+                                              const uint8_t* __restrict__ codes, int L, int use_onehot, const RsaTable& table,
+                                              float* __restrict__ ws, int m, int p0) {
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
     const int half = wave & 1, quarter = wave >> 1;
-    const int m = blockIdx.y, p0 = blockIdx.x * RSA_TILE;
     const RsaModel M = rsa_model(table, m);
     const float* mu_emb = static_cast<const float*>(table.p[0]);
     const float* sd_emb = static_cast<const float*>(table.p[1]);
@@ -152,6 +154,13 @@ __global__ __launch_bounds__(RSA_STEM_THREADS) void rsa_stem_kernel(const float*
         }
     }
 }
+__global__ __launch_bounds__(RSA_STEM_THREADS) void rsa_stem_kernel(const float* __restrict__ emb, int64_t emb_stride,
+                                                                    const uint8_t* __restrict__ codes, int L, int use_onehot,
+                                                                    const RsaTable table, float* __restrict__ ws) {
+    __shared__ float Xs[RSA_STEM_XS];
+    __shared__ float Red[RSA_STEM_RED];
+    rsa_stem_body(Xs, Red, emb, emb_stride, codes, L, use_onehot, table, ws, blockIdx.y, blockIdx.x * RSA_TILE);
+}
 
 // out[j] += sum_ci Wt[ci][co] * Xs[(pb + j)][ci], ci ascending: thread (co, 8 positions); Xs rows are read as wave-wide broadcasts
 template <int NP>
@@ -188,11 +197,9 @@ __device__ __forceinline__ void ln_tile(const float* Src, float* Dst, const floa
 }
 
 // ---------------------------------------------------------------------------------------------------------------- launch 2
-__global__ __launch_bounds__(RSA_THREADS) void rsa_conv2_kernel(int L, const RsaTable table, float* __restrict__ ws) {
-    __shared__ __attribute__((aligned(16))) float Xs[(RSA_TILE + 2) * RSA_CH];
-    __shared__ float Ps[4 * RSA_CH];
+__device__ __forceinline__ void rsa_conv2_body(float* Xs, float* Ps, int L, const RsaTable& table, float* __restrict__ ws, int m,
+                                               int p0) {
     const int t = threadIdx.x, co = t & 63, pg = t >> 6;
-    const int m = blockIdx.y, p0 = blockIdx.x * RSA_TILE;
     const RsaModel M = rsa_model(table, m);
     float* base = ws + (size_t)m * rsa_model_floats(L);
     const float* h1 = base;
@@ -221,16 +228,23 @@ __global__ __launch_bounds__(RSA_THREADS) void rsa_conv2_kernel(int L, const Rsa
     }
     Ps[pg * RSA_CH + co] = sum;
     __syncthreads();
-    if (t < RSA_CH) part[(size_t)blockIdx.x * RSA_CH + t] = ((Ps[t] + Ps[RSA_CH + t]) + Ps[2 * RSA_CH + t]) + Ps[3 * RSA_CH + t];
+    if (t < RSA_CH) part[(size_t)(p0 / RSA_TILE) * RSA_CH + t] = ((Ps[t] + Ps[RSA_CH + t]) + Ps[2 * RSA_CH + t]) + Ps[3 * RSA_CH + t];
+}
+__global__ __launch_bounds__(RSA_THREADS) void rsa_conv2_kernel(int L, const RsaTable table, float* __restrict__ ws) {
+    __shared__ __attribute__((aligned(16))) float Xs[(RSA_TILE + 2) * RSA_CH];
+    __shared__ float Ps[4 * RSA_CH];
+    rsa_conv2_body(Xs, Ps, L, table, ws, blockIdx.y, blockIdx.x * RSA_TILE);
 }
 
 // ---------------------------------------------------------------------------------------------------------------- launch 3
-__global__ __launch_bounds__(RSA_THREADS) void rsa_mix_kernel(int L, const RsaTable table, float* __restrict__ ws) {
-    __shared__ __attribute__((aligned(16))) float Ys[RSA_TILE * RSA_CH];
-    __shared__ __attribute__((aligned(16))) float Xs[RSA_TILE * RSA_CH];
-    __shared__ float Mean[RSA_CH], Z[4], Gate[RSA_CH];
+// Sc: the squeeze-excite's scratch -- the channel means [64], the hidden units [4], the gate [64]
+constexpr int RSA_MIX_SC = 2 * RSA_CH + 4;
+__device__ __forceinline__ void rsa_mix_body(float* Ys, float* Xs, float* Sc, int L, const RsaTable& table, float* __restrict__ ws,
+                                             int m, int p0) {
+    float* Mean = Sc;
+    float* Z = Sc + RSA_CH;
+    float* Gate = Sc + RSA_CH + 4;
     const int t = threadIdx.x, co = t & 63, pg = t >> 6;
-    const int m = blockIdx.y, p0 = blockIdx.x * RSA_TILE;
     const RsaModel M = rsa_model(table, m);
     float* base = ws + (size_t)m * rsa_model_floats(L);
     const float* sh = base + (size_t)L * RSA_CH;
@@ -287,18 +301,22 @@ __global__ __launch_bounds__(RSA_THREADS) void rsa_mix_kernel(int L, const RsaTa
         }
     }
 }
+__global__ __launch_bounds__(RSA_THREADS) void rsa_mix_kernel(int L, const RsaTable table, float* __restrict__ ws) {
+    __shared__ __attribute__((aligned(16))) float Ys[RSA_TILE * RSA_CH];
+    __shared__ __attribute__((aligned(16))) float Xs[RSA_TILE * RSA_CH];
+    __shared__ float Sc[RSA_MIX_SC];
+    rsa_mix_body(Ys, Xs, Sc, L, table, ws, blockIdx.y, blockIdx.x * RSA_TILE);
+}
 
 // ---------------------------------------------------------------------------------------------------------------- launch 4
 // Thread (query ql = t / 8, head h = t % 8) owns one row of one head's attention: sweep 1 finds the row maximum, sweep 2 the
 // exponentials, their sum and the weighted values (the softmax of the reference, no running rescale).  Sums over the keys are
 // two-level: inside a 64-key chunk, then over the chunks.
-__global__ __launch_bounds__(RSA_THREADS) void rsa_attn_kernel(int L, const RsaTable table, float* __restrict__ ws,
-                                                               float* __restrict__ logits, float* __restrict__ probs) {
-    __shared__ __attribute__((aligned(16))) float KV[2 * RSA_KEYS * RSA_CH];      // K / V chunk; later the MLP's hidden tile [32][256]
-    __shared__ __attribute__((aligned(16))) float Ys[RSA_TILE * RSA_CH];
-    __shared__ __attribute__((aligned(16))) float Xs[RSA_TILE * RSA_CH];
+// The keys are [0, L) of the member's own K / V and nothing else; logits / probs: the member's [K, L] (either may be null).
+__device__ __forceinline__ void rsa_attn_body(float* KV, float* Ys, float* Xs, int L, const RsaTable& table,
+                                              const float* __restrict__ ws, int m, int p0, float* __restrict__ logits,
+                                              float* __restrict__ probs) {
     const int t = threadIdx.x, co = t & 63, pg = t >> 6;
-    const int m = blockIdx.y, p0 = blockIdx.x * RSA_TILE;
     const RsaModel M = rsa_model(table, m);
     const float* base = ws + (size_t)m * rsa_model_floats(L);
     const float* y = base + (size_t)3 * L * RSA_CH;
@@ -437,6 +455,87 @@ __global__ __launch_bounds__(RSA_THREADS) void rsa_attn_kernel(int L, const RsaT
         }
     }
 }
+__global__ __launch_bounds__(RSA_THREADS) void rsa_attn_kernel(int L, const RsaTable table, float* __restrict__ ws,
+                                                               float* __restrict__ logits, float* __restrict__ probs) {
+    __shared__ __attribute__((aligned(16))) float KV[2 * RSA_KEYS * RSA_CH];      // K / V chunk; later the MLP's hidden tile [32][256]
+    __shared__ __attribute__((aligned(16))) float Ys[RSA_TILE * RSA_CH];
+    __shared__ __attribute__((aligned(16))) float Xs[RSA_TILE * RSA_CH];
+    rsa_attn_body(KV, Ys, Xs, L, table, ws, blockIdx.y, blockIdx.x * RSA_TILE, logits, probs);
+}
+
+// ---- several alignments per launch (rnamsm_rsa_head_packed) --------------------------------------------------------------------
+// Every member has its own K model slabs in the workspace (floats [ws_off, ws_off + K * rsa_model_floats(L)) behind the descriptor
+// table): its tile sums, K and V live there, so the squeeze mean and the attention keys of a member are its own and nothing else.
+// A launch has the SUM of the members' 32-position tiles as gridDim.x (gridDim.y = the model, as in the lone launches), and a
+// block finds its member by a binary search over the tile prefix sums of the descriptor table (B <= 1024: at most ten
+// wave-uniform loads of a table that stays in L2).  From there on it runs the lone kernel's body on the member's own
+// (embedding, L, workspace base, tile): the same bits.
+struct RsaMember {           // 64 bytes
+    const float* emb;
+    int64_t emb_stride;
+    const uint8_t* codes;
+    float* logits;
+    float* probs;
+    int64_t ws_off;          // floats of the members' slabs before it
+    int32_t L;
+    int32_t tile0;           // tiles of the members before it
+    int32_t pad_[2];
+};
+static_assert(sizeof(RsaMember) == 64, "RsaMember layout");
+
+__device__ __forceinline__ int rsa_member_of_tile(const RsaMember* __restrict__ mem, int B, int tile) {
+    int lo = 0, hi = B;      // mem[lo].tile0 <= tile < mem[hi].tile0 (mem[B].tile0 = the grid)
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (mem[mid].tile0 <= tile) lo = mid;
+        else hi = mid;
+    }
+    return lo;
+}
+
+__global__ __launch_bounds__(RSA_STEM_THREADS) void rsa_stem_packed_kernel(const RsaMember* __restrict__ mem, int B, int use_onehot,
+                                                                           const RsaTable table, float* __restrict__ ws) {
+    __shared__ float Xs[RSA_STEM_XS];
+    __shared__ float Red[RSA_STEM_RED];
+    const RsaMember* b = mem + rsa_member_of_tile(mem, B, (int)blockIdx.x);
+    rsa_stem_body(Xs, Red, b->emb, b->emb_stride, b->codes, b->L, use_onehot, table, ws + b->ws_off, blockIdx.y,
+                  ((int)blockIdx.x - b->tile0) * RSA_TILE);
+}
+
+__global__ __launch_bounds__(RSA_THREADS) void rsa_conv2_packed_kernel(const RsaMember* __restrict__ mem, int B, const RsaTable table,
+                                                                       float* __restrict__ ws) {
+    __shared__ __attribute__((aligned(16))) float Xs[(RSA_TILE + 2) * RSA_CH];
+    __shared__ float Ps[4 * RSA_CH];
+    const RsaMember* b = mem + rsa_member_of_tile(mem, B, (int)blockIdx.x);
+    rsa_conv2_body(Xs, Ps, b->L, table, ws + b->ws_off, blockIdx.y, ((int)blockIdx.x - b->tile0) * RSA_TILE);
+}
+
+__global__ __launch_bounds__(RSA_THREADS) void rsa_mix_packed_kernel(const RsaMember* __restrict__ mem, int B, const RsaTable table,
+                                                                     float* __restrict__ ws) {
+    __shared__ __attribute__((aligned(16))) float Ys[RSA_TILE * RSA_CH];
+    __shared__ __attribute__((aligned(16))) float Xs[RSA_TILE * RSA_CH];
+    __shared__ float Sc[RSA_MIX_SC];
+    const RsaMember* b = mem + rsa_member_of_tile(mem, B, (int)blockIdx.x);
+    rsa_mix_body(Ys, Xs, Sc, b->L, table, ws + b->ws_off, blockIdx.y, ((int)blockIdx.x - b->tile0) * RSA_TILE);
+}
+
+__global__ __launch_bounds__(RSA_THREADS) void rsa_attn_packed_kernel(const RsaMember* __restrict__ mem, int B, const RsaTable table,
+                                                                      const float* __restrict__ ws) {
+    __shared__ __attribute__((aligned(16))) float KV[2 * RSA_KEYS * RSA_CH];
+    __shared__ __attribute__((aligned(16))) float Ys[RSA_TILE * RSA_CH];
+    __shared__ __attribute__((aligned(16))) float Xs[RSA_TILE * RSA_CH];
+    const RsaMember* b = mem + rsa_member_of_tile(mem, B, (int)blockIdx.x);
+    rsa_attn_body(KV, Ys, Xs, b->L, table, ws + b->ws_off, blockIdx.y, ((int)blockIdx.x - b->tile0) * RSA_TILE, b->logits, b->probs);
+}
+
+// The descriptors travel as kernel arguments, 32 (2 KB) per launch, on the caller's stream: no host buffer has to outlive the call
+// (as rnamsm_ss_head_packed's do).
+struct RsaMemberChunk { RsaMember m[32]; };
+__global__ void rsa_members_kernel(RsaMemberChunk chunk, int n, RsaMember* __restrict__ dev) {
+    if ((int)threadIdx.x < n) dev[threadIdx.x] = chunk.m[threadIdx.x];
+}
+
+constexpr size_t rsa_members_bytes(int B) { return ((size_t)B * sizeof(RsaMember) + 255) & ~(size_t)255; }
 
 }  // namespace
 }  // namespace rnamsm
@@ -481,5 +580,90 @@ extern "C" int rnamsm_rsa_head(const float* emb, int64_t emb_row_stride, const u
     RNAMSM_CHECK_LAUNCH("rsa_mix");
     hipLaunchKernelGGL(rsa_attn_kernel, grid, dim3(RSA_THREADS), 0, s, L, table, ws, logits, probs);
     RNAMSM_CHECK_LAUNCH("rsa_attn");
+    return RNAMSM_OK;
+}
+
+extern "C" size_t rnamsm_rsa_head_packed_workspace_bytes(int B, const int* Ls, int n_models) {
+    if (B < 1 || B > RNAMSM_RSA_MAX_BATCH || !Ls || n_models < 1 || n_models > RNAMSM_RSA_MAX_MODELS) return 0;
+    size_t floats = 0;
+    for (int b = 0; b < B; ++b) {
+        if (Ls[b] < 1 || Ls[b] > RNAMSM_RSA_MAX_L) return 0;
+        floats += (size_t)n_models * rsa_model_floats(Ls[b]);
+    }
+    return rsa_members_bytes(B) + floats * sizeof(float);
+}
+
+extern "C" int rnamsm_rsa_head_packed(const rnamsm_rsa_item* items, int B, int n_models, int use_onehot, const void* const* weights,
+                                      void* workspace, size_t workspace_bytes, void* stream) {
+    // every refusal comes before the first launch: a refused call leaves the stream and the outputs untouched
+    RNAMSM_CHECK_ARG(items && weights && workspace, "rsa_head_packed: null pointer");
+    RNAMSM_CHECK_ARG(B >= 1 && B <= RNAMSM_RSA_MAX_BATCH, "rsa_head_packed: B=%d outside [1, %d]", B, RNAMSM_RSA_MAX_BATCH);
+    RNAMSM_CHECK_ARG(n_models >= 1 && n_models <= RNAMSM_RSA_MAX_MODELS, "rsa_head_packed: n_models=%d outside [1, %d]", n_models,
+                     RNAMSM_RSA_MAX_MODELS);
+    size_t floats = 0;
+    int64_t tiles_total = 0;
+    for (int b = 0; b < B; ++b) {
+        const rnamsm_rsa_item& it = items[b];
+        RNAMSM_CHECK_ARG(it.L >= 1 && it.L <= RNAMSM_RSA_MAX_L, "rsa_head_packed: member %d: L=%d outside [1, %d]", b, it.L,
+                         RNAMSM_RSA_MAX_L);
+        RNAMSM_CHECK_ARG(it.emb && it.base_codes, "rsa_head_packed: member %d: null pointer", b);
+        RNAMSM_CHECK_ARG(it.logits || it.probs, "rsa_head_packed: member %d: neither probs nor logits given", b);
+        RNAMSM_CHECK_ARG(it.emb_row_stride >= RSA_EMB, "rsa_head_packed: member %d: embedding row stride %lld < %d", b,
+                         (long long)it.emb_row_stride, RSA_EMB);
+        RNAMSM_CHECK_ARG(aligned16(it.emb), "rsa_head_packed: member %d: the embedding is not 16-byte aligned", b);
+        RNAMSM_CHECK_ARG(((uintptr_t)it.logits & 3u) == 0 && ((uintptr_t)it.probs & 3u) == 0,
+                         "rsa_head_packed: member %d: an output pointer is not 4-byte aligned", b);
+        floats += (size_t)n_models * rsa_model_floats(it.L);
+        tiles_total += (it.L + RSA_TILE - 1) / RSA_TILE;
+    }
+    RNAMSM_CHECK_ARG(aligned16(workspace), "rsa_head_packed: 16-byte alignment of the workspace");
+    RNAMSM_CHECK_ARG(workspace_bytes >= rsa_members_bytes(B) + floats * sizeof(float), "rsa_head_packed: workspace too small");
+    const int nw = RNAMSM_RSA_GLOBAL_WEIGHTS + RNAMSM_RSA_WEIGHTS_PER_MODEL * n_models;
+    for (int i = 0; i < nw; ++i) {
+        if (!use_onehot && (i == 2 || i == 3)) continue;        // the one-hot statistics are not read
+        RNAMSM_CHECK_ARG(weights[i], "rsa_head_packed: weight pointer %d is null", i);
+        RNAMSM_CHECK_ARG(aligned16(weights[i]), "rsa_head_packed: weight pointer %d is not 16-byte aligned", i);
+    }
+    RsaTable table;
+    for (int i = 0; i < RSA_TABLE_MAX; ++i) table.p[i] = i < nw ? weights[i] : nullptr;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    RsaMember* mem = static_cast<RsaMember*>(workspace);
+    float* ws = reinterpret_cast<float*>(static_cast<char*>(workspace) + rsa_members_bytes(B));
+    int64_t ws_off = 0;
+    int32_t tile0 = 0;
+    for (int b0 = 0; b0 < B; b0 += 32) {
+        RsaMemberChunk chunk;
+        const int n = B - b0 < 32 ? B - b0 : 32;
+        for (int i = 0; i < 32; ++i) {
+            RsaMember& m = chunk.m[i];
+            if (i >= n) {
+                m = chunk.m[0];
+                continue;
+            }
+            const rnamsm_rsa_item& it = items[b0 + i];
+            m.emb = it.emb;
+            m.emb_stride = it.emb_row_stride;
+            m.codes = it.base_codes;
+            m.logits = it.logits;
+            m.probs = it.probs;
+            m.ws_off = ws_off;
+            m.L = it.L;
+            m.tile0 = tile0;
+            m.pad_[0] = m.pad_[1] = 0;
+            ws_off += (int64_t)n_models * (int64_t)rsa_model_floats(it.L);
+            tile0 += (it.L + RSA_TILE - 1) / RSA_TILE;
+        }
+        hipLaunchKernelGGL(rsa_members_kernel, dim3(1), dim3(32), 0, s, chunk, n, mem + b0);
+        RNAMSM_CHECK_LAUNCH("rsa_members");
+    }
+    const dim3 grid((unsigned)tiles_total, (unsigned)n_models);      // the members' own tiles, nothing for a short member beside a long one
+    hipLaunchKernelGGL(rsa_stem_packed_kernel, grid, dim3(RSA_STEM_THREADS), 0, s, mem, B, use_onehot ? 1 : 0, table, ws);
+    RNAMSM_CHECK_LAUNCH("rsa_stem (packed)");
+    hipLaunchKernelGGL(rsa_conv2_packed_kernel, grid, dim3(RSA_THREADS), 0, s, mem, B, table, ws);
+    RNAMSM_CHECK_LAUNCH("rsa_conv2 (packed)");
+    hipLaunchKernelGGL(rsa_mix_packed_kernel, grid, dim3(RSA_THREADS), 0, s, mem, B, table, ws);
+    RNAMSM_CHECK_LAUNCH("rsa_mix (packed)");
+    hipLaunchKernelGGL(rsa_attn_packed_kernel, grid, dim3(RSA_THREADS), 0, s, mem, B, table, ws);
+    RNAMSM_CHECK_LAUNCH("rsa_attn (packed)");
     return RNAMSM_OK;
 }

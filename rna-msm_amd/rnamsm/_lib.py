@@ -41,6 +41,7 @@ W_RSA_MODEL = ("stem", "bn1.scale", "bn1.shift", "shortcut.1.scale", "shortcut.1
                "mlp.2.bias", "final.weight", "final.bias")
 RSA_MAX_L = 1024
 RSA_MAX_MODELS = 8
+RSA_MAX_BATCH = 1024
 RSA_CIN_PAD = 800
 
 
@@ -54,6 +55,12 @@ class SsItem(ctypes.Structure):
     """rnamsm_ss_item: one structure of an rnamsm_ss_head_packed batch (device pointers as integers)."""
     _fields_ = [("atp", c_void_p), ("atp_plane_stride", c_int64), ("base_codes", c_void_p), ("L", ctypes.c_int32),
                 ("logits", c_void_p), ("probs", c_void_p)]
+
+
+class RsaItem(ctypes.Structure):
+    """rnamsm_rsa_item: one alignment of an rnamsm_rsa_head_packed batch (device pointers as integers)."""
+    _fields_ = [("emb", c_void_p), ("emb_row_stride", c_int64), ("base_codes", c_void_p), ("L", ctypes.c_int32),
+                ("probs", c_void_p), ("logits", c_void_p)]
 
 
 _SIGNATURES = {
@@ -115,6 +122,8 @@ _SIGNATURES = {
     "rnamsm_rsa_head_workspace_bytes": (c_size_t, [c_int, c_int]),
     "rnamsm_rsa_head": (c_int, [c_void_p, c_int64, c_void_p, c_int, c_int, c_int, POINTER(c_void_p), c_void_p, c_void_p, c_void_p,
                                 c_size_t, c_void_p]),
+    "rnamsm_rsa_head_packed_workspace_bytes": (c_size_t, [c_int, POINTER(c_int), c_int]),
+    "rnamsm_rsa_head_packed": (c_int, [POINTER(RsaItem), c_int, c_int, c_int, POINTER(c_void_p), c_void_p, c_size_t, c_void_p]),
     "rnamsm_greedy_select_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
     "rnamsm_greedy_select": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
     "rnamsm_msa_weights": (c_int, [c_void_p, c_int, c_int, c_double, c_void_p, c_void_p]),

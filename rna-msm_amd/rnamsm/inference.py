@@ -437,16 +437,17 @@ def extract_feat(cfg: Config, model: Optional[MSATransformer] = None, gather_to_
         with torch.no_grad():
             pending = reader.submit(read, mine[0]) if reader and len(mine) else None
             def deliver(idx: int, emb: torch.Tensor, atp: torch.Tensor, after: Optional[torch.cuda.Event] = None,
-                        toks: Optional[torch.Tensor] = None, ss_probs: Optional[torch.Tensor] = None) -> None:
-                """ss_probs: this alignment's base-pair probabilities where its group's batched head (ss_group) has already computed
-                them; absent, the lone head runs here."""
+                        toks: Optional[torch.Tensor] = None, ss_probs: Optional[torch.Tensor] = None,
+                        rsa_vals: Optional[torch.Tensor] = None) -> None:
+                """ss_probs / rsa_vals: this alignment's base-pair probabilities / [K, L] RSA where its group's batched head (ss_group,
+                rsa_group) has already computed them; absent, the lone head runs here."""
                 ss_out = None
                 if ss_model is not None:          # the head reads atp where it lies (a packed group's slice included)
                     tok_row = toks[0, 1:]
                     ss_out = (ss_probs if ss_probs is not None else ss_model.predict(atp, ss_lut[tok_row]), tok_row)
                 if rsa_model is not None:         # the ensemble reads emb where it lies
                     tok_row = toks[0, 1:]
-                    ss_out = (ss_out or ()) + (rsa_model.predict(emb, rsa_lut[tok_row]), tok_row)
+                    ss_out = (ss_out or ()) + (rsa_vals if rsa_vals is not None else rsa_model.predict(emb, rsa_lut[tok_row]), tok_row)
                 if ss_out is not None and after is not None:         # the copies wait for the heads too
                     after = torch.cuda.Event()
                     after.record(torch.cuda.current_stream())
@@ -462,14 +463,23 @@ def extract_feat(cfg: Config, model: Optional[MSATransformer] = None, gather_to_
                     return [None] * len(atps)
                 return ss_model.predict_many(atps, [ss_lut[t[0, 1:]] for t in toks_])
 
+            def rsa_group(embs: List[torch.Tensor], toks_: List[torch.Tensor]) -> List[Optional[torch.Tensor]]:
+                """The RSA ensemble of a whole group in one launch set (RSAEnsemble.predict_many: four launches cover all the members'
+                tiles, each member's [K, L] is the lone head's bits); a list of None when the head is off."""
+                if rsa_model is None:
+                    return [None] * len(embs)
+                return rsa_model.predict_many(embs, [rsa_lut[t[0, 1:]] for t in toks_])
+
             def deliver_group(members_, outs, ev: Optional[torch.cuda.Event] = None) -> None:
                 embs, atps = [o["emb"].contiguous() for o in outs], [o["atp"].contiguous() for o in outs]
-                probs = ss_group(atps, [t for _, t in members_])
-                if ss_model is not None and ev is not None:           # the copies wait for the batched head too
+                toks_ = [t for _, t in members_]
+                probs = ss_group(atps, toks_)
+                vals = rsa_group(embs, toks_)
+                if (ss_model is not None or rsa_model is not None) and ev is not None:      # the copies wait for both batched heads too
                     ev = torch.cuda.Event()
                     ev.record(torch.cuda.current_stream())
-                for (i, t), emb, atp, p in zip(members_, embs, atps, probs):
-                    deliver(i, emb, atp, ev, t, ss_probs=p)
+                for (i, t), emb, atp, p, v in zip(members_, embs, atps, probs, vals):
+                    deliver(i, emb, atp, ev, t, ss_probs=p, rsa_vals=v)
 
             # data.batch_small_msas: small alignments go through ONE launch set per group (forward_ragged: padded into one
             # frame, every MSA scaled by its own depth); a lone forward of a few hundred tokens costs 5.5 ms on a mostly

@@ -659,6 +659,56 @@ def rsa_head(emb: torch.Tensor, base_codes: torch.Tensor, ptrs, n_models: int, u
 
 
 @_on_operand_device
+def rsa_head_packed(embs: Sequence[torch.Tensor], codes: Sequence[torch.Tensor], ptrs, n_models: int, use_onehot: bool,
+                    want: str = "probs") -> List[torch.Tensor]:
+    """RNA-MSM RSA ensemble over several alignments in one set of four launches (rnamsm_rsa_head_packed): embs[b] [L_b, 768] fp32,
+    codes[b] uint8 [L_b], the operand rules of rsa_head per member (row slices of one wider buffer are read in place) -> a list of
+    [n_models, L_b] tensors, each bit-identical to rsa_head on that member alone.  One workspace and one output allocation per
+    call: the returned tensors are views of one buffer."""
+    if want not in ("probs", "logits"):
+        raise ValueError(f"rsa_head_packed: want must be 'probs' or 'logits', got {want!r}")
+    embs, codes = list(embs), list(codes)
+    if len(embs) != len(codes):
+        raise ValueError(f"rsa_head_packed: {len(embs)} embeddings for {len(codes)} base-code rows")
+    if not embs:
+        return []
+    B = len(embs)
+    if B > _lib.RSA_MAX_BATCH:
+        raise ValueError(f"rsa_head_packed: {B} alignments exceed the limit of {_lib.RSA_MAX_BATCH} per call")
+    device = embs[0].device if isinstance(embs[0], torch.Tensor) else None
+    for b in range(B):
+        emb, bc = embs[b], codes[b]
+        _dev(emb, f"emb[{b}]")
+        if emb.dim() != 2 or emb.shape[1] != 768:
+            raise ValueError(f"rsa_head_packed: emb[{b}] must be [L, 768], got {tuple(emb.shape)}")
+        if emb.device != device:
+            raise ValueError(f"rsa_head_packed: emb[{b}] lies on {emb.device}, emb[0] on {device}")
+        L = emb.shape[0]
+        if not 1 <= L <= _lib.RSA_MAX_L:
+            raise ValueError(f"rsa_head_packed: emb[{b}]: L = {L} outside [1, {_lib.RSA_MAX_L}]")
+        if emb.stride(1) != 1 or (L > 1 and emb.stride(0) < 768) or emb.data_ptr() % 16:
+            embs[b] = emb.contiguous()
+        _dev(bc, f"base_codes[{b}]", torch.uint8)
+        if bc.dim() != 1 or bc.shape[0] != L:
+            raise ValueError(f"rsa_head_packed: {tuple(bc.shape)} base codes for emb[{b}] of L = {L}")
+        codes[b] = bc.contiguous()
+    lib = _lib.load()
+    Ls = [int(e.shape[0]) for e in embs]
+    ws = torch.empty(lib.rnamsm_rsa_head_packed_workspace_bytes(B, (_lib.c_int * B)(*Ls), n_models), dtype=torch.uint8, device=device)
+    out = torch.empty(n_models * sum(Ls), device=device, dtype=torch.float32)
+    items = (_lib.RsaItem * B)()
+    outs, off = [], 0
+    for b, L in enumerate(Ls):
+        o = out[off:off + n_models * L].view(n_models, L)
+        off += n_models * L
+        outs.append(o)
+        items[b] = _lib.RsaItem(embs[b].data_ptr(), embs[b].stride(0) if L > 1 else 768, codes[b].data_ptr(), L,
+                                o.data_ptr() if want == "probs" else None, o.data_ptr() if want == "logits" else None)
+    _lib.check(lib.rnamsm_rsa_head_packed(items, B, n_models, 1 if use_onehot else 0, ptrs, ws.data_ptr(), ws.numel(), _stream()))
+    return outs
+
+
+@_on_operand_device
 def greedy_select(msa_u8: torch.Tensor, num_seqs: int, mode: str = "max") -> torch.Tensor:
     """msa uint8 [N, L] on the device -> int32 [num_seqs] ascending row indices (utils/align.py:128-148)."""
     if mode not in ("max", "min"):

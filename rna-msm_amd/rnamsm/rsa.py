@@ -3,7 +3,8 @@
 `RSAPredictor` carries the parameters of one of the reference's `FrameModel(Cin, 1, planes=64, depth=1)` networks under the same
 names and shapes, so a state_dict taken from an upstream model loads with strict=True; `RSAEnsemble` holds K of them and the
 normalisation statistics, and its arithmetic is one HIP entry point (rnamsm_rsa_head: all members in four launches, exact fp32)
-that reads the [L, 768] embedding where it lies on the device.  `load_ensemble` reads an upstream model directory -- its `.pt`
+that reads the [L, 768] embedding where it lies on the device; `predict_many` runs a list of alignments through the same four
+launches (rnamsm_rsa_head_packed), every result the lone call's bits.  `load_ensemble` reads an upstream model directory -- its `.pt`
 files are pickled whole modules and are opened with no upstream code importable -- and `write_rsa_files` is the reference's
 host arithmetic and text format (predict.py: doSavePredict_single, per model and for the ensemble), byte for byte.
 """
@@ -31,6 +32,27 @@ HEADS = 8
 BN_EPS = 1e-5
 ASA_SCALE = {"A": 400, "U": 350, "C": 350, "G": 400}       # predict.py: BASES 'AUCG', asa_std
 _BASES = "AUCG"
+# positions of one packed call: 32768 x 7 x 64 floats x K of workspace is 176 MB at K = 3 and 470 MB at K = 8, the order of the SS
+# head's 403 MB ceiling (a condition, not a measurement)
+RSA_CHUNK_POSITIONS = 32768
+
+
+def plan_rsa_chunks(Ls: Sequence[int], max_positions: int = RSA_CHUNK_POSITIONS, max_batch: int = _lib.RSA_MAX_BATCH) -> List[List[int]]:
+    """Indices of `Ls` split into consecutive calls of rnamsm_rsa_head_packed, in list order: a chunk takes the next alignment as
+    long as its sum of L stays within max_positions and its length within max_batch (greedy, so no two neighbouring chunks could
+    have been one).  An alignment larger than the budget by itself -- impossible at the default, L <= 1024 -- is a chunk of its
+    own."""
+    chunks: List[List[int]] = []
+    positions = 0
+    for i, L in enumerate(Ls):
+        n = int(L)
+        if chunks and positions + n <= max_positions and len(chunks[-1]) < max_batch:
+            chunks[-1].append(i)
+            positions += n
+        else:
+            chunks.append([i])
+            positions = n
+    return chunks
 
 
 class _BasicBlock(nn.Module):
@@ -218,6 +240,47 @@ class RSAEnsemble(nn.Module):
         return self._run(emb, seq, "logits")
 
     forward = predict
+
+    def _run_many(self, embs: Sequence[torch.Tensor], seqs: Sequence, want: str) -> List[torch.Tensor]:
+        embs, seqs = list(embs), list(seqs)
+        if len(embs) != len(seqs):
+            raise ValueError(f"RSAEnsemble: {len(embs)} embeddings for {len(seqs)} sequences")
+        codes = []
+        for b, (emb, seq) in enumerate(zip(embs, seqs)):       # shapes and lengths first: they are wrong on any device
+            if not isinstance(emb, torch.Tensor):
+                raise _lib.RnamsmError(f"RSAEnsemble: embs[{b}] must be a tensor on the HIP device (no CPU path exists)")
+            if emb.dim() != 2 or emb.shape[1] != EMBED_DIM:
+                raise ValueError(f"RSAEnsemble: embs[{b}] must be [L, {EMBED_DIM}], got {tuple(emb.shape)}")
+            L = emb.shape[0]
+            if not 1 <= L <= _lib.RSA_MAX_L:
+                raise ValueError(f"RSAEnsemble: embs[{b}]: L = {L} outside the head's range [1, {_lib.RSA_MAX_L}]")
+            if isinstance(seq, str):
+                seq = base_codes(seq)
+            c = torch.as_tensor(seq).reshape(-1)
+            if c.numel() != L:
+                raise ValueError(f"RSAEnsemble: seqs[{b}] has length {c.numel()} for an embedding of L = {L}")
+            codes.append(c)
+        for b, emb in enumerate(embs):
+            if not emb.is_cuda:
+                raise _lib.RnamsmError(f"RSAEnsemble: embs[{b}] must be a tensor on the HIP device (no CPU path exists)")
+        codes = [c.to(device=e.device, dtype=torch.uint8) for c, e in zip(codes, embs)]
+        if not embs:
+            return []
+        ptrs, _ = self._packed_weights()
+        out: List[torch.Tensor] = []
+        for chunk in plan_rsa_chunks([e.shape[0] for e in embs]):
+            out += ops.rsa_head_packed([embs[i] for i in chunk], [codes[i] for i in chunk], ptrs, len(self.members), self.use_onehot,
+                                       want)
+        return out
+
+    def predict_many(self, embs: Sequence[torch.Tensor], seqs: Sequence) -> List[torch.Tensor]:
+        """predict() of every (embs[b], seqs[b]) in as few launch sets as plan_rsa_chunks allows (rnamsm_rsa_head_packed: all the
+        alignments of a call share each of the four launches); every [K, L_b] result is bit-identical to predict() on that
+        alignment alone."""
+        return self._run_many(embs, seqs, "probs")
+
+    def logits_many(self, embs: Sequence[torch.Tensor], seqs: Sequence) -> List[torch.Tensor]:
+        return self._run_many(embs, seqs, "logits")
 
 
 # ---------------------------------------------------------------------- loading an upstream model directory

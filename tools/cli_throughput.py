@@ -29,6 +29,18 @@ if os.environ.get("SS_BLOCKS"):                          # the SS key on (data.s
     import ss_truth
     SS_MODEL = os.path.join(tempfile.mkdtemp(prefix="rnamsm_cli_ss_", dir=os.environ.get("SCRATCH", "/tmp")), "rna-msm_attention.pt")
     torch.save({k: torch.from_numpy(v) for k, v in ss_truth.make_state(int(os.environ["SS_BLOCKS"]), seed=0).items()}, SS_MODEL)
+RSA_DIR = ""
+if os.environ.get("RSA_MODELS"):                         # the RSA key on (data.rsa_model_dir): that many random one-hot members (3 = the shipped ensemble's size)
+    import pickle
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import rsa_truth
+    RSA_DIR = tempfile.mkdtemp(prefix="rnamsm_cli_rsa_", dir=os.environ.get("SCRATCH", "/tmp"))
+    for k in range(int(os.environ["RSA_MODELS"])):
+        torch.save({n: torch.from_numpy(v) for n, v in rsa_truth.make_state(11 + k).items()}, os.path.join(RSA_DIR, f"model_pcc_{k}.pt"))
+    st = rsa_truth.load_stats("oh")
+    for name, key in (("statistic_dict_oh.pickle", "oh"), ("statistic_dict_emb.pickle", "emb")):
+        with open(os.path.join(RSA_DIR, name), "wb") as f:
+            pickle.dump({"mu": st[key + "_mu"], "std": st[key + "_std"]}, f)
 rng = np.random.RandomState(0)
 letters = np.array(list("ACGU-"))
 for mode in (False, True, False, True) if N else ():     # N=0: the small-alignment lists alone
@@ -46,6 +58,7 @@ for mode in (False, True, False, True) if N else ():     # N=0: the small-alignm
     cfg.data.root_path, cfg.data.MSA_path, cfg.data.MSA_list = root, "results", "rna_id.txt"
     cfg.data.sample_method, cfg.data.max_seqs_per_msa = "first", M
     cfg.data.ss_model_path = SS_MODEL
+    cfg.data.rsa_model_dir = RSA_DIR
     torch.cuda.synchronize(); t0 = time.perf_counter()
     extract_feat(cfg, model=model, async_io=mode)
     torch.cuda.synchronize(); dt = time.perf_counter() - t0
@@ -82,6 +95,7 @@ for label, (dlo, dhi), (llo, lhi) in (("tiny", (2, 13), (40, 81)), ("small", (4,
             cfg.data.sample_method, cfg.data.max_seqs_per_msa, cfg.data.batch_small_msas = "first", 64, bool(batching)
             cfg.data.pack_small_msas = batching is True
             cfg.data.ss_model_path = SS_MODEL
+            cfg.data.rsa_model_dir = RSA_DIR
             torch.cuda.synchronize(); t0 = time.perf_counter()
             extract_feat(cfg, model=model)
             torch.cuda.synchronize(); dt = time.perf_counter() - t0
