@@ -445,6 +445,54 @@ struct PackedMsa {           // 64 bytes
     int32_t pad_;
 };
 static_assert(sizeof(PackedMsa) == 64, "PackedMsa layout");
+
+// ---- descriptor tables of the batched stages (PackedMsa here, SsMember in ss_head.hip, RsaMember in rsa_head.hip): one upload, one
+// search.  The descriptors travel host -> device as kernel arguments, 32 (2 KB) per launch, on the caller's stream: no host buffer
+// has to outlive the call.
+template <class T>
+struct MemberChunk { T m[32]; };
+template <class T>
+__global__ void members_kernel(MemberChunk<T> chunk, int n, T* __restrict__ dev) {
+    if ((int)threadIdx.x < n) dev[threadIdx.x] = chunk.m[threadIdx.x];
+}
+// dev[b] = fill(b) for b = 0 .. B-1; fill is called in member order, so running prefix sums can live in the caller's lambda.
+// The unused entries of the last chunk repeat its entry 0.  name: the launch's name in an error text.
+template <class T, class Fill>
+int upload_members(T* dev, int B, Fill fill, hipStream_t stream, const char* name) {
+    static_assert(sizeof(T) == 64, "descriptor layout");
+    for (int b0 = 0; b0 < B; b0 += 32) {
+        MemberChunk<T> chunk;
+        const int n = B - b0 < 32 ? B - b0 : 32;
+        for (int i = 0; i < 32; ++i) chunk.m[i] = i < n ? fill(b0 + i) : chunk.m[0];
+        hipLaunchKernelGGL(members_kernel<T>, dim3(1), dim3(32), 0, stream, chunk, n, dev + b0);
+        RNAMSM_CHECK_LAUNCH(name);
+    }
+    return RNAMSM_OK;
+}
+// The member that holds `key` (a tile, a pixel): the last of mem[0 .. B) whose prefix sum `field` is <= key.  B <= 1024: at most
+// ten loads of a table that stays in L2, wave-uniform where the key is.
+template <class T, class F, class K>
+__device__ __forceinline__ int member_of(const T* __restrict__ mem, int B, K key, F T::*field) {
+    int lo = 0, hi = B;      // mem[lo].*field <= key < mem[hi].*field (mem[B].*field = the total)
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (mem[mid].*field <= key) lo = mid;
+        else hi = mid;
+    }
+    return lo;
+}
+
+// Every entry of a head's weight-pointer table is non-null and 16-byte aligned, but for the entries named by skip_mask (bit i =
+// entry i), which the call does not read.  prefix: the entry point's name in the refusal.
+template <class P>
+int check_weight_table(const char* prefix, const P* weights, int nw, unsigned skip_mask = 0u) {
+    for (int i = 0; i < nw; ++i) {
+        if (i < 32 && ((skip_mask >> i) & 1u)) continue;
+        RNAMSM_CHECK_ARG(weights[i], "%s: weight pointer %d is null", prefix, i);
+        RNAMSM_CHECK_ARG(aligned16(weights[i]), "%s: weight pointer %d is not 16-byte aligned", prefix, i);
+    }
+    return RNAMSM_OK;
+}
 int packed_descriptors_upload(const PackedMsa* host, int B, PackedMsa* dev, hipStream_t stream);
 int embed_ln_packed(const int64_t* tokens, const float* embed_tokens, const float* embed_positions, const float* row_pos,
                     const float* gamma, const float* beta, float* out, const PackedMsa* pk, int B, int64_t T, int D, int vocab,

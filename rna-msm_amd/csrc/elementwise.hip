@@ -436,21 +436,8 @@ int embed_ln_packed(const int64_t* tokens, const float* embed_tokens, const floa
     RNAMSM_CHECK_LAUNCH("embed_ln (packed)");
     return RNAMSM_OK;
 }
-// PackedMsa descriptors host -> device WITHOUT a host buffer that has to outlive the call: they travel as kernel arguments,
-// 32 (2 KB) per launch
-struct PackedChunk { PackedMsa m[32]; };
-__global__ void packed_descriptors_kernel(PackedChunk chunk, int n, PackedMsa* __restrict__ dev) {
-    if ((int)threadIdx.x < n) dev[threadIdx.x] = chunk.m[threadIdx.x];
-}
 int packed_descriptors_upload(const PackedMsa* host, int B, PackedMsa* dev, hipStream_t stream) {
-    for (int b0 = 0; b0 < B; b0 += 32) {
-        PackedChunk chunk;
-        const int n = B - b0 < 32 ? B - b0 : 32;
-        for (int i = 0; i < 32; ++i) chunk.m[i] = host[b0 + (i < n ? i : 0)];
-        hipLaunchKernelGGL(packed_descriptors_kernel, dim3(1), dim3(32), 0, stream, chunk, n, dev + b0);
-        RNAMSM_CHECK_LAUNCH("packed_descriptors");
-    }
-    return RNAMSM_OK;
+    return upload_members(dev, B, [host](int b) { return host[b]; }, stream, "packed_descriptors");
 }
 int pack_outputs_packed(const float* x_final, const float* row_attn, float* emb, float* atp, const PackedMsa* pk, int B, int max_C, int D,
                         int num_layers, int H, double total_out_floats, int* err_flag, hipStream_t stream) {

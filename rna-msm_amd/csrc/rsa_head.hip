@@ -51,14 +51,41 @@ enum {   // indices inside a member's slice
 };
 static_assert(W_OUT_B + 1 == RNAMSM_RSA_WEIGHTS_PER_MODEL, "weight table layout");
 
+// ---- the member of a block ------------------------------------------------------------------------------------------------------
+// One kernel per stage serves the lone call (rnamsm_rsa_head) and the batched one (rnamsm_rsa_head_packed).  A launch has the SUM
+// of the members' 32-position tiles as gridDim.x and the model as gridDim.y.  Batched, mem is the device table of the B members
+// and a block finds its own by a search over the tile prefix sums (common.h: member_of); lone, mem is null and the one member is
+// the kernel argument itself (tile0 = 0, ws_off = 0: the caller's workspace with no table in front).  Either way the stage's body
+// runs on the member's own (embedding, L, workspace base, tile): one arithmetic, so a member's bits depend on nothing else.
+// The choice is a template argument, not a test of mem: one definition, two code objects.  With the test inside the kernel the
+// compiler reads the descriptor through ONE flat load of a selected address (table or kernel argument) and L, the offsets and the
+// pointers land in vector registers: +4 to +8 VGPRs over the lone kernels in three of the four stages.
+// Every member has its own K model slabs in the workspace (floats [ws_off, ws_off + K * rsa_model_floats(L))): its tile sums, K
+// and V live there, so the squeeze mean and the attention keys of a member are its own.
+struct RsaMember {           // 64 bytes
+    const float* emb;
+    int64_t emb_stride;
+    const uint8_t* codes;
+    float* logits;
+    float* probs;
+    int64_t ws_off;          // floats of the members' slabs before it
+    int32_t L;
+    int32_t tile0;           // tiles of the members before it
+    int32_t pad_[2];
+};
+static_assert(sizeof(RsaMember) == 64, "RsaMember layout");
+template <bool PACKED>
+__device__ __forceinline__ RsaMember rsa_member(const RsaMember* __restrict__ mem, int B, const RsaMember& lone) {
+    if (PACKED) return mem[member_of(mem, B, (int)blockIdx.x, &RsaMember::tile0)];
+    return lone;
+}
+
 // ---------------------------------------------------------------------------------------------------------------- launch 1
 // Block (tile of 32 positions, model).  Per 32-channel step the tile [32 channels][34 positions] is staged normalised; wave
 // (half, quarter) multiplies its 8 channels of the step into four 32 x 32 accumulators (conv taps 0..2 and the shortcut, which is
 // the centre tap of the same staged input against a second weight slab) for output channels half*32 ..+32.  The four quarters are
 // then summed in fixed order through LDS.
-// The four bodies are shared by the lone kernels (tile from blockIdx, one sequence) and the packed ones (tile and sequence from a
-// descriptor): one arithmetic on the member's own (embedding, L, workspace base, tile), so a member's bits do not depend on which
-// of the two ran it.  ws is the MEMBER's base (its K model slabs); LDS is the calling kernel's.
+// In the four bodies ws is the MEMBER's base (its K model slabs); LDS is the calling kernel's.
 constexpr int RSA_STEM_XS = RSA_KC * RSA_XP;
 constexpr int RSA_STEM_RED = 3 * 2 * 2 * 16 * 64;
 __device__ __forceinline__ void rsa_stem_body(float* Xs, float* Red, const float* __restrict__ emb, int64_t emb_stride,
@@ -154,12 +181,14 @@ __device__ __forceinline__ void rsa_stem_body(float* Xs, float* Red, const float
         }
     }
 }
-__global__ __launch_bounds__(RSA_STEM_THREADS) void rsa_stem_kernel(const float* __restrict__ emb, int64_t emb_stride,
-                                                                    const uint8_t* __restrict__ codes, int L, int use_onehot,
-                                                                    const RsaTable table, float* __restrict__ ws) {
+template <bool PACKED>
+__global__ __launch_bounds__(RSA_STEM_THREADS) void rsa_stem_kernel(const RsaMember* __restrict__ mem, int B, const RsaMember lone,
+                                                                    int use_onehot, const RsaTable table, float* __restrict__ ws) {
     __shared__ float Xs[RSA_STEM_XS];
     __shared__ float Red[RSA_STEM_RED];
-    rsa_stem_body(Xs, Red, emb, emb_stride, codes, L, use_onehot, table, ws, blockIdx.y, blockIdx.x * RSA_TILE);
+    const RsaMember m = rsa_member<PACKED>(mem, B, lone);
+    rsa_stem_body(Xs, Red, m.emb, m.emb_stride, m.codes, m.L, use_onehot, table, ws + m.ws_off, blockIdx.y,
+                  ((int)blockIdx.x - m.tile0) * RSA_TILE);
 }
 
 // out[j] += sum_ci Wt[ci][co] * Xs[(pb + j)][ci], ci ascending: thread (co, 8 positions); Xs rows are read as wave-wide broadcasts
@@ -230,10 +259,13 @@ __device__ __forceinline__ void rsa_conv2_body(float* Xs, float* Ps, int L, cons
     __syncthreads();
     if (t < RSA_CH) part[(size_t)(p0 / RSA_TILE) * RSA_CH + t] = ((Ps[t] + Ps[RSA_CH + t]) + Ps[2 * RSA_CH + t]) + Ps[3 * RSA_CH + t];
 }
-__global__ __launch_bounds__(RSA_THREADS) void rsa_conv2_kernel(int L, const RsaTable table, float* __restrict__ ws) {
+template <bool PACKED>
+__global__ __launch_bounds__(RSA_THREADS) void rsa_conv2_kernel(const RsaMember* __restrict__ mem, int B, const RsaMember lone,
+                                                                const RsaTable table, float* __restrict__ ws) {
     __shared__ __attribute__((aligned(16))) float Xs[(RSA_TILE + 2) * RSA_CH];
     __shared__ float Ps[4 * RSA_CH];
-    rsa_conv2_body(Xs, Ps, L, table, ws, blockIdx.y, blockIdx.x * RSA_TILE);
+    const RsaMember m = rsa_member<PACKED>(mem, B, lone);
+    rsa_conv2_body(Xs, Ps, m.L, table, ws + m.ws_off, blockIdx.y, ((int)blockIdx.x - m.tile0) * RSA_TILE);
 }
 
 // ---------------------------------------------------------------------------------------------------------------- launch 3
@@ -301,11 +333,14 @@ __device__ __forceinline__ void rsa_mix_body(float* Ys, float* Xs, float* Sc, in
         }
     }
 }
-__global__ __launch_bounds__(RSA_THREADS) void rsa_mix_kernel(int L, const RsaTable table, float* __restrict__ ws) {
+template <bool PACKED>
+__global__ __launch_bounds__(RSA_THREADS) void rsa_mix_kernel(const RsaMember* __restrict__ mem, int B, const RsaMember lone,
+                                                              const RsaTable table, float* __restrict__ ws) {
     __shared__ __attribute__((aligned(16))) float Ys[RSA_TILE * RSA_CH];
     __shared__ __attribute__((aligned(16))) float Xs[RSA_TILE * RSA_CH];
     __shared__ float Sc[RSA_MIX_SC];
-    rsa_mix_body(Ys, Xs, Sc, L, table, ws, blockIdx.y, blockIdx.x * RSA_TILE);
+    const RsaMember m = rsa_member<PACKED>(mem, B, lone);
+    rsa_mix_body(Ys, Xs, Sc, m.L, table, ws + m.ws_off, blockIdx.y, ((int)blockIdx.x - m.tile0) * RSA_TILE);
 }
 
 // ---------------------------------------------------------------------------------------------------------------- launch 4
@@ -455,87 +490,43 @@ __device__ __forceinline__ void rsa_attn_body(float* KV, float* Ys, float* Xs, i
         }
     }
 }
-__global__ __launch_bounds__(RSA_THREADS) void rsa_attn_kernel(int L, const RsaTable table, float* __restrict__ ws,
-                                                               float* __restrict__ logits, float* __restrict__ probs) {
+template <bool PACKED>
+__global__ __launch_bounds__(RSA_THREADS) void rsa_attn_kernel(const RsaMember* __restrict__ mem, int B, const RsaMember lone,
+                                                               const RsaTable table, const float* __restrict__ ws) {
     __shared__ __attribute__((aligned(16))) float KV[2 * RSA_KEYS * RSA_CH];      // K / V chunk; later the MLP's hidden tile [32][256]
     __shared__ __attribute__((aligned(16))) float Ys[RSA_TILE * RSA_CH];
     __shared__ __attribute__((aligned(16))) float Xs[RSA_TILE * RSA_CH];
-    rsa_attn_body(KV, Ys, Xs, L, table, ws, blockIdx.y, blockIdx.x * RSA_TILE, logits, probs);
-}
-
-// ---- several alignments per launch (rnamsm_rsa_head_packed) --------------------------------------------------------------------
-// Every member has its own K model slabs in the workspace (floats [ws_off, ws_off + K * rsa_model_floats(L)) behind the descriptor
-// table): its tile sums, K and V live there, so the squeeze mean and the attention keys of a member are its own and nothing else.
-// A launch has the SUM of the members' 32-position tiles as gridDim.x (gridDim.y = the model, as in the lone launches), and a
-// block finds its member by a binary search over the tile prefix sums of the descriptor table (B <= 1024: at most ten
-// wave-uniform loads of a table that stays in L2).  From there on it runs the lone kernel's body on the member's own
-// (embedding, L, workspace base, tile): the same bits.
-struct RsaMember {           // 64 bytes
-    const float* emb;
-    int64_t emb_stride;
-    const uint8_t* codes;
-    float* logits;
-    float* probs;
-    int64_t ws_off;          // floats of the members' slabs before it
-    int32_t L;
-    int32_t tile0;           // tiles of the members before it
-    int32_t pad_[2];
-};
-static_assert(sizeof(RsaMember) == 64, "RsaMember layout");
-
-__device__ __forceinline__ int rsa_member_of_tile(const RsaMember* __restrict__ mem, int B, int tile) {
-    int lo = 0, hi = B;      // mem[lo].tile0 <= tile < mem[hi].tile0 (mem[B].tile0 = the grid)
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (mem[mid].tile0 <= tile) lo = mid;
-        else hi = mid;
-    }
-    return lo;
-}
-
-__global__ __launch_bounds__(RSA_STEM_THREADS) void rsa_stem_packed_kernel(const RsaMember* __restrict__ mem, int B, int use_onehot,
-                                                                           const RsaTable table, float* __restrict__ ws) {
-    __shared__ float Xs[RSA_STEM_XS];
-    __shared__ float Red[RSA_STEM_RED];
-    const RsaMember* b = mem + rsa_member_of_tile(mem, B, (int)blockIdx.x);
-    rsa_stem_body(Xs, Red, b->emb, b->emb_stride, b->codes, b->L, use_onehot, table, ws + b->ws_off, blockIdx.y,
-                  ((int)blockIdx.x - b->tile0) * RSA_TILE);
-}
-
-__global__ __launch_bounds__(RSA_THREADS) void rsa_conv2_packed_kernel(const RsaMember* __restrict__ mem, int B, const RsaTable table,
-                                                                       float* __restrict__ ws) {
-    __shared__ __attribute__((aligned(16))) float Xs[(RSA_TILE + 2) * RSA_CH];
-    __shared__ float Ps[4 * RSA_CH];
-    const RsaMember* b = mem + rsa_member_of_tile(mem, B, (int)blockIdx.x);
-    rsa_conv2_body(Xs, Ps, b->L, table, ws + b->ws_off, blockIdx.y, ((int)blockIdx.x - b->tile0) * RSA_TILE);
-}
-
-__global__ __launch_bounds__(RSA_THREADS) void rsa_mix_packed_kernel(const RsaMember* __restrict__ mem, int B, const RsaTable table,
-                                                                     float* __restrict__ ws) {
-    __shared__ __attribute__((aligned(16))) float Ys[RSA_TILE * RSA_CH];
-    __shared__ __attribute__((aligned(16))) float Xs[RSA_TILE * RSA_CH];
-    __shared__ float Sc[RSA_MIX_SC];
-    const RsaMember* b = mem + rsa_member_of_tile(mem, B, (int)blockIdx.x);
-    rsa_mix_body(Ys, Xs, Sc, b->L, table, ws + b->ws_off, blockIdx.y, ((int)blockIdx.x - b->tile0) * RSA_TILE);
-}
-
-__global__ __launch_bounds__(RSA_THREADS) void rsa_attn_packed_kernel(const RsaMember* __restrict__ mem, int B, const RsaTable table,
-                                                                      const float* __restrict__ ws) {
-    __shared__ __attribute__((aligned(16))) float KV[2 * RSA_KEYS * RSA_CH];
-    __shared__ __attribute__((aligned(16))) float Ys[RSA_TILE * RSA_CH];
-    __shared__ __attribute__((aligned(16))) float Xs[RSA_TILE * RSA_CH];
-    const RsaMember* b = mem + rsa_member_of_tile(mem, B, (int)blockIdx.x);
-    rsa_attn_body(KV, Ys, Xs, b->L, table, ws + b->ws_off, blockIdx.y, ((int)blockIdx.x - b->tile0) * RSA_TILE, b->logits, b->probs);
-}
-
-// The descriptors travel as kernel arguments, 32 (2 KB) per launch, on the caller's stream: no host buffer has to outlive the call
-// (as rnamsm_ss_head_packed's do).
-struct RsaMemberChunk { RsaMember m[32]; };
-__global__ void rsa_members_kernel(RsaMemberChunk chunk, int n, RsaMember* __restrict__ dev) {
-    if ((int)threadIdx.x < n) dev[threadIdx.x] = chunk.m[threadIdx.x];
+    const RsaMember m = rsa_member<PACKED>(mem, B, lone);
+    rsa_attn_body(KV, Ys, Xs, m.L, table, ws + m.ws_off, blockIdx.y, ((int)blockIdx.x - m.tile0) * RSA_TILE, m.logits, m.probs);
 }
 
 constexpr size_t rsa_members_bytes(int B) { return ((size_t)B * sizeof(RsaMember) + 255) & ~(size_t)255; }
+
+// The four launches over `tiles` tiles of n_models models each: PACKED with mem / B the uploaded table of a batch, else null / 1
+// and the lone member.  weights: checked by the caller.
+template <bool PACKED>
+int rsa_launch(const RsaMember* mem, int B, const RsaMember& lone, int64_t tiles, int n_models, int use_onehot,
+               const void* const* weights, float* ws, hipStream_t s) {
+    const int nw = RNAMSM_RSA_GLOBAL_WEIGHTS + RNAMSM_RSA_WEIGHTS_PER_MODEL * n_models;
+    RsaTable table;
+    for (int i = 0; i < RSA_TABLE_MAX; ++i) table.p[i] = i < nw ? weights[i] : nullptr;
+    const dim3 grid((unsigned)tiles, (unsigned)n_models);      // the members' own tiles, nothing for a short member beside a long one
+    hipLaunchKernelGGL(rsa_stem_kernel<PACKED>, grid, dim3(RSA_STEM_THREADS), 0, s, mem, B, lone, use_onehot ? 1 : 0, table, ws);
+    RNAMSM_CHECK_LAUNCH(PACKED ? "rsa_stem (packed)" : "rsa_stem");
+    hipLaunchKernelGGL(rsa_conv2_kernel<PACKED>, grid, dim3(RSA_THREADS), 0, s, mem, B, lone, table, ws);
+    RNAMSM_CHECK_LAUNCH(PACKED ? "rsa_conv2 (packed)" : "rsa_conv2");
+    hipLaunchKernelGGL(rsa_mix_kernel<PACKED>, grid, dim3(RSA_THREADS), 0, s, mem, B, lone, table, ws);
+    RNAMSM_CHECK_LAUNCH(PACKED ? "rsa_mix (packed)" : "rsa_mix");
+    hipLaunchKernelGGL(rsa_attn_kernel<PACKED>, grid, dim3(RSA_THREADS), 0, s, mem, B, lone, table, ws);
+    RNAMSM_CHECK_LAUNCH(PACKED ? "rsa_attn (packed)" : "rsa_attn");
+    return RNAMSM_OK;
+}
+
+// the entries of the table that a call reads: all, but for the one-hot statistics (2, 3) of an embedding-only ensemble
+int rsa_check_weights(const char* prefix, const void* const* weights, int n_models, int use_onehot) {
+    return check_weight_table(prefix, weights, RNAMSM_RSA_GLOBAL_WEIGHTS + RNAMSM_RSA_WEIGHTS_PER_MODEL * n_models,
+                              use_onehot ? 0u : 0xCu);
+}
 
 }  // namespace
 }  // namespace rnamsm
@@ -560,27 +551,10 @@ extern "C" int rnamsm_rsa_head(const float* emb, int64_t emb_row_stride, const u
     RNAMSM_CHECK_ARG(aligned16(workspace) && aligned16(emb), "rsa_head: 16-byte alignment of the embedding and the workspace");
     RNAMSM_CHECK_ARG((!probs || (reinterpret_cast<uintptr_t>(probs) & 3u) == 0) && (!logits || (reinterpret_cast<uintptr_t>(logits) & 3u) == 0),
                      "rsa_head: misaligned output");
-    const int nw = RNAMSM_RSA_GLOBAL_WEIGHTS + RNAMSM_RSA_WEIGHTS_PER_MODEL * n_models;
-    for (int i = 0; i < nw; ++i) {
-        if (!use_onehot && (i == 2 || i == 3)) continue;        // the one-hot statistics are not read
-        RNAMSM_CHECK_ARG(weights[i], "rsa_head: weight pointer %d is null", i);
-        RNAMSM_CHECK_ARG(aligned16(weights[i]), "rsa_head: weight pointer %d is not 16-byte aligned", i);
-    }
-    RsaTable table;
-    for (int i = 0; i < RSA_TABLE_MAX; ++i) table.p[i] = i < nw ? weights[i] : nullptr;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    float* ws = static_cast<float*>(workspace);
-    const dim3 grid((unsigned)((L + RSA_TILE - 1) / RSA_TILE), (unsigned)n_models);
-    hipLaunchKernelGGL(rsa_stem_kernel, grid, dim3(RSA_STEM_THREADS), 0, s, emb, emb_row_stride, base_codes, L, use_onehot ? 1 : 0,
-                       table, ws);
-    RNAMSM_CHECK_LAUNCH("rsa_stem");
-    hipLaunchKernelGGL(rsa_conv2_kernel, grid, dim3(RSA_THREADS), 0, s, L, table, ws);
-    RNAMSM_CHECK_LAUNCH("rsa_conv2");
-    hipLaunchKernelGGL(rsa_mix_kernel, grid, dim3(RSA_THREADS), 0, s, L, table, ws);
-    RNAMSM_CHECK_LAUNCH("rsa_mix");
-    hipLaunchKernelGGL(rsa_attn_kernel, grid, dim3(RSA_THREADS), 0, s, L, table, ws, logits, probs);
-    RNAMSM_CHECK_LAUNCH("rsa_attn");
-    return RNAMSM_OK;
+    if (int rc = rsa_check_weights("rsa_head", weights, n_models, use_onehot)) return rc;
+    const RsaMember lone = {emb, emb_row_stride, base_codes, logits, probs, 0, L, 0, {0, 0}};
+    return rsa_launch<false>(nullptr, 1, lone, (L + RSA_TILE - 1) / RSA_TILE, n_models, use_onehot, weights, static_cast<float*>(workspace),
+                             static_cast<hipStream_t>(stream));
 }
 
 extern "C" size_t rnamsm_rsa_head_packed_workspace_bytes(int B, const int* Ls, int n_models) {
@@ -618,52 +592,19 @@ extern "C" int rnamsm_rsa_head_packed(const rnamsm_rsa_item* items, int B, int n
     }
     RNAMSM_CHECK_ARG(aligned16(workspace), "rsa_head_packed: 16-byte alignment of the workspace");
     RNAMSM_CHECK_ARG(workspace_bytes >= rsa_members_bytes(B) + floats * sizeof(float), "rsa_head_packed: workspace too small");
-    const int nw = RNAMSM_RSA_GLOBAL_WEIGHTS + RNAMSM_RSA_WEIGHTS_PER_MODEL * n_models;
-    for (int i = 0; i < nw; ++i) {
-        if (!use_onehot && (i == 2 || i == 3)) continue;        // the one-hot statistics are not read
-        RNAMSM_CHECK_ARG(weights[i], "rsa_head_packed: weight pointer %d is null", i);
-        RNAMSM_CHECK_ARG(aligned16(weights[i]), "rsa_head_packed: weight pointer %d is not 16-byte aligned", i);
-    }
-    RsaTable table;
-    for (int i = 0; i < RSA_TABLE_MAX; ++i) table.p[i] = i < nw ? weights[i] : nullptr;
+    if (int rc = rsa_check_weights("rsa_head_packed", weights, n_models, use_onehot)) return rc;
     hipStream_t s = static_cast<hipStream_t>(stream);
     RsaMember* mem = static_cast<RsaMember*>(workspace);
-    float* ws = reinterpret_cast<float*>(static_cast<char*>(workspace) + rsa_members_bytes(B));
     int64_t ws_off = 0;
     int32_t tile0 = 0;
-    for (int b0 = 0; b0 < B; b0 += 32) {
-        RsaMemberChunk chunk;
-        const int n = B - b0 < 32 ? B - b0 : 32;
-        for (int i = 0; i < 32; ++i) {
-            RsaMember& m = chunk.m[i];
-            if (i >= n) {
-                m = chunk.m[0];
-                continue;
-            }
-            const rnamsm_rsa_item& it = items[b0 + i];
-            m.emb = it.emb;
-            m.emb_stride = it.emb_row_stride;
-            m.codes = it.base_codes;
-            m.logits = it.logits;
-            m.probs = it.probs;
-            m.ws_off = ws_off;
-            m.L = it.L;
-            m.tile0 = tile0;
-            m.pad_[0] = m.pad_[1] = 0;
-            ws_off += (int64_t)n_models * (int64_t)rsa_model_floats(it.L);
-            tile0 += (it.L + RSA_TILE - 1) / RSA_TILE;
-        }
-        hipLaunchKernelGGL(rsa_members_kernel, dim3(1), dim3(32), 0, s, chunk, n, mem + b0);
-        RNAMSM_CHECK_LAUNCH("rsa_members");
-    }
-    const dim3 grid((unsigned)tiles_total, (unsigned)n_models);      // the members' own tiles, nothing for a short member beside a long one
-    hipLaunchKernelGGL(rsa_stem_packed_kernel, grid, dim3(RSA_STEM_THREADS), 0, s, mem, B, use_onehot ? 1 : 0, table, ws);
-    RNAMSM_CHECK_LAUNCH("rsa_stem (packed)");
-    hipLaunchKernelGGL(rsa_conv2_packed_kernel, grid, dim3(RSA_THREADS), 0, s, mem, B, table, ws);
-    RNAMSM_CHECK_LAUNCH("rsa_conv2 (packed)");
-    hipLaunchKernelGGL(rsa_mix_packed_kernel, grid, dim3(RSA_THREADS), 0, s, mem, B, table, ws);
-    RNAMSM_CHECK_LAUNCH("rsa_mix (packed)");
-    hipLaunchKernelGGL(rsa_attn_packed_kernel, grid, dim3(RSA_THREADS), 0, s, mem, B, table, ws);
-    RNAMSM_CHECK_LAUNCH("rsa_attn (packed)");
-    return RNAMSM_OK;
+    const int rc = upload_members(mem, B, [&](int b) {
+        const rnamsm_rsa_item& it = items[b];
+        const RsaMember m = {it.emb, it.emb_row_stride, it.base_codes, it.logits, it.probs, ws_off, it.L, tile0, {0, 0}};
+        ws_off += (int64_t)n_models * (int64_t)rsa_model_floats(it.L);
+        tile0 += (it.L + RSA_TILE - 1) / RSA_TILE;
+        return m;
+    }, s, "rsa_members");
+    if (rc != RNAMSM_OK) return rc;
+    return rsa_launch<true>(mem, B, RsaMember{}, tiles_total, n_models, use_onehot, weights,
+                            reinterpret_cast<float*>(static_cast<char*>(workspace) + rsa_members_bytes(B)), s);
 }

@@ -143,11 +143,37 @@ __device__ __forceinline__ void store_tile(const f32x4 (&acc)[2][3], const float
     }
 }
 
+// ---- the member of a block ------------------------------------------------------------------------------------------------------
+// One kernel per stage serves the lone call (rnamsm_ss_head) and the batched one (rnamsm_ss_head_packed).  The images of a batch lie
+// back to back in the two workspace images (member b's first pixel is pixel pix0 of the buffer), and a launch has the SUM of the
+// members' tiles as a flat grid.  Batched, mem is the device table of the B members and a block finds its own by a search over the
+// tile prefix sums (common.h: member_of); lone, mem is null and the one member is the kernel argument itself (tile0 = 0, pix0 = 0:
+// the caller's workspace with no table in front).  Either way the stage's body runs on the member's own (image, L, tile): one
+// arithmetic, so a structure's bits depend on nothing else.
+// The choice is a template argument, not a test of mem: one definition, two code objects.  With the test inside the kernel the
+// compiler reads the descriptor through ONE flat load of a selected address (table or kernel argument) and L, the offsets and the
+// pointers land in vector registers: +5 to +14 VGPRs over the lone kernels in every stage.
+struct SsMember {            // 64 bytes
+    const float* atp;
+    int64_t plane_stride;
+    const uint8_t* codes;
+    float* logits;
+    float* probs;
+    int64_t pix0;            // pixels of the members before it
+    int32_t L, tiles;        // tiles = ceil(L / 16): its launches' share is tiles x tiles blocks, row by row
+    int32_t tile0;           // blocks of the members before it
+    int32_t pad_;
+};
+static_assert(sizeof(SsMember) == 64, "SsMember layout");
+template <bool PACKED, class K, class F>
+__device__ __forceinline__ SsMember ss_member(const SsMember* __restrict__ mem, int B, const SsMember& lone, K key, F SsMember::*field) {
+    if (PACKED) return mem[member_of(mem, B, key, field)];
+    return lone;
+}
+
 // Stem: 3x3, 128 -> 48 with bias.  The input planes are built while staging: one-hot channels from the base codes
 // (0..3 = A, C, G, U; any other value = the all-zero vector of OneHotEncoder(handle_unknown='ignore')), the 120 maps read
 // in place from atp (plane c - 8 at c_plane_stride * (c - 8), rows of L floats).  Four chunks of 32 channels.
-// The body is shared by the lone kernel (tile from blockIdx, one image) and the packed one (tile and image from a descriptor):
-// one arithmetic, so a structure's bits do not depend on which of the two ran it.
 __device__ __forceinline__ void ss_stem_body(float* S, const float* __restrict__ atp, int64_t plane_stride,
                                              const uint8_t* __restrict__ codes, const float* __restrict__ w,
                                              const float* __restrict__ bias, float* __restrict__ out, int L, int y0, int x0) {
@@ -174,12 +200,15 @@ __device__ __forceinline__ void ss_stem_body(float* S, const float* __restrict__
     }
     store_tile<false>(acc, bias, out, y0, x0, L);
 }
-__global__ __launch_bounds__(SS_THREADS) void ss_stem_kernel(const float* __restrict__ atp, int64_t plane_stride,
-                                                             const uint8_t* __restrict__ codes, const float* __restrict__ w,
-                                                             const float* __restrict__ bias, float* __restrict__ out, int L) {
+template <bool PACKED>
+__global__ __launch_bounds__(SS_THREADS) void ss_stem_kernel(const SsMember* __restrict__ mem, int B, const SsMember lone,
+                                                             const float* __restrict__ w, const float* __restrict__ bias,
+                                                             float* __restrict__ out) {
     extern __shared__ f32x4 ss_smem[];
-    ss_stem_body(reinterpret_cast<float*>(ss_smem), atp, plane_stride, codes, w, bias, out, L, blockIdx.y * SS_TILE,
-                 blockIdx.x * SS_TILE);
+    const SsMember m = ss_member<PACKED>(mem, B, lone, (int)blockIdx.x, &SsMember::tile0);
+    const int t = (int)blockIdx.x - m.tile0, ty = t / m.tiles, tx = t - ty * m.tiles;
+    ss_stem_body(reinterpret_cast<float*>(ss_smem), m.atp, m.plane_stride, m.codes, w, bias, out + (size_t)m.pix0 * SS_CH, m.L,
+                 ty * SS_TILE, tx * SS_TILE);
 }
 
 // Trunk conv: out (+)= conv_KS(relu(LN(x))), 48 -> 48, no bias.  RESIDUAL: out is the residual stream, updated in place.
@@ -212,13 +241,17 @@ __device__ __forceinline__ void ss_conv_body(float* S, const float* __restrict__
     window_mma<KS, 3>(S, SW, SS_LDC, w, SS_CH, 0, acc);
     store_tile<RESIDUAL>(acc, nullptr, out, y0, x0, L);
 }
-template <int KS, bool RESIDUAL>
-__global__ __launch_bounds__(SS_THREADS) void ss_conv_kernel(const float* __restrict__ x, const float* __restrict__ gamma,
+template <int KS, bool RESIDUAL, bool PACKED>
+__global__ __launch_bounds__(SS_THREADS) void ss_conv_kernel(const SsMember* __restrict__ mem, int B, const SsMember lone,
+                                                             const float* __restrict__ x, const float* __restrict__ gamma,
                                                              const float* __restrict__ beta, const float* __restrict__ w,
-                                                             float* out, int L) {
+                                                             float* out) {
     extern __shared__ f32x4 ss_smem[];
-    ss_conv_body<KS, RESIDUAL>(reinterpret_cast<float*>(ss_smem), x, gamma, beta, w, out, L, blockIdx.y * SS_TILE,
-                               blockIdx.x * SS_TILE);
+    const SsMember m = ss_member<PACKED>(mem, B, lone, (int)blockIdx.x, &SsMember::tile0);
+    const int t = (int)blockIdx.x - m.tile0, ty = t / m.tiles, tx = t - ty * m.tiles;
+    const size_t off = (size_t)m.pix0 * SS_CH;
+    ss_conv_body<KS, RESIDUAL>(reinterpret_cast<float*>(ss_smem), x + off, gamma, beta, w, out + off, m.L, ty * SS_TILE,
+                               tx * SS_TILE);
 }
 
 // Head: logits = fc1(relu(LN(x))) (fc1: Linear(48, 1)), probs = sigmoid(logits); one thread per pixel.
@@ -241,90 +274,16 @@ __device__ __forceinline__ void ss_out_body(const float* __restrict__ pixel, con
     if (logits) logits[i] = z;
     if (probs) probs[i] = 1.f / (1.f + expf(-z));
 }
-__global__ __launch_bounds__(256) void ss_out_kernel(const float* __restrict__ x, const float* __restrict__ gamma,
+// n pixels of the whole buffer; a thread finds its pixel's member by the pixel prefix sums
+template <bool PACKED>
+__global__ __launch_bounds__(256) void ss_out_kernel(const SsMember* __restrict__ mem, int B, const SsMember lone,
+                                                     const float* __restrict__ x, const float* __restrict__ gamma,
                                                      const float* __restrict__ beta, const float* __restrict__ fw,
-                                                     const float* __restrict__ fb, float* __restrict__ logits,
-                                                     float* __restrict__ probs, int64_t n) {
+                                                     const float* __restrict__ fb, int64_t n) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
-    ss_out_body(x + i * SS_CH, gamma, beta, fw, fb, logits, probs, i);
-}
-
-// ---- several structures per launch (rnamsm_ss_head_packed) ---------------------------------------------------------------------
-// The images of a batch lie back to back in the two workspace images (member b's first pixel is pixel pix0 of the buffer); a
-// launch has the SUM of the members' tiles as a flat grid, and a block finds its member by a binary search over the tile prefix
-// sums of this descriptor table (B <= 1024: at most ten wave-uniform loads of a table that stays in L2).  From there on it runs
-// the lone kernel's body on the member's own (image, L, tile): the same bits.
-struct SsMember {            // 64 bytes
-    const float* atp;
-    int64_t plane_stride;
-    const uint8_t* codes;
-    float* logits;
-    float* probs;
-    int64_t pix0;            // pixels of the members before it
-    int32_t L, tiles;        // tiles = ceil(L / 16): its launches' share is tiles x tiles blocks
-    int32_t tile0;           // blocks of the members before it
-    int32_t pad_;
-};
-static_assert(sizeof(SsMember) == 64, "SsMember layout");
-
-__device__ __forceinline__ int ss_member_of_tile(const SsMember* __restrict__ mem, int B, int tile) {
-    int lo = 0, hi = B;      // mem[lo].tile0 <= tile < mem[hi].tile0 (mem[B].tile0 = the grid)
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (mem[mid].tile0 <= tile) lo = mid;
-        else hi = mid;
-    }
-    return lo;
-}
-__device__ __forceinline__ int ss_member_of_pixel(const SsMember* __restrict__ mem, int B, int64_t pixel) {
-    int lo = 0, hi = B;
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (mem[mid].pix0 <= pixel) lo = mid;
-        else hi = mid;
-    }
-    return lo;
-}
-
-__global__ __launch_bounds__(SS_THREADS) void ss_stem_packed_kernel(const SsMember* __restrict__ mem, int B,
-                                                                    const float* __restrict__ w, const float* __restrict__ bias,
-                                                                    float* __restrict__ out) {
-    extern __shared__ f32x4 ss_smem[];
-    const SsMember m = mem[ss_member_of_tile(mem, B, (int)blockIdx.x)];
-    const int t = (int)blockIdx.x - m.tile0, ty = t / m.tiles, tx = t - ty * m.tiles;
-    ss_stem_body(reinterpret_cast<float*>(ss_smem), m.atp, m.plane_stride, m.codes, w, bias, out + (size_t)m.pix0 * SS_CH, m.L,
-                 ty * SS_TILE, tx * SS_TILE);
-}
-
-template <int KS, bool RESIDUAL>
-__global__ __launch_bounds__(SS_THREADS) void ss_conv_packed_kernel(const SsMember* __restrict__ mem, int B,
-                                                                    const float* __restrict__ x, const float* __restrict__ gamma,
-                                                                    const float* __restrict__ beta, const float* __restrict__ w,
-                                                                    float* out) {
-    extern __shared__ f32x4 ss_smem[];
-    const SsMember* m = mem + ss_member_of_tile(mem, B, (int)blockIdx.x);
-    const int L = m->L, tiles = m->tiles, t = (int)blockIdx.x - m->tile0, ty = t / tiles, tx = t - ty * tiles;
-    const size_t off = (size_t)m->pix0 * SS_CH;
-    ss_conv_body<KS, RESIDUAL>(reinterpret_cast<float*>(ss_smem), x + off, gamma, beta, w, out + off, L, ty * SS_TILE,
-                               tx * SS_TILE);
-}
-
-__global__ __launch_bounds__(256) void ss_out_packed_kernel(const SsMember* __restrict__ mem, int B, const float* __restrict__ x,
-                                                            const float* __restrict__ gamma, const float* __restrict__ beta,
-                                                            const float* __restrict__ fw, const float* __restrict__ fb,
-                                                            int64_t n) {
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= n) return;
-    const SsMember* m = mem + ss_member_of_pixel(mem, B, i);
-    ss_out_body(x + i * SS_CH, gamma, beta, fw, fb, m->logits, m->probs, i - m->pix0);
-}
-
-// The descriptors travel as kernel arguments, 32 (2 KB) per launch, on the caller's stream: no host buffer has to outlive the call
-// (packed_descriptors_upload does the same for PackedMsa).
-struct SsMemberChunk { SsMember m[32]; };
-__global__ void ss_members_kernel(SsMemberChunk chunk, int n, SsMember* __restrict__ dev) {
-    if ((int)threadIdx.x < n) dev[threadIdx.x] = chunk.m[threadIdx.x];
+    const SsMember m = ss_member<PACKED>(mem, B, lone, i, &SsMember::pix0);
+    ss_out_body(x + i * SS_CH, gamma, beta, fw, fb, m.logits, m.probs, i - m.pix0);
 }
 
 constexpr size_t ss_members_bytes(int B) { return ((size_t)B * sizeof(SsMember) + 255) & ~(size_t)255; }
@@ -337,6 +296,43 @@ int allow_lds(K kernel, size_t bytes, DeviceOnce& once) {
         once.mark();
     }
     return RNAMSM_OK;
+}
+
+// The launches over `blocks` tiles and `pixels` pixels (xs, ts: the two [pixels][48] images): PACKED with mem / B the uploaded table
+// of a batch, else null / 1 and the lone member.  weights: checked by the caller; conv1.weight, conv1.bias, bn1.weight, bn1.bias,
+// then per block conv1.weight, bn1.weight, bn1.bias, conv2.weight, bn2.weight, bn2.bias, then fc1.weight, fc1.bias (include/rnamsm.h)
+template <bool PACKED>
+int ss_launch(const SsMember* mem, int B, const SsMember& lone, int64_t blocks, int64_t pixels, int num_blocks,
+              const float* const* weights, float* xs, hipStream_t s) {
+    float* ts = xs + (size_t)pixels * SS_CH;
+    const dim3 grid((unsigned)blocks);           // the members' own tiles, nothing for a small member beside a large one
+    hipLaunchKernelGGL(ss_stem_kernel<PACKED>, grid, dim3(SS_THREADS), SS_STEM_LDS_BYTES, s, mem, B, lone, weights[0], weights[1], xs);
+    RNAMSM_CHECK_LAUNCH(PACKED ? "ss_stem (packed)" : "ss_stem");
+    for (int k = 0; k < num_blocks; ++k) {
+        const float* const* bw = weights + 4 + RNAMSM_SS_WEIGHTS_PER_BLOCK * k;
+        hipLaunchKernelGGL((ss_conv_kernel<3, false, PACKED>), grid, dim3(SS_THREADS), ss_trunk_lds_bytes(3), s, mem, B, lone, xs, bw[1], bw[2],
+                           bw[0], ts);
+        RNAMSM_CHECK_LAUNCH(PACKED ? "ss_conv3x3 (packed)" : "ss_conv3x3");
+        hipLaunchKernelGGL((ss_conv_kernel<5, true, PACKED>), grid, dim3(SS_THREADS), ss_trunk_lds_bytes(5), s, mem, B, lone, ts, bw[4], bw[5],
+                           bw[3], xs);
+        RNAMSM_CHECK_LAUNCH(PACKED ? "ss_conv5x5 (packed)" : "ss_conv5x5");
+    }
+    const float* const* hw = weights + 4 + RNAMSM_SS_WEIGHTS_PER_BLOCK * num_blocks;
+    hipLaunchKernelGGL(ss_out_kernel<PACKED>, dim3((unsigned)((pixels + 255) / 256)), dim3(256), 0, s, mem, B, lone, xs, weights[2], weights[3],
+                       hw[0], hw[1], pixels);
+    RNAMSM_CHECK_LAUNCH(PACKED ? "ss_out (packed)" : "ss_out");
+    return RNAMSM_OK;
+}
+
+// the last step before anything is enqueued: the weight table, then the dynamic LDS of the kernels ss_launch<PACKED> runs, once per device
+template <bool PACKED>
+int ss_check_weights_and_lds(const char* prefix, const float* const* weights, int num_blocks) {
+    static DeviceOnce once_stem, once3, once5;
+    int rc = check_weight_table(prefix, weights, RNAMSM_SS_GLOBAL_WEIGHTS + RNAMSM_SS_WEIGHTS_PER_BLOCK * num_blocks);
+    if (rc == RNAMSM_OK) rc = allow_lds(ss_stem_kernel<PACKED>, SS_STEM_LDS_BYTES, once_stem);
+    if (rc == RNAMSM_OK) rc = allow_lds(ss_conv_kernel<3, false, PACKED>, ss_trunk_lds_bytes(3), once3);
+    if (rc == RNAMSM_OK) rc = allow_lds(ss_conv_kernel<5, true, PACKED>, ss_trunk_lds_bytes(5), once5);
+    return rc;
 }
 
 }  // namespace
@@ -360,41 +356,11 @@ extern "C" int rnamsm_ss_head(const float* atp, int64_t atp_plane_stride, const 
     RNAMSM_CHECK_ARG(atp_plane_stride >= (int64_t)L * L, "ss_head: atp plane stride %lld < L*L", (long long)atp_plane_stride);
     RNAMSM_CHECK_ARG(workspace_bytes >= rnamsm_ss_head_workspace_bytes(L), "ss_head: workspace too small");
     RNAMSM_CHECK_ARG(aligned16(workspace), "ss_head: 16-byte alignment of the workspace");
-    const int nw = RNAMSM_SS_GLOBAL_WEIGHTS + RNAMSM_SS_WEIGHTS_PER_BLOCK * num_blocks;
-    for (int i = 0; i < nw; ++i) {
-        RNAMSM_CHECK_ARG(weights[i], "ss_head: weight pointer %d is null", i);
-        RNAMSM_CHECK_ARG(aligned16(weights[i]), "ss_head: weight pointer %d is not 16-byte aligned", i);
-    }
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    float* xs = static_cast<float*>(workspace);
-    float* ts = xs + (size_t)L * L * SS_CH;
-    static DeviceOnce once_stem, once3, once5;
-    int rc;
-    if ((rc = allow_lds(ss_stem_kernel, SS_STEM_LDS_BYTES, once_stem)) != RNAMSM_OK) return rc;
-    if ((rc = allow_lds(ss_conv_kernel<3, false>, ss_trunk_lds_bytes(3), once3)) != RNAMSM_OK) return rc;
-    if ((rc = allow_lds(ss_conv_kernel<5, true>, ss_trunk_lds_bytes(5), once5)) != RNAMSM_OK) return rc;
-    const unsigned tiles = (unsigned)((L + SS_TILE - 1) / SS_TILE);
-    const dim3 grid(tiles, tiles);
-    // weight table: conv1.weight, conv1.bias, bn1.weight, bn1.bias, then per block conv1.weight, bn1.weight, bn1.bias,
-    // conv2.weight, bn2.weight, bn2.bias, then fc1.weight, fc1.bias (include/rnamsm.h)
-    hipLaunchKernelGGL(ss_stem_kernel, grid, dim3(SS_THREADS), SS_STEM_LDS_BYTES, s, atp, atp_plane_stride, base_codes, weights[0],
-                       weights[1], xs, L);
-    RNAMSM_CHECK_LAUNCH("ss_stem");
-    for (int k = 0; k < num_blocks; ++k) {
-        const float* const* bw = weights + 4 + RNAMSM_SS_WEIGHTS_PER_BLOCK * k;
-        hipLaunchKernelGGL((ss_conv_kernel<3, false>), grid, dim3(SS_THREADS), ss_trunk_lds_bytes(3), s, xs, bw[1], bw[2], bw[0],
-                           ts, L);
-        RNAMSM_CHECK_LAUNCH("ss_conv3x3");
-        hipLaunchKernelGGL((ss_conv_kernel<5, true>), grid, dim3(SS_THREADS), ss_trunk_lds_bytes(5), s, ts, bw[4], bw[5], bw[3],
-                           xs, L);
-        RNAMSM_CHECK_LAUNCH("ss_conv5x5");
-    }
-    const float* const* hw = weights + 4 + RNAMSM_SS_WEIGHTS_PER_BLOCK * num_blocks;
-    const int64_t n = (int64_t)L * L;
-    hipLaunchKernelGGL(ss_out_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, xs, weights[2], weights[3], hw[0], hw[1],
-                       logits, probs, n);
-    RNAMSM_CHECK_LAUNCH("ss_out");
-    return RNAMSM_OK;
+    if (int rc = ss_check_weights_and_lds<false>("ss_head", weights, num_blocks)) return rc;
+    const int tiles = (L + SS_TILE - 1) / SS_TILE;
+    const SsMember lone = {atp, atp_plane_stride, base_codes, logits, probs, 0, L, tiles, 0, 0};
+    return ss_launch<false>(nullptr, 1, lone, (int64_t)tiles * tiles, (int64_t)L * L, num_blocks, weights, static_cast<float*>(workspace),
+                            static_cast<hipStream_t>(stream));
 }
 
 extern "C" size_t rnamsm_ss_head_packed_workspace_bytes(int B, const int* Ls) {
@@ -431,63 +397,20 @@ extern "C" int rnamsm_ss_head_packed(const rnamsm_ss_item* items, int B, int num
     RNAMSM_CHECK_ARG(aligned16(workspace), "ss_head_packed: 16-byte alignment of the workspace");
     RNAMSM_CHECK_ARG(workspace_bytes >= ss_members_bytes(B) + 2 * (size_t)pixels * SS_CH * sizeof(float),
                      "ss_head_packed: workspace too small");
-    const int nw = RNAMSM_SS_GLOBAL_WEIGHTS + RNAMSM_SS_WEIGHTS_PER_BLOCK * num_blocks;
-    for (int i = 0; i < nw; ++i) {
-        RNAMSM_CHECK_ARG(weights[i], "ss_head_packed: weight pointer %d is null", i);
-        RNAMSM_CHECK_ARG(aligned16(weights[i]), "ss_head_packed: weight pointer %d is not 16-byte aligned", i);
-    }
+    if (int rc = ss_check_weights_and_lds<true>("ss_head_packed", weights, num_blocks)) return rc;
     hipStream_t s = static_cast<hipStream_t>(stream);
     SsMember* mem = static_cast<SsMember*>(workspace);
-    float* xs = reinterpret_cast<float*>(static_cast<char*>(workspace) + ss_members_bytes(B));
-    float* ts = xs + (size_t)pixels * SS_CH;
-    static DeviceOnce once_stem, once3, once5;
-    int rc;
-    if ((rc = allow_lds(ss_stem_packed_kernel, SS_STEM_LDS_BYTES, once_stem)) != RNAMSM_OK) return rc;
-    if ((rc = allow_lds(ss_conv_packed_kernel<3, false>, ss_trunk_lds_bytes(3), once3)) != RNAMSM_OK) return rc;
-    if ((rc = allow_lds(ss_conv_packed_kernel<5, true>, ss_trunk_lds_bytes(5), once5)) != RNAMSM_OK) return rc;
     int64_t pix0 = 0;
     int32_t tile0 = 0;
-    for (int b0 = 0; b0 < B; b0 += 32) {
-        SsMemberChunk chunk;
-        const int n = B - b0 < 32 ? B - b0 : 32;
-        for (int i = 0; i < 32; ++i) {
-            SsMember& m = chunk.m[i];
-            if (i >= n) {
-                m = chunk.m[0];
-                continue;
-            }
-            const rnamsm_ss_item& it = items[b0 + i];
-            m.atp = it.atp;
-            m.plane_stride = it.atp_plane_stride;
-            m.codes = it.base_codes;
-            m.logits = it.logits;
-            m.probs = it.probs;
-            m.pix0 = pix0;
-            m.L = it.L;
-            m.tiles = (it.L + SS_TILE - 1) / SS_TILE;
-            m.tile0 = tile0;
-            m.pad_ = 0;
-            pix0 += (int64_t)it.L * it.L;
-            tile0 += m.tiles * m.tiles;
-        }
-        hipLaunchKernelGGL(ss_members_kernel, dim3(1), dim3(32), 0, s, chunk, n, mem + b0);
-        RNAMSM_CHECK_LAUNCH("ss_members");
-    }
-    const dim3 grid((unsigned)tiles_total);          // the members' own tiles, nothing for a small member beside a large one
-    hipLaunchKernelGGL(ss_stem_packed_kernel, grid, dim3(SS_THREADS), SS_STEM_LDS_BYTES, s, mem, B, weights[0], weights[1], xs);
-    RNAMSM_CHECK_LAUNCH("ss_stem (packed)");
-    for (int k = 0; k < num_blocks; ++k) {
-        const float* const* bw = weights + 4 + RNAMSM_SS_WEIGHTS_PER_BLOCK * k;
-        hipLaunchKernelGGL((ss_conv_packed_kernel<3, false>), grid, dim3(SS_THREADS), ss_trunk_lds_bytes(3), s, mem, B, xs, bw[1], bw[2],
-                           bw[0], ts);
-        RNAMSM_CHECK_LAUNCH("ss_conv3x3 (packed)");
-        hipLaunchKernelGGL((ss_conv_packed_kernel<5, true>), grid, dim3(SS_THREADS), ss_trunk_lds_bytes(5), s, mem, B, ts, bw[4], bw[5],
-                           bw[3], xs);
-        RNAMSM_CHECK_LAUNCH("ss_conv5x5 (packed)");
-    }
-    const float* const* hw = weights + 4 + RNAMSM_SS_WEIGHTS_PER_BLOCK * num_blocks;
-    hipLaunchKernelGGL(ss_out_packed_kernel, dim3((unsigned)((pixels + 255) / 256)), dim3(256), 0, s, mem, B, xs, weights[2], weights[3],
-                       hw[0], hw[1], pixels);
-    RNAMSM_CHECK_LAUNCH("ss_out (packed)");
-    return RNAMSM_OK;
+    const int rc = upload_members(mem, B, [&](int b) {
+        const rnamsm_ss_item& it = items[b];
+        const int32_t tiles = (it.L + SS_TILE - 1) / SS_TILE;
+        const SsMember m = {it.atp, it.atp_plane_stride, it.base_codes, it.logits, it.probs, pix0, it.L, tiles, tile0, 0};
+        pix0 += (int64_t)it.L * it.L;
+        tile0 += tiles * tiles;
+        return m;
+    }, s, "ss_members");
+    if (rc != RNAMSM_OK) return rc;
+    return ss_launch<true>(mem, B, SsMember{}, tiles_total, pixels, num_blocks, weights,
+                           reinterpret_cast<float*>(static_cast<char*>(workspace) + ss_members_bytes(B)), s);
 }

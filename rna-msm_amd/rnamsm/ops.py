@@ -556,6 +556,21 @@ def contact_head(row_attn: torch.Tensor, weight: torch.Tensor, bias: torch.Tenso
     return out
 
 
+def _ss_operands(fn: str, atp: torch.Tensor, bc: torch.Tensor, name: str, bc_name: str):
+    """The operand rules of one structure, for ss_head and for every member of ss_head_packed: -> (atp, base_codes, L) as the
+    library reads them (maps whose rows or planes do not lie as [L, L] planes at least L*L apart are copied)."""
+    _dev(atp, name)
+    if atp.dim() != 3 or atp.shape[0] != 120 or atp.shape[1] != atp.shape[2]:
+        raise ValueError(f"{fn}: {name} must be [120, L, L], got {tuple(atp.shape)}")
+    L = atp.shape[-1]
+    if atp.stride(2) != 1 or atp.stride(1) != L or atp.stride(0) < L * L:
+        atp = atp.contiguous()
+    _dev(bc, bc_name, torch.uint8)
+    if bc.dim() != 1 or bc.shape[0] != L:
+        raise ValueError(f"{fn}: {bc.shape[0] if bc.dim() == 1 else tuple(bc.shape)} base codes for {name} of L = {L}")
+    return atp, bc.contiguous(), L
+
+
 @_on_operand_device
 def ss_head(atp: torch.Tensor, base_codes: torch.Tensor, ptrs, num_blocks: int, want: str = "probs") -> torch.Tensor:
     """RNA-MSM-SS head (rnamsm_ss_head): atp [120, L, L] fp32 (planes may lie further apart than L*L: a slice of a wider
@@ -563,21 +578,14 @@ def ss_head(atp: torch.Tensor, base_codes: torch.Tensor, ptrs, num_blocks: int, 
     (ctypes c_void_p array, rnamsm.ss.SSPredictor) -> [L, L] fp32 probabilities (want="probs") or logits (want="logits")."""
     if want not in ("probs", "logits"):
         raise ValueError(f"ss_head: want must be 'probs' or 'logits', got {want!r}")
-    if atp.dim() != 3 or atp.shape[0] != 120 or atp.shape[1] != atp.shape[2]:
-        raise ValueError(f"ss_head: atp must be [120, L, L], got {tuple(atp.shape)}")
-    L = atp.shape[-1]
-    if atp.stride(2) != 1 or atp.stride(1) != L:
-        atp = atp.contiguous()
-    if base_codes.dim() != 1 or base_codes.shape[0] != L:
-        raise ValueError(f"ss_head: {base_codes.shape[0] if base_codes.dim() == 1 else tuple(base_codes.shape)} base codes "
-                         f"for atp of L = {L}")
+    atp, base_codes, L = _ss_operands("ss_head", atp, base_codes, "atp", "base_codes")
     lib = _lib.load()
     ws = torch.empty(max(lib.rnamsm_ss_head_workspace_bytes(L), 16), dtype=torch.uint8, device=atp.device)
     out = torch.empty(L, L, device=atp.device, dtype=torch.float32)
-    ptr = _dev(out, want)
-    _lib.check(lib.rnamsm_ss_head(_dev(atp, "atp"), atp.stride(0), _dev(base_codes.contiguous(), "base_codes", torch.uint8), L,
-                                  num_blocks, ptrs, ptr if want == "logits" else None, ptr if want == "probs" else None,
-                                  ws.data_ptr(), ws.numel(), _stream()))
+    ptr = out.data_ptr()
+    _lib.check(lib.rnamsm_ss_head(atp.data_ptr(), atp.stride(0), base_codes.data_ptr(), L, num_blocks, ptrs,
+                                  ptr if want == "logits" else None, ptr if want == "probs" else None, ws.data_ptr(), ws.numel(),
+                                  _stream()))
     return out
 
 
@@ -599,24 +607,15 @@ def ss_head_packed(atps: Sequence[torch.Tensor], codes: Sequence[torch.Tensor], 
     if B > _lib.SS_MAX_BATCH:
         raise ValueError(f"ss_head_packed: {B} structures exceed the limit of {_lib.SS_MAX_BATCH} per call")
     device = atps[0].device if isinstance(atps[0], torch.Tensor) else None
+    Ls = []
     for b in range(B):
-        atp, bc = atps[b], codes[b]
-        _dev(atp, f"atp[{b}]")
-        if atp.dim() != 3 or atp.shape[0] != 120 or atp.shape[1] != atp.shape[2]:
-            raise ValueError(f"ss_head_packed: atp[{b}] must be [120, L, L], got {tuple(atp.shape)}")
-        if atp.device != device:
-            raise ValueError(f"ss_head_packed: atp[{b}] lies on {atp.device}, atp[0] on {device}")
-        L = atp.shape[-1]
+        atps[b], codes[b], L = _ss_operands("ss_head_packed", atps[b], codes[b], f"atp[{b}]", f"base_codes[{b}]")
+        if atps[b].device != device:
+            raise ValueError(f"ss_head_packed: atp[{b}] lies on {atps[b].device}, atp[0] on {device}")
         if not 1 <= L <= _lib.SS_MAX_L:
             raise ValueError(f"ss_head_packed: atp[{b}]: L = {L} outside [1, {_lib.SS_MAX_L}]")
-        if atp.stride(2) != 1 or atp.stride(1) != L or atp.stride(0) < L * L:
-            atps[b] = atp.contiguous()
-        _dev(bc, f"base_codes[{b}]", torch.uint8)
-        if bc.dim() != 1 or bc.shape[0] != L:
-            raise ValueError(f"ss_head_packed: {bc.shape[0] if bc.dim() == 1 else tuple(bc.shape)} base codes for atp[{b}] of L = {L}")
-        codes[b] = bc.contiguous()
+        Ls.append(L)
     lib = _lib.load()
-    Ls = [int(a.shape[-1]) for a in atps]
     ws = torch.empty(lib.rnamsm_ss_head_packed_workspace_bytes(B, (_lib.c_int * B)(*Ls)), dtype=torch.uint8, device=device)
     out = torch.empty(sum(L * L for L in Ls), device=device, dtype=torch.float32)
     items = (_lib.SsItem * B)()
@@ -631,6 +630,22 @@ def ss_head_packed(atps: Sequence[torch.Tensor], codes: Sequence[torch.Tensor], 
     return outs
 
 
+def _rsa_operands(fn: str, emb: torch.Tensor, bc: torch.Tensor, name: str, bc_name: str):
+    """The operand rules of one alignment, for rsa_head and for every member of rsa_head_packed: -> (emb, row stride, base_codes,
+    L) as the library reads them (an embedding whose rows are not contiguous, overlap or do not start at a 16-byte boundary is
+    copied)."""
+    _dev(emb, name)
+    if emb.dim() != 2 or emb.shape[1] != 768:
+        raise ValueError(f"{fn}: {name} must be [L, 768], got {tuple(emb.shape)}")
+    L = emb.shape[0]
+    if emb.stride(1) != 1 or (L > 1 and emb.stride(0) < 768) or emb.data_ptr() % 16:
+        emb = emb.contiguous()
+    _dev(bc, bc_name, torch.uint8)
+    if bc.dim() != 1 or bc.shape[0] != L:
+        raise ValueError(f"{fn}: {tuple(bc.shape)} base codes for {name} of L = {L}")
+    return emb, emb.stride(0) if L > 1 else 768, bc.contiguous(), L
+
+
 @_on_operand_device
 def rsa_head(emb: torch.Tensor, base_codes: torch.Tensor, ptrs, n_models: int, use_onehot: bool, want: str = "probs") -> torch.Tensor:
     """RNA-MSM RSA ensemble (rnamsm_rsa_head): emb [L, 768] fp32 (rows may lie further apart than 768 floats: a slice of the
@@ -638,21 +653,12 @@ def rsa_head(emb: torch.Tensor, base_codes: torch.Tensor, ptrs, n_models: int, u
     (rnamsm.rsa.RSAEnsemble) -> [n_models, L] fp32 RSA (want="probs") or the pre-sigmoid values (want="logits")."""
     if want not in ("probs", "logits"):
         raise ValueError(f"rsa_head: want must be 'probs' or 'logits', got {want!r}")
-    if not isinstance(emb, torch.Tensor) or not emb.is_cuda:
-        raise _lib.RnamsmError("rsa_head: emb: expected a tensor on the HIP device (no CPU path exists)")
-    if emb.dim() != 2 or emb.shape[1] != 768:
-        raise ValueError(f"rsa_head: emb must be [L, 768], got {tuple(emb.shape)}")
-    L = emb.shape[0]
-    if emb.stride(1) != 1 or (L > 1 and emb.stride(0) < 768) or emb.data_ptr() % 16:
-        emb = emb.contiguous()
-    if base_codes.dim() != 1 or base_codes.shape[0] != L:
-        raise ValueError(f"rsa_head: {tuple(base_codes.shape)} base codes for an embedding of L = {L}")
+    emb, stride, base_codes, L = _rsa_operands("rsa_head", emb, base_codes, "emb", "base_codes")
     lib = _lib.load()
     ws = torch.empty(max(lib.rnamsm_rsa_head_workspace_bytes(L, n_models), 16), dtype=torch.uint8, device=emb.device)
     out = torch.empty(n_models, L, device=emb.device, dtype=torch.float32)
-    ptr = _dev(out, want)
-    _lib.check(lib.rnamsm_rsa_head(_dev(emb, "emb"), emb.stride(0) if L > 1 else 768,
-                                   _dev(base_codes.contiguous(), "base_codes", torch.uint8), L, n_models, 1 if use_onehot else 0, ptrs,
+    ptr = out.data_ptr()
+    _lib.check(lib.rnamsm_rsa_head(emb.data_ptr(), stride, base_codes.data_ptr(), L, n_models, 1 if use_onehot else 0, ptrs,
                                    ptr if want == "probs" else None, ptr if want == "logits" else None, ws.data_ptr(), ws.numel(),
                                    _stream()))
     return out
@@ -676,24 +682,16 @@ def rsa_head_packed(embs: Sequence[torch.Tensor], codes: Sequence[torch.Tensor],
     if B > _lib.RSA_MAX_BATCH:
         raise ValueError(f"rsa_head_packed: {B} alignments exceed the limit of {_lib.RSA_MAX_BATCH} per call")
     device = embs[0].device if isinstance(embs[0], torch.Tensor) else None
+    Ls, strides = [], []
     for b in range(B):
-        emb, bc = embs[b], codes[b]
-        _dev(emb, f"emb[{b}]")
-        if emb.dim() != 2 or emb.shape[1] != 768:
-            raise ValueError(f"rsa_head_packed: emb[{b}] must be [L, 768], got {tuple(emb.shape)}")
-        if emb.device != device:
-            raise ValueError(f"rsa_head_packed: emb[{b}] lies on {emb.device}, emb[0] on {device}")
-        L = emb.shape[0]
+        embs[b], stride, codes[b], L = _rsa_operands("rsa_head_packed", embs[b], codes[b], f"emb[{b}]", f"base_codes[{b}]")
+        if embs[b].device != device:
+            raise ValueError(f"rsa_head_packed: emb[{b}] lies on {embs[b].device}, emb[0] on {device}")
         if not 1 <= L <= _lib.RSA_MAX_L:
             raise ValueError(f"rsa_head_packed: emb[{b}]: L = {L} outside [1, {_lib.RSA_MAX_L}]")
-        if emb.stride(1) != 1 or (L > 1 and emb.stride(0) < 768) or emb.data_ptr() % 16:
-            embs[b] = emb.contiguous()
-        _dev(bc, f"base_codes[{b}]", torch.uint8)
-        if bc.dim() != 1 or bc.shape[0] != L:
-            raise ValueError(f"rsa_head_packed: {tuple(bc.shape)} base codes for emb[{b}] of L = {L}")
-        codes[b] = bc.contiguous()
+        Ls.append(L)
+        strides.append(stride)
     lib = _lib.load()
-    Ls = [int(e.shape[0]) for e in embs]
     ws = torch.empty(lib.rnamsm_rsa_head_packed_workspace_bytes(B, (_lib.c_int * B)(*Ls), n_models), dtype=torch.uint8, device=device)
     out = torch.empty(n_models * sum(Ls), device=device, dtype=torch.float32)
     items = (_lib.RsaItem * B)()
@@ -702,7 +700,7 @@ def rsa_head_packed(embs: Sequence[torch.Tensor], codes: Sequence[torch.Tensor],
         o = out[off:off + n_models * L].view(n_models, L)
         off += n_models * L
         outs.append(o)
-        items[b] = _lib.RsaItem(embs[b].data_ptr(), embs[b].stride(0) if L > 1 else 768, codes[b].data_ptr(), L,
+        items[b] = _lib.RsaItem(embs[b].data_ptr(), strides[b], codes[b].data_ptr(), L,
                                 o.data_ptr() if want == "probs" else None, o.data_ptr() if want == "logits" else None)
     _lib.check(lib.rnamsm_rsa_head_packed(items, B, n_models, 1 if use_onehot else 0, ptrs, ws.data_ptr(), ws.numel(), _stream()))
     return outs

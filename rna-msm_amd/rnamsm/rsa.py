@@ -24,7 +24,7 @@ import torch
 from torch import nn
 
 from . import _lib, ops
-from .ss import base_codes
+from .ss import base_codes, plan_chunks
 
 EMBED_DIM = 768
 PLANES = 64
@@ -42,17 +42,7 @@ def plan_rsa_chunks(Ls: Sequence[int], max_positions: int = RSA_CHUNK_POSITIONS,
     long as its sum of L stays within max_positions and its length within max_batch (greedy, so no two neighbouring chunks could
     have been one).  An alignment larger than the budget by itself -- impossible at the default, L <= 1024 -- is a chunk of its
     own."""
-    chunks: List[List[int]] = []
-    positions = 0
-    for i, L in enumerate(Ls):
-        n = int(L)
-        if chunks and positions + n <= max_positions and len(chunks[-1]) < max_batch:
-            chunks[-1].append(i)
-            positions += n
-        else:
-            chunks.append([i])
-            positions = n
-    return chunks
+    return plan_chunks([int(L) for L in Ls], max_positions, max_batch)
 
 
 class _BasicBlock(nn.Module):
@@ -217,19 +207,27 @@ class RSAEnsemble(nn.Module):
         self._pack_key = None
         return super()._apply(fn, *args, **kwargs)
 
-    def _run(self, emb: torch.Tensor, seq: Union[str, np.ndarray, torch.Tensor], want: str) -> torch.Tensor:
-        if not isinstance(emb, torch.Tensor) or not emb.is_cuda:
-            raise _lib.RnamsmError("RSAEnsemble: emb must be a tensor on the HIP device (no CPU path exists)")
+    @staticmethod
+    def _codes_of(emb, seq, name: str, seq_name: str, on_device: bool) -> torch.Tensor:
+        """The checks of one (embedding, sequence) pair, named as the caller's arguments (`emb` / `embs[3]`) -> its base codes, flat.
+        on_device: refuse an embedding off the HIP device here, before its shape (False: the caller does that for every item
+        afterwards)."""
+        if not isinstance(emb, torch.Tensor) or (on_device and not emb.is_cuda):
+            raise _lib.RnamsmError(f"RSAEnsemble: {name} must be a tensor on the HIP device (no CPU path exists)")
         if emb.dim() != 2 or emb.shape[1] != EMBED_DIM:
-            raise ValueError(f"RSAEnsemble: emb must be [L, {EMBED_DIM}], got {tuple(emb.shape)}")
+            raise ValueError(f"RSAEnsemble: {name} must be [L, {EMBED_DIM}], got {tuple(emb.shape)}")
         L = emb.shape[0]
         if not 1 <= L <= _lib.RSA_MAX_L:
-            raise ValueError(f"RSAEnsemble: L = {L} outside the head's range [1, {_lib.RSA_MAX_L}]")
+            raise ValueError(f"RSAEnsemble: {name}: L = {L} outside the head's range [1, {_lib.RSA_MAX_L}]")
         if isinstance(seq, str):
             seq = base_codes(seq)
-        codes = torch.as_tensor(seq).to(device=emb.device, dtype=torch.uint8).reshape(-1)
+        codes = torch.as_tensor(seq).reshape(-1)
         if codes.numel() != L:
-            raise ValueError(f"RSAEnsemble: sequence of length {codes.numel()} for an embedding of L = {L}")
+            raise ValueError(f"RSAEnsemble: {seq_name} has length {codes.numel()} for an embedding of L = {L}")
+        return codes
+
+    def _run(self, emb: torch.Tensor, seq: Union[str, np.ndarray, torch.Tensor], want: str) -> torch.Tensor:
+        codes = self._codes_of(emb, seq, "emb", "seq", True).to(device=emb.device, dtype=torch.uint8)
         ptrs, _ = self._packed_weights()
         return ops.rsa_head(emb, codes, ptrs, len(self.members), self.use_onehot, want)
 
@@ -245,21 +243,8 @@ class RSAEnsemble(nn.Module):
         embs, seqs = list(embs), list(seqs)
         if len(embs) != len(seqs):
             raise ValueError(f"RSAEnsemble: {len(embs)} embeddings for {len(seqs)} sequences")
-        codes = []
-        for b, (emb, seq) in enumerate(zip(embs, seqs)):       # shapes and lengths first: they are wrong on any device
-            if not isinstance(emb, torch.Tensor):
-                raise _lib.RnamsmError(f"RSAEnsemble: embs[{b}] must be a tensor on the HIP device (no CPU path exists)")
-            if emb.dim() != 2 or emb.shape[1] != EMBED_DIM:
-                raise ValueError(f"RSAEnsemble: embs[{b}] must be [L, {EMBED_DIM}], got {tuple(emb.shape)}")
-            L = emb.shape[0]
-            if not 1 <= L <= _lib.RSA_MAX_L:
-                raise ValueError(f"RSAEnsemble: embs[{b}]: L = {L} outside the head's range [1, {_lib.RSA_MAX_L}]")
-            if isinstance(seq, str):
-                seq = base_codes(seq)
-            c = torch.as_tensor(seq).reshape(-1)
-            if c.numel() != L:
-                raise ValueError(f"RSAEnsemble: seqs[{b}] has length {c.numel()} for an embedding of L = {L}")
-            codes.append(c)
+        # shapes and lengths first: they are wrong on any device
+        codes = [self._codes_of(emb, seq, f"embs[{b}]", f"seqs[{b}]", False) for b, (emb, seq) in enumerate(zip(embs, seqs))]
         for b, emb in enumerate(embs):
             if not emb.is_cuda:
                 raise _lib.RnamsmError(f"RSAEnsemble: embs[{b}] must be a tensor on the HIP device (no CPU path exists)")

@@ -42,16 +42,21 @@ def plan_ss_chunks(Ls: Sequence[int], max_pixels: int = SS_CHUNK_PIXELS, max_bat
     as long as its sum of L^2 stays within max_pixels and its length within max_batch (greedy, so no two neighbouring chunks
     could have been one).  A structure larger than the budget by itself -- impossible at the default, L <= 1024 -- is a chunk of
     its own."""
+    return plan_chunks([int(L) * int(L) for L in Ls], max_pixels, max_batch)
+
+
+def plan_chunks(weights: Sequence[int], budget: int, max_batch: int) -> List[List[int]]:
+    """Indices of `weights` split greedily into consecutive chunks, in list order: a chunk takes the next item as long as its sum
+    of weights stays within budget and its length within max_batch; an item heavier than the budget is a chunk of its own."""
     chunks: List[List[int]] = []
-    pixels = 0
-    for i, L in enumerate(Ls):
-        n = int(L) * int(L)
-        if chunks and pixels + n <= max_pixels and len(chunks[-1]) < max_batch:
+    total = 0
+    for i, n in enumerate(weights):
+        if chunks and total + n <= budget and len(chunks[-1]) < max_batch:
             chunks[-1].append(i)
-            pixels += n
+            total += n
         else:
             chunks.append([i])
-            pixels = n
+            total = n
     return chunks
 
 
@@ -122,19 +127,26 @@ class SSPredictor(nn.Module):
         self._pack_key = None
         return super()._apply(fn, *args, **kwargs)
 
-    def _run(self, atp: torch.Tensor, seq: Union[str, np.ndarray, torch.Tensor], want: str) -> torch.Tensor:
-        if not isinstance(atp, torch.Tensor) or not atp.is_cuda:
-            raise _lib.RnamsmError("SSPredictor: atp must be a tensor on the HIP device (no CPU path exists)")
+    @staticmethod
+    def _codes_of(atp, seq, name: str, seq_name: str, on_device: bool) -> torch.Tensor:
+        """The checks of one (maps, sequence) pair, named as the caller's arguments (`atp` / `atps[3]`) -> its base codes, flat.
+        on_device: refuse maps off the HIP device here, before their shape (False: the caller does that for every item afterwards)."""
+        if not isinstance(atp, torch.Tensor) or (on_device and not atp.is_cuda):
+            raise _lib.RnamsmError(f"SSPredictor: {name} must be a tensor on the HIP device (no CPU path exists)")
         if atp.dim() != 3 or atp.shape[0] != NUM_MAPS or atp.shape[1] != atp.shape[2]:
-            raise ValueError(f"SSPredictor: atp must be [{NUM_MAPS}, L, L], got {tuple(atp.shape)}")
+            raise ValueError(f"SSPredictor: {name} must be [{NUM_MAPS}, L, L], got {tuple(atp.shape)}")
         L = atp.shape[-1]
         if L > _lib.SS_MAX_L:
-            raise ValueError(f"SSPredictor: L = {L} exceeds the head's limit of {_lib.SS_MAX_L}")
+            raise ValueError(f"SSPredictor: {name}: L = {L} exceeds the head's limit of {_lib.SS_MAX_L}")
         if isinstance(seq, str):
             seq = base_codes(seq)
-        codes = torch.as_tensor(seq).to(device=atp.device, dtype=torch.uint8).reshape(-1)
+        codes = torch.as_tensor(seq).reshape(-1)
         if codes.numel() != L:
-            raise ValueError(f"SSPredictor: sequence of length {codes.numel()} for attention maps of L = {L}")
+            raise ValueError(f"SSPredictor: {seq_name} has length {codes.numel()} for attention maps of L = {L}")
+        return codes
+
+    def _run(self, atp: torch.Tensor, seq: Union[str, np.ndarray, torch.Tensor], want: str) -> torch.Tensor:
+        codes = self._codes_of(atp, seq, "atp", "seq", True).to(device=atp.device, dtype=torch.uint8)
         ptrs, _ = self._packed_weights()
         return ops.ss_head(atp, codes, ptrs, self.num_blocks, want)
 
@@ -150,21 +162,8 @@ class SSPredictor(nn.Module):
         atps, seqs = list(atps), list(seqs)
         if len(atps) != len(seqs):
             raise ValueError(f"SSPredictor: {len(atps)} attention maps for {len(seqs)} sequences")
-        codes = []
-        for b, (atp, seq) in enumerate(zip(atps, seqs)):       # shapes and lengths first: they are wrong on any device
-            if not isinstance(atp, torch.Tensor):
-                raise _lib.RnamsmError(f"SSPredictor: atps[{b}] must be a tensor on the HIP device (no CPU path exists)")
-            if atp.dim() != 3 or atp.shape[0] != NUM_MAPS or atp.shape[1] != atp.shape[2]:
-                raise ValueError(f"SSPredictor: atps[{b}] must be [{NUM_MAPS}, L, L], got {tuple(atp.shape)}")
-            L = atp.shape[-1]
-            if L > _lib.SS_MAX_L:
-                raise ValueError(f"SSPredictor: atps[{b}]: L = {L} exceeds the head's limit of {_lib.SS_MAX_L}")
-            if isinstance(seq, str):
-                seq = base_codes(seq)
-            c = torch.as_tensor(seq).reshape(-1)
-            if c.numel() != L:
-                raise ValueError(f"SSPredictor: seqs[{b}] has length {c.numel()} for attention maps of L = {L}")
-            codes.append(c)
+        # shapes and lengths first: they are wrong on any device
+        codes = [self._codes_of(atp, seq, f"atps[{b}]", f"seqs[{b}]", False) for b, (atp, seq) in enumerate(zip(atps, seqs))]
         for b, atp in enumerate(atps):
             if not atp.is_cuda:
                 raise _lib.RnamsmError(f"SSPredictor: atps[{b}] must be a tensor on the HIP device (no CPU path exists)")

@@ -107,6 +107,19 @@ def test_tile_and_chunk_counts_at_the_limit():
         _same_bits(probs[b], ens.predict(e, s), f"probs of member {b}")
 
 
+def test_more_members_than_one_descriptor_launch():
+    """33 alignments: the descriptor table goes up in two launches (32 + 1), so a member on either side of that seam must find
+    its own entry.  L drawn from 1..70 (one to three tiles, one or two key chunks)."""
+    ens = _ensemble("rand3")[0]
+    Ls = [int(v) for v in np.random.RandomState(33).randint(1, 71, size=33)]
+    embs, seqs = _cases(Ls, 900)
+    logits, probs = ens.logits_many(embs, seqs), ens.predict_many(embs, seqs)
+    assert len(logits) == len(probs) == 33
+    for b, (e, s) in enumerate(zip(embs, seqs)):
+        _same_bits(logits[b], ens.logits(e, s), f"logits of member {b} (L = {Ls[b]})")
+        _same_bits(probs[b], ens.predict(e, s), f"probs of member {b} (L = {Ls[b]})")
+
+
 SENTINEL = -7.0
 
 

@@ -85,6 +85,19 @@ def test_sixteen_blocks_have_the_lone_head_s_bits():
         _same_bits(probs[b], head.predict(a, s), f"probs of member {b}")
 
 
+def test_more_members_than_one_descriptor_launch():
+    """33 structures: the descriptor table goes up in two launches (32 + 1), so a member on either side of that seam must find
+    its own entry.  One block, L drawn from 1..20 (one or two tiles a side): a few milliseconds."""
+    head = _predictor(ss_truth.make_state(1, seed=23), 1)
+    Ls = [int(v) for v in np.random.RandomState(33).randint(1, 21, size=33)]
+    atps, seqs = _cases(Ls, 700)
+    logits, probs = head.logits_many(atps, seqs), head.predict_many(atps, seqs)
+    assert len(logits) == len(probs) == 33
+    for b, (a, s) in enumerate(zip(atps, seqs)):
+        _same_bits(logits[b], head.logits(a, s), f"logits of member {b} (L = {Ls[b]})")
+        _same_bits(probs[b], head.predict(a, s), f"probs of member {b} (L = {Ls[b]})")
+
+
 def _call_c(model, atps, strides, codes, wants, poison=True):
     """rnamsm_ss_head_packed itself.  wants[b]: a subset of {"logits", "probs"}.  The workspace is filled with NaN first.
     Returns per member {"logits": tensor or None, "probs": tensor or None}."""
