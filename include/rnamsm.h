@@ -357,6 +357,8 @@ int rnamsm_contact_head(const float* row_attn, const float* weight, const float*
  * workspace: rnamsm_ss_head_workspace_bytes(L) bytes (two [L*L, 48] fp32 images), 16-byte aligned; 0 for an L outside
  * [1, RNAMSM_SS_MAX_L].  Refused (RNAMSM_ERR_INVALID): L outside [1, RNAMSM_SS_MAX_L], num_blocks outside
  * [1, RNAMSM_SS_MAX_BLOCKS], atp_plane_stride < L*L, a null or misaligned pointer, a short workspace.
+ * A NaN or an inf in atp is not refused: it comes out as NaN exactly where the reference network gives NaN (every ReLU carries
+ * a NaN on, as nn.ReLU does) -- the pixels within 1 + 3 num_blocks of it -- and every other pixel keeps the bits it has without it.
  * No atomics: the same inputs give the same bits on every run. */
 #define RNAMSM_SS_MAX_L 1024
 #define RNAMSM_SS_MAX_BLOCKS 64
@@ -384,6 +386,8 @@ int rnamsm_ss_head(const float* atp, int64_t atp_plane_stride, const uint8_t* ba
  * num_blocks out of range, a member's L out of range, a null pointer (items, weights, workspace, a member's atp or
  * base_codes, a weight), a member with neither logits nor probs, a float pointer that is not 4-byte aligned, a weight pointer
  * or workspace that is not 16-byte aligned, atp_plane_stride < L*L, a short workspace.
+ * A non-finite input comes out as NaN exactly where the reference network gives NaN, as for rnamsm_ss_head, and a member never
+ * affects another: the neighbours of a poisoned member stay finite and keep their bits.
  * No atomics: the same inputs give the same bits on every run. */
 typedef struct {                 /* one structure of the batch */
     const float*   atp;          /* device: plane p at atp + p * atp_plane_stride, rows of L floats */
@@ -427,6 +431,8 @@ int rnamsm_ss_head_packed(const rnamsm_ss_item* items, int B, int num_blocks, co
  * caller-owned (nothing is allocated inside); 0 for L or n_models outside their limits.
  * Refused (RNAMSM_ERR_INVALID) before anything is launched: L outside [1, RNAMSM_RSA_MAX_L], n_models outside
  * [1, RNAMSM_RSA_MAX_MODELS], emb_row_stride < 768, a null or misaligned pointer, a short workspace.
+ * A NaN or an inf in emb is not refused: it comes out as NaN exactly where the reference network gives NaN (every ReLU carries
+ * a NaN on, as nn.ReLU does) -- through the squeeze mean and the attention that is every position of every member.
  * No atomics, one fixed summation order: the same bits on every run, and member k's row does not depend on the other members. */
 #define RNAMSM_RSA_MAX_L 1024
 #define RNAMSM_RSA_MAX_MODELS 8
@@ -456,6 +462,8 @@ int rnamsm_rsa_head(const float* emb, int64_t emb_row_stride, const uint8_t* bas
  * n_models out of range, a member's L out of range, a null pointer (items, weights, workspace, a member's emb or base_codes, a
  * weight), a member with neither probs nor logits, emb_row_stride < 768, an embedding, weight pointer or workspace that is not
  * 16-byte aligned, an output that is not 4-byte aligned, a short workspace.
+ * A non-finite input comes out as NaN exactly where the reference network gives NaN, as for rnamsm_rsa_head, and a member never
+ * affects another: the neighbours of a poisoned member stay finite and keep their bits.
  * No atomics: the same inputs give the same bits on every run. */
 typedef struct {                 /* one alignment of the batch */
     const float*   emb;          /* device: row p at emb + p * emb_row_stride, 768 floats; 16-byte aligned */

@@ -193,6 +193,11 @@ __device__ __forceinline__ float wave_max(float v) {
     return v;
 }
 
+// ReLU as nn.ReLU computes it: v where v > 0, NaN where v is NaN, +0 otherwise.  fmaxf is IEEE maxNum (fmaxf(NaN, 0) = 0) and would
+// turn a poisoned activation into a plausible finite one; the IEEE-2019 maximum is one v_maximum3_f32 on this target, as fmaxf is
+// one v_max_f32, and gives fmaxf's bits for every input that is not NaN.
+__device__ __forceinline__ float relu_nan(float v) { return __builtin_elementwise_maximum(v, 0.f); }
+
 // LayerNorm of one row held as up to four float4 per lane (D <= 1024), biased variance, two passes like ATen's CPU kernel.
 // ONE arithmetic for every kernel that normalises a row (layernorm_kernel, embed_ln_kernel, layernorm_split_kernel): the
 // fused steps are written as fmaf and nothing else has the a * b + c shape, so -ffp-contract=fast has no choice to make and two

@@ -175,7 +175,7 @@ __device__ __forceinline__ void rsa_stem_body(float* Xs, float* Red, const float
         for (int i = 0; i < 16; ++i) {
             const int p = p0 + (i & 3) + 8 * (i >> 2) + 4 * kk;      // accumulator layout: common.h mfma32
             if (p < L) {
-                h1[(size_t)p * RSA_CH + co] = fmaxf(fmaf(conv[i], s1, b1), 0.f);
+                h1[(size_t)p * RSA_CH + co] = relu_nan(fmaf(conv[i], s1, b1));
                 sh[(size_t)p * RSA_CH + co] = fmaf(shortcut[i], ss, bs);
             }
         }
@@ -250,7 +250,7 @@ __device__ __forceinline__ void rsa_conv2_body(float* Xs, float* Ps, int L, cons
     for (int j = 0; j < 8; ++j) {
         const int p = p0 + pg * 8 + j;
         if (p < L) {
-            const float v = fmaxf(fmaf(acc[j], s2, b2), 0.f);
+            const float v = relu_nan(fmaf(acc[j], s2, b2));
             h2[(size_t)p * RSA_CH + co] = v;
             sum += v;
         }
@@ -295,7 +295,7 @@ __device__ __forceinline__ void rsa_mix_body(float* Ys, float* Xs, float* Sc, in
     if (t < 4) {
         float z = 0.f;
         for (int c = 0; c < RSA_CH; ++c) z = fmaf(M.w[W_SE1_W][t * RSA_CH + c], Mean[c], z);
-        Z[t] = fmaxf(z + M.w[W_SE1_B][t], 0.f);
+        Z[t] = relu_nan(z + M.w[W_SE1_B][t]);
     }
     __syncthreads();
     if (t < RSA_CH) {
@@ -310,7 +310,7 @@ __device__ __forceinline__ void rsa_mix_body(float* Ys, float* Xs, float* Sc, in
         const int p = p0 + i / RSA_CH, c = i % RSA_CH;
         float v = 0.f;
         if (p < L) {
-            v = fmaxf(fmaf(h2[(size_t)p * RSA_CH + c], Gate[c], sh[(size_t)p * RSA_CH + c]), 0.f);
+            v = relu_nan(fmaf(h2[(size_t)p * RSA_CH + c], Gate[c], sh[(size_t)p * RSA_CH + c]));
             y[(size_t)p * RSA_CH + c] = v;
         }
         Ys[i] = v;

@@ -113,7 +113,7 @@ __device__ __forceinline__ void ln_relu48(f32x4 (&v)[12], const float* __restric
     for (int i = 0; i < 12; ++i) {
         const f32x4 gm = *reinterpret_cast<const f32x4*>(gamma + 4 * i), bt = *reinterpret_cast<const f32x4*>(beta + 4 * i);
 #pragma unroll
-        for (int k = 0; k < 4; ++k) v[i][k] = fmaxf(fmaf((v[i][k] - mean) * rstd, gm[k], bt[k]), 0.f);
+        for (int k = 0; k < 4; ++k) v[i][k] = relu_nan(fmaf((v[i][k] - mean) * rstd, gm[k], bt[k]));
     }
 }
 

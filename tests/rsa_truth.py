@@ -176,3 +176,17 @@ def compare(got, t64, t32, label: str = "", l2_mult: float = L2_MULT) -> float:
     assert err <= l2_mult * max(drift, L2_FLOOR), msg
     assert d <= ew_bar, msg
     return d
+
+
+def compare_masked(got, t64, t32, label: str = "", min_finite: float = 0.0, expect_nan: bool = True,
+                   l2_mult: float = L2_MULT) -> float:
+    """compare() for truths that hold NaN (a non-finite input; the squeeze mean and the attention spread it over the whole member):
+    the rule of ss_truth.compare_masked -- `got` is NaN exactly where the fp64 truth is and holds no inf the truth does not hold, at
+    least the share min_finite of the truth is finite, a NaN is there where the caller expects one -- then compare() itself on the
+    elements where the fp64 truth is finite.  Returns the max-abs on those (0 where there is none)."""
+    from ss_truth import check_nan_pattern
+    got, t64, t32 = (np.asarray(a, dtype=np.float64) for a in (got, t64, t32))
+    fin = check_nan_pattern(got, t64, t32, label, min_finite, expect_nan)
+    if not fin.any():
+        return 0.0
+    return compare(got[fin], t64[fin], t32[fin], f"{label} [{int(fin.sum())} of {fin.size} finite]", l2_mult=l2_mult)

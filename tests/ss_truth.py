@@ -151,3 +151,61 @@ def compare(got, t64, t32, label: str = "", seams: bool = False, floor: float = 
     assert err <= l2_mult * max(drift, l2_floor), msg
     assert d.max() <= ew_bar, msg
     return float(d.max())
+
+
+def check_nan_pattern(got, t64, t32, label: str, min_finite: float, expect_nan: bool) -> np.ndarray:
+    """The non-finite side of a masked comparison, shared with rsa_truth.compare_masked: `got` is NaN exactly where the fp64
+    truth is and holds no inf the truth does not hold; at least the share min_finite of the truth is finite, and at least one
+    element is NaN where the caller expects one (so neither side of the comparison passes on an empty set).  The fp32
+    restatement must be finite wherever the fp64 truth is: it is the yardstick of the bars there.  Returns the mask of the finite
+    elements of t64."""
+    assert got.shape == t64.shape == t32.shape, label
+    nan64, fin64 = np.isnan(t64), np.isfinite(t64)
+    share = float(fin64.mean())
+    assert share >= min_finite, f"{label}: only {share:.3f} of the truth is finite, {min_finite} asked for"
+    assert nan64.any() or not expect_nan, f"{label}: a NaN was expected in the truth and there is none"
+    wrong = np.isnan(got) != nan64
+    assert not wrong.any(), (f"{label}: NaN pattern differs from the truth's at {int(wrong.sum())} of {got.size} elements "
+                             f"(truth {int(nan64.sum())} NaN, got {int(np.isnan(got).sum())}); first at "
+                             f"{tuple(int(v) for v in np.argwhere(wrong)[0])}")
+    extra_inf = np.isinf(got) & ~np.isinf(t64)
+    assert not extra_inf.any(), f"{label}: {int(extra_inf.sum())} inf where the truth has none"
+    assert np.isfinite(t32[fin64]).all(), f"{label}: the fp32 restatement is not finite where the fp64 truth is"
+    return fin64
+
+
+def compare_masked(got, t64, t32, label: str = "", min_finite: float = 0.0, expect_nan: bool = True, **bars) -> float:
+    """compare() for truths that hold NaN (a non-finite input: the reference's ReLU, LayerNorm and convolutions carry it over the
+    receptive square): the NaN pattern first (check_nan_pattern), then compare() itself -- the same bars, multiples and floors
+    -- on the elements where the fp64 truth is finite.  bars: compare's floor / l2_mult.  Returns the max-abs on the finite
+    elements (0 where there is none)."""
+    got, t64, t32 = (np.asarray(a, dtype=np.float64) for a in (got, t64, t32))
+    fin = check_nan_pattern(got, t64, t32, label, min_finite, expect_nan)
+    if not fin.any():
+        return 0.0
+    return compare(got[fin], t64[fin], t32[fin], f"{label} [{int(fin.sum())} of {fin.size} finite]", **bars)
+
+
+def small_maps_case(L: int, seed: int):
+    """The inputs of the non-finite tests (CPU and GPU): maps uniform in [0, 0.1), float32 [120, L, L], and a sequence with one
+    character outside A, C, G, U."""
+    rng = np.random.RandomState(seed)
+    atp = (0.1 * rng.rand(120, L, L)).astype(np.float32)
+    seq = "".join(rng.choice(list("ACGU"), L))
+    if L > 3:
+        seq = seq[:2] + "N" + seq[3:]
+    return atp, seq
+
+
+def poisoned(atp: np.ndarray, plane: int, pixel, value: float) -> np.ndarray:
+    """A copy of atp with the one element [plane, pixel] set to value (NaN, +inf, -inf)."""
+    out = np.array(atp, copy=True)
+    out[plane, pixel[0], pixel[1]] = value
+    return out
+
+
+def receptive_square(L: int, num_blocks: int, pixel) -> np.ndarray:
+    """bool [L, L]: the output pixels whose window holds the input pixel -- within receptive_margin of it, clipped at the border."""
+    m = receptive_margin(num_blocks)
+    idx = np.arange(L)
+    return (np.abs(idx - pixel[0]) <= m)[:, None] & (np.abs(idx - pixel[1]) <= m)[None, :]

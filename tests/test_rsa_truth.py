@@ -1,4 +1,5 @@
-"""The RSA restatement (tests/rsa_truth.py) against the reference's own outputs (tests/golden/rsa/, make_golden_rsa.py)."""
+"""The RSA restatement (tests/rsa_truth.py) against the reference's own outputs (tests/golden/rsa/, make_golden_rsa.py), and what it does
+with a NaN or an inf in one embedding element (the truth tests/test_gpu_rsa_nonfinite.py stands on)."""
 import os
 
 import numpy as np
@@ -81,3 +82,48 @@ def test_make_state_has_the_reference_names_and_shapes():
     assert set(ref) == set(mine)
     assert all(ref[k].shape == mine[k].shape for k in ref)
     assert T.make_state(1, cin=769)["net.0.0.conv1.weight"].shape == (64, 769, 3)
+
+
+def _poisoned_logits(kind, value, dtype):
+    """make_state(11) at L = 70 with embedding element [40, 5] set to value; kind 'oh': the one-hot network (773 channels),
+    'emb': the embedding-only one (769)."""
+    L = 70
+    rng = np.random.RandomState(70)
+    st = T.load_stats(kind)
+    emb = (st["emb_mu"] + st["emb_std"] * rng.standard_normal((L, 768))).astype(np.float32)
+    seq = "".join(rng.choice(list("ACGUN"), L))
+    sd = T.make_state(11, cin=773 if kind == "oh" else 769)
+    clean = T.logits(T.features(emb, seq, st, use_onehot=kind == "oh"), sd, dtype)
+    emb[40, 5] = value
+    return clean, T.logits(T.features(emb, seq, st, use_onehot=kind == "oh"), sd, dtype)
+
+
+@pytest.mark.parametrize("kind", ["oh", "emb"])
+@pytest.mark.parametrize("value", ["nan", "inf", "-inf"])
+def test_one_bad_embedding_element_makes_every_logit_nan(kind, value):
+    """The squeeze mean and the attention spread a NaN over the whole member: all L logits NaN, none inf, in fp64 and fp32."""
+    for dtype in (torch.float64, torch.float32):
+        clean, y = _poisoned_logits(kind, float(value), dtype)
+        assert np.isfinite(clean).all() and clean.shape == y.shape == (70,)
+        assert np.isnan(y).all(), (kind, value, dtype, int(np.isnan(y).sum()))
+
+
+def test_masked_comparison_reads_the_pattern_before_the_bars():
+    clean64, nan64 = _poisoned_logits("oh", float("nan"), torch.float64)
+    clean32, nan32 = (a.astype(np.float64) for a in _poisoned_logits("oh", float("nan"), torch.float32))
+    assert T.compare_masked(nan32.astype(np.float32), nan64, nan32, "all NaN") == 0.0
+    for got in (clean32.astype(np.float32), np.full(70, np.inf, dtype=np.float32)):       # laundered; inf in place of NaN
+        with pytest.raises(AssertionError):
+            T.compare_masked(got, nan64, nan32, "wrong on purpose")
+    with pytest.raises(AssertionError):
+        T.compare_masked(nan32.astype(np.float32), nan64, nan32, "not finite enough", min_finite=0.5)
+    with pytest.raises(AssertionError):
+        T.compare_masked(clean32.astype(np.float32), clean64, clean32, "no NaN to expect")
+    # a truth that is part NaN: the bars on the rest
+    half64, half32 = clean64.copy(), clean32.copy()
+    half64[:30] = half32[:30] = np.nan
+    got = half32.astype(np.float32)
+    assert T.compare_masked(got, half64, half32, "half", min_finite=0.5) < 1e-4
+    got[50] += np.float32(1e-3)
+    with pytest.raises(AssertionError):
+        T.compare_masked(got, half64, half32, "half, one logit off", min_finite=0.5)
