@@ -37,7 +37,8 @@ __global__ __launch_bounds__(256) void greedy_dist_kernel(const uint8_t* __restr
     if (lane == 0) hist[(int64_t)(step - 1) * N + row] = (uint16_t)m;
 }
 
-// numpy's pairwise summation (DOUBLE_pairwise_sum) over h[0], h[stride], .., n terms, term = lut[count]
+// numpy's pairwise summation (DOUBLE_pairwise_sum) over h[0], h[stride], .., n terms, term = lut[count].  DEPTH = levels of
+// splitting available: the caller's must cover its longest history, or a piece of more than 128 terms ends up as one leaf
 template <int DEPTH>
 __device__ __forceinline__ double pairwise_sum(const uint16_t* __restrict__ h, int64_t stride, int n,
                                                const double* __restrict__ lut) {
@@ -75,8 +76,10 @@ __global__ __launch_bounds__(256) void greedy_score_kernel(const uint16_t* __res
     const int row = blockIdx.x * 256 + threadIdx.x;
     if (row >= N) return;
     if (taken[row]) { score[row] = -INFINITY; return; }
-    // 128 * 2^4 = 2048 >= the 1023 steps the model's 1024-row limit allows (checked by the entry point)
-    const double mean = pairwise_sum<4>(hist + row, N, step, lut) / (double)step;
+    // the entry point admits num_seqs <= 2048, i.e. histories of up to 2047 terms.  numpy rounds every LEFT half down to a
+    // multiple of 8, so the right halves grow: 2047 -> 1031 -> 519 -> 263 -> 135 -> 64 + 71 takes FIVE levels (four leave a
+    // piece of more than 128 terms from 1929 terms on, which must not be summed as one leaf); tests/test_pairwise_order.py
+    const double mean = pairwise_sum<5>(hist + row, N, step, lut) / (double)step;
     score[row] = minimise ? -mean : mean;          // argmin as argmax of the negated value
 }
 
