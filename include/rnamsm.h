@@ -402,6 +402,31 @@ size_t rnamsm_ss_head_packed_workspace_bytes(int B, const int* Ls);
 int rnamsm_ss_head_packed(const rnamsm_ss_item* items, int B, int num_blocks, const float* const* weights,
                           void* workspace, size_t workspace_bytes, void* stream);
 
+/* f4, the text of the probabilities -- the bytes np.savetxt(path, probs, delimiter="\t") writes for the [L, L] probabilities of
+ * rnamsm_ss_head (the reference's `<name>.prob`), produced on the device: L*L records of 25 bytes, "%.18e" of the element (24
+ * characters for every float32 in [0, 1]: d.dddddddddddddddddde-XX, the digits computed exactly in integers) and then '\t', or
+ * '\n' behind the last column of a row.  rnamsm_ss_prob_text_bytes(L) = 25 L^2, or 0 for an L outside [1, RNAMSM_SS_MAX_L].
+ * probs [L, L] fp32 row-major (device); text: rnamsm_ss_prob_text_bytes(L) bytes, 16-byte aligned (device); fallback: one int32
+ * (device).  The call sets *fallback to 0 and then, from every thread that meets an element outside [0, 1] -- a set sign bit
+ * (-0.0 included), a value above 1.0, a NaN, an inf -- to 1, with plain stores (no atomics): text is exact when the word reads 0
+ * and unspecified when it reads 1 (the caller then formats that matrix on the host, where a NaN-poisoned map comes out as `nan`
+ * fields).  Nothing is allocated inside the call and it takes no workspace.
+ * Packed: B members in one call, every member's text and word exactly those of the lone call on it, whatever its company.  items:
+ * a HOST array, read during the call and free to go afterwards (the descriptors travel as kernel arguments, 32 members per
+ * launch).  Members may share a fallback word (it then reads 1 when any of them left the domain); their texts must not overlap.
+ * Refused (RNAMSM_ERR_INVALID) before anything is enqueued, rnamsm_last_error naming the member where one is at fault: B outside
+ * [1, RNAMSM_SS_MAX_BATCH], an L outside [1, RNAMSM_SS_MAX_L], a null pointer, probs or fallback not 4-byte aligned, text not
+ * 16-byte aligned. */
+typedef struct {                 /* one matrix of the batch */
+    const float* probs;          /* device [L, L] */
+    int32_t      L;              /* 1 .. RNAMSM_SS_MAX_L */
+    uint8_t*     text;           /* device, 25 L^2 bytes, 16-byte aligned */
+    int32_t*     fallback;       /* device, one word */
+} rnamsm_ss_text_item;
+size_t rnamsm_ss_prob_text_bytes(int L);
+int rnamsm_ss_prob_text(const float* probs, int L, uint8_t* text, int32_t* fallback, void* stream);
+int rnamsm_ss_prob_text_packed(const rnamsm_ss_text_item* items, int B, void* stream);
+
 /* f5 -- RNA-MSM RSA (relative solvent accessibility) predictor (_downstream_tasks/RSA: predict.py, model/_0811/model_entry.py
  * FrameModel(Cin, 1, planes 64, depth 1, BatchNorm1d)) for an ensemble of n_models members in one set of four launches, exact fp32:
  *   x[c, p]  = (onehot(code[p])[c] - mu_oh[c]) / std_oh[c]  (c < 4, only with use_onehot),

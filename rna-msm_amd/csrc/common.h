@@ -460,15 +460,22 @@ template <class T>
 __global__ void members_kernel(MemberChunk<T> chunk, int n, T* __restrict__ dev) {
     if ((int)threadIdx.x < n) dev[threadIdx.x] = chunk.m[threadIdx.x];
 }
-// dev[b] = fill(b) for b = 0 .. B-1; fill is called in member order, so running prefix sums can live in the caller's lambda.
-// The unused entries of the last chunk repeat its entry 0.  name: the launch's name in an error text.
+// The chunk of members b0 .. b0 + n - 1 (n = what is left of B, at most 32): fill is called in member order, so running prefix
+// sums can live in the caller's lambda.  The unused entries of the last chunk repeat its entry 0.
+template <class T, class Fill>
+MemberChunk<T> member_chunk(int b0, int B, Fill& fill, int& n) {
+    static_assert(sizeof(T) == 64, "descriptor layout");
+    MemberChunk<T> chunk;
+    n = B - b0 < 32 ? B - b0 : 32;
+    for (int i = 0; i < 32; ++i) chunk.m[i] = i < n ? fill(b0 + i) : chunk.m[0];
+    return chunk;
+}
+// dev[b] = fill(b) for b = 0 .. B-1.  name: the launch's name in an error text.
 template <class T, class Fill>
 int upload_members(T* dev, int B, Fill fill, hipStream_t stream, const char* name) {
-    static_assert(sizeof(T) == 64, "descriptor layout");
     for (int b0 = 0; b0 < B; b0 += 32) {
-        MemberChunk<T> chunk;
-        const int n = B - b0 < 32 ? B - b0 : 32;
-        for (int i = 0; i < 32; ++i) chunk.m[i] = i < n ? fill(b0 + i) : chunk.m[0];
+        int n;
+        const MemberChunk<T> chunk = member_chunk<T>(b0, B, fill, n);
         hipLaunchKernelGGL(members_kernel<T>, dim3(1), dim3(32), 0, stream, chunk, n, dev + b0);
         RNAMSM_CHECK_LAUNCH(name);
     }

@@ -32,6 +32,7 @@ W_SS_BLOCK = ("conv1.weight", "bn1.weight", "bn1.bias", "conv2.weight", "bn2.wei
 W_SS_HEAD = ("fc1.weight", "fc1.bias")
 SS_MAX_L = 1024
 SS_MAX_BATCH = 1024
+SS_TEXT_RECORD = 25                # bytes of one element of the .prob text: "%.18e" and its separator
 
 # index tables of rnamsm_rsa_head's weight-pointer array (include/rnamsm.h): four statistics, then 26 packed entries per member
 W_RSA_GLOBAL = ("mu_emb", "std_emb", "mu_oh", "std_oh")
@@ -55,6 +56,11 @@ class SsItem(ctypes.Structure):
     """rnamsm_ss_item: one structure of an rnamsm_ss_head_packed batch (device pointers as integers)."""
     _fields_ = [("atp", c_void_p), ("atp_plane_stride", c_int64), ("base_codes", c_void_p), ("L", ctypes.c_int32),
                 ("logits", c_void_p), ("probs", c_void_p)]
+
+
+class SsTextItem(ctypes.Structure):
+    """rnamsm_ss_text_item: one matrix of an rnamsm_ss_prob_text_packed batch (device pointers as integers)."""
+    _fields_ = [("probs", c_void_p), ("L", ctypes.c_int32), ("text", c_void_p), ("fallback", c_void_p)]
 
 
 class RsaItem(ctypes.Structure):
@@ -119,6 +125,9 @@ _SIGNATURES = {
                                c_void_p]),
     "rnamsm_ss_head_packed_workspace_bytes": (c_size_t, [c_int, POINTER(c_int)]),
     "rnamsm_ss_head_packed": (c_int, [POINTER(SsItem), c_int, c_int, POINTER(c_void_p), c_void_p, c_size_t, c_void_p]),
+    "rnamsm_ss_prob_text_bytes": (c_size_t, [c_int]),
+    "rnamsm_ss_prob_text": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
+    "rnamsm_ss_prob_text_packed": (c_int, [POINTER(SsTextItem), c_int, c_void_p]),
     "rnamsm_rsa_head_workspace_bytes": (c_size_t, [c_int, c_int]),
     "rnamsm_rsa_head": (c_int, [c_void_p, c_int64, c_void_p, c_int, c_int, c_int, POINTER(c_void_p), c_void_p, c_void_p, c_void_p,
                                 c_size_t, c_void_p]),

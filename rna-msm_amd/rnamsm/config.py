@@ -43,6 +43,9 @@ class DataConfig:                       # RNA_MSM_Inference.py:20-32
     # SS_result/<id>.{ct,bpseq,prob} are written next to the .npy files (_downstream_tasks/SS/predict.py's files; the sequence
     # is row 0 of the tokens the forward ran on, so a T of the alignment reads as U there)
     ss_model_path: str = ""
+    # with the SS head on: SS_result/<id>.prob is formatted on the device (rnamsm_ss_prob_text) and written as one block; false =
+    # np.savetxt on the writer thread, as before.  The same bytes either way.
+    ss_prob_text: bool = True
     # extra (not in the reference): "" = off; else an RSA model directory of the reference (_downstream_tasks/RSA/models/OH+RNA-MSM_Emb:
     # model_pcc_*.pt and the statistic_dict*.pickle files): the solvent-accessibility ensemble (rnamsm.rsa) then runs on every
     # alignment's embedding where it lies on the device, and RSA_result/<id>_<k>/<id>.txt, RSA_result/<id>_ensemble/<id>.txt are

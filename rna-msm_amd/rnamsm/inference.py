@@ -342,15 +342,27 @@ def extract_feat(cfg: Config, model: Optional[MSATransformer] = None, gather_to_
         for code, ch in enumerate("ACGU"):
             ss_lut[alphabet.tok_to_idx[ch]] = code
         ss_lut = ss_lut.to(device)
+    # data.ss_prob_text (default on): the `.prob` text is formatted on the device behind the head (rnamsm.ss.prob_text) and the
+    # writer thread's share of it is one binary write, where np.savetxt formats L^2 numbers under the GIL; the files are the same
+    # bytes.  Under gather_to_rank0 the host path stays: the gathered items keep their tensors_per_item.
+    ss_text_on = ss_model is not None and bool(getattr(cfg.data, "ss_prob_text", True)) and not (gather_to_rank0 and world > 1)
 
-    def ss_text_jobs(rna_id: str, probs, tok_row) -> list:
-        """Writer jobs of SS_result/<id>.*: the query's tokens first (turned into its letters), then the probabilities."""
-        seq = []
+    def ss_text_jobs(rna_id: str, probs, tok_row, text=None, fallback=None) -> list:
+        """Writer jobs of SS_result/<id>.*: the query's tokens first (turned into its letters), the device-made `.prob` text and its
+        fallback word where the formatter is on, then the probabilities (still needed for the pairs)."""
+        seq, made = [], []
 
         def letters(toks: np.ndarray) -> None:
             seq.append("".join(alphabet.all_toks[int(t)] for t in toks))
 
-        return [(letters, tok_row), (lambda prob: ss.write_ss_files(prob, seq[0], rna_id, save_dir), probs)]
+        def finish(prob: np.ndarray) -> None:
+            if made:
+                ss.write_ss_files(prob, seq[0], rna_id, save_dir, prob_text=made[0], fallback=int(made[1][0]))
+            else:
+                ss.write_ss_files(prob, seq[0], rna_id, save_dir)
+
+        extra = [(made.append, text), (made.append, fallback)] if text is not None else []
+        return [(letters, tok_row)] + extra + [(finish, probs)]
     # data.rsa_model_dir: the solvent-accessibility ensemble on each alignment's device-resident embedding (rnamsm.rsa)
     rsa_model = rsa.load_ensemble(cfg.data.rsa_model_dir, device) if getattr(cfg.data, "rsa_model_dir", "") else None
     if rsa_model is not None:
@@ -370,12 +382,14 @@ def extract_feat(cfg: Config, model: Optional[MSATransformer] = None, gather_to_
         return [(letters, tok_row), (lambda v: rsa.write_rsa_files(v, seq[0], rna_id, save_dir, rsa_model.model_names, rsa_rng), values)]
 
     def head_jobs(rna_id: str, heads) -> list:
-        """heads: the tensors deliver() appended for the heads that are on -- (probabilities, tokens) of SS, then (RSA, tokens)."""
+        """heads: the tensors deliver() appended for the heads that are on -- (probabilities, tokens) of SS, with (text, fallback
+        word) behind them where the formatter is on, then (RSA, tokens)."""
         heads = list(heads or ())
         jobs = []
         if ss_model is not None and heads:
-            jobs += ss_text_jobs(rna_id, heads[0], heads[1])
-            heads = heads[2:]
+            n = 4 if ss_text_on else 2
+            jobs += ss_text_jobs(rna_id, *heads[:n])
+            heads = heads[n:]
         if rsa_model is not None and heads:
             jobs += rsa_text_jobs(rna_id, heads[0], heads[1])
         return jobs
@@ -406,8 +420,9 @@ def extract_feat(cfg: Config, model: Optional[MSATransformer] = None, gather_to_
     reader = ThreadPoolExecutor(1, thread_name_prefix="rnamsm-msa-reader") if async_io else None
 
     def emit(rna_id: str, emb: torch.Tensor, atp: torch.Tensor, after: Optional[torch.cuda.Event] = None, ss_out=None) -> None:
-        """ss_out: the heads' device tensors -- (probabilities [L, L], query tokens [L]) when data.ss_model_path is set, then
-        (RSA [K, L], query tokens [L]) when data.rsa_model_dir is set."""
+        """ss_out: the heads' device tensors -- (probabilities [L, L], query tokens [L]) when data.ss_model_path is set, with
+        (`.prob` text [25 L^2], fallback word [1]) behind them when data.ss_prob_text is on, then (RSA [K, L], query tokens [L]) when
+        data.rsa_model_dir is set."""
         extra = head_jobs(rna_id, ss_out)
         if writer is not None:
             writer.submit([(save_dir / f"{rna_id}_atp.npy", atp), (save_dir / f"{rna_id}_emb.npy", emb)] + extra,
@@ -438,13 +453,16 @@ def extract_feat(cfg: Config, model: Optional[MSATransformer] = None, gather_to_
             pending = reader.submit(read, mine[0]) if reader and len(mine) else None
             def deliver(idx: int, emb: torch.Tensor, atp: torch.Tensor, after: Optional[torch.cuda.Event] = None,
                         toks: Optional[torch.Tensor] = None, ss_probs: Optional[torch.Tensor] = None,
-                        rsa_vals: Optional[torch.Tensor] = None) -> None:
+                        rsa_vals: Optional[torch.Tensor] = None, ss_text: Optional[tuple] = None) -> None:
                 """ss_probs / rsa_vals: this alignment's base-pair probabilities / [K, L] RSA where its group's batched head (ss_group,
-                rsa_group) has already computed them; absent, the lone head runs here."""
+                rsa_group) has already computed them; absent, the lone head runs here.  ss_text: (text, fallback word) of ss_probs
+                from the group's one formatter call."""
                 ss_out = None
                 if ss_model is not None:          # the head reads atp where it lies (a packed group's slice included)
                     tok_row = toks[0, 1:]
                     ss_out = (ss_probs if ss_probs is not None else ss_model.predict(atp, ss_lut[tok_row]), tok_row)
+                    if ss_text_on:                # the formatter runs behind the head, before the event the copies wait for
+                        ss_out += tuple(ss_text) if ss_text is not None else ss.prob_text(ss_out[0])
                 if rsa_model is not None:         # the ensemble reads emb where it lies
                     tok_row = toks[0, 1:]
                     ss_out = (ss_out or ()) + (rsa_vals if rsa_vals is not None else rsa_model.predict(emb, rsa_lut[tok_row]), tok_row)
@@ -474,12 +492,13 @@ def extract_feat(cfg: Config, model: Optional[MSATransformer] = None, gather_to_
                 embs, atps = [o["emb"].contiguous() for o in outs], [o["atp"].contiguous() for o in outs]
                 toks_ = [t for _, t in members_]
                 probs = ss_group(atps, toks_)
+                texts = ss.prob_text_many(probs) if ss_text_on else [None] * len(probs)      # one packed call per group
                 vals = rsa_group(embs, toks_)
                 if (ss_model is not None or rsa_model is not None) and ev is not None:      # the copies wait for both batched heads too
                     ev = torch.cuda.Event()
                     ev.record(torch.cuda.current_stream())
-                for (i, t), emb, atp, p, v in zip(members_, embs, atps, probs, vals):
-                    deliver(i, emb, atp, ev, t, ss_probs=p, rsa_vals=v)
+                for (i, t), emb, atp, p, v, tx in zip(members_, embs, atps, probs, vals, texts):
+                    deliver(i, emb, atp, ev, t, ss_probs=p, rsa_vals=v, ss_text=tx)
 
             # data.batch_small_msas: small alignments go through ONE launch set per group (forward_ragged: padded into one
             # frame, every MSA scaled by its own depth); a lone forward of a few hundred tokens costs 5.5 ms on a mostly

@@ -630,6 +630,65 @@ def ss_head_packed(atps: Sequence[torch.Tensor], codes: Sequence[torch.Tensor], 
     return outs
 
 
+def _ss_text_operand(fn: str, probs: torch.Tensor, name: str):
+    """One [L, L] matrix of ss_prob_text / ss_prob_text_packed as the library reads it -> (probs, L)."""
+    _dev(probs, name)
+    if probs.dim() != 2 or probs.shape[0] != probs.shape[1]:
+        raise ValueError(f"{fn}: {name} must be [L, L], got {tuple(probs.shape)}")
+    L = probs.shape[0]
+    if not 1 <= L <= _lib.SS_MAX_L:
+        raise ValueError(f"{fn}: {name}: L = {L} outside [1, {_lib.SS_MAX_L}]")
+    return probs.contiguous(), L
+
+
+@_on_operand_device
+def ss_prob_text(probs: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The `.prob` text of [L, L] fp32 probabilities, written on the device (rnamsm_ss_prob_text): -> (uint8 [25 L^2], the
+    bytes of np.savetxt(f, probs, delimiter="\\t"); int32 [1], the fallback word: 1 when an element lies outside [0, 1] -- NaN,
+    inf and -0.0 included -- and the text is then not to be used)."""
+    probs, L = _ss_text_operand("ss_prob_text", probs, "probs")
+    lib = _lib.load()
+    text = torch.empty(lib.rnamsm_ss_prob_text_bytes(L), dtype=torch.uint8, device=probs.device)
+    fallback = torch.empty(1, dtype=torch.int32, device=probs.device)
+    _lib.check(lib.rnamsm_ss_prob_text(probs.data_ptr(), L, text.data_ptr(), fallback.data_ptr(), _stream()))
+    return text, fallback
+
+
+@_on_operand_device
+def ss_prob_text_packed(probs: Sequence[torch.Tensor]) -> List[Tuple[torch.Tensor, torch.Tensor]]:
+    """ss_prob_text of every probs[b] ([L_b, L_b]) in one call (rnamsm_ss_prob_text_packed) -> a list of (text, fallback word),
+    each exactly what ss_prob_text gives for that matrix alone.  One text and one word allocation per call: the returned tensors
+    are views (every text starts on a 16-byte boundary of the buffer)."""
+    probs = list(probs)
+    if not probs:
+        return []
+    B = len(probs)
+    if B > _lib.SS_MAX_BATCH:
+        raise ValueError(f"ss_prob_text_packed: {B} matrices exceed the limit of {_lib.SS_MAX_BATCH} per call")
+    device = probs[0].device if isinstance(probs[0], torch.Tensor) else None
+    Ls = []
+    for b in range(B):
+        probs[b], L = _ss_text_operand("ss_prob_text_packed", probs[b], f"probs[{b}]")
+        if probs[b].device != device:
+            raise ValueError(f"ss_prob_text_packed: probs[{b}] lies on {probs[b].device}, probs[0] on {device}")
+        Ls.append(L)
+    lib = _lib.load()
+    offs, total = [], 0
+    for L in Ls:
+        offs.append(total)
+        total += (_lib.SS_TEXT_RECORD * L * L + 15) & ~15
+    buf = torch.empty(total, dtype=torch.uint8, device=device)
+    words = torch.empty(B, dtype=torch.int32, device=device)
+    items = (_lib.SsTextItem * B)()
+    outs = []
+    for b, (L, off) in enumerate(zip(Ls, offs)):
+        text, word = buf[off:off + _lib.SS_TEXT_RECORD * L * L], words[b:b + 1]
+        items[b] = _lib.SsTextItem(probs[b].data_ptr(), L, text.data_ptr(), word.data_ptr())
+        outs.append((text, word))
+    _lib.check(lib.rnamsm_ss_prob_text_packed(items, B, _stream()))
+    return outs
+
+
 def _rsa_operands(fn: str, emb: torch.Tensor, bc: torch.Tensor, name: str, bc_name: str):
     """The operand rules of one alignment, for rsa_head and for every member of rsa_head_packed: -> (emb, row stride, base_codes,
     L) as the library reads them (an embedding whose rows are not contiguous, overlap or do not start at a 16-byte boundary is

@@ -4,7 +4,8 @@
 `rna-msm_attention.pt` state_dict loads with strict=True; its arithmetic is one HIP entry point (rnamsm_ss_head, exact fp32
 on the matrix cores) that reads the [120, L, L] maps where they lie on the device.  `write_ss_files` is the reference's
 post-processing (code/post_processing/processing_output.py: prob_to_secondary_structure without the VARNA plots): the
-same `.ct`, `.bpseq` and `.prob` files, byte for byte.
+same `.ct`, `.bpseq` and `.prob` files, byte for byte.  `prob_text` / `prob_text_many` format the `.prob` text on the device
+(rnamsm_ss_prob_text), so that the writer's share of it is one binary write.
 """
 from __future__ import annotations
 
@@ -191,6 +192,22 @@ def load_predictor(path: Union[str, Path], device, num_blocks: int = 16) -> SSPr
     return model.eval().to(device)
 
 
+def prob_text(probs: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The bytes of `<name>.prob` for the [L, L] probabilities `probs` on the HIP device -> (uint8 [25 L^2], int32 [1]): the text
+    np.savetxt would write, and the fallback word -- 1 when an element has no fixed-width form (outside [0, 1]: a NaN-poisoned
+    map), in which case the text must not be used (write_ss_files then takes the np.savetxt path)."""
+    return ops.ss_prob_text(probs)
+
+
+def prob_text_many(probs: Sequence[torch.Tensor]) -> List[Tuple[torch.Tensor, torch.Tensor]]:
+    """prob_text() of every matrix in as few calls as the batch limit allows; each result is the lone call's."""
+    probs = list(probs)
+    out: List[Tuple[torch.Tensor, torch.Tensor]] = []
+    for i in range(0, len(probs), _lib.SS_MAX_BATCH):
+        out += ops.ss_prob_text_packed(probs[i:i + _lib.SS_MAX_BATCH])
+    return out
+
+
 # ---------------------------------------------------------------------- post-processing (processing_output.py)
 def _multiplet_free(pairs: List[Tuple[int, int]], prob: np.ndarray) -> List[Tuple[int, int]]:
     """multiplets_free_bp: while some base is in two or more pairs, drop -- for every such base, in ascending base order,
@@ -221,12 +238,22 @@ def secondary_structure(prob: np.ndarray) -> List[Tuple[int, int]]:
     return _multiplet_free(pairs, prob)
 
 
-def write_ss_files(prob: np.ndarray, seq: str, name: str, output_dir: Union[str, Path]) -> List[Tuple[int, int]]:
-    """`<output_dir>/SS_result/<name>.{ct,bpseq,prob}` as the reference writes them; returns the pairs."""
+def write_ss_files(prob: np.ndarray, seq: str, name: str, output_dir: Union[str, Path], prob_text=None,
+                   fallback: int = 0) -> List[Tuple[int, int]]:
+    """`<output_dir>/SS_result/<name>.{ct,bpseq,prob}` as the reference writes them; returns the pairs.
+    prob_text, fallback: the text and the fallback word of prob_text(prob), on the host (bytes or a uint8 array of 25 L^2).  With a
+    text and fallback == 0 the `.prob` file is one binary write of it; otherwise np.savetxt formats `prob` as before -- the same
+    bytes either way."""
     prob = np.asarray(prob, dtype=np.float32)
     L = len(seq)
     if prob.shape != (L, L):
         raise ValueError(f"write_ss_files: probabilities of shape {prob.shape} for a sequence of length {L}")
+    if prob_text is not None and not int(fallback):
+        prob_text = memoryview(prob_text if isinstance(prob_text, (bytes, bytearray)) else np.ascontiguousarray(prob_text, dtype=np.uint8))
+        if prob_text.nbytes != _lib.SS_TEXT_RECORD * L * L:
+            raise ValueError(f"write_ss_files: a text of {prob_text.nbytes} bytes for a sequence of length {L}")
+    else:
+        prob_text = None
     pairs = secondary_structure(prob)
     out = os.path.join(str(output_dir), "SS_result")
     os.makedirs(out, exist_ok=True)
@@ -243,5 +270,9 @@ def write_ss_files(prob: np.ndarray, seq: str, name: str, output_dir: Union[str,
                header=f"{L}\t\t{name}\t\tRNAMSM_SS output\n", comments="")
     bp = np.vstack((fmt_int(idx), bases, fmt_int(partner))).T
     np.savetxt(os.path.join(out, name + ".bpseq"), bp, delimiter=" ", fmt="%s", header="#" + name, comments="")
-    np.savetxt(os.path.join(out, name + ".prob"), prob, delimiter="\t")
+    if prob_text is not None:
+        with open(os.path.join(out, name + ".prob"), "wb") as f:
+            f.write(prob_text)
+    else:
+        np.savetxt(os.path.join(out, name + ".prob"), prob, delimiter="\t")
     return pairs
