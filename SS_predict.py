@@ -55,8 +55,8 @@ def main(argv=None):
             sys.exit(f"SS_predict.py: {name}: sequence of length {len(seq)} but attention maps of L = {atp.shape[-1]} "
                      f"in {atp_path}")
         with torch.no_grad():
-            prob = model.predict(atp_dev, seq).cpu().numpy()
-        ss.write_ss_files(prob, seq, name, args.featdir)
+            prob, partner, counts, ct_body, bpseq_body = (t.cpu().numpy() for t in model.predict_structure(atp_dev, seq))
+        ss.write_ss_files(prob, seq, name, args.featdir, partner=partner, counts=counts, ct_body=ct_body, bpseq_body=bpseq_body)
         print(f"{name}: {os.path.join(args.featdir, 'SS_result', name)}.{{ct,bpseq,prob}}")
 
 

@@ -427,6 +427,48 @@ size_t rnamsm_ss_prob_text_bytes(int L);
 int rnamsm_ss_prob_text(const float* probs, int L, uint8_t* text, int32_t* fallback, void* stream);
 int rnamsm_ss_prob_text_packed(const rnamsm_ss_text_item* items, int B, void* stream);
 
+/* f4, the predicted structure -- the reference's prob_to_secondary_structure (code/post_processing/processing_output.py: the upper
+ * triangle above 0.516, multiplets_free_bp, the .ct and .bpseq tables; without the VARNA plots) on the [L, L] probabilities where they
+ * lie on the device.  The decoding as a graph process: {i, j}, i < j, is an edge iff probs[i, j] > float32(0.516) (only the upper
+ * triangle is read; NaN is never an edge, +inf is one); in a round every base of degree >= 2 marks its incident edge of lowest
+ * probability, on equal values the one to the lowest partner, and all marked edges are removed at once; rounds repeat until no base
+ * has two partners (at most L - 2).  Every float pattern has a defined outcome: the decoding has no fallback.
+ * probs [L, L] fp32 row-major; letters uint8 [L]: the sequence's characters as the tables print them (all device memory).  Outputs:
+ *   partner int32 [L]      0 = unpaired, else the partner's 1-based index: the fifth .ct column, the third .bpseq column
+ *   counts  int32 [4]      {pairs, bytes written to ct, bytes written to bpseq, fallback}
+ *   ct      the body of `<name>.ct`: L lines "%d\t\t%c\t\t%d\t\t%d\t\t%d\t\t%d\n" of (i, letter, i - 1, i + 1 or 0 on the last line,
+ *           partner, i), i = 1 .. L; the caller prepends the header line that carries the name
+ *   bpseq   the body of `<name>.bpseq`: L lines "%d %c %d\n" of (i, letter, partner)
+ * ct / bpseq hold at least the bounds of rnamsm_ss_struct_text_bytes(L, &ct_bytes, &bpseq_bytes) (32 L and 12 L: the longest lines
+ * at L = 1024); bytes behind counts[1] / counts[2] are not written.  A letter of 0 or >= 128 -- nothing the host writer prints as
+ * that one byte -- sets counts[3] = 1 (one plain store per structure): its two bodies are then unspecified and the caller writes
+ * its tables on the host; partner and counts[0] are valid either way.
+ * workspace: rnamsm_ss_pairs_workspace_bytes(B, Ls) bytes (B = 1 and &L for the lone call), 16-byte aligned, caller-owned (nothing
+ * is allocated inside): the members' adjacency bit matrices, L x ceil(L / 64) 64-bit words each, rounded up to 256 bytes.  The
+ * size is 0 for B outside [1, RNAMSM_SS_MAX_BATCH], a null Ls or an L outside [1, RNAMSM_SS_MAX_L].  Its contents on entry do not
+ * matter.
+ * Packed: B members of unlike L, one workgroup each, 32 members per launch (the descriptors travel as kernel arguments; items is a
+ * HOST array, free to go after the call).  A member's four outputs are byte-identical to the lone call's, whatever its company;
+ * the members' outputs must not overlap.
+ * Refused (RNAMSM_ERR_INVALID) before anything is enqueued, rnamsm_last_error naming the member where one is at fault: B outside
+ * [1, RNAMSM_SS_MAX_BATCH], an L outside [1, RNAMSM_SS_MAX_L], a null pointer, probs / partner / counts not 4-byte aligned, a
+ * workspace that is not 16-byte aligned or too short.
+ * No atomics: the same inputs give the same bytes on every run. */
+typedef struct {                 /* one structure of the batch */
+    const float*   probs;        /* device [L, L] */
+    const uint8_t* letters;      /* device [L] */
+    int32_t        L;            /* 1 .. RNAMSM_SS_MAX_L */
+    int32_t*       partner;      /* device [L] */
+    int32_t*       counts;       /* device [4] */
+    uint8_t*       ct;           /* device, 32 L bytes */
+    uint8_t*       bpseq;        /* device, 12 L bytes */
+} rnamsm_ss_pairs_item;
+size_t rnamsm_ss_pairs_workspace_bytes(int B, const int* Ls);
+int rnamsm_ss_struct_text_bytes(int L, size_t* ct_bytes, size_t* bpseq_bytes);
+int rnamsm_ss_pairs(const float* probs, const uint8_t* letters, int L, int32_t* partner, int32_t* counts, uint8_t* ct,
+                    uint8_t* bpseq, void* workspace, size_t workspace_bytes, void* stream);
+int rnamsm_ss_pairs_packed(const rnamsm_ss_pairs_item* items, int B, void* workspace, size_t workspace_bytes, void* stream);
+
 /* f5 -- RNA-MSM RSA (relative solvent accessibility) predictor (_downstream_tasks/RSA: predict.py, model/_0811/model_entry.py
  * FrameModel(Cin, 1, planes 64, depth 1, BatchNorm1d)) for an ensemble of n_models members in one set of four launches, exact fp32:
  *   x[c, p]  = (onehot(code[p])[c] - mu_oh[c]) / std_oh[c]  (c < 4, only with use_onehot),

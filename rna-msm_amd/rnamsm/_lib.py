@@ -33,6 +33,7 @@ W_SS_HEAD = ("fc1.weight", "fc1.bias")
 SS_MAX_L = 1024
 SS_MAX_BATCH = 1024
 SS_TEXT_RECORD = 25                # bytes of one element of the .prob text: "%.18e" and its separator
+SS_CT_LINE_MAX, SS_BPSEQ_LINE_MAX = 32, 12      # rnamsm_ss_struct_text_bytes: bytes of the longest .ct / .bpseq line at L = 1024
 
 # index tables of rnamsm_rsa_head's weight-pointer array (include/rnamsm.h): four statistics, then 26 packed entries per member
 W_RSA_GLOBAL = ("mu_emb", "std_emb", "mu_oh", "std_oh")
@@ -61,6 +62,12 @@ class SsItem(ctypes.Structure):
 class SsTextItem(ctypes.Structure):
     """rnamsm_ss_text_item: one matrix of an rnamsm_ss_prob_text_packed batch (device pointers as integers)."""
     _fields_ = [("probs", c_void_p), ("L", ctypes.c_int32), ("text", c_void_p), ("fallback", c_void_p)]
+
+
+class SsPairsItem(ctypes.Structure):
+    """rnamsm_ss_pairs_item: one structure of an rnamsm_ss_pairs_packed batch (device pointers as integers)."""
+    _fields_ = [("probs", c_void_p), ("letters", c_void_p), ("L", ctypes.c_int32), ("partner", c_void_p), ("counts", c_void_p),
+                ("ct", c_void_p), ("bpseq", c_void_p)]
 
 
 class RsaItem(ctypes.Structure):
@@ -128,6 +135,10 @@ _SIGNATURES = {
     "rnamsm_ss_prob_text_bytes": (c_size_t, [c_int]),
     "rnamsm_ss_prob_text": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
     "rnamsm_ss_prob_text_packed": (c_int, [POINTER(SsTextItem), c_int, c_void_p]),
+    "rnamsm_ss_pairs_workspace_bytes": (c_size_t, [c_int, POINTER(c_int)]),
+    "rnamsm_ss_struct_text_bytes": (c_int, [c_int, POINTER(c_size_t), POINTER(c_size_t)]),
+    "rnamsm_ss_pairs": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "rnamsm_ss_pairs_packed": (c_int, [POINTER(SsPairsItem), c_int, c_void_p, c_size_t, c_void_p]),
     "rnamsm_rsa_head_workspace_bytes": (c_size_t, [c_int, c_int]),
     "rnamsm_rsa_head": (c_int, [c_void_p, c_int64, c_void_p, c_int, c_int, c_int, POINTER(c_void_p), c_void_p, c_void_p, c_void_p,
                                 c_size_t, c_void_p]),

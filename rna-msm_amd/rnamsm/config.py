@@ -46,6 +46,10 @@ class DataConfig:                       # RNA_MSM_Inference.py:20-32
     # with the SS head on: SS_result/<id>.prob is formatted on the device (rnamsm_ss_prob_text) and written as one block; false =
     # np.savetxt on the writer thread, as before.  The same bytes either way.
     ss_prob_text: bool = True
+    # with the SS head on: the base pairs are decoded and the bodies of SS_result/<id>.ct / .bpseq written on the device
+    # (rnamsm_ss_pairs); with ss_prob_text on as well the [L, L] probabilities never reach the host.  false = secondary_structure and
+    # np.savetxt on the writer thread, as before.  The same bytes either way.
+    ss_pairs_device: bool = True
     # extra (not in the reference): "" = off; else an RSA model directory of the reference (_downstream_tasks/RSA/models/OH+RNA-MSM_Emb:
     # model_pcc_*.pt and the statistic_dict*.pickle files): the solvent-accessibility ensemble (rnamsm.rsa) then runs on every
     # alignment's embedding where it lies on the device, and RSA_result/<id>_<k>/<id>.txt, RSA_result/<id>_ensemble/<id>.txt are

@@ -347,22 +347,44 @@ def extract_feat(cfg: Config, model: Optional[MSATransformer] = None, gather_to_
     # bytes.  Under gather_to_rank0 the host path stays: the gathered items keep their tensors_per_item.
     ss_text_on = ss_model is not None and bool(getattr(cfg.data, "ss_prob_text", True)) and not (gather_to_rank0 and world > 1)
 
-    def ss_text_jobs(rna_id: str, probs, tok_row, text=None, fallback=None) -> list:
+    # data.ss_pairs_device (default on): the pairs are decoded and the bodies of `.ct` / `.bpseq` written on the device behind the head
+    # (rnamsm.ss.structure), so the writer thread no longer runs secondary_structure and two np.savetxt tables per structure; with
+    # the formatter on as well no [L, L] float tensor is copied to the host at all.  The host path stays under gather_to_rank0.
+    ss_pairs_on = ss_model is not None and bool(getattr(cfg.data, "ss_pairs_device", True)) and not (gather_to_rank0 and world > 1)
+    if ss_pairs_on:                    # a token that is no single ASCII character is 0: that structure's tables come from the host
+        ss_letters = torch.tensor([ord(t) if len(t) == 1 and ord(t) < 128 else 0 for t in alphabet.all_toks], dtype=torch.uint8).to(device)
+
+    def ss_text_jobs(rna_id: str, probs, tok_row, *made_on_device) -> list:
         """Writer jobs of SS_result/<id>.*: the query's tokens first (turned into its letters), the device-made `.prob` text and its
-        fallback word where the formatter is on, then the probabilities (still needed for the pairs)."""
-        seq, made = [], []
+        fallback word where the formatter is on, the partner vector, the counts and the two bodies where the decoding is on, then the
+        probabilities -- unless both are on: then they stay on the device, and are fetched by the worker only for a map whose text
+        could not be formatted (a NaN-poisoned one)."""
+        seq, made, tables = [], [], []
+        text_kinds = 2 if ss_text_on else 0
 
         def letters(toks: np.ndarray) -> None:
             seq.append("".join(alphabet.all_toks[int(t)] for t in toks))
 
-        def finish(prob: np.ndarray) -> None:
+        def finish(prob: Optional[np.ndarray]) -> None:
+            kw = {}
             if made:
-                ss.write_ss_files(prob, seq[0], rna_id, save_dir, prob_text=made[0], fallback=int(made[1][0]))
-            else:
-                ss.write_ss_files(prob, seq[0], rna_id, save_dir)
+                kw.update(prob_text=made[0], fallback=int(made[1][0]))
+            if tables:
+                kw.update(partner=tables[0], counts=tables[1], ct_body=tables[2], bpseq_body=tables[3])
+            ss.write_ss_files(prob, seq[0], rna_id, save_dir, **kw)
 
-        extra = [(made.append, text), (made.append, fallback)] if text is not None else []
-        return [(letters, tok_row)] + extra + [(finish, probs)]
+        def finish_without_probs(last: np.ndarray) -> None:
+            tables.append(last)
+            finish(probs.cpu().numpy() if int(made[1][0]) else None)      # behind the worker's event: the head has run
+
+        jobs = [(letters, tok_row)] + [(made.append, t) for t in made_on_device[:text_kinds]]
+        struct = made_on_device[text_kinds:]
+        if not struct:
+            return jobs + [(finish, probs)]
+        jobs += [(tables.append, t) for t in struct[:3]]
+        if ss_text_on:
+            return jobs + [(finish_without_probs, struct[3])]
+        return jobs + [(tables.append, struct[3]), (finish, probs)]
     # data.rsa_model_dir: the solvent-accessibility ensemble on each alignment's device-resident embedding (rnamsm.rsa)
     rsa_model = rsa.load_ensemble(cfg.data.rsa_model_dir, device) if getattr(cfg.data, "rsa_model_dir", "") else None
     if rsa_model is not None:
@@ -383,11 +405,12 @@ def extract_feat(cfg: Config, model: Optional[MSATransformer] = None, gather_to_
 
     def head_jobs(rna_id: str, heads) -> list:
         """heads: the tensors deliver() appended for the heads that are on -- (probabilities, tokens) of SS, with (text, fallback
-        word) behind them where the formatter is on, then (RSA, tokens)."""
+        word) behind them where the formatter is on and (partner, counts, ct body, bpseq body) where the decoding is, then (RSA,
+        tokens)."""
         heads = list(heads or ())
         jobs = []
         if ss_model is not None and heads:
-            n = 4 if ss_text_on else 2
+            n = 2 + 2 * ss_text_on + 4 * ss_pairs_on
             jobs += ss_text_jobs(rna_id, *heads[:n])
             heads = heads[n:]
         if rsa_model is not None and heads:
@@ -421,8 +444,8 @@ def extract_feat(cfg: Config, model: Optional[MSATransformer] = None, gather_to_
 
     def emit(rna_id: str, emb: torch.Tensor, atp: torch.Tensor, after: Optional[torch.cuda.Event] = None, ss_out=None) -> None:
         """ss_out: the heads' device tensors -- (probabilities [L, L], query tokens [L]) when data.ss_model_path is set, with
-        (`.prob` text [25 L^2], fallback word [1]) behind them when data.ss_prob_text is on, then (RSA [K, L], query tokens [L]) when
-        data.rsa_model_dir is set."""
+        (`.prob` text [25 L^2], fallback word [1]) behind them when data.ss_prob_text is on and (partner [L], counts [4], ct body,
+        bpseq body) when data.ss_pairs_device is, then (RSA [K, L], query tokens [L]) when data.rsa_model_dir is set."""
         extra = head_jobs(rna_id, ss_out)
         if writer is not None:
             writer.submit([(save_dir / f"{rna_id}_atp.npy", atp), (save_dir / f"{rna_id}_emb.npy", emb)] + extra,
@@ -453,16 +476,19 @@ def extract_feat(cfg: Config, model: Optional[MSATransformer] = None, gather_to_
             pending = reader.submit(read, mine[0]) if reader and len(mine) else None
             def deliver(idx: int, emb: torch.Tensor, atp: torch.Tensor, after: Optional[torch.cuda.Event] = None,
                         toks: Optional[torch.Tensor] = None, ss_probs: Optional[torch.Tensor] = None,
-                        rsa_vals: Optional[torch.Tensor] = None, ss_text: Optional[tuple] = None) -> None:
+                        rsa_vals: Optional[torch.Tensor] = None, ss_text: Optional[tuple] = None,
+                        ss_struct: Optional[tuple] = None) -> None:
                 """ss_probs / rsa_vals: this alignment's base-pair probabilities / [K, L] RSA where its group's batched head (ss_group,
                 rsa_group) has already computed them; absent, the lone head runs here.  ss_text: (text, fallback word) of ss_probs
-                from the group's one formatter call."""
+                from the group's one formatter call; ss_struct: (partner, counts, ct body, bpseq body) from its one decoding call."""
                 ss_out = None
                 if ss_model is not None:          # the head reads atp where it lies (a packed group's slice included)
                     tok_row = toks[0, 1:]
                     ss_out = (ss_probs if ss_probs is not None else ss_model.predict(atp, ss_lut[tok_row]), tok_row)
                     if ss_text_on:                # the formatter runs behind the head, before the event the copies wait for
                         ss_out += tuple(ss_text) if ss_text is not None else ss.prob_text(ss_out[0])
+                    if ss_pairs_on:               # ... and so does the decoding: one lone call
+                        ss_out += tuple(ss_struct) if ss_struct is not None else ss.structure(ss_out[0], ss_letters[tok_row])
                 if rsa_model is not None:         # the ensemble reads emb where it lies
                     tok_row = toks[0, 1:]
                     ss_out = (ss_out or ()) + (rsa_vals if rsa_vals is not None else rsa_model.predict(emb, rsa_lut[tok_row]), tok_row)
@@ -493,12 +519,14 @@ def extract_feat(cfg: Config, model: Optional[MSATransformer] = None, gather_to_
                 toks_ = [t for _, t in members_]
                 probs = ss_group(atps, toks_)
                 texts = ss.prob_text_many(probs) if ss_text_on else [None] * len(probs)      # one packed call per group
+                structs = (ss.structure_many(probs, [ss_letters[t[0, 1:]] for t in toks_]) if ss_pairs_on
+                           else [None] * len(probs))                                           # one packed call per group
                 vals = rsa_group(embs, toks_)
                 if (ss_model is not None or rsa_model is not None) and ev is not None:      # the copies wait for both batched heads too
                     ev = torch.cuda.Event()
                     ev.record(torch.cuda.current_stream())
-                for (i, t), emb, atp, p, v, tx in zip(members_, embs, atps, probs, vals, texts):
-                    deliver(i, emb, atp, ev, t, ss_probs=p, rsa_vals=v, ss_text=tx)
+                for (i, t), emb, atp, p, v, tx, st in zip(members_, embs, atps, probs, vals, texts, structs):
+                    deliver(i, emb, atp, ev, t, ss_probs=p, rsa_vals=v, ss_text=tx, ss_struct=st)
 
             # data.batch_small_msas: small alignments go through ONE launch set per group (forward_ragged: padded into one
             # frame, every MSA scaled by its own depth); a lone forward of a few hundred tokens costs 5.5 ms on a mostly

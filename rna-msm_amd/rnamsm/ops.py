@@ -689,6 +689,75 @@ def ss_prob_text_packed(probs: Sequence[torch.Tensor]) -> List[Tuple[torch.Tenso
     return outs
 
 
+def _ss_pairs_operands(fn: str, probs: torch.Tensor, letters: torch.Tensor, name: str, letters_name: str):
+    """One structure of ss_pairs / ss_pairs_packed as the library reads it -> (probs, letters, L)."""
+    probs, L = _ss_text_operand(fn, probs, name)
+    _dev(letters, letters_name, torch.uint8)
+    if letters.dim() != 1 or letters.shape[0] != L:
+        raise ValueError(f"{fn}: {letters.shape[0] if letters.dim() == 1 else tuple(letters.shape)} letters for {name} of L = {L}")
+    return probs, letters.contiguous(), L
+
+
+@_on_operand_device
+def ss_pairs(probs: torch.Tensor, letters: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """The structure of [L, L] fp32 probabilities, decoded on the device (rnamsm_ss_pairs); letters uint8 [L]: the sequence's
+    characters -> (partner int32 [L]: 0 or the partner's 1-based index; counts int32 [4]: pairs, bytes of the .ct body, bytes of
+    the .bpseq body, fallback; the .ct body uint8 [32 L]; the .bpseq body uint8 [12 L]).  Only the first counts[1] / counts[2] bytes
+    of the bodies are written; with counts[3] == 1 (a letter of 0 or >= 128) they are not to be used."""
+    return _ss_pairs_run("ss_pairs", [probs], [letters])[0]
+
+
+@_on_operand_device
+def ss_pairs_packed(probs: Sequence[torch.Tensor], letters: Sequence[torch.Tensor]):
+    """ss_pairs of every (probs[b], letters[b]) in one call (rnamsm_ss_pairs_packed: one workgroup per structure) -> a list of
+    (partner, counts, ct body, bpseq body), each byte-identical to ss_pairs on that structure alone.  One allocation per output kind
+    and one workspace per call: the returned tensors are views."""
+    return _ss_pairs_run("ss_pairs_packed", probs, letters)
+
+
+def _ss_pairs_run(_fn: str, probs, letters):
+    probs, letters = list(probs), list(letters)
+    if len(probs) != len(letters):
+        raise ValueError(f"{_fn}: {len(probs)} matrices for {len(letters)} letter rows")
+    if not probs:
+        return []
+    B = len(probs)
+    if B > _lib.SS_MAX_BATCH:
+        raise ValueError(f"{_fn}: {B} structures exceed the limit of {_lib.SS_MAX_BATCH} per call")
+    device = probs[0].device if isinstance(probs[0], torch.Tensor) else None
+    lone = _fn == "ss_pairs"
+    Ls = []
+    for b in range(B):
+        probs[b], letters[b], L = _ss_pairs_operands(_fn, probs[b], letters[b], "probs" if lone else f"probs[{b}]",
+                                                     "letters" if lone else f"letters[{b}]")
+        if probs[b].device != device or letters[b].device != device:
+            raise ValueError(f"{_fn}: probs[{b}] / letters[{b}] lie on {probs[b].device} / {letters[b].device}, probs[0] on {device}")
+        Ls.append(L)
+    lib = _lib.load()
+    total = sum(Ls)
+    ws = torch.empty(lib.rnamsm_ss_pairs_workspace_bytes(B, (_lib.c_int * B)(*Ls)), dtype=torch.uint8, device=device)
+    partner = torch.empty(total, dtype=torch.int32, device=device)
+    counts = torch.empty(B, 4, dtype=torch.int32, device=device)
+    ct = torch.empty(_lib.SS_CT_LINE_MAX * total, dtype=torch.uint8, device=device)
+    bpseq = torch.empty(_lib.SS_BPSEQ_LINE_MAX * total, dtype=torch.uint8, device=device)
+    outs, off = [], 0
+    for b, L in enumerate(Ls):
+        outs.append((partner[off:off + L], counts[b], ct[_lib.SS_CT_LINE_MAX * off:_lib.SS_CT_LINE_MAX * (off + L)],
+                     bpseq[_lib.SS_BPSEQ_LINE_MAX * off:_lib.SS_BPSEQ_LINE_MAX * (off + L)]))
+        off += L
+    if lone:
+        o = outs[0]
+        _lib.check(lib.rnamsm_ss_pairs(probs[0].data_ptr(), letters[0].data_ptr(), Ls[0], o[0].data_ptr(), o[1].data_ptr(),
+                                       o[2].data_ptr(), o[3].data_ptr(), ws.data_ptr(), ws.numel(), _stream()))
+        return outs
+    items = (_lib.SsPairsItem * B)()
+    for b, o in enumerate(outs):
+        items[b] = _lib.SsPairsItem(probs[b].data_ptr(), letters[b].data_ptr(), Ls[b], o[0].data_ptr(), o[1].data_ptr(),
+                                    o[2].data_ptr(), o[3].data_ptr())
+    _lib.check(lib.rnamsm_ss_pairs_packed(items, B, ws.data_ptr(), ws.numel(), _stream()))
+    return outs
+
+
 def _rsa_operands(fn: str, emb: torch.Tensor, bc: torch.Tensor, name: str, bc_name: str):
     """The operand rules of one alignment, for rsa_head and for every member of rsa_head_packed: -> (emb, row stride, base_codes,
     L) as the library reads them (an embedding whose rows are not contiguous, overlap or do not start at a 16-byte boundary is

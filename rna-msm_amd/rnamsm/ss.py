@@ -5,14 +5,15 @@
 on the matrix cores) that reads the [120, L, L] maps where they lie on the device.  `write_ss_files` is the reference's
 post-processing (code/post_processing/processing_output.py: prob_to_secondary_structure without the VARNA plots): the
 same `.ct`, `.bpseq` and `.prob` files, byte for byte.  `prob_text` / `prob_text_many` format the `.prob` text on the device
-(rnamsm_ss_prob_text), so that the writer's share of it is one binary write.
+(rnamsm_ss_prob_text), so that the writer's share of it is one binary write; `structure` / `structure_many` decode the base pairs
+and write the bodies of `.ct` / `.bpseq` there too (rnamsm_ss_pairs), so that the probabilities need not leave the device at all.
 """
 from __future__ import annotations
 
 import ctypes
 import os
 from pathlib import Path
-from typing import List, Sequence, Tuple, Union
+from typing import List, Optional, Sequence, Tuple, Union
 
 import numpy as np
 import torch
@@ -183,6 +184,22 @@ class SSPredictor(nn.Module):
     def logits_many(self, atps: Sequence[torch.Tensor], seqs: Sequence) -> List[torch.Tensor]:
         return self._run_many(atps, seqs, "logits")
 
+    def predict_structure(self, atp: torch.Tensor, seq, letters=None):
+        """predict() and structure() of its result -> (probs, partner, counts, ct body, bpseq body), all on the device.  letters:
+        the characters the tables print (uint8 [L]); taken from seq when that is a str."""
+        probs = self.predict(atp, seq)
+        return (probs,) + structure(probs, _letters_for(seq, letters, probs.device))
+
+    def predict_structure_many(self, atps: Sequence[torch.Tensor], seqs: Sequence, letters: Optional[Sequence] = None):
+        """predict_many() and structure_many() of its results -> a list of predict_structure()'s tuples, each the lone call's."""
+        seqs = list(seqs)
+        probs = self.predict_many(atps, seqs)
+        letters = list(letters) if letters is not None else [None] * len(seqs)
+        if len(letters) != len(seqs):
+            raise ValueError(f"SSPredictor: {len(letters)} letter rows for {len(seqs)} sequences")
+        rows = [_letters_for(s, l, p.device) for s, l, p in zip(seqs, letters, probs)]
+        return [(p,) + st for p, st in zip(probs, structure_many(probs, rows))]
+
 
 def load_predictor(path: Union[str, Path], device, num_blocks: int = 16) -> SSPredictor:
     """`rna-msm_attention.pt` (a plain state_dict) -> an SSPredictor on `device`, loaded strictly."""
@@ -206,6 +223,49 @@ def prob_text_many(probs: Sequence[torch.Tensor]) -> List[Tuple[torch.Tensor, to
     for i in range(0, len(probs), _lib.SS_MAX_BATCH):
         out += ops.ss_prob_text_packed(probs[i:i + _lib.SS_MAX_BATCH])
     return out
+
+
+def letter_codes(seq: str) -> np.ndarray:
+    """uint8 [L]: the bytes the tables print for seq; 0 for a character that is no single ASCII byte (the device then leaves the
+    two tables of that structure to the host writer)."""
+    return np.fromiter((ord(c) if ord(c) < 128 else 0 for c in seq), dtype=np.uint8, count=len(seq))
+
+
+def _letters_for(seq, letters, device) -> torch.Tensor:
+    if letters is None:
+        if not isinstance(seq, str):
+            raise ValueError("SSPredictor: letters are needed where the sequence is given as base codes")
+        letters = letter_codes(seq)
+    return torch.as_tensor(letters).reshape(-1).to(device=device, dtype=torch.uint8)
+
+
+def structure(probs: torch.Tensor, letters: torch.Tensor):
+    """The predicted structure of the [L, L] probabilities `probs` on the HIP device (rnamsm_ss_pairs); letters uint8 [L] on the
+    device -> (partner int32 [L]: 0 = unpaired, else the partner's 1-based index; counts int32 [4]: pairs, bytes of the `.ct` body,
+    bytes of the `.bpseq` body, fallback; ct body uint8 [32 L]; bpseq body uint8 [12 L]): what secondary_structure and the two
+    np.savetxt tables of write_ss_files give on the host, byte for byte.  fallback == 1 (a letter of 0 or >= 128): the bodies are
+    not to be used; the partner vector is valid either way."""
+    return ops.ss_pairs(probs, letters)
+
+
+def structure_many(probs: Sequence[torch.Tensor], letters: Sequence[torch.Tensor]):
+    """structure() of every (probs[b], letters[b]) in as few calls as the batch limit allows; each result is the lone call's."""
+    probs, letters = list(probs), list(letters)
+    if len(probs) != len(letters):
+        raise ValueError(f"structure_many: {len(probs)} matrices for {len(letters)} letter rows")
+    out = []
+    for i in range(0, len(probs), _lib.SS_MAX_BATCH):
+        out += ops.ss_pairs_packed(probs[i:i + _lib.SS_MAX_BATCH], letters[i:i + _lib.SS_MAX_BATCH])
+    return out
+
+
+def pairs_from_partner(partner) -> List[Tuple[int, int]]:
+    """The list secondary_structure returns -- pairs (i, j), i < j, 0-based, sorted -- from a partner vector (0 = unpaired, else the
+    partner's 1-based index)."""
+    if isinstance(partner, torch.Tensor):
+        partner = partner.cpu().numpy()
+    partner = np.asarray(partner).reshape(-1)
+    return [(int(i), int(partner[i]) - 1) for i in np.nonzero(partner)[0] if partner[i] - 1 > i]
 
 
 # ---------------------------------------------------------------------- post-processing (processing_output.py)
@@ -238,29 +298,9 @@ def secondary_structure(prob: np.ndarray) -> List[Tuple[int, int]]:
     return _multiplet_free(pairs, prob)
 
 
-def write_ss_files(prob: np.ndarray, seq: str, name: str, output_dir: Union[str, Path], prob_text=None,
-                   fallback: int = 0) -> List[Tuple[int, int]]:
-    """`<output_dir>/SS_result/<name>.{ct,bpseq,prob}` as the reference writes them; returns the pairs.
-    prob_text, fallback: the text and the fallback word of prob_text(prob), on the host (bytes or a uint8 array of 25 L^2).  With a
-    text and fallback == 0 the `.prob` file is one binary write of it; otherwise np.savetxt formats `prob` as before -- the same
-    bytes either way."""
-    prob = np.asarray(prob, dtype=np.float32)
+def _tables_on_host(out: str, name: str, seq: str, partner: np.ndarray) -> None:
+    """`<out>/<name>.ct` and `.bpseq` as the reference builds them: string tables through np.savetxt."""
     L = len(seq)
-    if prob.shape != (L, L):
-        raise ValueError(f"write_ss_files: probabilities of shape {prob.shape} for a sequence of length {L}")
-    if prob_text is not None and not int(fallback):
-        prob_text = memoryview(prob_text if isinstance(prob_text, (bytes, bytearray)) else np.ascontiguousarray(prob_text, dtype=np.uint8))
-        if prob_text.nbytes != _lib.SS_TEXT_RECORD * L * L:
-            raise ValueError(f"write_ss_files: a text of {prob_text.nbytes} bytes for a sequence of length {L}")
-    else:
-        prob_text = None
-    pairs = secondary_structure(prob)
-    out = os.path.join(str(output_dir), "SS_result")
-    os.makedirs(out, exist_ok=True)
-    partner = np.zeros(L, dtype=int)
-    for i, j in pairs:
-        partner[i] = j + 1
-        partner[j] = i + 1
     idx = np.arange(1, L + 1)
     bases = np.array(list(seq))
     fmt_int = lambda a: np.char.mod("%d", a)          # noqa: E731
@@ -270,6 +310,69 @@ def write_ss_files(prob: np.ndarray, seq: str, name: str, output_dir: Union[str,
                header=f"{L}\t\t{name}\t\tRNAMSM_SS output\n", comments="")
     bp = np.vstack((fmt_int(idx), bases, fmt_int(partner))).T
     np.savetxt(os.path.join(out, name + ".bpseq"), bp, delimiter=" ", fmt="%s", header="#" + name, comments="")
+
+
+def _tables_from_bodies(out: str, name: str, L: int, ct_body, bpseq_body) -> None:
+    """The same two files from device-made bodies: the header line and one binary write each.  np.savetxt ends the header with a
+    newline of its own: the .ct header, which ends in one already, is followed by an empty line."""
+    for ext, head, body in ((".ct", f"{L}\t\t{name}\t\tRNAMSM_SS output\n\n", ct_body), (".bpseq", f"#{name}\n", bpseq_body)):
+        with open(os.path.join(out, name + ext), "wb") as f:
+            f.write(head.encode("ascii"))
+            f.write(body)
+
+
+def write_ss_files(prob: Optional[np.ndarray], seq: str, name: str, output_dir: Union[str, Path], prob_text=None,
+                   fallback: int = 0, *, partner=None, counts=None, ct_body=None, bpseq_body=None) -> List[Tuple[int, int]]:
+    """`<output_dir>/SS_result/<name>.{ct,bpseq,prob}` as the reference writes them; returns the pairs.
+    prob_text, fallback: the text and the fallback word of prob_text(prob), on the host (bytes or a uint8 array of 25 L^2).  With a
+    text and fallback == 0 the `.prob` file is one binary write of it; otherwise np.savetxt formats `prob` as before -- the same
+    bytes either way.
+    partner, counts, ct_body, bpseq_body: the results of structure(prob, letters), on the host.  With a partner vector the pairs are
+    read from it instead of being decoded from `prob`; with the bodies and counts too, and counts[3] == 0, `.ct` and `.bpseq` are a
+    header line and one binary write each -- otherwise np.savetxt builds the two tables as before, the same bytes either way.
+    `prob` may be None when neither file needs it: a partner vector and a usable `.prob` text are given."""
+    L = len(seq)
+    if prob is not None:
+        prob = np.asarray(prob, dtype=np.float32)
+        if prob.shape != (L, L):
+            raise ValueError(f"write_ss_files: probabilities of shape {prob.shape} for a sequence of length {L}")
+    if prob_text is not None and not int(fallback):
+        prob_text = memoryview(prob_text if isinstance(prob_text, (bytes, bytearray)) else np.ascontiguousarray(prob_text, dtype=np.uint8))
+        if prob_text.nbytes != _lib.SS_TEXT_RECORD * L * L:
+            raise ValueError(f"write_ss_files: a text of {prob_text.nbytes} bytes for a sequence of length {L}")
+    else:
+        prob_text = None
+    if prob is None and (partner is None or prob_text is None):
+        raise ValueError("write_ss_files: without probabilities a partner vector and a usable .prob text are needed")
+    if partner is not None:
+        partner = np.asarray(partner).reshape(-1).astype(int)
+        if partner.shape[0] != L:
+            raise ValueError(f"write_ss_files: a partner vector of {partner.shape[0]} entries for a sequence of length {L}")
+        pairs = pairs_from_partner(partner)
+    else:
+        pairs = secondary_structure(prob)
+        partner = np.zeros(L, dtype=int)
+        for i, j in pairs:
+            partner[i] = j + 1
+            partner[j] = i + 1
+    bodies = None
+    if ct_body is not None and bpseq_body is not None and counts is not None and name.isascii():
+        counts = np.asarray(counts).reshape(-1)
+        if counts.shape[0] != 4:
+            raise ValueError(f"write_ss_files: {counts.shape[0]} counts, not 4")
+        if not int(counts[3]):
+            bodies = []
+            for body, n in ((ct_body, int(counts[1])), (bpseq_body, int(counts[2]))):
+                body = memoryview(body if isinstance(body, (bytes, bytearray)) else np.ascontiguousarray(body, dtype=np.uint8))
+                if not 0 < n <= body.nbytes:
+                    raise ValueError(f"write_ss_files: a body of {body.nbytes} bytes for a count of {n}")
+                bodies.append(body[:n])
+    out = os.path.join(str(output_dir), "SS_result")
+    os.makedirs(out, exist_ok=True)
+    if bodies is not None:
+        _tables_from_bodies(out, name, L, bodies[0], bodies[1])
+    else:
+        _tables_on_host(out, name, seq, partner)
     if prob_text is not None:
         with open(os.path.join(out, name + ".prob"), "wb") as f:
             f.write(prob_text)
