@@ -83,18 +83,18 @@ class _AsyncNpyWriter:
             try:
                 if self._err is None:
                     event.synchronize()
-                    for path, host in jobs:
-                        if callable(path):                  # a host-side consumer (the SS text files) instead of a .npy
-                            path(host.numpy())
+                    for path, hosts in jobs:
+                        if callable(path):                  # a host-side consumer (a head's text files) instead of a .npy
+                            path(*(h.numpy() for h in hosts))
                         else:
-                            np.save(path, host.numpy())
+                            np.save(path, hosts[0].numpy())
                     done()
             except BaseException as e:                  # noqa: BLE001  (reported by close())
                 self._err = e
 
     def submit(self, jobs, done, after: Optional[torch.cuda.Event] = None) -> None:
-        """jobs: [(path, device tensor)], written in this order (a callable in place of the path is called with the host array);
-        done(): called by the worker after the last file.
+        """jobs: [(path, device tensor)], written in this order; a callable in place of the path is called with the host array, or,
+        where the job carries a tuple of tensors, with the host array of each; done(): called by the worker after the last file.
         after: an event recorded behind the kernels that produced the tensors -- the copies then wait for THAT point of the compute
         stream only, not for what was enqueued since (the next packed group's forward: the CLI's pipelined pool); None = for
         everything enqueued so far."""
@@ -104,11 +104,14 @@ class _AsyncNpyWriter:
             self._stream.wait_stream(torch.cuda.current_stream())
         staged = []
         with torch.cuda.stream(self._stream):
-            for path, t in jobs:
-                host = torch.empty(t.shape, dtype=t.dtype, pin_memory=True)
-                host.copy_(t, non_blocking=True)
-                t.record_stream(self._stream)           # the allocator must not recycle t before the copy has run
-                staged.append((path, host))
+            for path, tensors in jobs:
+                hosts = []
+                for t in tensors if isinstance(tensors, tuple) else (tensors,):
+                    host = torch.empty(t.shape, dtype=t.dtype, pin_memory=True)
+                    host.copy_(t, non_blocking=True)
+                    t.record_stream(self._stream)       # the allocator must not recycle t before the copy has run
+                    hosts.append(host)
+                staged.append((path, hosts))
             event = torch.cuda.Event()
             event.record(self._stream)
         self._q.put((event, staged, done))              # blocks when `depth` MSAs are already in flight
@@ -335,87 +338,24 @@ def extract_feat(cfg: Config, model: Optional[MSATransformer] = None, gather_to_
 
     save_dir = root / cfg.data.MSA_path
     save_dir.mkdir(parents=True, exist_ok=True)
-    # data.ss_model_path: the secondary-structure head on each alignment's device-resident maps (rnamsm.ss)
-    ss_model = ss.load_predictor(cfg.data.ss_model_path, device) if getattr(cfg.data, "ss_model_path", "") else None
-    if ss_model is not None:
-        ss_lut = torch.full((len(alphabet.all_toks),), 255, dtype=torch.uint8)
-        for code, ch in enumerate("ACGU"):
-            ss_lut[alphabet.tok_to_idx[ch]] = code
-        ss_lut = ss_lut.to(device)
+    # The heads that are on, SS before RSA: each reads an alignment's device-resident outputs and makes one record of it (rnamsm.ss.SSHead:
+    # data.ss_model_path, the maps; rnamsm.rsa.RSAHead: data.rsa_model_dir, the embedding).
     # data.ss_prob_text (default on): the `.prob` text is formatted on the device behind the head (rnamsm.ss.prob_text) and the
     # writer thread's share of it is one binary write, where np.savetxt formats L^2 numbers under the GIL; the files are the same
-    # bytes.  Under gather_to_rank0 the host path stays: the gathered items keep their tensors_per_item.
-    ss_text_on = ss_model is not None and bool(getattr(cfg.data, "ss_prob_text", True)) and not (gather_to_rank0 and world > 1)
-
-    # data.ss_pairs_device (default on): the pairs are decoded and the bodies of `.ct` / `.bpseq` written on the device behind the head
+    # bytes.  data.ss_pairs_device (default on): the pairs are decoded and the bodies of `.ct` / `.bpseq` written on the device too
     # (rnamsm.ss.structure), so the writer thread no longer runs secondary_structure and two np.savetxt tables per structure; with
-    # the formatter on as well no [L, L] float tensor is copied to the host at all.  The host path stays under gather_to_rank0.
-    ss_pairs_on = ss_model is not None and bool(getattr(cfg.data, "ss_pairs_device", True)) and not (gather_to_rank0 and world > 1)
-    if ss_pairs_on:                    # a token that is no single ASCII character is 0: that structure's tables come from the host
-        ss_letters = torch.tensor([ord(t) if len(t) == 1 and ord(t) < 128 else 0 for t in alphabet.all_toks], dtype=torch.uint8).to(device)
-
-    def ss_text_jobs(rna_id: str, probs, tok_row, *made_on_device) -> list:
-        """Writer jobs of SS_result/<id>.*: the query's tokens first (turned into its letters), the device-made `.prob` text and its
-        fallback word where the formatter is on, the partner vector, the counts and the two bodies where the decoding is on, then the
-        probabilities -- unless both are on: then they stay on the device, and are fetched by the worker only for a map whose text
-        could not be formatted (a NaN-poisoned one)."""
-        seq, made, tables = [], [], []
-        text_kinds = 2 if ss_text_on else 0
-
-        def letters(toks: np.ndarray) -> None:
-            seq.append("".join(alphabet.all_toks[int(t)] for t in toks))
-
-        def finish(prob: Optional[np.ndarray]) -> None:
-            kw = {}
-            if made:
-                kw.update(prob_text=made[0], fallback=int(made[1][0]))
-            if tables:
-                kw.update(partner=tables[0], counts=tables[1], ct_body=tables[2], bpseq_body=tables[3])
-            ss.write_ss_files(prob, seq[0], rna_id, save_dir, **kw)
-
-        def finish_without_probs(last: np.ndarray) -> None:
-            tables.append(last)
-            finish(probs.cpu().numpy() if int(made[1][0]) else None)      # behind the worker's event: the head has run
-
-        jobs = [(letters, tok_row)] + [(made.append, t) for t in made_on_device[:text_kinds]]
-        struct = made_on_device[text_kinds:]
-        if not struct:
-            return jobs + [(finish, probs)]
-        jobs += [(tables.append, t) for t in struct[:3]]
-        if ss_text_on:
-            return jobs + [(finish_without_probs, struct[3])]
-        return jobs + [(tables.append, struct[3]), (finish, probs)]
-    # data.rsa_model_dir: the solvent-accessibility ensemble on each alignment's device-resident embedding (rnamsm.rsa)
-    rsa_model = rsa.load_ensemble(cfg.data.rsa_model_dir, device) if getattr(cfg.data, "rsa_model_dir", "") else None
-    if rsa_model is not None:
-        rsa_lut = torch.full((len(alphabet.all_toks),), 255, dtype=torch.uint8)
-        for code, ch in enumerate("ACGU"):
-            rsa_lut[alphabet.tok_to_idx[ch]] = code
-        rsa_lut = rsa_lut.to(device)
-        rsa_rng = random.Random(2022)         # the reference program's seed; drawn from on the writer thread, in delivery order
-
-    def rsa_text_jobs(rna_id: str, values, tok_row) -> list:
-        """Writer jobs of RSA_result/<id>_*/<id>.txt: the query's tokens first (turned into its letters), then the members' RSA."""
-        seq = []
-
-        def letters(toks: np.ndarray) -> None:
-            seq.append("".join(alphabet.all_toks[int(t)] for t in toks))
-
-        return [(letters, tok_row), (lambda v: rsa.write_rsa_files(v, seq[0], rna_id, save_dir, rsa_model.model_names, rsa_rng), values)]
-
-    def head_jobs(rna_id: str, heads) -> list:
-        """heads: the tensors deliver() appended for the heads that are on -- (probabilities, tokens) of SS, with (text, fallback
-        word) behind them where the formatter is on and (partner, counts, ct body, bpseq body) where the decoding is, then (RSA,
-        tokens)."""
-        heads = list(heads or ())
-        jobs = []
-        if ss_model is not None and heads:
-            n = 2 + 2 * ss_text_on + 4 * ss_pairs_on
-            jobs += ss_text_jobs(rna_id, *heads[:n])
-            heads = heads[n:]
-        if rsa_model is not None and heads:
-            jobs += rsa_text_jobs(rna_id, heads[0], heads[1])
-        return jobs
+    # the formatter on as well no [L, L] float tensor is copied to the host at all.  Under gather_to_rank0 both stay off (the host
+    # path): the gathered items are the probabilities and the tokens.
+    gathering = gather_to_rank0 and world > 1
+    ss_path, rsa_dir = getattr(cfg.data, "ss_model_path", ""), getattr(cfg.data, "rsa_model_dir", "")
+    base_lut = ss.token_base_codes(alphabet, device) if ss_path or rsa_dir else None
+    heads: list = []
+    if ss_path:
+        heads.append(ss.SSHead(ss.load_predictor(ss_path, device), alphabet, base_lut, device,
+                               text_on=bool(getattr(cfg.data, "ss_prob_text", True)) and not gathering,
+                               pairs_on=bool(getattr(cfg.data, "ss_pairs_device", True)) and not gathering))
+    if rsa_dir:         # (the reference program's seed; drawn from on the writer thread, in delivery order)
+        heads.append(rsa.RSAHead(rsa.load_ensemble(rsa_dir, device), alphabet, base_lut, random.Random(2022)))
     rng = np.random.RandomState(42)
     mine = sharding.shard_indices(len(ids), rank, world)
     written: List[str] = []
@@ -438,22 +378,24 @@ def extract_feat(cfg: Config, model: Optional[MSATransformer] = None, gather_to_
                                  rng=rng)
         return crop_tokens(tokens, cfg.data.max_seqlen, rng)
 
-    gathering = gather_to_rank0 and world > 1
     writer = _AsyncNpyWriter(device) if async_io and (not gathering or rank == 0) else None
     reader = ThreadPoolExecutor(1, thread_name_prefix="rnamsm-msa-reader") if async_io else None
 
-    def emit(rna_id: str, emb: torch.Tensor, atp: torch.Tensor, after: Optional[torch.cuda.Event] = None, ss_out=None) -> None:
-        """ss_out: the heads' device tensors -- (probabilities [L, L], query tokens [L]) when data.ss_model_path is set, with
-        (`.prob` text [25 L^2], fallback word [1]) behind them when data.ss_prob_text is on and (partner [L], counts [4], ct body,
-        bpseq body) when data.ss_pairs_device is, then (RSA [K, L], query tokens [L]) when data.rsa_model_dir is set."""
-        extra = head_jobs(rna_id, ss_out)
+    def emit(rna_id: str, emb: torch.Tensor, atp: torch.Tensor, after: Optional[torch.cuda.Event] = None, records=()) -> None:
+        """records: this alignment's record of every head that is on, in the order of `heads`; each becomes one writer job."""
+        extra = [h.writer_job(r, rna_id, save_dir) for h, r in zip(heads, records)]
         if writer is not None:
             writer.submit([(save_dir / f"{rna_id}_atp.npy", atp), (save_dir / f"{rna_id}_emb.npy", emb)] + extra,
                           lambda r=rna_id: written.append(r), after=after)
         else:
-            for fn, t in extra:
-                fn(t.cpu().numpy())
+            for fn, tensors in extra:
+                fn(*(t.cpu().numpy() for t in tensors))
             write(rna_id, emb.cpu().numpy(), atp.cpu().numpy())
+
+    def records_of(flat) -> list:
+        """A gathered item's tensors behind emb and atp -> the heads' records (the inverse of deliver()'s flattening)."""
+        flat = iter(flat)
+        return [h.unflatten([next(flat) for _ in range(h.n_tensors)]) for h in heads]
 
     # gather_to_rank0: outputs travel to rank 0 one ROUND (one MSA per rank) at a time, round k's RCCL transfers
     # overlapping round k+1's forward, and are handed to the writer as they arrive -- at most one round is resident
@@ -468,65 +410,37 @@ def extract_feat(cfg: Config, model: Optional[MSATransformer] = None, gather_to_
                                f"(every rank then writes its own files)")
         if label != "primary" and rank == 0:
             print(f"gather to rank 0: {label}")
-    gatherer = sharding.RoundGatherer(len(ids), on_item=lambda i, ts: emit(ids[i], ts[0], ts[1], ss_out=ts[2:] or None),
-                                      tensors_per_item=2 + 2 * (ss_model is not None) + 2 * (rsa_model is not None),
+    item_tensors = 2 + sum(h.n_tensors for h in heads)                # emb, atp, then every head's flattened record
+    gatherer = sharding.RoundGatherer(len(ids), on_item=lambda i, ts: emit(ids[i], ts[0], ts[1], records=records_of(ts[2:])),
+                                      tensors_per_item=item_tensors,
                                       dst=0, device=device, group=gather_group) if gathering else None
     try:
         with torch.no_grad():
             pending = reader.submit(read, mine[0]) if reader and len(mine) else None
             def deliver(idx: int, emb: torch.Tensor, atp: torch.Tensor, after: Optional[torch.cuda.Event] = None,
-                        toks: Optional[torch.Tensor] = None, ss_probs: Optional[torch.Tensor] = None,
-                        rsa_vals: Optional[torch.Tensor] = None, ss_text: Optional[tuple] = None,
-                        ss_struct: Optional[tuple] = None) -> None:
-                """ss_probs / rsa_vals: this alignment's base-pair probabilities / [K, L] RSA where its group's batched head (ss_group,
-                rsa_group) has already computed them; absent, the lone head runs here.  ss_text: (text, fallback word) of ss_probs
-                from the group's one formatter call; ss_struct: (partner, counts, ct body, bpseq body) from its one decoding call."""
-                ss_out = None
-                if ss_model is not None:          # the head reads atp where it lies (a packed group's slice included)
-                    tok_row = toks[0, 1:]
-                    ss_out = (ss_probs if ss_probs is not None else ss_model.predict(atp, ss_lut[tok_row]), tok_row)
-                    if ss_text_on:                # the formatter runs behind the head, before the event the copies wait for
-                        ss_out += tuple(ss_text) if ss_text is not None else ss.prob_text(ss_out[0])
-                    if ss_pairs_on:               # ... and so does the decoding: one lone call
-                        ss_out += tuple(ss_struct) if ss_struct is not None else ss.structure(ss_out[0], ss_letters[tok_row])
-                if rsa_model is not None:         # the ensemble reads emb where it lies
-                    tok_row = toks[0, 1:]
-                    ss_out = (ss_out or ()) + (rsa_vals if rsa_vals is not None else rsa_model.predict(emb, rsa_lut[tok_row]), tok_row)
-                if ss_out is not None and after is not None:         # the copies wait for the heads too
-                    after = torch.cuda.Event()
-                    after.record(torch.cuda.current_stream())
+                        toks: Optional[torch.Tensor] = None, records: Optional[list] = None) -> None:
+                """records: this alignment's record of every head, where its group's batched heads (deliver_group) have made them;
+                absent, the lone heads run here, on emb and atp where they lie (a packed group's slices included)."""
+                if records is None:
+                    records = [h.one(emb, atp, toks[0, 1:]) for h in heads]
+                    if heads and after is not None:             # the copies wait for the heads too
+                        after = torch.cuda.Event()
+                        after.record(torch.cuda.current_stream())
                 if gatherer is not None:
-                    gatherer.submit(idx, (emb, atp) + (ss_out or ()))
+                    gatherer.submit(idx, (emb, atp) + tuple(t for h, r in zip(heads, records) for t in h.flatten(r)))
                 else:
-                    emit(ids[idx], emb, atp, after, ss_out)
-
-            def ss_group(atps: List[torch.Tensor], toks_: List[torch.Tensor]) -> List[Optional[torch.Tensor]]:
-                """The SS head of a whole group in one launch set (SSPredictor.predict_many: every launch covers all the members'
-                tiles, each member's probabilities are the lone head's bits); a list of None when the head is off."""
-                if ss_model is None:
-                    return [None] * len(atps)
-                return ss_model.predict_many(atps, [ss_lut[t[0, 1:]] for t in toks_])
-
-            def rsa_group(embs: List[torch.Tensor], toks_: List[torch.Tensor]) -> List[Optional[torch.Tensor]]:
-                """The RSA ensemble of a whole group in one launch set (RSAEnsemble.predict_many: four launches cover all the members'
-                tiles, each member's [K, L] is the lone head's bits); a list of None when the head is off."""
-                if rsa_model is None:
-                    return [None] * len(embs)
-                return rsa_model.predict_many(embs, [rsa_lut[t[0, 1:]] for t in toks_])
+                    emit(ids[idx], emb, atp, after, records)
 
             def deliver_group(members_, outs, ev: Optional[torch.cuda.Event] = None) -> None:
+                """Every head once over the whole group (one launch set per stage; each member's record is the lone head's bits), then
+                the members one by one."""
                 embs, atps = [o["emb"].contiguous() for o in outs], [o["atp"].contiguous() for o in outs]
-                toks_ = [t for _, t in members_]
-                probs = ss_group(atps, toks_)
-                texts = ss.prob_text_many(probs) if ss_text_on else [None] * len(probs)      # one packed call per group
-                structs = (ss.structure_many(probs, [ss_letters[t[0, 1:]] for t in toks_]) if ss_pairs_on
-                           else [None] * len(probs))                                           # one packed call per group
-                vals = rsa_group(embs, toks_)
-                if (ss_model is not None or rsa_model is not None) and ev is not None:      # the copies wait for both batched heads too
+                per_head = [h.many(embs, atps, [t[0, 1:] for _, t in members_]) for h in heads]
+                if heads and ev is not None:                    # the copies wait for the batched heads too
                     ev = torch.cuda.Event()
                     ev.record(torch.cuda.current_stream())
-                for (i, t), emb, atp, p, v, tx, st in zip(members_, embs, atps, probs, vals, texts, structs):
-                    deliver(i, emb, atp, ev, t, ss_probs=p, rsa_vals=v, ss_text=tx, ss_struct=st)
+                for n, ((i, t), emb, atp) in enumerate(zip(members_, embs, atps)):
+                    deliver(i, emb, atp, ev, t, records=[recs[n] for recs in per_head])
 
             # data.batch_small_msas: small alignments go through ONE launch set per group (forward_ragged: padded into one
             # frame, every MSA scaled by its own depth); a lone forward of a few hundred tokens costs 5.5 ms on a mostly

@@ -556,6 +556,49 @@ def contact_head(row_attn: torch.Tensor, weight: torch.Tensor, bias: torch.Tenso
     return out
 
 
+def _want(fn: str, want: str) -> None:
+    if want not in ("probs", "logits"):
+        raise ValueError(f"{fn}: want must be 'probs' or 'logits', got {want!r}")
+
+
+def _members(fn: str, rule, cap: int, max_L: Optional[int], nouns, operands, checked: int = 1, lone: bool = False):
+    """The prologue of a packed call.  operands: {name: sequence}, the per-member operands in the order `rule` takes them (one
+    sequence or two); nouns: what the two sequences and the members are called in the messages.  The counts must match and stay
+    within `cap`; then every member goes through rule(fn, *operands, *names) -- names `atp[3]`, or plain `atp` for a lone call -- which
+    returns it as the library reads it, L last; its first `checked` tensors must lie on the device of member 0 and, with a max_L, L
+    within [1, max_L].  -> (rule's results per member, device); ([], None) for an empty call."""
+    names = list(operands)
+    seqs = [list(s) for s in operands.values()]
+    if len(seqs) == 2 and len(seqs[0]) != len(seqs[1]):
+        raise ValueError(f"{fn}: {len(seqs[0])} {nouns[0]} for {len(seqs[1])} {nouns[1]}")
+    B = len(seqs[0])
+    if not B:
+        return [], None
+    if B > cap:
+        raise ValueError(f"{fn}: {B} {nouns[2]} exceed the limit of {cap} per call")
+    device = seqs[0][0].device if isinstance(seqs[0][0], torch.Tensor) else None
+    members = []
+    for b in range(B):
+        m = rule(fn, *(s[b] for s in seqs), *(n if lone else f"{n}[{b}]" for n in names))
+        on = [t.device for t in m[:checked]]
+        if any(d != device for d in on):
+            who = " / ".join(f"{n}[{b}]" for n in names[:checked])
+            raise ValueError(f"{fn}: {who} {'lies' if checked == 1 else 'lie'} on {' / '.join(map(str, on))}, {names[0]}[0] on {device}")
+        if max_L is not None and not 1 <= m[-1] <= max_L:
+            raise ValueError(f"{fn}: {names[0]}[{b}]: L = {m[-1]} outside [1, {max_L}]")
+        members.append(m)
+    return members, device
+
+
+def _carved(sizes: Sequence[int], device, dtype, align: int = 1) -> List[torch.Tensor]:
+    """One allocation -> a view of sizes[b] elements per member, each starting on a multiple of `align` elements."""
+    starts = [0]
+    for n in sizes:
+        starts.append(starts[-1] + -(-n // align) * align)
+    buf = torch.empty(starts[-1], dtype=dtype, device=device)
+    return [buf[s:s + n] for s, n in zip(starts, sizes)]
+
+
 def _ss_operands(fn: str, atp: torch.Tensor, bc: torch.Tensor, name: str, bc_name: str):
     """The operand rules of one structure, for ss_head and for every member of ss_head_packed: -> (atp, base_codes, L) as the
     library reads them (maps whose rows or planes do not lie as [L, L] planes at least L*L apart are copied)."""
@@ -576,8 +619,7 @@ def ss_head(atp: torch.Tensor, base_codes: torch.Tensor, ptrs, num_blocks: int, 
     """RNA-MSM-SS head (rnamsm_ss_head): atp [120, L, L] fp32 (planes may lie further apart than L*L: a slice of a wider
     buffer is read in place), base_codes uint8 [L] (0..3 = A, C, G, U, other = no base), ptrs: the packed weight table
     (ctypes c_void_p array, rnamsm.ss.SSPredictor) -> [L, L] fp32 probabilities (want="probs") or logits (want="logits")."""
-    if want not in ("probs", "logits"):
-        raise ValueError(f"ss_head: want must be 'probs' or 'logits', got {want!r}")
+    _want("ss_head", want)
     atp, base_codes, L = _ss_operands("ss_head", atp, base_codes, "atp", "base_codes")
     lib = _lib.load()
     ws = torch.empty(max(lib.rnamsm_ss_head_workspace_bytes(L), 16), dtype=torch.uint8, device=atp.device)
@@ -596,35 +638,18 @@ def ss_head_packed(atps: Sequence[torch.Tensor], codes: Sequence[torch.Tensor], 
     codes[b] uint8 [L_b], the operand rules of ss_head per member (slices of one wider buffer are read in place) -> a list of
     [L_b, L_b] tensors, each bit-identical to ss_head on that member alone.  One workspace and one output allocation per call:
     the returned tensors are views of one buffer."""
-    if want not in ("probs", "logits"):
-        raise ValueError(f"ss_head_packed: want must be 'probs' or 'logits', got {want!r}")
-    atps, codes = list(atps), list(codes)
-    if len(atps) != len(codes):
-        raise ValueError(f"ss_head_packed: {len(atps)} maps for {len(codes)} base-code rows")
-    if not atps:
+    _want("ss_head_packed", want)
+    members, device = _members("ss_head_packed", _ss_operands, _lib.SS_MAX_BATCH, _lib.SS_MAX_L,
+                               ("maps", "base-code rows", "structures"), {"atp": atps, "base_codes": codes})
+    if not members:
         return []
-    B = len(atps)
-    if B > _lib.SS_MAX_BATCH:
-        raise ValueError(f"ss_head_packed: {B} structures exceed the limit of {_lib.SS_MAX_BATCH} per call")
-    device = atps[0].device if isinstance(atps[0], torch.Tensor) else None
-    Ls = []
-    for b in range(B):
-        atps[b], codes[b], L = _ss_operands("ss_head_packed", atps[b], codes[b], f"atp[{b}]", f"base_codes[{b}]")
-        if atps[b].device != device:
-            raise ValueError(f"ss_head_packed: atp[{b}] lies on {atps[b].device}, atp[0] on {device}")
-        if not 1 <= L <= _lib.SS_MAX_L:
-            raise ValueError(f"ss_head_packed: atp[{b}]: L = {L} outside [1, {_lib.SS_MAX_L}]")
-        Ls.append(L)
+    B, Ls = len(members), [L for _, _, L in members]
     lib = _lib.load()
     ws = torch.empty(lib.rnamsm_ss_head_packed_workspace_bytes(B, (_lib.c_int * B)(*Ls)), dtype=torch.uint8, device=device)
-    out = torch.empty(sum(L * L for L in Ls), device=device, dtype=torch.float32)
+    outs = [o.view(L, L) for o, L in zip(_carved([L * L for L in Ls], device, torch.float32), Ls)]
     items = (_lib.SsItem * B)()
-    outs, off = [], 0
-    for b, L in enumerate(Ls):
-        o = out[off:off + L * L].view(L, L)
-        off += L * L
-        outs.append(o)
-        items[b] = _lib.SsItem(atps[b].data_ptr(), atps[b].stride(0), codes[b].data_ptr(), L, o.data_ptr() if want == "logits" else None,
+    for b, ((atp, bc, L), o) in enumerate(zip(members, outs)):
+        items[b] = _lib.SsItem(atp.data_ptr(), atp.stride(0), bc.data_ptr(), L, o.data_ptr() if want == "logits" else None,
                                o.data_ptr() if want == "probs" else None)
     _lib.check(lib.rnamsm_ss_head_packed(items, B, num_blocks, ptrs, ws.data_ptr(), ws.numel(), _stream()))
     return outs
@@ -659,32 +684,17 @@ def ss_prob_text_packed(probs: Sequence[torch.Tensor]) -> List[Tuple[torch.Tenso
     """ss_prob_text of every probs[b] ([L_b, L_b]) in one call (rnamsm_ss_prob_text_packed) -> a list of (text, fallback word),
     each exactly what ss_prob_text gives for that matrix alone.  One text and one word allocation per call: the returned tensors
     are views (every text starts on a 16-byte boundary of the buffer)."""
-    probs = list(probs)
-    if not probs:
+    members, device = _members("ss_prob_text_packed", _ss_text_operand, _lib.SS_MAX_BATCH, None, (None, None, "matrices"),
+                               {"probs": probs})
+    if not members:
         return []
-    B = len(probs)
-    if B > _lib.SS_MAX_BATCH:
-        raise ValueError(f"ss_prob_text_packed: {B} matrices exceed the limit of {_lib.SS_MAX_BATCH} per call")
-    device = probs[0].device if isinstance(probs[0], torch.Tensor) else None
-    Ls = []
-    for b in range(B):
-        probs[b], L = _ss_text_operand("ss_prob_text_packed", probs[b], f"probs[{b}]")
-        if probs[b].device != device:
-            raise ValueError(f"ss_prob_text_packed: probs[{b}] lies on {probs[b].device}, probs[0] on {device}")
-        Ls.append(L)
+    B = len(members)
     lib = _lib.load()
-    offs, total = [], 0
-    for L in Ls:
-        offs.append(total)
-        total += (_lib.SS_TEXT_RECORD * L * L + 15) & ~15
-    buf = torch.empty(total, dtype=torch.uint8, device=device)
-    words = torch.empty(B, dtype=torch.int32, device=device)
+    outs = list(zip(_carved([_lib.SS_TEXT_RECORD * L * L for _, L in members], device, torch.uint8, align=16),
+                    _carved([1] * B, device, torch.int32)))
     items = (_lib.SsTextItem * B)()
-    outs = []
-    for b, (L, off) in enumerate(zip(Ls, offs)):
-        text, word = buf[off:off + _lib.SS_TEXT_RECORD * L * L], words[b:b + 1]
-        items[b] = _lib.SsTextItem(probs[b].data_ptr(), L, text.data_ptr(), word.data_ptr())
-        outs.append((text, word))
+    for b, ((p, L), (text, word)) in enumerate(zip(members, outs)):
+        items[b] = _lib.SsTextItem(p.data_ptr(), L, text.data_ptr(), word.data_ptr())
     _lib.check(lib.rnamsm_ss_prob_text_packed(items, B, _stream()))
     return outs
 
@@ -716,44 +726,22 @@ def ss_pairs_packed(probs: Sequence[torch.Tensor], letters: Sequence[torch.Tenso
 
 
 def _ss_pairs_run(_fn: str, probs, letters):
-    probs, letters = list(probs), list(letters)
-    if len(probs) != len(letters):
-        raise ValueError(f"{_fn}: {len(probs)} matrices for {len(letters)} letter rows")
-    if not probs:
-        return []
-    B = len(probs)
-    if B > _lib.SS_MAX_BATCH:
-        raise ValueError(f"{_fn}: {B} structures exceed the limit of {_lib.SS_MAX_BATCH} per call")
-    device = probs[0].device if isinstance(probs[0], torch.Tensor) else None
     lone = _fn == "ss_pairs"
-    Ls = []
-    for b in range(B):
-        probs[b], letters[b], L = _ss_pairs_operands(_fn, probs[b], letters[b], "probs" if lone else f"probs[{b}]",
-                                                     "letters" if lone else f"letters[{b}]")
-        if probs[b].device != device or letters[b].device != device:
-            raise ValueError(f"{_fn}: probs[{b}] / letters[{b}] lie on {probs[b].device} / {letters[b].device}, probs[0] on {device}")
-        Ls.append(L)
+    members, device = _members(_fn, _ss_pairs_operands, _lib.SS_MAX_BATCH, None, ("matrices", "letter rows", "structures"),
+                               {"probs": probs, "letters": letters}, checked=2, lone=lone)
+    if not members:
+        return []
+    B, Ls = len(members), [L for _, _, L in members]
     lib = _lib.load()
-    total = sum(Ls)
     ws = torch.empty(lib.rnamsm_ss_pairs_workspace_bytes(B, (_lib.c_int * B)(*Ls)), dtype=torch.uint8, device=device)
-    partner = torch.empty(total, dtype=torch.int32, device=device)
-    counts = torch.empty(B, 4, dtype=torch.int32, device=device)
-    ct = torch.empty(_lib.SS_CT_LINE_MAX * total, dtype=torch.uint8, device=device)
-    bpseq = torch.empty(_lib.SS_BPSEQ_LINE_MAX * total, dtype=torch.uint8, device=device)
-    outs, off = [], 0
-    for b, L in enumerate(Ls):
-        outs.append((partner[off:off + L], counts[b], ct[_lib.SS_CT_LINE_MAX * off:_lib.SS_CT_LINE_MAX * (off + L)],
-                     bpseq[_lib.SS_BPSEQ_LINE_MAX * off:_lib.SS_BPSEQ_LINE_MAX * (off + L)]))
-        off += L
+    outs = list(zip(_carved(Ls, device, torch.int32), _carved([4] * B, device, torch.int32),
+                    _carved([_lib.SS_CT_LINE_MAX * L for L in Ls], device, torch.uint8),
+                    _carved([_lib.SS_BPSEQ_LINE_MAX * L for L in Ls], device, torch.uint8)))
+    args = [(p.data_ptr(), l.data_ptr(), L, *(t.data_ptr() for t in o)) for (p, l, L), o in zip(members, outs)]
     if lone:
-        o = outs[0]
-        _lib.check(lib.rnamsm_ss_pairs(probs[0].data_ptr(), letters[0].data_ptr(), Ls[0], o[0].data_ptr(), o[1].data_ptr(),
-                                       o[2].data_ptr(), o[3].data_ptr(), ws.data_ptr(), ws.numel(), _stream()))
+        _lib.check(lib.rnamsm_ss_pairs(*args[0], ws.data_ptr(), ws.numel(), _stream()))
         return outs
-    items = (_lib.SsPairsItem * B)()
-    for b, o in enumerate(outs):
-        items[b] = _lib.SsPairsItem(probs[b].data_ptr(), letters[b].data_ptr(), Ls[b], o[0].data_ptr(), o[1].data_ptr(),
-                                    o[2].data_ptr(), o[3].data_ptr())
+    items = (_lib.SsPairsItem * B)(*(_lib.SsPairsItem(*a) for a in args))
     _lib.check(lib.rnamsm_ss_pairs_packed(items, B, ws.data_ptr(), ws.numel(), _stream()))
     return outs
 
@@ -779,8 +767,7 @@ def rsa_head(emb: torch.Tensor, base_codes: torch.Tensor, ptrs, n_models: int, u
     """RNA-MSM RSA ensemble (rnamsm_rsa_head): emb [L, 768] fp32 (rows may lie further apart than 768 floats: a slice of the
     final representation is read in place), base_codes uint8 [L], ptrs: the packed weight table of the n_models members
     (rnamsm.rsa.RSAEnsemble) -> [n_models, L] fp32 RSA (want="probs") or the pre-sigmoid values (want="logits")."""
-    if want not in ("probs", "logits"):
-        raise ValueError(f"rsa_head: want must be 'probs' or 'logits', got {want!r}")
+    _want("rsa_head", want)
     emb, stride, base_codes, L = _rsa_operands("rsa_head", emb, base_codes, "emb", "base_codes")
     lib = _lib.load()
     ws = torch.empty(max(lib.rnamsm_rsa_head_workspace_bytes(L, n_models), 16), dtype=torch.uint8, device=emb.device)
@@ -799,36 +786,18 @@ def rsa_head_packed(embs: Sequence[torch.Tensor], codes: Sequence[torch.Tensor],
     codes[b] uint8 [L_b], the operand rules of rsa_head per member (row slices of one wider buffer are read in place) -> a list of
     [n_models, L_b] tensors, each bit-identical to rsa_head on that member alone.  One workspace and one output allocation per
     call: the returned tensors are views of one buffer."""
-    if want not in ("probs", "logits"):
-        raise ValueError(f"rsa_head_packed: want must be 'probs' or 'logits', got {want!r}")
-    embs, codes = list(embs), list(codes)
-    if len(embs) != len(codes):
-        raise ValueError(f"rsa_head_packed: {len(embs)} embeddings for {len(codes)} base-code rows")
-    if not embs:
+    _want("rsa_head_packed", want)
+    members, device = _members("rsa_head_packed", _rsa_operands, _lib.RSA_MAX_BATCH, _lib.RSA_MAX_L,
+                               ("embeddings", "base-code rows", "alignments"), {"emb": embs, "base_codes": codes})
+    if not members:
         return []
-    B = len(embs)
-    if B > _lib.RSA_MAX_BATCH:
-        raise ValueError(f"rsa_head_packed: {B} alignments exceed the limit of {_lib.RSA_MAX_BATCH} per call")
-    device = embs[0].device if isinstance(embs[0], torch.Tensor) else None
-    Ls, strides = [], []
-    for b in range(B):
-        embs[b], stride, codes[b], L = _rsa_operands("rsa_head_packed", embs[b], codes[b], f"emb[{b}]", f"base_codes[{b}]")
-        if embs[b].device != device:
-            raise ValueError(f"rsa_head_packed: emb[{b}] lies on {embs[b].device}, emb[0] on {device}")
-        if not 1 <= L <= _lib.RSA_MAX_L:
-            raise ValueError(f"rsa_head_packed: emb[{b}]: L = {L} outside [1, {_lib.RSA_MAX_L}]")
-        Ls.append(L)
-        strides.append(stride)
+    B, Ls = len(members), [m[-1] for m in members]
     lib = _lib.load()
     ws = torch.empty(lib.rnamsm_rsa_head_packed_workspace_bytes(B, (_lib.c_int * B)(*Ls), n_models), dtype=torch.uint8, device=device)
-    out = torch.empty(n_models * sum(Ls), device=device, dtype=torch.float32)
+    outs = [o.view(n_models, L) for o, L in zip(_carved([n_models * L for L in Ls], device, torch.float32), Ls)]
     items = (_lib.RsaItem * B)()
-    outs, off = [], 0
-    for b, L in enumerate(Ls):
-        o = out[off:off + n_models * L].view(n_models, L)
-        off += n_models * L
-        outs.append(o)
-        items[b] = _lib.RsaItem(embs[b].data_ptr(), strides[b], codes[b].data_ptr(), L,
+    for b, ((emb, stride, bc, L), o) in enumerate(zip(members, outs)):
+        items[b] = _lib.RsaItem(emb.data_ptr(), stride, bc.data_ptr(), L,
                                 o.data_ptr() if want == "probs" else None, o.data_ptr() if want == "logits" else None)
     _lib.check(lib.rnamsm_rsa_head_packed(items, B, n_models, 1 if use_onehot else 0, ptrs, ws.data_ptr(), ws.numel(), _stream()))
     return outs

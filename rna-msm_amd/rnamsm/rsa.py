@@ -6,7 +6,8 @@ normalisation statistics, and its arithmetic is one HIP entry point (rnamsm_rsa_
 that reads the [L, 768] embedding where it lies on the device; `predict_many` runs a list of alignments through the same four
 launches (rnamsm_rsa_head_packed), every result the lone call's bits.  `load_ensemble` reads an upstream model directory -- its `.pt`
 files are pickled whole modules and are opened with no upstream code importable -- and `write_rsa_files` is the reference's
-host arithmetic and text format (predict.py: doSavePredict_single, per model and for the ensemble), byte for byte.
+host arithmetic and text format (predict.py: doSavePredict_single, per model and for the ensemble), byte for byte.  `RSAHead` is the
+ensemble as the CLI runs it: it makes one `RSAResult` per alignment and turns it into the job that writes the texts.
 """
 from __future__ import annotations
 
@@ -17,7 +18,7 @@ import pickle
 import re
 import types
 from pathlib import Path
-from typing import Dict, List, Optional, Sequence, Tuple, Union
+from typing import Dict, List, NamedTuple, Optional, Sequence, Tuple, Union
 
 import numpy as np
 import torch
@@ -393,3 +394,44 @@ def write_rsa_files(rsa_k: np.ndarray, seq: str, name: str, output_dir: Union[st
         asas.append(asa)
     mean = np.array(asas).mean(0)
     return _save_single(name, seq, None, os.path.join(out, f"{name}_ensemble"), f"{name} predict by ensemble model\n", rng, asa=mean)
+
+
+# ---------------------------------------------------------------------- the head in the CLI (rnamsm.inference.extract_feat)
+class RSAResult(NamedTuple):
+    """One alignment's results of the RSA ensemble, on the device (or, on the writer's side, their host copies)."""
+    values: torch.Tensor                          # [K, L] the members' RSA
+    tokens: torch.Tensor                          # [L] the query's tokens
+
+
+class RSAHead:
+    """data.rsa_model_dir in the CLI: the ensemble, the base-code look-up table indexed by token, the members' names and the
+    generator the texts draw from (the reference program's seed, 2022; drawn from by the writer, in delivery order)."""
+    n_tensors = 2
+
+    def __init__(self, model: Optional[RSAEnsemble], alphabet, base_lut: Optional[torch.Tensor], rng, model_names: Optional[Sequence[str]] = None):
+        self.model, self.base_lut, self.rng = model, base_lut, rng
+        self.model_names = list(model_names if model_names is not None else model.model_names)
+        self.all_toks = list(alphabet.all_toks)
+
+    def one(self, emb: torch.Tensor, atp: torch.Tensor, tokens: torch.Tensor) -> RSAResult:
+        """A lone alignment through the lone head; emb is read where it lies (atp is not read: the heads share one signature)."""
+        return RSAResult(self.model.predict(emb, self.base_lut[tokens]), tokens)
+
+    def many(self, embs: Sequence[torch.Tensor], atps: Sequence[torch.Tensor], tokens: Sequence[torch.Tensor]) -> List[RSAResult]:
+        """A group in one launch set (predict_many): every member's [K, L] is the lone head's bits."""
+        values = self.model.predict_many(embs, [self.base_lut[t] for t in tokens])
+        return [RSAResult(v, t) for v, t in zip(values, tokens)]
+
+    def flatten(self, rec: RSAResult) -> list:
+        return list(rec)
+
+    def unflatten(self, tensors: Sequence) -> RSAResult:
+        return RSAResult(*tensors)
+
+    def writer_job(self, rec: RSAResult, name: str, output_dir):
+        """-> (write, tensors): write(*host copies of tensors) writes <output_dir>/RSA_result/<name>_*/<name>.txt through
+        write_rsa_files."""
+        def write(tokens, values) -> None:
+            write_rsa_files(values, "".join(self.all_toks[int(t)] for t in tokens), name, output_dir, self.model_names, self.rng)
+
+        return write, (rec.tokens, rec.values)

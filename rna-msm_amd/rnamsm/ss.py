@@ -7,13 +7,14 @@ post-processing (code/post_processing/processing_output.py: prob_to_secondary_st
 same `.ct`, `.bpseq` and `.prob` files, byte for byte.  `prob_text` / `prob_text_many` format the `.prob` text on the device
 (rnamsm_ss_prob_text), so that the writer's share of it is one binary write; `structure` / `structure_many` decode the base pairs
 and write the bodies of `.ct` / `.bpseq` there too (rnamsm_ss_pairs), so that the probabilities need not leave the device at all.
+`SSHead` is the head as the CLI runs it: it makes one `SSResult` per alignment and turns it into the job that writes the three files.
 """
 from __future__ import annotations
 
 import ctypes
 import os
 from pathlib import Path
-from typing import List, Optional, Sequence, Tuple, Union
+from typing import Callable, List, NamedTuple, Optional, Sequence, Tuple, Union
 
 import numpy as np
 import torch
@@ -379,3 +380,96 @@ def write_ss_files(prob: Optional[np.ndarray], seq: str, name: str, output_dir: 
     else:
         np.savetxt(os.path.join(out, name + ".prob"), prob, delimiter="\t")
     return pairs
+
+
+# ---------------------------------------------------------------------- the head in the CLI (rnamsm.inference.extract_feat)
+def token_base_codes(alphabet, device) -> torch.Tensor:
+    """uint8 [number of tokens] on `device`: a token's base code (0..3 for A, C, G, U, else 255), the look-up table both heads index
+    with the query's tokens."""
+    lut = torch.full((len(alphabet.all_toks),), 255, dtype=torch.uint8)
+    for code, ch in enumerate("ACGU"):
+        lut[alphabet.tok_to_idx[ch]] = code
+    return lut.to(device)
+
+
+class SSResult(NamedTuple):
+    """One alignment's results of the SS head, on the device (or, on the writer's side, their host copies)."""
+    probs: Optional[torch.Tensor]                 # [L, L] base-pair probabilities
+    tokens: torch.Tensor                          # [L] the query's tokens
+    text: Optional[tuple] = None                  # prob_text(probs): (text, fallback word); None where the formatter is off
+    structure: Optional[tuple] = None             # structure(probs, letters): (partner, counts, ct body, bpseq body); None where off
+
+
+class SSHead:
+    """data.ss_model_path in the CLI: the predictor, the two look-up tables indexed by token (base codes; the letters the tables
+    print) and the two switches -- text_on (data.ss_prob_text: the `.prob` text is formatted on the device) and pairs_on
+    (data.ss_pairs_device: the pairs are decoded and the bodies of `.ct` / `.bpseq` written there)."""
+
+    def __init__(self, model: Optional[SSPredictor], alphabet, base_lut: Optional[torch.Tensor], device, text_on: bool = True,
+                 pairs_on: bool = True):
+        self.model, self.base_lut, self.text_on, self.pairs_on = model, base_lut, bool(text_on), bool(pairs_on)
+        self.all_toks = list(alphabet.all_toks)
+        # a token that is no single ASCII character is 0: that structure's tables come from the host
+        self.letters_lut = torch.tensor([ord(t) if len(t) == 1 and ord(t) < 128 else 0 for t in self.all_toks],
+                                        dtype=torch.uint8).to(device) if self.pairs_on else None
+        self.n_tensors = 2 + 2 * self.text_on + 4 * self.pairs_on
+
+    # ------------------------------------------------------------------ records
+    def one(self, emb: torch.Tensor, atp: torch.Tensor, tokens: torch.Tensor) -> SSResult:
+        """A lone alignment through the lone ops; atp is read where it lies (emb is not read: the heads share one signature).  The
+        formatter and the decoding run behind the head."""
+        probs = self.model.predict(atp, self.base_lut[tokens])
+        return SSResult(probs, tokens, tuple(prob_text(probs)) if self.text_on else None,
+                        tuple(structure(probs, self.letters_lut[tokens])) if self.pairs_on else None)
+
+    def many(self, embs: Sequence[torch.Tensor], atps: Sequence[torch.Tensor], tokens: Sequence[torch.Tensor]) -> List[SSResult]:
+        """A group in one launch set per stage (predict_many, prob_text_many, structure_many): every member's record holds the bits
+        and bytes of one()."""
+        probs = self.model.predict_many(atps, [self.base_lut[t] for t in tokens])
+        texts = prob_text_many(probs) if self.text_on else [None] * len(probs)
+        structs = structure_many(probs, [self.letters_lut[t] for t in tokens]) if self.pairs_on else [None] * len(probs)
+        return [SSResult(p, t, None if tx is None else tuple(tx), None if st is None else tuple(st))
+                for p, t, tx, st in zip(probs, tokens, texts, structs)]
+
+    # ------------------------------------------------------------------ the gather's flat lists
+    def flatten(self, rec: SSResult) -> list:
+        return [rec.probs, rec.tokens, *(rec.text or ()), *(rec.structure or ())]
+
+    def unflatten(self, tensors: Sequence) -> SSResult:
+        """The record of flatten()'s list (n_tensors entries), by this head's switches."""
+        if len(tensors) != self.n_tensors:
+            raise ValueError(f"SSHead: {len(tensors)} tensors for a record of {self.n_tensors}")
+        it = iter(tensors)
+        probs, tokens = next(it), next(it)
+        text = (next(it), next(it)) if self.text_on else None
+        return SSResult(probs, tokens, text, (next(it), next(it), next(it), next(it)) if self.pairs_on else None)
+
+    # ------------------------------------------------------------------ files
+    def letters(self, tokens) -> str:
+        return "".join(self.all_toks[int(t)] for t in tokens)
+
+    def writer_job(self, rec: SSResult, name: str, output_dir, fetch_probs: Optional[Callable[[], np.ndarray]] = None):
+        """-> (write, tensors): write(*host copies of tensors) writes <output_dir>/SS_result/<name>.{ct,bpseq,prob} through
+        write_ss_files.  The tensors are the query's tokens, the text and its fallback word, the partner vector, the counts and the two
+        bodies, as far as the record has them, then the probabilities -- unless it has both a text and a structure: then they stay where
+        they are, and write() fetches them (fetch_probs; default: from rec.probs) only for a map whose text could not be formatted (a
+        NaN-poisoned one)."""
+        probs, has_text, has_structure = rec.probs, rec.text is not None, rec.structure is not None
+        lazy = has_text and has_structure
+        if fetch_probs is None:         # holds the probabilities alone: the job's other tensors are released once their copies have run
+            fetch_probs = lambda: probs.cpu().numpy()      # noqa: E731  (behind the writer's event: the head has run)
+
+        def write(tokens, *made) -> None:
+            made, kw = list(made), {}
+            if has_text:
+                kw.update(prob_text=made.pop(0), fallback=int(made.pop(0)[0]))
+            if has_structure:
+                kw.update(partner=made.pop(0), counts=made.pop(0), ct_body=made.pop(0), bpseq_body=made.pop(0))
+            if lazy:
+                prob = fetch_probs() if kw["fallback"] else None
+            else:
+                prob = made.pop(0)
+            assert not made
+            write_ss_files(prob, self.letters(tokens), name, output_dir, **kw)
+
+        return write, (rec.tokens, *(rec.text or ()), *(rec.structure or ()), *(() if lazy else (probs,)))

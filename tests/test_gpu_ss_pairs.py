@@ -337,7 +337,8 @@ def _count_calls(monkeypatch):
     real_submit = inference._AsyncNpyWriter.submit
 
     def submit(self, job_list, done, after=None):
-        jobs.extend((tuple(t.shape), t.dtype) for _, t in job_list)
+        for _, t in job_list:                   # every tensor of a job: a head's job carries a tuple of them
+            jobs.extend((tuple(x.shape), x.dtype) for x in (t if isinstance(t, tuple) else (t,)))
         return real_submit(self, job_list, done, after=after)
 
     monkeypatch.setattr(inference._AsyncNpyWriter, "submit", submit)
