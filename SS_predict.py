@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Drop-in for the reference's _downstream_tasks/SS/predict.py (RNA-MSM-SS) on MI355X.
 
-    python SS_predict.py --rootdir DIR --featdir results --rnaid 2DRB_1 --device cuda
+    python SS_predict.py --rootdir DIR --featdir results --rnaid 2DRB_1 --device cuda [--gemm-dtype bf16]
 
 Reads `<featdir>/<rnaid>.fasta` (each record's description is its name) and `<featdir>/<rnaid>_atp.npy` (the [120, L, L]
 maps RNA_MSM_Inference.py writes), runs the 16-block head of `<rootdir>/model/rna-msm_attention.pt` on the HIP device
@@ -23,6 +23,8 @@ def get_args(argv=None):
     p.add_argument("--rnaid", default="2DRB_1", type=str)
     p.add_argument("--plots", default="False", type=str, help="not supported here (VARNA plots)")
     p.add_argument("--device", default="cuda", type=str, help="cuda or cuda:N (the HIP device; there is no CPU path)")
+    p.add_argument("--gemm-dtype", default="f32", type=str,
+                   help="arithmetic of the head's convolutions: f32 (exact, default) or bf16 (bf16 matrix cores, fp32 accumulation)")
     return p.parse_args(argv)
 
 
@@ -33,6 +35,9 @@ def main(argv=None):
                  "the .ct file it would draw is written as usual")
     if not args.device.startswith("cuda"):
         sys.exit(f"SS_predict.py: --device {args.device}: this build runs on the HIP device only (--device cuda)")
+    from rnamsm.config import SS_GEMM_DTYPES
+    if args.gemm_dtype not in SS_GEMM_DTYPES:
+        sys.exit(f"SS_predict.py: --gemm-dtype {args.gemm_dtype}: not one of {', '.join(SS_GEMM_DTYPES)}")
     import numpy as np
     import torch
     from rnamsm import ss
@@ -45,7 +50,8 @@ def main(argv=None):
         if not os.path.isfile(path):
             sys.exit(f"SS_predict.py: {path} not found")
     device = torch.device(args.device)
-    model = ss.load_predictor(model_path, device)
+    model = ss.load_predictor(model_path, device, gemm_dtype=args.gemm_dtype)
+    print(f"SS head arithmetic: {args.gemm_dtype}")
     atp = np.load(atp_path)
     if atp.ndim != 3 or atp.shape[0] != ss.NUM_MAPS or atp.shape[1] != atp.shape[2]:
         sys.exit(f"SS_predict.py: {atp_path} holds an array of shape {atp.shape}, not [{ss.NUM_MAPS}, L, L]")

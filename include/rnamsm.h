@@ -402,6 +402,29 @@ size_t rnamsm_ss_head_packed_workspace_bytes(int B, const int* Ls);
 int rnamsm_ss_head_packed(const rnamsm_ss_item* items, int B, int num_blocks, const float* const* weights,
                           void* workspace, size_t workspace_bytes, void* stream);
 
+/* f4 in bf16 -- the SS head with its convolutions on the bf16 matrix cores (v_mfma_f32_16x16x32_bf16), opt-in: rnamsm_ss_head and
+ * rnamsm_ss_head_packed keep their arithmetic and their bits.  The arithmetic contract:
+ *   bf16, rounded to nearest even (NaN stays NaN, +-inf stays +-inf): the conv operands -- the stem's inputs (the 120 maps and the 8
+ *     one-hot planes), each block's relu(LN(x)) activations (both convs), every conv weight;
+ *   fp32: the accumulation of every conv, the residual image x (and the block's middle image), the LayerNorm statistics and affine,
+ *     the stem bias, the output pass (final LN + ReLU + fc1 + sigmoid).
+ *   Zero padding is of relu(LN(x)); every ReLU carries a NaN on; no atomics and one summation order per pixel, so the same inputs
+ *   give the same bits on every run, and a member of a packed call has the bits of the lone bf16 call on it, whatever its company
+ *   and place.  A non-finite input comes out as NaN exactly where the reference network gives NaN, as for rnamsm_ss_head.
+ * Arguments, workspace sizes (the same two fp32 images) and refusals are those of rnamsm_ss_head / rnamsm_ss_head_packed, made
+ * before anything is enqueued.  weights: the table of rnamsm_ss_head in which the conv entries ([0] and, per block, 4 + 6k and
+ * 4 + 6k + 3) point to bf16 planes of the same tap-major shape [kh][kw][48 out][in]; every other entry is fp32 as before.
+ * rnamsm_ss_pack_conv16 makes such planes on the device: out[i] = bf16(w[i]), i < n, from the fp32 tap-major weights (w 4-byte,
+ * out 16-byte aligned; n in [1, 2^31]). */
+int rnamsm_ss_pack_conv16(const float* w, uint16_t* out, int64_t n, void* stream);
+size_t rnamsm_ss_head16_workspace_bytes(int L);
+int rnamsm_ss_head16(const float* atp, int64_t atp_plane_stride, const uint8_t* base_codes, int L, int num_blocks,
+                     const void* const* weights, float* logits, float* probs, void* workspace, size_t workspace_bytes,
+                     void* stream);
+size_t rnamsm_ss_head16_packed_workspace_bytes(int B, const int* Ls);
+int rnamsm_ss_head16_packed(const rnamsm_ss_item* items, int B, int num_blocks, const void* const* weights,
+                            void* workspace, size_t workspace_bytes, void* stream);
+
 /* f4, the text of the probabilities -- the bytes np.savetxt(path, probs, delimiter="\t") writes for the [L, L] probabilities of
  * rnamsm_ss_head (the reference's `<name>.prob`), produced on the device: L*L records of 25 bytes, "%.18e" of the element (24
  * characters for every float32 in [0, 1]: d.dddddddddddddddddde-XX, the digits computed exactly in integers) and then '\t', or

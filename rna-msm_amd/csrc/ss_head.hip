@@ -16,19 +16,16 @@
 // Activations live in the caller's workspace as two NHWC [L*L][48] fp32 images: the residual stream x and the block's
 // middle t.  The 5x5 conv adds x in its epilogue and writes x in place (each output element is read and then written
 // by the one lane that owns it).
-#include "common.h"
+#include "ss_head_common.h"
 
 namespace rnamsm {
 namespace {
 
-constexpr int SS_CH = 48;                      // trunk channels
-constexpr int SS_TILE = 16;                    // output tile: 16 x 16 pixels
 constexpr int SS_THREADS = 512;                // 8 waves, 2 output rows each
 constexpr int SS_LDC = SS_CH + 4;              // LDS pixel stride (floats) of the trunk's staged window
 constexpr int SS_STEM_CK = 32;                 // stem: input channels per staged chunk (4 chunks of the 128)
 constexpr int SS_STEM_LDC = SS_STEM_CK + 4;
 constexpr int SS_STEM_SW = SS_TILE + 2;
-constexpr float SS_LN_EPS = 1e-5f;             // nn.LayerNorm default
 
 constexpr size_t ss_trunk_lds_bytes(int ks) {
     return (size_t)(SS_TILE + ks - 1) * (SS_TILE + ks - 1) * SS_LDC * sizeof(float);
@@ -94,29 +91,6 @@ __device__ __forceinline__ void zero_acc16(f32x4 (&acc)[2][3]) {
         for (int nt = 0; nt < 3; ++nt) acc[mt][nt] = f32x4{0.f, 0.f, 0.f, 0.f};
 }
 
-// relu(LayerNorm(v)) of one pixel's 48 channels, in place (biased variance, two passes)
-__device__ __forceinline__ void ln_relu48(f32x4 (&v)[12], const float* __restrict__ gamma, const float* __restrict__ beta) {
-    float s = 0.f;
-#pragma unroll
-    for (int i = 0; i < 12; ++i) s += (v[i][0] + v[i][1]) + (v[i][2] + v[i][3]);
-    const float mean = s * (1.f / SS_CH);
-    float s2 = 0.f;
-#pragma unroll
-    for (int i = 0; i < 12; ++i)
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const float d = v[i][k] - mean;
-            s2 = fmaf(d, d, s2);
-        }
-    const float rstd = 1.f / sqrtf(s2 * (1.f / SS_CH) + SS_LN_EPS);
-#pragma unroll
-    for (int i = 0; i < 12; ++i) {
-        const f32x4 gm = *reinterpret_cast<const f32x4*>(gamma + 4 * i), bt = *reinterpret_cast<const f32x4*>(beta + 4 * i);
-#pragma unroll
-        for (int k = 0; k < 4; ++k) v[i][k] = relu_nan(fmaf((v[i][k] - mean) * rstd, gm[k], bt[k]));
-    }
-}
-
 // Epilogue: lane (r, g) holds D[pixel col 4g + t][channel 16 nt + r] of output row 2w + mt.
 // bias: per-channel bias (stem) or null; RESIDUAL: out += (in place: out is the residual stream).
 template <bool RESIDUAL>
@@ -141,34 +115,6 @@ __device__ __forceinline__ void store_tile(const f32x4 (&acc)[2][3], const float
             }
         }
     }
-}
-
-// ---- the member of a block ------------------------------------------------------------------------------------------------------
-// One kernel per stage serves the lone call (rnamsm_ss_head) and the batched one (rnamsm_ss_head_packed).  The images of a batch lie
-// back to back in the two workspace images (member b's first pixel is pixel pix0 of the buffer), and a launch has the SUM of the
-// members' tiles as a flat grid.  Batched, mem is the device table of the B members and a block finds its own by a search over the
-// tile prefix sums (common.h: member_of); lone, mem is null and the one member is the kernel argument itself (tile0 = 0, pix0 = 0:
-// the caller's workspace with no table in front).  Either way the stage's body runs on the member's own (image, L, tile): one
-// arithmetic, so a structure's bits depend on nothing else.
-// The choice is a template argument, not a test of mem: one definition, two code objects.  With the test inside the kernel the
-// compiler reads the descriptor through ONE flat load of a selected address (table or kernel argument) and L, the offsets and the
-// pointers land in vector registers: +5 to +14 VGPRs over the lone kernels in every stage.
-struct SsMember {            // 64 bytes
-    const float* atp;
-    int64_t plane_stride;
-    const uint8_t* codes;
-    float* logits;
-    float* probs;
-    int64_t pix0;            // pixels of the members before it
-    int32_t L, tiles;        // tiles = ceil(L / 16): its launches' share is tiles x tiles blocks, row by row
-    int32_t tile0;           // blocks of the members before it
-    int32_t pad_;
-};
-static_assert(sizeof(SsMember) == 64, "SsMember layout");
-template <bool PACKED, class K, class F>
-__device__ __forceinline__ SsMember ss_member(const SsMember* __restrict__ mem, int B, const SsMember& lone, K key, F SsMember::*field) {
-    if (PACKED) return mem[member_of(mem, B, key, field)];
-    return lone;
 }
 
 // Stem: 3x3, 128 -> 48 with bias.  The input planes are built while staging: one-hot channels from the base codes
@@ -252,50 +198,6 @@ __global__ __launch_bounds__(SS_THREADS) void ss_conv_kernel(const SsMember* __r
     const size_t off = (size_t)m.pix0 * SS_CH;
     ss_conv_body<KS, RESIDUAL>(reinterpret_cast<float*>(ss_smem), x + off, gamma, beta, w, out + off, m.L, ty * SS_TILE,
                                tx * SS_TILE);
-}
-
-// Head: logits = fc1(relu(LN(x))) (fc1: Linear(48, 1)), probs = sigmoid(logits); one thread per pixel.
-// pixel: the 48 channels of the pixel; i: its index inside its own [L, L] outputs
-__device__ __forceinline__ void ss_out_body(const float* __restrict__ pixel, const float* __restrict__ gamma,
-                                            const float* __restrict__ beta, const float* __restrict__ fw,
-                                            const float* __restrict__ fb, float* __restrict__ logits, float* __restrict__ probs,
-                                            int64_t i) {
-    const f32x4* src = reinterpret_cast<const f32x4*>(pixel);
-    f32x4 v[12];
-#pragma unroll
-    for (int k = 0; k < 12; ++k) v[k] = src[k];
-    ln_relu48(v, gamma, beta);
-    float z = 0.f;
-#pragma unroll
-    for (int k = 0; k < 12; ++k)
-#pragma unroll
-        for (int t = 0; t < 4; ++t) z = fmaf(v[k][t], fw[4 * k + t], z);
-    z += fb[0];
-    if (logits) logits[i] = z;
-    if (probs) probs[i] = 1.f / (1.f + expf(-z));
-}
-// n pixels of the whole buffer; a thread finds its pixel's member by the pixel prefix sums
-template <bool PACKED>
-__global__ __launch_bounds__(256) void ss_out_kernel(const SsMember* __restrict__ mem, int B, const SsMember lone,
-                                                     const float* __restrict__ x, const float* __restrict__ gamma,
-                                                     const float* __restrict__ beta, const float* __restrict__ fw,
-                                                     const float* __restrict__ fb, int64_t n) {
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= n) return;
-    const SsMember m = ss_member<PACKED>(mem, B, lone, i, &SsMember::pix0);
-    ss_out_body(x + i * SS_CH, gamma, beta, fw, fb, m.logits, m.probs, i - m.pix0);
-}
-
-constexpr size_t ss_members_bytes(int B) { return ((size_t)B * sizeof(SsMember) + 255) & ~(size_t)255; }
-
-template <class K>
-int allow_lds(K kernel, size_t bytes, DeviceOnce& once) {
-    if (once.pending()) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-        if (e != hipSuccess) return fail(RNAMSM_ERR_HIP, "ss_head: hipFuncSetAttribute: %s", hipGetErrorString(e));
-        once.mark();
-    }
-    return RNAMSM_OK;
 }
 
 // The launches over `blocks` tiles and `pixels` pixels (xs, ts: the two [pixels][48] images): PACKED with mem / B the uploaded table

@@ -30,6 +30,7 @@ W_LAYER = ("row_ln_g", "row_ln_b", "row_wqkv", "row_bqkv", "row_wo", "row_bo",
 W_SS_STEM = ("conv1.weight", "conv1.bias", "bn1.weight", "bn1.bias")
 W_SS_BLOCK = ("conv1.weight", "bn1.weight", "bn1.bias", "conv2.weight", "bn2.weight", "bn2.bias")
 W_SS_HEAD = ("fc1.weight", "fc1.bias")
+SS_GEMM_DTYPES = ("f32", "bf16")   # arithmetics of the SS head's convolutions: rnamsm_ss_head / rnamsm_ss_head16
 SS_MAX_L = 1024
 SS_MAX_BATCH = 1024
 SS_TEXT_RECORD = 25                # bytes of one element of the .prob text: "%.18e" and its separator
@@ -132,6 +133,12 @@ _SIGNATURES = {
                                c_void_p]),
     "rnamsm_ss_head_packed_workspace_bytes": (c_size_t, [c_int, POINTER(c_int)]),
     "rnamsm_ss_head_packed": (c_int, [POINTER(SsItem), c_int, c_int, POINTER(c_void_p), c_void_p, c_size_t, c_void_p]),
+    "rnamsm_ss_pack_conv16": (c_int, [c_void_p, c_void_p, c_int64, c_void_p]),
+    "rnamsm_ss_head16_workspace_bytes": (c_size_t, [c_int]),
+    "rnamsm_ss_head16": (c_int, [c_void_p, c_int64, c_void_p, c_int, c_int, POINTER(c_void_p), c_void_p, c_void_p, c_void_p, c_size_t,
+                                 c_void_p]),
+    "rnamsm_ss_head16_packed_workspace_bytes": (c_size_t, [c_int, POINTER(c_int)]),
+    "rnamsm_ss_head16_packed": (c_int, [POINTER(SsItem), c_int, c_int, POINTER(c_void_p), c_void_p, c_size_t, c_void_p]),
     "rnamsm_ss_prob_text_bytes": (c_size_t, [c_int]),
     "rnamsm_ss_prob_text": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
     "rnamsm_ss_prob_text_packed": (c_int, [POINTER(SsTextItem), c_int, c_void_p]),

@@ -11,6 +11,14 @@ from dataclasses import dataclass, field
 from pathlib import Path
 from typing import List, Tuple
 
+from ._lib import SS_GEMM_DTYPES        # data.ss_gemm_dtype
+
+
+def check_ss_gemm_dtype(value: str) -> str:
+    if value not in SS_GEMM_DTYPES:
+        raise ValueError(f"data.ss_gemm_dtype={value!r} is not one of {', '.join(SS_GEMM_DTYPES)}")
+    return value
+
 
 @dataclass
 class DataConfig:                       # RNA_MSM_Inference.py:20-32
@@ -50,6 +58,9 @@ class DataConfig:                       # RNA_MSM_Inference.py:20-32
     # (rnamsm_ss_pairs); with ss_prob_text on as well the [L, L] probabilities never reach the host.  false = secondary_structure and
     # np.savetxt on the writer thread, as before.  The same bytes either way.
     ss_pairs_device: bool = True
+    # with the SS head on: the arithmetic of its convolutions -- f32 (exact, default) | bf16 (rnamsm_ss_head16: bf16 operands on
+    # the matrix cores; accumulation, residual image and LayerNorm stay fp32).  Its own key: it does NOT follow model.gemm_dtype.
+    ss_gemm_dtype: str = "f32"
     # extra (not in the reference): "" = off; else an RSA model directory of the reference (_downstream_tasks/RSA/models/OH+RNA-MSM_Emb:
     # model_pcc_*.pt and the statistic_dict*.pickle files): the solvent-accessibility ensemble (rnamsm.rsa) then runs on every
     # alignment's embedding where it lies on the device, and RSA_result/<id>_<k>/<id>.txt, RSA_result/<id>_ensemble/<id>.txt are
@@ -124,4 +135,5 @@ def parse_overrides(argv: List[str], cfg: Config = None) -> Config:
         if key not in names:
             raise KeyError(f"unknown key {key!r} in group {group!r}")
         setattr(node, key, _coerce(value, getattr(node, key)))
+    check_ss_gemm_dtype(cfg.data.ss_gemm_dtype)
     return cfg

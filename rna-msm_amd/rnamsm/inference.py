@@ -21,7 +21,7 @@ import torch
 
 from . import ops, rsa, sharding, ss
 from .alphabet import RNAAlphabet
-from .config import Config
+from .config import Config, check_ss_gemm_dtype
 from .model import MSATransformer
 from .msa import load_msa_tokens
 
@@ -307,6 +307,7 @@ def extract_feat(cfg: Config, model: Optional[MSATransformer] = None, gather_to_
                  async_io: bool = True) -> List[str]:
     """async_io: read/tokenise the next alignment on a helper thread while the GPU runs the current one, and move the
     outputs to disk through `_AsyncNpyWriter`; False = the reference's strictly sequential loop (same files)."""
+    ss_dtype = check_ss_gemm_dtype(getattr(cfg.data, "ss_gemm_dtype", "f32"))
     device = torch.device(cfg.data.device)
     if device.type != "cuda":
         raise RuntimeError("this build runs on the MI355X HIP path only (data.device=cuda); there is no CPU path")
@@ -351,7 +352,11 @@ def extract_feat(cfg: Config, model: Optional[MSATransformer] = None, gather_to_
     base_lut = ss.token_base_codes(alphabet, device) if ss_path or rsa_dir else None
     heads: list = []
     if ss_path:
-        heads.append(ss.SSHead(ss.load_predictor(ss_path, device), alphabet, base_lut, device,
+        if rank == 0:
+            print(f"SS head arithmetic: {ss_dtype} (data.ss_gemm_dtype; independent of model.gemm_dtype={cfg.model.gemm_dtype})")
+        predictor = ss.load_predictor(ss_path, device)
+        predictor.gemm_dtype = ss_dtype
+        heads.append(ss.SSHead(predictor, alphabet, base_lut, device,
                                text_on=bool(getattr(cfg.data, "ss_prob_text", True)) and not gathering,
                                pairs_on=bool(getattr(cfg.data, "ss_pairs_device", True)) and not gathering))
     if rsa_dir:         # (the reference program's seed; drawn from on the writer thread, in delivery order)

@@ -614,44 +614,65 @@ def _ss_operands(fn: str, atp: torch.Tensor, bc: torch.Tensor, name: str, bc_nam
     return atp, bc.contiguous(), L
 
 
+def _ss_entries(fn: str, gemm_dtype: str):
+    """(lone, lone size, packed, packed size): the entry points of the SS head in the arithmetic `gemm_dtype`."""
+    if gemm_dtype not in _lib.SS_GEMM_DTYPES:
+        raise ValueError(f"{fn}: gemm_dtype must be one of {', '.join(_lib.SS_GEMM_DTYPES)}, got {gemm_dtype!r}")
+    lib, stem = _lib.load(), "rnamsm_ss_head16" if gemm_dtype == "bf16" else "rnamsm_ss_head"
+    return tuple(getattr(lib, stem + tail) for tail in ("", "_workspace_bytes", "_packed", "_packed_workspace_bytes"))
+
+
 @_on_operand_device
-def ss_head(atp: torch.Tensor, base_codes: torch.Tensor, ptrs, num_blocks: int, want: str = "probs") -> torch.Tensor:
+def ss_pack_conv16(w: torch.Tensor) -> torch.Tensor:
+    """The bf16 planes of a conv weight for rnamsm_ss_head16 (rnamsm_ss_pack_conv16): w fp32, tap-major [kh][kw][out][in],
+    contiguous -> the same shape in bf16, each element rounded to nearest even on the device."""
+    _dev(w, "w")
+    if not w.is_contiguous():
+        raise ValueError("ss_pack_conv16: w must be contiguous")
+    out = torch.empty(w.shape, device=w.device, dtype=torch.bfloat16)
+    _lib.check(_lib.load().rnamsm_ss_pack_conv16(w.data_ptr(), out.data_ptr(), w.numel(), _stream()))
+    return out
+
+
+@_on_operand_device
+def ss_head(atp: torch.Tensor, base_codes: torch.Tensor, ptrs, num_blocks: int, want: str = "probs",
+            gemm_dtype: str = "f32") -> torch.Tensor:
     """RNA-MSM-SS head (rnamsm_ss_head): atp [120, L, L] fp32 (planes may lie further apart than L*L: a slice of a wider
     buffer is read in place), base_codes uint8 [L] (0..3 = A, C, G, U, other = no base), ptrs: the packed weight table
-    (ctypes c_void_p array, rnamsm.ss.SSPredictor) -> [L, L] fp32 probabilities (want="probs") or logits (want="logits")."""
+    (ctypes c_void_p array, rnamsm.ss.SSPredictor) -> [L, L] fp32 probabilities (want="probs") or logits (want="logits").
+    gemm_dtype="bf16": rnamsm_ss_head16, with ptrs the table whose conv entries are bf16 planes (ss_pack_conv16)."""
     _want("ss_head", want)
+    head, head_bytes, _, _ = _ss_entries("ss_head", gemm_dtype)
     atp, base_codes, L = _ss_operands("ss_head", atp, base_codes, "atp", "base_codes")
-    lib = _lib.load()
-    ws = torch.empty(max(lib.rnamsm_ss_head_workspace_bytes(L), 16), dtype=torch.uint8, device=atp.device)
+    ws = torch.empty(max(head_bytes(L), 16), dtype=torch.uint8, device=atp.device)
     out = torch.empty(L, L, device=atp.device, dtype=torch.float32)
     ptr = out.data_ptr()
-    _lib.check(lib.rnamsm_ss_head(atp.data_ptr(), atp.stride(0), base_codes.data_ptr(), L, num_blocks, ptrs,
-                                  ptr if want == "logits" else None, ptr if want == "probs" else None, ws.data_ptr(), ws.numel(),
-                                  _stream()))
+    _lib.check(head(atp.data_ptr(), atp.stride(0), base_codes.data_ptr(), L, num_blocks, ptrs,
+                    ptr if want == "logits" else None, ptr if want == "probs" else None, ws.data_ptr(), ws.numel(), _stream()))
     return out
 
 
 @_on_operand_device
 def ss_head_packed(atps: Sequence[torch.Tensor], codes: Sequence[torch.Tensor], ptrs, num_blocks: int,
-                   want: str = "probs") -> List[torch.Tensor]:
+                   want: str = "probs", gemm_dtype: str = "f32") -> List[torch.Tensor]:
     """RNA-MSM-SS head over several structures in one set of launches (rnamsm_ss_head_packed): atps[b] [120, L_b, L_b] fp32,
     codes[b] uint8 [L_b], the operand rules of ss_head per member (slices of one wider buffer are read in place) -> a list of
     [L_b, L_b] tensors, each bit-identical to ss_head on that member alone.  One workspace and one output allocation per call:
-    the returned tensors are views of one buffer."""
+    the returned tensors are views of one buffer.  gemm_dtype="bf16": rnamsm_ss_head16_packed, ptrs as for ss_head."""
     _want("ss_head_packed", want)
+    _, _, packed, packed_bytes = _ss_entries("ss_head_packed", gemm_dtype)
     members, device = _members("ss_head_packed", _ss_operands, _lib.SS_MAX_BATCH, _lib.SS_MAX_L,
                                ("maps", "base-code rows", "structures"), {"atp": atps, "base_codes": codes})
     if not members:
         return []
     B, Ls = len(members), [L for _, _, L in members]
-    lib = _lib.load()
-    ws = torch.empty(lib.rnamsm_ss_head_packed_workspace_bytes(B, (_lib.c_int * B)(*Ls)), dtype=torch.uint8, device=device)
+    ws = torch.empty(packed_bytes(B, (_lib.c_int * B)(*Ls)), dtype=torch.uint8, device=device)
     outs = [o.view(L, L) for o, L in zip(_carved([L * L for L in Ls], device, torch.float32), Ls)]
     items = (_lib.SsItem * B)()
     for b, ((atp, bc, L), o) in enumerate(zip(members, outs)):
         items[b] = _lib.SsItem(atp.data_ptr(), atp.stride(0), bc.data_ptr(), L, o.data_ptr() if want == "logits" else None,
                                o.data_ptr() if want == "probs" else None)
-    _lib.check(lib.rnamsm_ss_head_packed(items, B, num_blocks, ptrs, ws.data_ptr(), ws.numel(), _stream()))
+    _lib.check(packed(items, B, num_blocks, ptrs, ws.data_ptr(), ws.numel(), _stream()))
     return outs
 
 

@@ -37,7 +37,9 @@ def base_codes(seq: str) -> np.ndarray:
     return _CODE[raw]
 
 
-SS_CHUNK_PIXELS = 1024 * 1024   # pixels of one packed call: the workspace of one lone L = 1024 call (403 MB)
+# pixels of one packed call: the workspace of one lone L = 1024 call (403 MB).  The bf16 head keeps both workspace images in fp32
+# (rnamsm_ss_head16_packed_workspace_bytes = rnamsm_ss_head_packed_workspace_bytes), so one budget serves both arithmetics.
+SS_CHUNK_PIXELS = 1024 * 1024
 
 
 def plan_ss_chunks(Ls: Sequence[int], max_pixels: int = SS_CHUNK_PIXELS, max_batch: int = _lib.SS_MAX_BATCH) -> List[List[int]]:
@@ -79,28 +81,55 @@ class SSPredictor(nn.Module):
 
     predict(atp, seq) -> [L, L] base-pair probabilities (sigmoid of the head, what predict.py hands to the post-processing);
     logits(atp, seq) -> the pre-sigmoid values.  atp: the [120, L, L] fp32 maps on the HIP device (a view whose planes lie
-    further apart is read in place); seq: the query sequence (str) or its base codes (uint8 [L], see base_codes)."""
+    further apart is read in place); seq: the query sequence (str) or its base codes (uint8 [L], see base_codes).
+    gemm_dtype: "f32" (default: rnamsm_ss_head, exact fp32) or "bf16" (rnamsm_ss_head16: conv operands in bf16, everything else
+    fp32); every method that runs the head follows it, and nothing else does -- the formatter and the decoding read whatever
+    probabilities the head made."""
 
-    def __init__(self, num_blocks: int = 16):
+    def __init__(self, num_blocks: int = 16, gemm_dtype: str = "f32"):
         super().__init__()
         if not 1 <= num_blocks <= 64:
             raise ValueError(f"num_blocks must be in [1, 64], got {num_blocks}")
         self.num_blocks = num_blocks
+        self.gemm_dtype = gemm_dtype
         self.conv1 = nn.Conv2d(IN_PLANES, CHANNELS, 3, padding=1)
         self.bn1 = nn.LayerNorm(CHANNELS)
         self.layer1 = nn.Sequential(*[_Block() for _ in range(num_blocks)])
         self.fc1 = nn.Linear(CHANNELS, 1)
         self._pack_key = None
         self._pack = None
+        self._pack16 = None
+
+    @property
+    def gemm_dtype(self) -> str:
+        return self._gemm_dtype
+
+    @gemm_dtype.setter
+    def gemm_dtype(self, value: str) -> None:
+        if value not in _lib.SS_GEMM_DTYPES:
+            raise ValueError(f"SSPredictor: gemm_dtype must be one of {', '.join(_lib.SS_GEMM_DTYPES)}, got {value!r}")
+        self._gemm_dtype = value
 
     # ------------------------------------------------------------------ weight table of rnamsm_ss_head
     def _packed_weights(self):
         """The weight-pointer table in the kernel layout (conv weights tap-major [kh][kw][out][in]), rebuilt when a parameter was
-        replaced or written in place since (its data_ptr or version counter moved) -- the MSATransformer._packed_weights rule."""
+        replaced or written in place since (its data_ptr or version counter moved) -- the MSATransformer._packed_weights rule.
+        In the bf16 mode: the table of rnamsm_ss_head16, whose conv entries are bf16 planes made on the device from those of the
+        fp32 table, once per pack key."""
         params = list(self.parameters())
         key = tuple((p.data_ptr(), p._version, p.device) for p in params)
-        if key == self._pack_key:
+        if key != self._pack_key:
+            self._pack = self._fp32_table(key)
+            self._pack16 = None
+        if self._gemm_dtype != "bf16":
             return self._pack
+        if self._pack16 is None:
+            ptrs, keep = self._pack
+            planes = {i: ops.ss_pack_conv16(t) for i, t in enumerate(keep) if t.dim() == 4}
+            self._pack16 = ((ctypes.c_void_p * len(keep))(*[planes.get(i, t).data_ptr() for i, t in enumerate(keep)]), (keep, planes))
+        return self._pack16
+
+    def _fp32_table(self, key):
         if self.conv1.weight.device.type != "cuda":
             raise _lib.RnamsmError("SSPredictor must be moved to the HIP device (.to('cuda')): no CPU path exists")
         keep: List[torch.Tensor] = []
@@ -151,7 +180,7 @@ class SSPredictor(nn.Module):
     def _run(self, atp: torch.Tensor, seq: Union[str, np.ndarray, torch.Tensor], want: str) -> torch.Tensor:
         codes = self._codes_of(atp, seq, "atp", "seq", True).to(device=atp.device, dtype=torch.uint8)
         ptrs, _ = self._packed_weights()
-        return ops.ss_head(atp, codes, ptrs, self.num_blocks, want)
+        return ops.ss_head(atp, codes, ptrs, self.num_blocks, want, self._gemm_dtype)
 
     def predict(self, atp: torch.Tensor, seq) -> torch.Tensor:
         return self._run(atp, seq, "probs")
@@ -174,7 +203,8 @@ class SSPredictor(nn.Module):
         ptrs, _ = self._packed_weights()
         out: List[torch.Tensor] = []
         for chunk in plan_ss_chunks([a.shape[-1] for a in atps]):
-            out += ops.ss_head_packed([atps[i] for i in chunk], [codes[i] for i in chunk], ptrs, self.num_blocks, want)
+            out += ops.ss_head_packed([atps[i] for i in chunk], [codes[i] for i in chunk], ptrs, self.num_blocks, want,
+                                      self._gemm_dtype)
         return out
 
     def predict_many(self, atps: Sequence[torch.Tensor], seqs: Sequence) -> List[torch.Tensor]:
@@ -202,10 +232,10 @@ class SSPredictor(nn.Module):
         return [(p,) + st for p, st in zip(probs, structure_many(probs, rows))]
 
 
-def load_predictor(path: Union[str, Path], device, num_blocks: int = 16) -> SSPredictor:
+def load_predictor(path: Union[str, Path], device, num_blocks: int = 16, gemm_dtype: str = "f32") -> SSPredictor:
     """`rna-msm_attention.pt` (a plain state_dict) -> an SSPredictor on `device`, loaded strictly."""
     state = torch.load(path, map_location="cpu")
-    model = SSPredictor(num_blocks)
+    model = SSPredictor(num_blocks, gemm_dtype)
     model.load_state_dict(state, strict=True)
     return model.eval().to(device)
 
