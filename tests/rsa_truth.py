@@ -2,12 +2,10 @@
 FrameModel, model/_0713/resnet.py BasicBlock, model/_0713/mingpt.py Block) restated in torch functional form, at any dtype.
 Test infrastructure only: tests/test_rsa_truth.py ties it to the reference's own outputs (tests/golden/rsa/); the GPU tests then
 check the HIP head against it at every size."""
-import math
 import os
 
 import numpy as np
 import torch
-import torch.nn.functional as F
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "rsa")
 EMB, PLANES, HEADS = 768, 64, 8
@@ -91,41 +89,13 @@ def logits(x: np.ndarray, state: dict, dtype=torch.float64, pad=None) -> np.ndar
 
 
 def logits_torch(x: torch.Tensor, sd: dict, pad=None) -> torch.Tensor:
-    """The same on tensors that already share a dtype and a device (the eager-PyTorch side of tools/rsa_head_timing.py)."""
-    x = x[None]
-    b = "net.0.0."
-
-    def bn(h, name):
-        return F.batch_norm(h, sd[name + ".running_mean"], sd[name + ".running_var"], sd[name + ".weight"], sd[name + ".bias"],
-                            training=False, eps=1e-5)
-
-    if pad is None:
-        c1 = F.conv1d(x, sd[b + "conv1.weight"], padding=1)
-    else:
-        col = pad[None, :, None]
-        c1 = F.conv1d(torch.cat([col, x, col], dim=2), sd[b + "conv1.weight"])
-    h = torch.relu(bn(c1, b + "bn1"))
-    h = torch.relu(bn(F.conv1d(h, sd[b + "conv2.weight"], padding=1), b + "bn2"))
-    w = h.mean(dim=2, keepdim=True)
-    w = torch.relu(F.conv1d(w, sd[b + "fc1.weight"], sd[b + "fc1.bias"]))
-    w = torch.sigmoid(F.conv1d(w, sd[b + "fc2.weight"], sd[b + "fc2.bias"]))
-    y = torch.relu(h * w + bn(F.conv1d(x, sd[b + "shortcut.0.weight"]), b + "shortcut.1"))
-    y = y[0].t()                                                             # [L, 64]
-    g = "net.1.0."
-    L = y.shape[0]
-    t = F.layer_norm(y, (PLANES,), sd[g + "ln1.weight"], sd[g + "ln1.bias"], eps=1e-5)
-
-    def heads(name):
-        return F.linear(t, sd[g + f"attn.{name}.weight"], sd[g + f"attn.{name}.bias"]).view(L, HEADS, PLANES // HEADS).transpose(0, 1)
-
-    q, k, v = heads("query"), heads("key"), heads("value")
-    att = torch.softmax((q @ k.transpose(-2, -1)) * (1.0 / math.sqrt(PLANES // HEADS)), dim=-1)
-    ctx = (att @ v).transpose(0, 1).contiguous().view(L, PLANES)
-    y = y + F.linear(ctx, sd[g + "attn.proj.weight"], sd[g + "attn.proj.bias"])
-    t = F.layer_norm(y, (PLANES,), sd[g + "ln2.weight"], sd[g + "ln2.bias"], eps=1e-5)
-    t = F.linear(F.gelu(F.linear(t, sd[g + "mlp.0.weight"], sd[g + "mlp.0.bias"])), sd[g + "mlp.2.weight"], sd[g + "mlp.2.bias"])
-    y = y + t
-    return F.linear(y, sd["final.weight"], sd["final.bias"])[:, 0]
+    """The same on tensors that already share a dtype and a device (the eager-PyTorch side of tools/rsa_head_timing.py): the
+    composition of the four stages of tests/rsa_stages.py, bit for bit the single function it was
+    (tests/test_rsa_stages_host.py)."""
+    import rsa_stages as S                # the network cut at the head's four launches; rsa_stages imports this module
+    h1, shortcut = S.stem(x, sd, pad=pad)
+    h2, total = S.conv2(h1, sd, tile=None)                   # one "tile": the mean is torch's own reduction over the sequence
+    return S.attn(*S.mix(shortcut, h2, total, sd), sd)
 
 
 def load_state(name: str) -> dict:

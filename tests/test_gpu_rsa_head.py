@@ -5,7 +5,8 @@ chunks of 64, so the lengths cover each side of the edges 32, 64, 96 and 128 (31
 every position touches the padding), the shipped example's 35 and the limit (1023, 1024).  Bars: rsa_truth.compare -- rel-L2 to
 fp64 within 2 x the fp32 CPU restatement's on the same input (4 x at L <= 3, where one to nine logits make the ratio a matter of
 single roundings: measured 2.5 for one make_state member at L = 2, rsa_truth.L2_MULT_SHORT), element-wise within 2 x its max-abs
-+ 4 fp32 ulps of the largest |logit|."""
++ 4 fp32 ulps of the largest |logit|.
+Stage by stage (h1 .. v, the tile sums and the logits, each on the head's own input image): tests/test_gpu_rsa_head_stages.py."""
 import ctypes
 import os
 import random
