@@ -7,7 +7,8 @@ Reads `<featdir>/<rnaid>.fasta` (each record's description is its name) and `<fe
 RNA_MSM_Inference.py writes), runs the ensemble of `<rootdir>/models/OH+RNA-MSM_Emb` (model_pcc_*.pt in sorted order and the two
 statistic_dict_*.pickle files) on the HIP device (rnamsm.rsa.RSAEnsemble: all members in one set of launches) and writes
 `<featdir>/RSA_result/<name>_<k>/<name>.txt` per member and `<featdir>/RSA_result/<name>_ensemble/<name>.txt` as the reference
-does.  `random` is seeded with 2022 as there.  Not written: the reference's two PNG plots; no device but the HIP one.
+does.  `random` is seeded with 2022 as there.  --text-device (default): the tables are computed and formatted on the device
+(rnamsm_rsa_text) and written as one block each; --no-text-device: the host arithmetic and np.savetxt, the same bytes.  Not written: the reference's two PNG plots; no device but the HIP one.
 """
 import os
 import random
@@ -24,6 +25,9 @@ def get_args(argv=None):
     p.add_argument("--featdir", default=os.path.join(ROOT, "results"), type=str)
     p.add_argument("--rnaid", default="2DRB_1", type=str)
     p.add_argument("--device", default="cuda", type=str, help="cuda or cuda:N (the HIP device; there is no CPU path)")
+    p.add_argument("--text-device", dest="text_device", action="store_true", default=True,
+                   help="format the tables on the device (default); the same bytes as --no-text-device")
+    p.add_argument("--no-text-device", dest="text_device", action="store_false", help="format the tables on the host (np.savetxt)")
     return p.parse_args(argv)
 
 
@@ -53,8 +57,13 @@ def main(argv=None):
         if emb.ndim != 2 or emb.shape != (len(seq), rsa.EMBED_DIM):
             sys.exit(f"RSA_predict.py: {name}: sequence of length {len(seq)} but an embedding of shape {emb.shape} in {emb_path}")
         with torch.no_grad():
-            values = ens.predict(torch.from_numpy(np.ascontiguousarray(emb, dtype=np.float32)).to(device), seq).cpu().numpy()
-        rsa.write_rsa_files(values, seq, name, args.featdir, ens.model_names, random)
+            emb_dev = torch.from_numpy(np.ascontiguousarray(emb, dtype=np.float32)).to(device)
+            if args.text_device:
+                values, text = ens.predict_text(emb_dev, seq)
+                text = tuple(t.cpu().numpy() for t in text)
+            else:
+                values, text = ens.predict(emb_dev, seq), None
+        rsa.write_rsa_files(values.cpu().numpy(), seq, name, args.featdir, ens.model_names, random, text=text)
         print(f"{name}: {os.path.join(args.featdir, 'RSA_result', name)}_{{0..{len(ens) - 1},ensemble}}/{name}.txt")
 
 

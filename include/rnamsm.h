@@ -568,6 +568,47 @@ size_t rnamsm_rsa_head_packed_workspace_bytes(int B, const int* Ls, int n_models
 int rnamsm_rsa_head_packed(const rnamsm_rsa_item* items, int B, int n_models, int use_onehot, const void* const* weights,
                            void* workspace, size_t workspace_bytes, void* stream);
 
+/* f5, the text of the tables -- the bodies of the reference's `RSA_result/<name>_<k>/<name>.txt` (one per member) and
+ * `<name>_ensemble/<name>.txt` (predict.py: doSavePredict_single), written on the device from the [n_models, L] RSA of
+ * rnamsm_rsa_head, byte for byte.  Per position p, in float64 (K = n_models):
+ *   scale[p] = 400 for the letter A or G, 350 for C, U or T (T scales as U; the letter column prints the letter itself)
+ *   member k: asa_k = double(rsa[k][p]) * scale[p], rsa_k = double(rsa[k][p])
+ *   ensemble: asa_e = (((asa_0 + asa_1) + ...) + asa_{K-1}) / K in that order, rsa_e = asa_e / scale[p]     (IEEE, nothing fused)
+ * A body is L lines "%d\t\t%c\t\t%.2f\t\t%.3f\n" of (p + 1, letter[p], asa, rsa): "%.2f" / "%.3f" are the double's exact binary
+ * value rounded half to even at that decimal, computed in integers.  The caller prepends the header, which carries the names.
+ * rsa [n_models, L] fp32 row-major, letters uint8 [L]: the sequence's characters (all device memory).  Outputs:
+ *   text    rnamsm_rsa_text_bytes(L, n_models) = (n_models + 1) x RNAMSM_RSA_TEXT_LINE_MAX x L bytes, 16-byte aligned: body f (member
+ *           f, or the ensemble for f = n_models) starts at f x RNAMSM_RSA_TEXT_LINE_MAX x L -- 23 bytes is the longest line at
+ *           L <= 1024; bytes behind a body's count are not written.  The size is 0 for L outside [1, RNAMSM_RSA_MAX_L] or n_models
+ *           outside [1, RNAMSM_RSA_MAX_MODELS].
+ *   counts  int32 [n_models + 3]: the bytes written to each of the n_models + 1 bodies, then the fallback word, then the zero word
+ *   ens     double [2, L] or null: asa_e, then rsa_e
+ * The fallback word reads 1 (else 0) when a member value is NaN or inf, has its sign bit set (-0.0 included) or lies above 1.0, or
+ * when a letter is none of A C G U T (the host path replaces such a letter by a base drawn from its generator): the bodies and ens
+ * are then unspecified (every write still stays inside its bound) and the caller formats that alignment on the host.  The zero word
+ * reads 1 (else 0) when a member's ASA or the ensemble's is exactly 0, where the reference exits.  With both words 0 the text is
+ * exact.  Each word is one plain store; no atomics, no workspace, nothing allocated: the same inputs give the same bytes on every
+ * run.
+ * Packed: B members of unlike L in one call, one workgroup per (member, table), 32 members per launch (the descriptors travel as
+ * kernel arguments; items is a HOST array, free to go after the call).  A member's bytes, counts and ens are those of the lone call
+ * on it, whatever its company and place; the members' outputs must not overlap.
+ * Refused (RNAMSM_ERR_INVALID) before anything is enqueued, rnamsm_last_error naming the member where one is at fault: B outside
+ * [1, RNAMSM_RSA_MAX_BATCH], n_models or an L out of range, a null pointer other than ens, rsa or counts not 4-byte aligned, ens
+ * not 8-byte aligned, text not 16-byte aligned. */
+#define RNAMSM_RSA_TEXT_LINE_MAX 23
+typedef struct {                 /* one alignment of the batch */
+    const float*   rsa;          /* device [n_models, L] */
+    const uint8_t* letters;      /* device [L] */
+    int32_t        L;            /* 1 .. RNAMSM_RSA_MAX_L */
+    uint8_t*       text;         /* device, rnamsm_rsa_text_bytes(L, n_models) bytes, 16-byte aligned */
+    int32_t*       counts;       /* device [n_models + 3] */
+    double*        ens;          /* device [2, L] or null */
+} rnamsm_rsa_text_item;
+size_t rnamsm_rsa_text_bytes(int L, int n_models);
+int rnamsm_rsa_text(const float* rsa, const uint8_t* letters, int L, int n_models, uint8_t* text, int32_t* counts, double* ens,
+                    void* stream);
+int rnamsm_rsa_text_packed(const rnamsm_rsa_text_item* items, int B, int n_models, void* stream);
+
 /* a7 -- the residual add of NormalizedResidualBlock around a layer that is NOT one of this library's (modules.py:396,
  * `x = residual + x`; around the library's own layers the add is fused into the layer's last GEMM): out[i] = a[i] + b[i], fp32,
  * out may alias a or b. */

@@ -46,6 +46,7 @@ RSA_MAX_L = 1024
 RSA_MAX_MODELS = 8
 RSA_MAX_BATCH = 1024
 RSA_CIN_PAD = 800
+RSA_TEXT_LINE_MAX = 23             # rnamsm_rsa_text_bytes: bytes of the longest line of an RSA_result table at L = 1024
 
 
 class ModelDims(ctypes.Structure):
@@ -75,6 +76,12 @@ class RsaItem(ctypes.Structure):
     """rnamsm_rsa_item: one alignment of an rnamsm_rsa_head_packed batch (device pointers as integers)."""
     _fields_ = [("emb", c_void_p), ("emb_row_stride", c_int64), ("base_codes", c_void_p), ("L", ctypes.c_int32),
                 ("probs", c_void_p), ("logits", c_void_p)]
+
+
+class RsaTextItem(ctypes.Structure):
+    """rnamsm_rsa_text_item: one alignment of an rnamsm_rsa_text_packed batch (device pointers as integers)."""
+    _fields_ = [("rsa", c_void_p), ("letters", c_void_p), ("L", ctypes.c_int32), ("text", c_void_p), ("counts", c_void_p),
+                ("ens", c_void_p)]
 
 
 _SIGNATURES = {
@@ -151,6 +158,9 @@ _SIGNATURES = {
                                 c_size_t, c_void_p]),
     "rnamsm_rsa_head_packed_workspace_bytes": (c_size_t, [c_int, POINTER(c_int), c_int]),
     "rnamsm_rsa_head_packed": (c_int, [POINTER(RsaItem), c_int, c_int, c_int, POINTER(c_void_p), c_void_p, c_size_t, c_void_p]),
+    "rnamsm_rsa_text_bytes": (c_size_t, [c_int, c_int]),
+    "rnamsm_rsa_text": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "rnamsm_rsa_text_packed": (c_int, [POINTER(RsaTextItem), c_int, c_int, c_void_p]),
     "rnamsm_greedy_select_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
     "rnamsm_greedy_select": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
     "rnamsm_msa_weights": (c_int, [c_void_p, c_int, c_int, c_double, c_void_p, c_void_p]),

@@ -66,6 +66,10 @@ class DataConfig:                       # RNA_MSM_Inference.py:20-32
     # alignment's embedding where it lies on the device, and RSA_result/<id>_<k>/<id>.txt, RSA_result/<id>_ensemble/<id>.txt are
     # written next to the .npy files (_downstream_tasks/RSA/predict.py's files, without the plots)
     rsa_model_dir: str = ""
+    # with the RSA head on: the K + 1 tables of RSA_result are computed (float64) and formatted on the device (rnamsm_rsa_text) and
+    # written as a header and one block each; false = the host arithmetic and np.savetxt on the writer thread, as before.  The same
+    # bytes either way; an alignment with a letter outside ACGUT in its query takes the host path by itself.
+    rsa_text_device: bool = True
 
 
 @dataclass

@@ -345,8 +345,10 @@ def extract_feat(cfg: Config, model: Optional[MSATransformer] = None, gather_to_
     # writer thread's share of it is one binary write, where np.savetxt formats L^2 numbers under the GIL; the files are the same
     # bytes.  data.ss_pairs_device (default on): the pairs are decoded and the bodies of `.ct` / `.bpseq` written on the device too
     # (rnamsm.ss.structure), so the writer thread no longer runs secondary_structure and two np.savetxt tables per structure; with
-    # the formatter on as well no [L, L] float tensor is copied to the host at all.  Under gather_to_rank0 both stay off (the host
-    # path): the gathered items are the probabilities and the tokens.
+    # the formatter on as well no [L, L] float tensor is copied to the host at all.  data.rsa_text_device (default on): the RSA
+    # head's K + 1 tables are computed and formatted on the device behind the head (rnamsm.rsa.table_text), so the writer thread no
+    # longer runs K + 1 np.savetxt tables per alignment.  Under gather_to_rank0 all three stay off (the host path): the gathered items
+    # are the heads' values and the tokens.
     gathering = gather_to_rank0 and world > 1
     ss_path, rsa_dir = getattr(cfg.data, "ss_model_path", ""), getattr(cfg.data, "rsa_model_dir", "")
     base_lut = ss.token_base_codes(alphabet, device) if ss_path or rsa_dir else None
@@ -359,8 +361,9 @@ def extract_feat(cfg: Config, model: Optional[MSATransformer] = None, gather_to_
         heads.append(ss.SSHead(predictor, alphabet, base_lut, device,
                                text_on=bool(getattr(cfg.data, "ss_prob_text", True)) and not gathering,
                                pairs_on=bool(getattr(cfg.data, "ss_pairs_device", True)) and not gathering))
-    if rsa_dir:         # (the reference program's seed; drawn from on the writer thread, in delivery order)
-        heads.append(rsa.RSAHead(rsa.load_ensemble(rsa_dir, device), alphabet, base_lut, random.Random(2022)))
+    if rsa_dir:         # (the reference program's seed; every alignment's draws are taken as its writer job is made, in delivery order)
+        heads.append(rsa.RSAHead(rsa.load_ensemble(rsa_dir, device), alphabet, base_lut, random.Random(2022),
+                                 text_on=bool(getattr(cfg.data, "rsa_text_device", True)) and not gathering, device=device))
     rng = np.random.RandomState(42)
     mine = sharding.shard_indices(len(ids), rank, world)
     written: List[str] = []

@@ -824,6 +824,64 @@ def rsa_head_packed(embs: Sequence[torch.Tensor], codes: Sequence[torch.Tensor],
     return outs
 
 
+def _rsa_text_operands(fn: str, rsa: torch.Tensor, letters: torch.Tensor, name: str, letters_name: str):
+    """One alignment of rsa_text / rsa_text_packed as the library reads it -> (rsa, letters, K, L)."""
+    _dev(rsa, name)
+    if rsa.dim() != 2:
+        raise ValueError(f"{fn}: {name} must be [n_models, L], got {tuple(rsa.shape)}")
+    K, L = rsa.shape
+    if not 1 <= K <= _lib.RSA_MAX_MODELS:
+        raise ValueError(f"{fn}: {name}: {K} members outside [1, {_lib.RSA_MAX_MODELS}]")
+    if not 1 <= L <= _lib.RSA_MAX_L:
+        raise ValueError(f"{fn}: {name}: L = {L} outside [1, {_lib.RSA_MAX_L}]")
+    _dev(letters, letters_name, torch.uint8)
+    if letters.dim() != 1 or letters.shape[0] != L:
+        raise ValueError(f"{fn}: {letters.shape[0] if letters.dim() == 1 else tuple(letters.shape)} letters for {name} of L = {L}")
+    return rsa.contiguous(), letters.contiguous(), K, L
+
+
+@_on_operand_device
+def rsa_text(rsa: torch.Tensor, letters: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """The bodies of the RSA_result tables of the members' [K, L] fp32 RSA, written on the device (rnamsm_rsa_text); letters uint8
+    [L]: the sequence's characters -> (text uint8 [(K + 1) x 23 L]: body f -- member f, the ensemble last -- starts at f x 23 L;
+    counts int32 [K + 3]: the bytes of each body, the fallback word, the zero word; ens float64 [2, L]: the ensemble's ASA and
+    RSA).  Only the first counts[f] bytes of a body are written; with counts[K + 1] == 1 (a value outside [0, 1] or a letter outside
+    ACGUT) text and ens are not to be used, and counts[K + 2] == 1 says that an ASA is exactly 0."""
+    return _rsa_text_run("rsa_text", [rsa], [letters])[0]
+
+
+@_on_operand_device
+def rsa_text_packed(rsa: Sequence[torch.Tensor], letters: Sequence[torch.Tensor]):
+    """rsa_text of every (rsa[b], letters[b]) in one call (rnamsm_rsa_text_packed: one workgroup per alignment and table; all the
+    members of one K) -> a list of (text, counts, ens), each byte-identical to rsa_text on that alignment alone.  One allocation per
+    output kind for the whole group: the returned tensors are views (every text starts on a 16-byte boundary of the buffer)."""
+    return _rsa_text_run("rsa_text_packed", rsa, letters)
+
+
+def _rsa_text_run(_fn: str, rsa, letters):
+    lone = _fn == "rsa_text"
+    members, device = _members(_fn, _rsa_text_operands, _lib.RSA_MAX_BATCH, None, ("value tables", "letter rows", "alignments"),
+                               {"rsa": rsa, "letters": letters}, checked=2, lone=lone)
+    if not members:
+        return []
+    B, K = len(members), members[0][2]
+    if any(m[2] != K for m in members):
+        raise ValueError(f"{_fn}: the alignments of one call share n_models; got {sorted({m[2] for m in members})}")
+    Ls = [m[3] for m in members]
+    lib = _lib.load()
+    outs = list(zip(_carved([(K + 1) * _lib.RSA_TEXT_LINE_MAX * L for L in Ls], device, torch.uint8, align=16),
+                    _carved([K + 3] * B, device, torch.int32),
+                    (e.view(2, L) for e, L in zip(_carved([2 * L for L in Ls], device, torch.float64), Ls))))
+    args = [(r.data_ptr(), l.data_ptr(), L, *(t.data_ptr() for t in o)) for (r, l, _, L), o in zip(members, outs)]
+    if lone:
+        r, l, L, text, counts, ens = args[0]
+        _lib.check(lib.rnamsm_rsa_text(r, l, L, K, text, counts, ens, _stream()))
+        return outs
+    items = (_lib.RsaTextItem * B)(*(_lib.RsaTextItem(*a) for a in args))
+    _lib.check(lib.rnamsm_rsa_text_packed(items, B, K, _stream()))
+    return outs
+
+
 @_on_operand_device
 def greedy_select(msa_u8: torch.Tensor, num_seqs: int, mode: str = "max") -> torch.Tensor:
     """msa uint8 [N, L] on the device -> int32 [num_seqs] ascending row indices (utils/align.py:128-148)."""

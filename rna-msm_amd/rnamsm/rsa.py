@@ -4,9 +4,11 @@
 names and shapes, so a state_dict taken from an upstream model loads with strict=True; `RSAEnsemble` holds K of them and the
 normalisation statistics, and its arithmetic is one HIP entry point (rnamsm_rsa_head: all members in four launches, exact fp32)
 that reads the [L, 768] embedding where it lies on the device; `predict_many` runs a list of alignments through the same four
-launches (rnamsm_rsa_head_packed), every result the lone call's bits.  `load_ensemble` reads an upstream model directory -- its `.pt`
+launches (rnamsm_rsa_head_packed), every result the lone call's bits; `predict_text[_many]` adds the bodies of the result tables,
+formatted on the device (rnamsm_rsa_text: `table_text`).  `load_ensemble` reads an upstream model directory -- its `.pt`
 files are pickled whole modules and are opened with no upstream code importable -- and `write_rsa_files` is the reference's
-host arithmetic and text format (predict.py: doSavePredict_single, per model and for the ensemble), byte for byte.  `RSAHead` is the
+host arithmetic and text format (predict.py: doSavePredict_single, per model and for the ensemble), byte for byte -- or, handed the
+device-made bodies, a header and one binary write per table, the same bytes.  `RSAHead` is the
 ensemble as the CLI runs it: it makes one `RSAResult` per alignment and turns it into the job that writes the texts.
 """
 from __future__ import annotations
@@ -25,7 +27,7 @@ import torch
 from torch import nn
 
 from . import _lib, ops
-from .ss import base_codes, plan_chunks
+from .ss import base_codes, letter_codes, plan_chunks
 
 EMBED_DIM = 768
 PLANES = 64
@@ -268,6 +270,22 @@ class RSAEnsemble(nn.Module):
     def logits_many(self, embs: Sequence[torch.Tensor], seqs: Sequence) -> List[torch.Tensor]:
         return self._run_many(embs, seqs, "logits")
 
+    def predict_text(self, emb: torch.Tensor, seq, letters=None):
+        """predict(), then the tables' text on the device -> ([K, L] RSA, table_text of it): what write_rsa_files(text=...) takes.
+        letters: the characters the tables print (uint8 [L]); by default those of seq, which then has to be a str."""
+        values = self.predict(emb, seq)
+        return values, table_text(values, _letters_for(seq, letters, values.device))
+
+    def predict_text_many(self, embs: Sequence[torch.Tensor], seqs: Sequence, letters: Optional[Sequence] = None):
+        """predict_text() of every alignment: predict_many, then one formatter call per group -> a list of (values, text record),
+        each the lone call's bits and bytes."""
+        seqs = list(seqs)
+        letters = [None] * len(seqs) if letters is None else list(letters)
+        if len(letters) != len(seqs):
+            raise ValueError(f"RSAEnsemble: {len(letters)} letter rows for {len(seqs)} sequences")
+        values = self.predict_many(embs, seqs)
+        return list(zip(values, table_text_many(values, [_letters_for(s, l, v.device) for s, l, v in zip(seqs, letters, values)])))
+
 
 # ---------------------------------------------------------------------- loading an upstream model directory
 class _Inert(nn.Module):
@@ -355,6 +373,35 @@ def load_ensemble(model_dir: Union[str, Path], device) -> RSAEnsemble:
     return ens.eval().to(device)
 
 
+# ---------------------------------------------------------------------- the tables' text on the device (rnamsm_rsa_text)
+def _letters_for(seq, letters, device) -> torch.Tensor:
+    if letters is None:
+        if not isinstance(seq, str):
+            raise ValueError("RSAEnsemble: letters are needed where the sequence is given as base codes")
+        letters = letter_codes(seq)
+    return torch.as_tensor(letters).reshape(-1).to(device=device, dtype=torch.uint8)
+
+
+def table_text(values: torch.Tensor, letters: torch.Tensor):
+    """The bodies of the K member tables and the ensemble table for the [K, L] RSA `values` on the HIP device; letters uint8 [L] on
+    the device -> (text uint8 [(K + 1) x 23 L], counts int32 [K + 3], ens float64 [2, L]): body f starts at f x 23 L and has
+    counts[f] bytes -- the lines np.savetxt writes in write_rsa_files, byte for byte; counts[K + 1] is the fallback word (1: a value
+    outside [0, 1] or a letter outside ACGUT -- the text is not to be used and write_rsa_files takes the host path), counts[K + 2]
+    the zero word (1: an ASA of exactly 0, where write_rsa_files raises); ens: the ensemble's (ASA, RSA) write_rsa_files returns."""
+    return ops.rsa_text(values, letters)
+
+
+def table_text_many(values: Sequence[torch.Tensor], letters: Sequence[torch.Tensor]):
+    """table_text() of every (values[b], letters[b]) in as few calls as the batch limit allows; each result is the lone call's."""
+    values, letters = list(values), list(letters)
+    if len(values) != len(letters):
+        raise ValueError(f"table_text_many: {len(values)} value tables for {len(letters)} letter rows")
+    out = []
+    for i in range(0, len(values), _lib.RSA_MAX_BATCH):
+        out += ops.rsa_text_packed(values[i:i + _lib.RSA_MAX_BATCH], letters[i:i + _lib.RSA_MAX_BATCH])
+    return out
+
+
 # ---------------------------------------------------------------------- host arithmetic and text files (predict.py)
 def _save_single(name: str, seq: str, rsa: Optional[np.ndarray], out_dir: str, des: str, rng, asa: Optional[np.ndarray] = None):
     """doSavePredict_single: ASA = RSA x the per-base scale in float64 (or RSA = ASA / scale when the ASA is given), one text file."""
@@ -376,17 +423,56 @@ def _save_single(name: str, seq: str, rsa: Optional[np.ndarray], out_dir: str, d
     return asa, rsa
 
 
+def _table_dirs(out: str, name: str, model_names: Sequence[str]):
+    """(directory, description) of every table, the members' and then the ensemble's."""
+    return ([(os.path.join(out, f"{name}_{i}"), f"{name} predict by {m}\n") for i, m in enumerate(model_names)]
+            + [(os.path.join(out, f"{name}_ensemble"), f"{name} predict by ensemble model\n")])
+
+
+def _tables_from_bodies(out: str, name: str, model_names: Sequence[str], bodies, rng) -> None:
+    """The K + 1 files from device-made bodies: the header np.savetxt writes (it ends the header with a newline of its own) and one
+    binary write each.  One draw per table all the same: the host path draws whether or not a letter is replaced, and a later
+    alignment's replacements must not move."""
+    for (out_dir, des), body in zip(_table_dirs(out, name, model_names), bodies):
+        os.makedirs(out_dir, exist_ok=True)
+        rng.randint(0, 3)
+        with open(os.path.join(out_dir, f"{name}.txt"), "wb") as f:
+            f.write(f"#{des}\n#index\t\tnt\t\tASA\t\tRSA\n\n".encode("ascii"))
+            f.write(body)
+
+
 def write_rsa_files(rsa_k: np.ndarray, seq: str, name: str, output_dir: Union[str, Path], model_names: Sequence[str],
-                    rng) -> Tuple[np.ndarray, np.ndarray]:
+                    rng, text=None) -> Tuple[np.ndarray, np.ndarray]:
     """`<output_dir>/RSA_result/<name>_<i>/<name>.txt` for every member and `.../<name>_ensemble/<name>.txt`, as the reference
     writes them (ensemble: mean of the members' ASA, RSA = ASA / scale); returns the ensemble's (ASA, RSA), float64 [L].
     rsa_k: [K, L] float32, the members' RSA.  rng: `random` (the module, seeded 2022 by the reference's program) or a
-    random.Random: K + 1 draws are taken from it.  An ASA of exactly 0 raises RnamsmError where the reference exits."""
+    random.Random: K + 1 draws are taken from it.  An ASA of exactly 0 raises RnamsmError where the reference exits.
+    text: the results of table_text(rsa_k, letters), on the host -- (text, counts, ens).  With its fallback word and its zero word
+    both 0 every file is a header and one binary write of its body; otherwise (and for a name np.savetxt would not write as ASCII)
+    the host arithmetic and np.savetxt run as before -- the same bytes, the same K + 1 draws and the same error either way."""
     rsa_k = np.asarray(rsa_k, dtype=np.float32)
     seq = str(seq)
     if rsa_k.ndim != 2 or rsa_k.shape[1] != len(seq) or rsa_k.shape[0] != len(model_names):
         raise ValueError(f"write_rsa_files: RSA of shape {rsa_k.shape} for {len(model_names)} models and a sequence of length {len(seq)}")
     out = os.path.join(str(output_dir), "RSA_result")
+    if text is not None and name.isascii() and all(str(m).isascii() for m in model_names):
+        body, counts, ens = text
+        K, L = rsa_k.shape
+        counts = np.asarray(counts).reshape(-1)
+        if counts.shape[0] != K + 3:
+            raise ValueError(f"write_rsa_files: {counts.shape[0]} counts for {K} models, not {K + 3}")
+        if not int(counts[K + 1]) and not int(counts[K + 2]):
+            body = memoryview(body if isinstance(body, (bytes, bytearray)) else np.ascontiguousarray(body, dtype=np.uint8))
+            bound = _lib.RSA_TEXT_LINE_MAX * L
+            ens = np.asarray(ens, dtype=np.float64)
+            if body.nbytes != (K + 1) * bound or ens.shape != (2, L):
+                raise ValueError(f"write_rsa_files: a text of {body.nbytes} bytes and an ensemble of shape {ens.shape} for {K} models "
+                                 f"and a sequence of length {L}")
+            if any(not 0 < int(n) <= bound for n in counts[:K + 1]):
+                raise ValueError(f"write_rsa_files: body counts {counts[:K + 1].tolist()} outside (0, {bound}]")
+            os.makedirs(out, exist_ok=True)
+            _tables_from_bodies(out, name, model_names, [body[f * bound:f * bound + int(counts[f])] for f in range(K + 1)], rng)
+            return ens[0], ens[1]
     os.makedirs(out, exist_ok=True)
     asas = []
     for i, model_name in enumerate(model_names):
@@ -397,41 +483,73 @@ def write_rsa_files(rsa_k: np.ndarray, seq: str, name: str, output_dir: Union[st
 
 
 # ---------------------------------------------------------------------- the head in the CLI (rnamsm.inference.extract_feat)
+class _Draws:
+    """The draws of one alignment's tables, taken ahead of time and handed out again in order (the `rng` of write_rsa_files)."""
+
+    def __init__(self, draws):
+        self._draws = list(draws)
+
+    def randint(self, a: int, b: int) -> int:
+        return self._draws.pop(0)
+
+
 class RSAResult(NamedTuple):
     """One alignment's results of the RSA ensemble, on the device (or, on the writer's side, their host copies)."""
     values: torch.Tensor                          # [K, L] the members' RSA
     tokens: torch.Tensor                          # [L] the query's tokens
+    text: Optional[tuple] = None                  # table_text(values, letters): (text, counts, ens); None where the formatter is off
 
 
 class RSAHead:
-    """data.rsa_model_dir in the CLI: the ensemble, the base-code look-up table indexed by token, the members' names and the
-    generator the texts draw from (the reference program's seed, 2022; drawn from by the writer, in delivery order)."""
-    n_tensors = 2
+    """data.rsa_model_dir in the CLI: the ensemble, the two look-up tables indexed by token (base codes; the letters the tables
+    print), the members' names, the generator the texts draw from (the reference program's seed, 2022; drawn from as the writer
+    jobs are made, in delivery order) and the switch text_on (data.rsa_text_device: the tables' bodies are formatted on the device)."""
 
-    def __init__(self, model: Optional[RSAEnsemble], alphabet, base_lut: Optional[torch.Tensor], rng, model_names: Optional[Sequence[str]] = None):
-        self.model, self.base_lut, self.rng = model, base_lut, rng
+    def __init__(self, model: Optional[RSAEnsemble], alphabet, base_lut: Optional[torch.Tensor], rng, model_names: Optional[Sequence[str]] = None,
+                 *, text_on: bool = False, device=None):
+        self.model, self.base_lut, self.rng, self.text_on = model, base_lut, rng, bool(text_on)
         self.model_names = list(model_names if model_names is not None else model.model_names)
         self.all_toks = list(alphabet.all_toks)
+        if device is None:
+            device = base_lut.device if base_lut is not None else "cpu"
+        # a token that is no single ASCII character is 0: no letter of the domain, so that alignment's tables come from the host
+        self.letters_lut = torch.tensor([ord(t) if len(t) == 1 and ord(t) < 128 else 0 for t in self.all_toks],
+                                        dtype=torch.uint8).to(device) if self.text_on else None
+        self.n_tensors = 2 + 3 * self.text_on
 
     def one(self, emb: torch.Tensor, atp: torch.Tensor, tokens: torch.Tensor) -> RSAResult:
-        """A lone alignment through the lone head; emb is read where it lies (atp is not read: the heads share one signature)."""
-        return RSAResult(self.model.predict(emb, self.base_lut[tokens]), tokens)
+        """A lone alignment through the lone head; emb is read where it lies (atp is not read: the heads share one signature).  The
+        formatter runs behind the head."""
+        values = self.model.predict(emb, self.base_lut[tokens])
+        return RSAResult(values, tokens, tuple(table_text(values, self.letters_lut[tokens])) if self.text_on else None)
 
     def many(self, embs: Sequence[torch.Tensor], atps: Sequence[torch.Tensor], tokens: Sequence[torch.Tensor]) -> List[RSAResult]:
-        """A group in one launch set (predict_many): every member's [K, L] is the lone head's bits."""
+        """A group in one launch set per stage (predict_many, table_text_many): every member's record holds the bits and bytes of
+        one()."""
         values = self.model.predict_many(embs, [self.base_lut[t] for t in tokens])
-        return [RSAResult(v, t) for v, t in zip(values, tokens)]
+        texts = table_text_many(values, [self.letters_lut[t] for t in tokens]) if self.text_on else [None] * len(values)
+        return [RSAResult(v, t, None if tx is None else tuple(tx)) for v, t, tx in zip(values, tokens, texts)]
 
     def flatten(self, rec: RSAResult) -> list:
-        return list(rec)
+        return [rec.values, rec.tokens, *(rec.text or ())]
 
     def unflatten(self, tensors: Sequence) -> RSAResult:
-        return RSAResult(*tensors)
+        """The record of flatten()'s list (n_tensors entries), by this head's switch."""
+        if len(tensors) != self.n_tensors:
+            raise ValueError(f"RSAHead: {len(tensors)} tensors for a record of {self.n_tensors}")
+        return RSAResult(tensors[0], tensors[1], tuple(tensors[2:5]) if self.text_on else None)
 
     def writer_job(self, rec: RSAResult, name: str, output_dir):
         """-> (write, tensors): write(*host copies of tensors) writes <output_dir>/RSA_result/<name>_*/<name>.txt through
-        write_rsa_files."""
-        def write(tokens, values) -> None:
-            write_rsa_files(values, "".join(self.all_toks[int(t)] for t in tokens), name, output_dir, self.model_names, self.rng)
+        write_rsa_files.  The tensors are the query's tokens and the values, then the text record where there is one: with its two
+        flag words clear the files are its bodies behind their headers, otherwise the host path formats the values as before.
+        The alignment's K + 1 draws are taken here, when the job is made -- in delivery order -- and handed to write(): the writer's
+        worker threads run the jobs of neighbouring alignments at the same time, and drawing there would let the order of the draws,
+        and with it the base a letter outside ACGUT is replaced by, depend on their timing."""
+        draws = _Draws(self.rng.randint(0, 3) for _ in range(len(self.model_names) + 1))
 
-        return write, (rec.tokens, rec.values)
+        def write(tokens, values, *text) -> None:
+            write_rsa_files(values, "".join(self.all_toks[int(t)] for t in tokens), name, output_dir, self.model_names, draws,
+                            text=text or None)
+
+        return write, (rec.tokens, rec.values, *(rec.text or ()))
