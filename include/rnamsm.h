@@ -339,6 +339,46 @@ size_t rnamsm_contact_head_workspace_bytes(int C, int nch);
 int rnamsm_contact_head(const float* row_attn, const float* weight, const float* bias, float* contacts,
                         void* workspace, size_t workspace_bytes, int C, int nch, void* stream);
 
+/* f1 on the stripped maps -- the same head on atp [nch, L, L], the maps as rnamsm_pack_outputs leaves them (<cls> gone):
+ * plane p at atp + p * plane_stride, rows of L floats (stride L*L for the packed [nch, L, L]; a larger stride reads the planes of
+ * a wider buffer in place, and nothing between the planes is read).  contacts [L, L].  workspace:
+ * rnamsm_contact_head_workspace_bytes(L + 1, nch) bytes -- rs [nch, L], then tot [nch].
+ * The kernels are those of rnamsm_contact_head with the layout as a parameter, and every sum keeps its order, so contacts are
+ * BIT-IDENTICAL to rnamsm_contact_head on the [nch, L+1, L+1] maps whose [1:, 1:] part holds the same values.
+ * Refused (RNAMSM_ERR_INVALID) before anything is enqueued: a null pointer, L outside [1, RNAMSM_CONTACT_MAX_L], nch <= 0,
+ * plane_stride < L * L, a short workspace. */
+#define RNAMSM_CONTACT_MAX_L 1023
+int rnamsm_contact_head_atp(const float* atp, int64_t plane_stride, int L, int nch, const float* weight, const float* bias,
+                            float* contacts, void* workspace, size_t workspace_bytes, void* stream);
+
+/* f1, several alignments per launch -- rnamsm_contact_head_atp over B maps of unlike L in ONE launch set: the row sums over
+ * sum_b ceil(L_b / 256) x nch blocks, the totals of the members of L > 256 (skipped where there is none), the regression over
+ * sum_b ceil(L_b / 32)^2 blocks -- each member's own blocks, never B x the longest member's -- and a block finds its member in a
+ * device descriptor table.
+ * The contract: a member's [L, L] contacts are BIT-IDENTICAL to rnamsm_contact_head on that alignment's [nch, L+1, L+1] maps
+ * alone, whatever its company, its place in the batch and its plane stride.  Each member's workspace slab holds its rs and tot
+ * and is its own: a non-finite member never reaches a neighbour.  Nothing is written behind the last slab.
+ * items: a HOST array of B entries, read during the call and free to go afterwards (the descriptors travel as kernel arguments
+ * on `stream`); the members' maps may be slices of one buffer, their contacts must not overlap.
+ * workspace: rnamsm_contact_head_packed_workspace_bytes(B, Ls, nch) bytes, 16-byte aligned, caller-owned (nothing is allocated
+ * inside): the descriptor table (64 bytes per member, rounded up to 256), then the members' slabs in order -- member b's is the
+ * lone call's workspace at the sum of the slabs before it.  The size is 0 for B outside [1, RNAMSM_CONTACT_MAX_BATCH], a null Ls,
+ * an L outside [1, RNAMSM_CONTACT_MAX_L] or nch <= 0.  Its contents on entry do not matter.
+ * Refused (RNAMSM_ERR_INVALID) before anything is enqueued, rnamsm_last_error naming the member where one is at fault: B out of
+ * range, nch <= 0, a null pointer (items, weight, bias, workspace, a member's atp or contacts), a member's L out of range, its
+ * plane_stride < L * L, a member pointer that is not 4-byte aligned, a workspace that is short or not 16-byte aligned.
+ * No atomics: the same inputs give the same bits on every run. */
+typedef struct {                 /* one alignment of the batch */
+    const float* atp;            /* device: plane p at atp + p * plane_stride, [L, L] row-major */
+    int64_t      plane_stride;   /* >= L * L */
+    int32_t      L;              /* 1 .. RNAMSM_CONTACT_MAX_L */
+    float*       contacts;       /* device [L, L] */
+} rnamsm_contact_item;
+#define RNAMSM_CONTACT_MAX_BATCH 1024
+size_t rnamsm_contact_head_packed_workspace_bytes(int B, const int* Ls, int nch);
+int rnamsm_contact_head_packed(const rnamsm_contact_item* items, int B, int nch, const float* weight, const float* bias,
+                               void* workspace, size_t workspace_bytes, void* stream);
+
 /* f4 -- RNA-MSM-SS secondary-structure head (_downstream_tasks/SS: predict.py, code/model.py ResNet._forward_impl with
  * num_blocks BasicBlocks; renet_b16 = 16) on the attention maps of one alignment, exact fp32:
  *   in[c, i, j] = onehot(seq[i])[c] (c < 4), onehot(seq[j])[c-4] (c < 8), atp[c-8, i, j] (c < 128)     i, j < L

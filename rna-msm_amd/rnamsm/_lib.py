@@ -42,6 +42,8 @@ W_RSA_MODEL = ("stem", "bn1.scale", "bn1.shift", "shortcut.1.scale", "shortcut.1
                "fc1.weight", "fc1.bias", "fc2.weight", "fc2.bias", "ln1.weight", "ln1.bias", "attn.qkv.weight", "attn.qkv.bias",
                "attn.proj.weight", "attn.proj.bias", "ln2.weight", "ln2.bias", "mlp.0.weight", "mlp.0.bias", "mlp.2.weight",
                "mlp.2.bias", "final.weight", "final.bias")
+CONTACT_MAX_L = 1023               # rnamsm_contact_head_atp / _packed: the stripped maps of C <= 1024 columns
+CONTACT_MAX_BATCH = 1024
 RSA_MAX_L = 1024
 RSA_MAX_MODELS = 8
 RSA_MAX_BATCH = 1024
@@ -76,6 +78,11 @@ class RsaItem(ctypes.Structure):
     """rnamsm_rsa_item: one alignment of an rnamsm_rsa_head_packed batch (device pointers as integers)."""
     _fields_ = [("emb", c_void_p), ("emb_row_stride", c_int64), ("base_codes", c_void_p), ("L", ctypes.c_int32),
                 ("probs", c_void_p), ("logits", c_void_p)]
+
+
+class ContactItem(ctypes.Structure):
+    """rnamsm_contact_item: one alignment of an rnamsm_contact_head_packed batch (device pointers as integers)."""
+    _fields_ = [("atp", c_void_p), ("plane_stride", c_int64), ("L", ctypes.c_int32), ("contacts", c_void_p)]
 
 
 class RsaTextItem(ctypes.Structure):
@@ -135,6 +142,9 @@ _SIGNATURES = {
     "rnamsm_pack_outputs": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
     "rnamsm_contact_head_workspace_bytes": (c_size_t, [c_int, c_int]),
     "rnamsm_contact_head": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_int, c_int, c_void_p]),
+    "rnamsm_contact_head_atp": (c_int, [c_void_p, c_int64, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "rnamsm_contact_head_packed_workspace_bytes": (c_size_t, [c_int, POINTER(c_int), c_int]),
+    "rnamsm_contact_head_packed": (c_int, [POINTER(ContactItem), c_int, c_int, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "rnamsm_ss_head_workspace_bytes": (c_size_t, [c_int]),
     "rnamsm_ss_head": (c_int, [c_void_p, c_int64, c_void_p, c_int, c_int, POINTER(c_void_p), c_void_p, c_void_p, c_void_p, c_size_t,
                                c_void_p]),

@@ -70,6 +70,10 @@ class DataConfig:                       # RNA_MSM_Inference.py:20-32
     # written as a header and one block each; false = the host arithmetic and np.savetxt on the writer thread, as before.  The same
     # bytes either way; an alignment with a letter outside ACGUT in its query takes the host path by itself.
     rsa_text_device: bool = True
+    # extra (not in the reference): the contact head (contact_head.regression.* of the checkpoint that is loaded anyway: symmetrize
+    # + APC + logistic regression on the row attentions, rnamsm.contacts) then runs on every alignment's atp where it lies on the
+    # device, and <id>_contacts.npy, (L, L) float32, is written next to <id>_emb.npy / <id>_atp.npy
+    contacts: bool = False
 
 
 @dataclass

@@ -1,0 +1,80 @@
+"""The contact head of the language model itself: base-pair probabilities from the row attentions by the reference's symmetrize +
+APC + logistic regression (ContactPredictionHead, `contact_head.regression.*` of the trunk's checkpoint).
+
+`predict_many` runs a list of stripped maps (atp [120, L, L], as forward_one and the packed drivers leave them) through as few
+launch sets as `plan_contact_chunks` allows (rnamsm_contact_head_packed), every result the bits of the lone call on the un-stripped
+maps.  `ContactHead` is the head as the CLI runs it (data.contacts): it makes one `ContactResult` per alignment from the atp where it
+lies on the device and turns it into the job that writes `<id>_contacts.npy`.
+"""
+from __future__ import annotations
+
+import os
+from typing import List, NamedTuple, Sequence
+
+import numpy as np
+import torch
+
+from . import _lib, ops
+from .ss import plan_chunks
+
+# pixels (sum of L^2) of one packed call: the SS head's budget.  The head's own workspace is 121 floats per position and its
+# outputs 4 MB at the budget, so the budget bounds nothing but the size of one output allocation (a condition, not a measurement).
+CONTACT_CHUNK_PIXELS = 1024 * 1024
+
+
+def plan_contact_chunks(Ls: Sequence[int], max_pixels: int = CONTACT_CHUNK_PIXELS,
+                        max_batch: int = _lib.CONTACT_MAX_BATCH) -> List[List[int]]:
+    """Indices of `Ls` split into consecutive calls of rnamsm_contact_head_packed, in list order: a chunk takes the next alignment
+    as long as its sum of L^2 stays within max_pixels and its length within max_batch (greedy); an alignment larger than the budget
+    by itself is a chunk of its own."""
+    return plan_chunks([int(L) * int(L) for L in Ls], max_pixels, max_batch)
+
+
+def predict_many(atps: Sequence[torch.Tensor], weight: torch.Tensor, bias: torch.Tensor) -> List[torch.Tensor]:
+    """contacts [L_b, L_b] of every atps[b] ([nch, L_b, L_b]), one packed call per chunk of plan_contact_chunks: each the bits of
+    ops.contact_head_atp on that member alone."""
+    atps = list(atps)
+    out: List[torch.Tensor] = []
+    for chunk in plan_contact_chunks([a.shape[-1] for a in atps]):
+        out += ops.contact_head_packed([atps[i] for i in chunk], weight, bias)
+    return out
+
+
+class ContactResult(NamedTuple):
+    """One alignment's result of the contact head, on the device (or, on the writer's side, its host copy)."""
+    contacts: torch.Tensor                        # [L, L]
+
+
+class ContactHead:
+    """data.contacts in the CLI: the regression's weight [nch] and bias [1] on the device (the trunk's own parameters)."""
+
+    n_tensors = 1
+
+    def __init__(self, weight: torch.Tensor, bias: torch.Tensor):
+        self.weight, self.bias = weight.detach().contiguous().view(-1), bias.detach().contiguous().view(-1)
+
+    def one(self, emb: torch.Tensor, atp: torch.Tensor, tokens: torch.Tensor) -> ContactResult:
+        """A lone alignment through the lone call; atp is read where it lies (emb and tokens are not read: the heads share one
+        signature)."""
+        return ContactResult(ops.contact_head_atp(atp, self.weight, self.bias))
+
+    def many(self, embs: Sequence[torch.Tensor], atps: Sequence[torch.Tensor], tokens: Sequence[torch.Tensor]) -> List[ContactResult]:
+        """A group in one launch set per chunk (predict_many): every member's record holds the bits of one()."""
+        return [ContactResult(c) for c in predict_many(atps, self.weight, self.bias)]
+
+    def flatten(self, rec: ContactResult) -> list:
+        return [rec.contacts]
+
+    def unflatten(self, tensors: Sequence) -> ContactResult:
+        if len(tensors) != self.n_tensors:
+            raise ValueError(f"ContactHead: {len(tensors)} tensors for a record of {self.n_tensors}")
+        return ContactResult(tensors[0])
+
+    def writer_job(self, rec: ContactResult, name: str, output_dir):
+        """-> (write, tensors): write(host copy of the contacts) is one np.save of <output_dir>/<name>_contacts.npy."""
+        path = os.path.join(output_dir, f"{name}_contacts.npy")
+
+        def write(contacts) -> None:
+            np.save(path, contacts)
+
+        return write, (rec.contacts,)

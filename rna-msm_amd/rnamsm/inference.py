@@ -19,7 +19,7 @@ from typing import Dict, List, Optional
 import numpy as np
 import torch
 
-from . import ops, rsa, sharding, ss
+from . import contacts, ops, rsa, sharding, ss
 from .alphabet import RNAAlphabet
 from .config import Config, check_ss_gemm_dtype
 from .model import MSATransformer
@@ -339,8 +339,9 @@ def extract_feat(cfg: Config, model: Optional[MSATransformer] = None, gather_to_
 
     save_dir = root / cfg.data.MSA_path
     save_dir.mkdir(parents=True, exist_ok=True)
-    # The heads that are on, SS before RSA: each reads an alignment's device-resident outputs and makes one record of it (rnamsm.ss.SSHead:
-    # data.ss_model_path, the maps; rnamsm.rsa.RSAHead: data.rsa_model_dir, the embedding).
+    # The heads that are on, SS before RSA before the contacts: each reads an alignment's device-resident outputs and makes one record
+    # of it (rnamsm.ss.SSHead: data.ss_model_path, the maps; rnamsm.rsa.RSAHead: data.rsa_model_dir, the embedding;
+    # rnamsm.contacts.ContactHead: data.contacts, the maps).
     # data.ss_prob_text (default on): the `.prob` text is formatted on the device behind the head (rnamsm.ss.prob_text) and the
     # writer thread's share of it is one binary write, where np.savetxt formats L^2 numbers under the GIL; the files are the same
     # bytes.  data.ss_pairs_device (default on): the pairs are decoded and the bodies of `.ct` / `.bpseq` written on the device too
@@ -364,6 +365,9 @@ def extract_feat(cfg: Config, model: Optional[MSATransformer] = None, gather_to_
     if rsa_dir:         # (the reference program's seed; every alignment's draws are taken as its writer job is made, in delivery order)
         heads.append(rsa.RSAHead(rsa.load_ensemble(rsa_dir, device), alphabet, base_lut, random.Random(2022),
                                  text_on=bool(getattr(cfg.data, "rsa_text_device", True)) and not gathering, device=device))
+    if bool(getattr(cfg.data, "contacts", False)):      # the trunk's own contact_head.regression.*: no further file to load
+        reg = model.contact_head.regression
+        heads.append(contacts.ContactHead(reg.weight, reg.bias))
     rng = np.random.RandomState(42)
     mine = sharding.shard_indices(len(ids), rank, world)
     written: List[str] = []

@@ -18,7 +18,7 @@ from typing import Dict, Iterable, List, Optional
 import torch
 import torch.nn as nn
 
-from . import _lib, ops
+from . import _lib, contacts, ops
 from .alphabet import RNAAlphabet
 from .modules import AxialTransformerLayer
 
@@ -761,6 +761,9 @@ class MSATransformer(nn.Module):
         if return_contacts:                                                         # model.py:412-414
             reg = self.contact_head.regression
             maps = torch.cat(atts, 0)
-            result["contacts"] = torch.stack(
-                [ops.contact_head(maps[b], reg.weight.detach(), reg.bias.detach()) for b in range(B)], 0)
+            if B == 1:
+                result["contacts"] = ops.contact_head(maps[0], reg.weight.detach(), reg.bias.detach()).unsqueeze(0)
+            else:       # one launch set for the batch (rnamsm_contact_head_packed: every member the lone call's bits)
+                atps = maps[..., 1:, 1:].reshape(B, -1, C - 1, C - 1)
+                result["contacts"] = torch.stack(contacts.predict_many(list(atps), reg.weight.detach(), reg.bias.detach()), 0)
         return result

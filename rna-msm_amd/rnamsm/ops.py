@@ -556,6 +556,70 @@ def contact_head(row_attn: torch.Tensor, weight: torch.Tensor, bias: torch.Tenso
     return out
 
 
+def _contact_operand(fn: str, atp: torch.Tensor, name: str):
+    """The operand rules of one alignment, for contact_head_atp and for every member of contact_head_packed: -> (atp, L) as the
+    library reads them (maps whose rows or planes do not lie as [L, L] planes at least L*L apart are copied)."""
+    _dev(atp, name)
+    if atp.dim() != 3 or atp.shape[0] < 1 or atp.shape[1] != atp.shape[2]:
+        raise ValueError(f"{fn}: {name} must be [nch, L, L], got {tuple(atp.shape)}")
+    L = atp.shape[-1]
+    if atp.stride(2) != 1 or atp.stride(1) != L or atp.stride(0) < L * L:
+        atp = atp.contiguous()
+    return atp, L
+
+
+def _contact_regression(weight: torch.Tensor, bias: torch.Tensor, nch: int, fn: str):
+    weight, bias = weight.contiguous().view(-1), bias.contiguous().view(-1)
+    _dev(weight, "weight")
+    _dev(bias, "bias")
+    if weight.numel() != nch or bias.numel() != 1:
+        raise ValueError(f"{fn}: regression of {weight.numel()} weights and {bias.numel()} biases for maps of {nch} channels")
+    return weight, bias
+
+
+@_on_operand_device
+def contact_head_atp(atp: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor) -> torch.Tensor:
+    """The contact head on the stripped maps (rnamsm_contact_head_atp): atp [nch, L, L] fp32 as forward_one / the packed drivers
+    leave it (planes may lie further apart than L*L: a slice of a wider buffer is read in place) -> contacts [L, L], the bits of
+    contact_head on the [nch, L+1, L+1] maps they were stripped from."""
+    members, _ = _members("contact_head_atp", _contact_operand, 1, _lib.CONTACT_MAX_L, (None, None, "alignments"), {"atp": [atp]},
+                          lone=True)
+    atp, L = members[0]
+    nch = atp.shape[0]
+    weight, bias = _contact_regression(weight, bias, nch, "contact_head_atp")
+    lib = _lib.load()
+    ws = torch.empty(lib.rnamsm_contact_head_workspace_bytes(L + 1, nch), dtype=torch.uint8, device=atp.device)
+    out = torch.empty(L, L, device=atp.device, dtype=torch.float32)
+    _lib.check(lib.rnamsm_contact_head_atp(atp.data_ptr(), atp.stride(0), L, nch, weight.data_ptr(), bias.data_ptr(), out.data_ptr(),
+                                           ws.data_ptr(), ws.numel(), _stream()))
+    return out
+
+
+@_on_operand_device
+def contact_head_packed(atps: Sequence[torch.Tensor], weight: torch.Tensor, bias: torch.Tensor) -> List[torch.Tensor]:
+    """The contact head over several alignments in one launch set (rnamsm_contact_head_packed): atps[b] [nch, L_b, L_b] fp32, the
+    operand rules of contact_head_atp per member (slices of one wider buffer are read in place) -> a list of [L_b, L_b] tensors,
+    each bit-identical to contact_head_atp on that member alone.  One workspace and one output allocation per call: the returned
+    tensors are views of one buffer."""
+    members, device = _members("contact_head_packed", _contact_operand, _lib.CONTACT_MAX_BATCH, _lib.CONTACT_MAX_L,
+                               (None, None, "alignments"), {"atp": atps})
+    if not members:
+        return []
+    B, Ls, nch = len(members), [L for _, L in members], members[0][0].shape[0]
+    for b, (atp, _) in enumerate(members):
+        if atp.shape[0] != nch:
+            raise ValueError(f"contact_head_packed: atp[{b}] has {atp.shape[0]} channels, atp[0] {nch}")
+    weight, bias = _contact_regression(weight, bias, nch, "contact_head_packed")
+    lib = _lib.load()
+    ws = torch.empty(lib.rnamsm_contact_head_packed_workspace_bytes(B, (_lib.c_int * B)(*Ls), nch), dtype=torch.uint8, device=device)
+    outs = [o.view(L, L) for o, L in zip(_carved([L * L for L in Ls], device, torch.float32), Ls)]
+    items = (_lib.ContactItem * B)()
+    for b, ((atp, L), o) in enumerate(zip(members, outs)):
+        items[b] = _lib.ContactItem(atp.data_ptr(), atp.stride(0), L, o.data_ptr())
+    _lib.check(lib.rnamsm_contact_head_packed(items, B, nch, weight.data_ptr(), bias.data_ptr(), ws.data_ptr(), ws.numel(), _stream()))
+    return outs
+
+
 def _want(fn: str, want: str) -> None:
     if want not in ("probs", "logits"):
         raise ValueError(f"{fn}: want must be 'probs' or 'logits', got {want!r}")
