@@ -379,6 +379,57 @@ size_t rnamsm_contact_head_packed_workspace_bytes(int B, const int* Ls, int nch)
 int rnamsm_contact_head_packed(const rnamsm_contact_item* items, int B, int nch, const float* weight, const float* bias,
                                void* workspace, size_t workspace_bytes, void* stream);
 
+/* f4 -- LM head on CHOSEN ROWS of a feature buffer (RobertaLMHead.forward, modules.py:303-319, plus the log-softmax and the
+ * wild-type subtraction of utils/likelihood.py), exact fp32.  For every selected row i of a member:
+ *   h      = gelu_erf(x_i . Wd^T + bd)                 Wd [D, D]
+ *   y      = LayerNorm(h; gamma, beta, eps)
+ *   logits = y . Wp^T + bp                             Wp [V, D]: the tied embed_tokens rows as they are (no padding)
+ *   logp   = logits - logsumexp(logits)                max-subtracted
+ *   scores = logp - logp[wt_i]                         nll = -logp[wt_i]
+ * x_i = x + (rows ? rows[i] : i) * ld, D floats: the gather happens in the kernel, a row that is not selected is never read and
+ * nothing is staged through a contiguous copy.  rows[i] is device data and is trusted: it must name a row of the caller's buffer.
+ * wt_i outside [0, V) is device data too and cannot be refused: that row's scores and nll are NaN, its logits and logp are what
+ * they would have been, and no index is formed from it.
+ * Two launches: the dense step on v_mfma_f32_32x32x2_f32 over (32-row tile) x (64-column tile) blocks with k in a fixed order (chains of 32 k,
+ * their sums added in ascending order), h into the workspace; then one wave per row for the LayerNorm, the V dot products and the log-softmax.  No atomics.  A
+ * row's result depends on that row's D values and the weights and on nothing else -- not on n, its position, its neighbours or
+ * the company in a packed call: a member of rnamsm_lm_head_packed has the BITS of rnamsm_lm_head on it alone, and a row selected
+ * twice gives the same bits twice.
+ * weights: HOST table of RNAMSM_LM_NUM_WEIGHTS device pointers, 16-byte aligned: dense W [D, D], dense b [D], LayerNorm gamma [D],
+ * beta [D], projection W [V, D], projection b [V].
+ * Each of the four outputs may be NULL; what is NULL is neither computed nor written.
+ * workspace: rnamsm_lm_head_workspace_bytes(n, D) = n * D floats (h); packed: two descriptor tables of B entries (each padded to
+ * 256 bytes), then the members' slabs back to back -- rnamsm_lm_head_packed_workspace_bytes(B, ns, D).  16-byte aligned,
+ * caller-owned, contents on entry do not matter; only a member's own n * D floats are written.  A size is 0 for arguments outside
+ * the limits.
+ * Refused (RNAMSM_ERR_INVALID) before anything is enqueued, rnamsm_last_error naming the member where one is at fault: a null
+ * pointer (item(s), weights, a weight, workspace, a member's x), D not a multiple of 64 in [64, RNAMSM_LM_MAX_D], V outside
+ * [1, RNAMSM_LM_MAX_V], B outside [1, RNAMSM_LM_MAX_BATCH], n < 1, the sum of n above RNAMSM_LM_MAX_ROWS, ld < D, x not 16-byte
+ * aligned or ld not a multiple of 4 (rows are read as 16-byte vectors), rows / wt / an output not 4-byte aligned, scores or nll
+ * asked without wt, every output NULL, a short or misaligned workspace. */
+#define RNAMSM_LM_MAX_D 1024
+#define RNAMSM_LM_MAX_V 64
+#define RNAMSM_LM_MAX_BATCH 1024
+#define RNAMSM_LM_MAX_ROWS 16777216
+#define RNAMSM_LM_NUM_WEIGHTS 6
+typedef struct {                 /* one member: n chosen rows of one feature buffer */
+    const float*   x;            /* device: row r at x + r * ld, D floats */
+    int64_t        ld;           /* row pitch in floats, >= D, a multiple of 4 */
+    const int32_t* rows;         /* device int32 [n], or NULL: rows 0 .. n-1 */
+    const int32_t* wt;           /* device int32 [n] (the wild-type token of every row), or NULL */
+    int32_t        n;            /* >= 1 */
+    float*         logits;       /* device [n, V], or NULL */
+    float*         logp;         /* device [n, V], or NULL */
+    float*         scores;       /* device [n, V], or NULL; needs wt */
+    float*         nll;          /* device [n], or NULL; needs wt */
+} rnamsm_lm_item;
+size_t rnamsm_lm_head_workspace_bytes(int n, int D);
+int rnamsm_lm_head(const rnamsm_lm_item* item, int D, int V, const float* const* weights, float eps, void* workspace,
+                   size_t workspace_bytes, void* stream);
+size_t rnamsm_lm_head_packed_workspace_bytes(int B, const int* ns, int D);
+int rnamsm_lm_head_packed(const rnamsm_lm_item* items, int B, int D, int V, const float* const* weights, float eps, void* workspace,
+                          size_t workspace_bytes, void* stream);
+
 /* f4 -- RNA-MSM-SS secondary-structure head (_downstream_tasks/SS: predict.py, code/model.py ResNet._forward_impl with
  * num_blocks BasicBlocks; renet_b16 = 16) on the attention maps of one alignment, exact fp32:
  *   in[c, i, j] = onehot(seq[i])[c] (c < 4), onehot(seq[j])[c-4] (c < 8), atp[c-8, i, j] (c < 128)     i, j < L

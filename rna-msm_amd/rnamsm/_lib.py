@@ -49,6 +49,10 @@ RSA_MAX_MODELS = 8
 RSA_MAX_BATCH = 1024
 RSA_CIN_PAD = 800
 RSA_TEXT_LINE_MAX = 23             # rnamsm_rsa_text_bytes: bytes of the longest line of an RSA_result table at L = 1024
+# rnamsm_lm_head / _packed (include/rnamsm.h): D a multiple of 64 up to LM_MAX_D, V up to LM_MAX_V, the rows of a call up to LM_MAX_ROWS
+LM_MAX_D, LM_MAX_V, LM_MAX_BATCH, LM_MAX_ROWS = 1024, 64, 1024, 1 << 24
+W_LM = ("dense.weight", "dense.bias", "layer_norm.weight", "layer_norm.bias", "weight", "bias")     # the weight table's order
+LM_OUTPUTS = ("logits", "logp", "scores", "nll")
 
 
 class ModelDims(ctypes.Structure):
@@ -83,6 +87,12 @@ class RsaItem(ctypes.Structure):
 class ContactItem(ctypes.Structure):
     """rnamsm_contact_item: one alignment of an rnamsm_contact_head_packed batch (device pointers as integers)."""
     _fields_ = [("atp", c_void_p), ("plane_stride", c_int64), ("L", ctypes.c_int32), ("contacts", c_void_p)]
+
+
+class LmItem(ctypes.Structure):
+    """rnamsm_lm_item: one member of an rnamsm_lm_head / rnamsm_lm_head_packed call (device pointers as integers)."""
+    _fields_ = [("x", c_void_p), ("ld", c_int64), ("rows", c_void_p), ("wt", c_void_p), ("n", ctypes.c_int32),
+                ("logits", c_void_p), ("logp", c_void_p), ("scores", c_void_p), ("nll", c_void_p)]
 
 
 class RsaTextItem(ctypes.Structure):
@@ -145,6 +155,10 @@ _SIGNATURES = {
     "rnamsm_contact_head_atp": (c_int, [c_void_p, c_int64, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "rnamsm_contact_head_packed_workspace_bytes": (c_size_t, [c_int, POINTER(c_int), c_int]),
     "rnamsm_contact_head_packed": (c_int, [POINTER(ContactItem), c_int, c_int, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "rnamsm_lm_head_workspace_bytes": (c_size_t, [c_int, c_int]),
+    "rnamsm_lm_head": (c_int, [POINTER(LmItem), c_int, c_int, POINTER(c_void_p), c_float, c_void_p, c_size_t, c_void_p]),
+    "rnamsm_lm_head_packed_workspace_bytes": (c_size_t, [c_int, POINTER(c_int), c_int]),
+    "rnamsm_lm_head_packed": (c_int, [POINTER(LmItem), c_int, c_int, c_int, POINTER(c_void_p), c_float, c_void_p, c_size_t, c_void_p]),
     "rnamsm_ss_head_workspace_bytes": (c_size_t, [c_int]),
     "rnamsm_ss_head": (c_int, [c_void_p, c_int64, c_void_p, c_int, c_int, POINTER(c_void_p), c_void_p, c_void_p, c_void_p, c_size_t,
                                c_void_p]),

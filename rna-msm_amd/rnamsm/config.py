@@ -13,10 +13,18 @@ from typing import List, Tuple
 
 from ._lib import SS_GEMM_DTYPES        # data.ss_gemm_dtype
 
+LM_SCORES_MODES = ("", "wt", "masked")   # data.lm_scores
+
 
 def check_ss_gemm_dtype(value: str) -> str:
     if value not in SS_GEMM_DTYPES:
         raise ValueError(f"data.ss_gemm_dtype={value!r} is not one of {', '.join(SS_GEMM_DTYPES)}")
+    return value
+
+
+def check_lm_scores(value: str) -> str:
+    if value not in LM_SCORES_MODES:
+        raise ValueError(f"data.lm_scores={value!r} is not one of {', '.join(repr(m) for m in LM_SCORES_MODES)}")
     return value
 
 
@@ -74,6 +82,12 @@ class DataConfig:                       # RNA_MSM_Inference.py:20-32
     # + APC + logistic regression on the row attentions, rnamsm.contacts) then runs on every alignment's atp where it lies on the
     # device, and <id>_contacts.npy, (L, L) float32, is written next to <id>_emb.npy / <id>_atp.npy
     contacts: bool = False
+    # extra (not in the reference's CLI; its utils/likelihood.py): "" = off; "wt" = the LM head (lm_head.* of the checkpoint that is
+    # loaded anyway, rnamsm.lm) on every alignment's emb where it lies, unmasked marginals, no further forward; "masked" = the masked
+    # pseudo-likelihood scan (rnamsm.likelihood.scan): one further forward per query position.  <id>_lm_scores.npy, (L, V) float32,
+    # log p(token) - log p(wild type) per query position, and <id>_lm_nll.npy, (L,) float32, are written next to <id>_emb.npy;
+    # log-probabilities are scores - nll[:, None], the pseudo-perplexity exp(mean(nll))
+    lm_scores: str = ""
 
 
 @dataclass
@@ -144,4 +158,5 @@ def parse_overrides(argv: List[str], cfg: Config = None) -> Config:
             raise KeyError(f"unknown key {key!r} in group {group!r}")
         setattr(node, key, _coerce(value, getattr(node, key)))
     check_ss_gemm_dtype(cfg.data.ss_gemm_dtype)
+    check_lm_scores(cfg.data.lm_scores)
     return cfg

@@ -19,7 +19,7 @@ from typing import Dict, List, Optional
 import numpy as np
 import torch
 
-from . import contacts, ops, rsa, sharding, ss
+from . import contacts, lm, ops, rsa, sharding, ss
 from .alphabet import RNAAlphabet
 from .config import Config, check_ss_gemm_dtype
 from .model import MSATransformer
@@ -339,9 +339,9 @@ def extract_feat(cfg: Config, model: Optional[MSATransformer] = None, gather_to_
 
     save_dir = root / cfg.data.MSA_path
     save_dir.mkdir(parents=True, exist_ok=True)
-    # The heads that are on, SS before RSA before the contacts: each reads an alignment's device-resident outputs and makes one record
+    # The heads that are on, SS before RSA before the contacts before the LM scores: each reads an alignment's device-resident outputs and makes one record
     # of it (rnamsm.ss.SSHead: data.ss_model_path, the maps; rnamsm.rsa.RSAHead: data.rsa_model_dir, the embedding;
-    # rnamsm.contacts.ContactHead: data.contacts, the maps).
+    # rnamsm.contacts.ContactHead: data.contacts, the maps; rnamsm.lm.LMHead: data.lm_scores, the embedding and the tokens).
     # data.ss_prob_text (default on): the `.prob` text is formatted on the device behind the head (rnamsm.ss.prob_text) and the
     # writer thread's share of it is one binary write, where np.savetxt formats L^2 numbers under the GIL; the files are the same
     # bytes.  data.ss_pairs_device (default on): the pairs are decoded and the bodies of `.ct` / `.bpseq` written on the device too
@@ -368,6 +368,9 @@ def extract_feat(cfg: Config, model: Optional[MSATransformer] = None, gather_to_
     if bool(getattr(cfg.data, "contacts", False)):      # the trunk's own contact_head.regression.*: no further file to load
         reg = model.contact_head.regression
         heads.append(contacts.ContactHead(reg.weight, reg.bias))
+    lm_mode = lm.check_lm_scores(getattr(cfg.data, "lm_scores", ""))
+    if lm_mode:         # the trunk's own lm_head.*: "wt" reads every alignment's emb where it lies, "masked" runs L further forwards
+        heads.append(lm.LMHead(model, lm_mode))
     rng = np.random.RandomState(42)
     mine = sharding.shard_indices(len(ids), rank, world)
     written: List[str] = []
@@ -429,12 +432,17 @@ def extract_feat(cfg: Config, model: Optional[MSATransformer] = None, gather_to_
     try:
         with torch.no_grad():
             pending = reader.submit(read, mine[0]) if reader and len(mine) else None
+            def head_tokens(h, toks: torch.Tensor) -> torch.Tensor:
+                """What a head is handed of an alignment's tokens [R, C]: the query behind <cls>; the whole matrix where the head asks
+                for it (rnamsm.lm.LMHead: the masked scan runs further forwards on it)."""
+                return toks if getattr(h, "whole_tokens", False) else toks[0, 1:]
+
             def deliver(idx: int, emb: torch.Tensor, atp: torch.Tensor, after: Optional[torch.cuda.Event] = None,
                         toks: Optional[torch.Tensor] = None, records: Optional[list] = None) -> None:
                 """records: this alignment's record of every head, where its group's batched heads (deliver_group) have made them;
                 absent, the lone heads run here, on emb and atp where they lie (a packed group's slices included)."""
                 if records is None:
-                    records = [h.one(emb, atp, toks[0, 1:]) for h in heads]
+                    records = [h.one(emb, atp, head_tokens(h, toks)) for h in heads]
                     if heads and after is not None:             # the copies wait for the heads too
                         after = torch.cuda.Event()
                         after.record(torch.cuda.current_stream())
@@ -447,7 +455,7 @@ def extract_feat(cfg: Config, model: Optional[MSATransformer] = None, gather_to_
                 """Every head once over the whole group (one launch set per stage; each member's record is the lone head's bits), then
                 the members one by one."""
                 embs, atps = [o["emb"].contiguous() for o in outs], [o["atp"].contiguous() for o in outs]
-                per_head = [h.many(embs, atps, [t[0, 1:] for _, t in members_]) for h in heads]
+                per_head = [h.many(embs, atps, [head_tokens(h, t) for _, t in members_]) for h in heads]
                 if heads and ev is not None:                    # the copies wait for the batched heads too
                     ev = torch.cuda.Event()
                     ev.record(torch.cuda.current_stream())

@@ -8,7 +8,7 @@ from __future__ import annotations
 
 import functools
 import math
-from typing import List, Optional, Sequence, Tuple
+from typing import List, NamedTuple, Optional, Sequence, Tuple
 
 import torch
 
@@ -943,6 +943,137 @@ def _rsa_text_run(_fn: str, rsa, letters):
         return outs
     items = (_lib.RsaTextItem * B)(*(_lib.RsaTextItem(*a) for a in args))
     _lib.check(lib.rnamsm_rsa_text_packed(items, B, K, _stream()))
+    return outs
+
+
+class LMWeights(NamedTuple):
+    """The LM head's weights as rnamsm_lm_head reads them: the six tensors in _lib.W_LM's order (kept alive here), the pointer
+    table, eps and the shape."""
+    tensors: tuple
+    ptrs: object
+    eps: float
+    D: int
+    V: int
+
+
+def lm_weights(dense_w: torch.Tensor, dense_b: torch.Tensor, ln_g: torch.Tensor, ln_b: torch.Tensor, proj_w: torch.Tensor,
+               proj_b: torch.Tensor, eps: float = 1e-5) -> LMWeights:
+    """Check and pin the weights of the LM head: dense [D, D] + [D], LayerNorm gamma / beta [D], projection [V, D] + [V] (the tied
+    embedding rows as they are), fp32 on one HIP device, D a multiple of 64 up to LM_MAX_D, V up to LM_MAX_V."""
+    ts = tuple(t.detach().contiguous() for t in (dense_w, dense_b, ln_g, ln_b, proj_w, proj_b))
+    for t, name in zip(ts, _lib.W_LM):
+        _dev(t, f"lm_head.{name}")
+        if t.device != ts[0].device:
+            raise ValueError(f"lm_weights: lm_head.{name} lies on {t.device}, lm_head.{_lib.W_LM[0]} on {ts[0].device}")
+    D = ts[0].shape[0]
+    V = ts[4].shape[0] if ts[4].dim() == 2 else -1
+    want = ((D, D), (D,), (D,), (D,), (V, D), (V,))
+    for t, name, shape in zip(ts, _lib.W_LM, want):
+        if tuple(t.shape) != shape:
+            raise ValueError(f"lm_weights: lm_head.{name} is {tuple(t.shape)}, expected {shape}")
+    if D % 64 or not 64 <= D <= _lib.LM_MAX_D or not 1 <= V <= _lib.LM_MAX_V:
+        raise ValueError(f"lm_weights: D = {D} must be a multiple of 64 in [64, {_lib.LM_MAX_D}] and V = {V} lie in [1, {_lib.LM_MAX_V}]")
+    ptrs = (_lib.c_void_p * len(ts))(*(t.data_ptr() for t in ts))
+    return LMWeights(ts, ptrs, float(eps), D, V)
+
+
+def _lm_want(fn: str, want, has_wt: bool) -> tuple:
+    if want is None:
+        want = _lib.LM_OUTPUTS if has_wt else _lib.LM_OUTPUTS[:2]
+    want = (want,) if isinstance(want, str) else tuple(want)
+    if not want or any(w not in _lib.LM_OUTPUTS for w in want) or len(set(want)) != len(want):
+        raise ValueError(f"{fn}: want must be a non-empty selection of {_lib.LM_OUTPUTS}, got {want!r}")
+    if not has_wt and ("scores" in want or "nll" in want):
+        raise ValueError(f"{fn}: scores / nll need wt (the wild-type token of every row)")
+    return want
+
+
+def _lm_operands(D: int, fn: str, x: torch.Tensor, rows, name: str, rows_name: str):
+    """The operand rules of one member of lm_head_rows / lm_head_packed: -> (x, rows, ld, n) as the library reads them.  x [N, D]
+    fp32 is read in place when its rows are contiguous, at least D apart by a multiple of 4 floats and 16-byte aligned (a column
+    or row slice of a wider buffer), else copied; rows (None: every row in order) become device int32 and must name rows of x."""
+    _dev(x, name)
+    if x.dim() != 2 or x.shape[1] != D or x.shape[0] < 1:
+        raise ValueError(f"{fn}: {name} must be [N, {D}] with N >= 1, got {tuple(x.shape)}")
+    N = x.shape[0]
+    if x.stride(1) != 1 or (N > 1 and (x.stride(0) < D or x.stride(0) % 4)) or x.data_ptr() % 16:
+        x = x.contiguous()
+    ld = x.stride(0) if N > 1 else D
+    if rows is None:
+        return x, None, ld, N
+    rows = torch.as_tensor(rows)
+    if rows.dim() != 1 or rows.numel() < 1 or rows.dtype not in (torch.int32, torch.int64):
+        raise ValueError(f"{fn}: {rows_name} must be a non-empty 1-D int32 / int64 index, got {tuple(rows.shape)} {rows.dtype}")
+    lo, hi = int(rows.min()), int(rows.max())           # (a device index costs one read-back: the kernel trusts what it is given)
+    if lo < 0 or hi >= N:
+        raise IndexError(f"{fn}: {rows_name} reaches [{lo}, {hi}], {name} has rows [0, {N})")
+    return x, rows.to(device=x.device, dtype=torch.int32).contiguous(), ld, rows.numel()
+
+
+def _lm_wt(fn: str, wt, n: int, device, name: str):
+    if wt is None:
+        return None
+    wt = torch.as_tensor(wt)
+    if wt.dim() != 1 or wt.numel() != n or wt.dtype not in (torch.int32, torch.int64):
+        raise ValueError(f"{fn}: {name} must be a 1-D int32 / int64 tensor of {n} tokens, got {tuple(wt.shape)} {wt.dtype}")
+    return wt.to(device=device, dtype=torch.int32).contiguous()
+
+
+def _lm_item(x, ld, rows, wt, n, outs: dict) -> "_lib.LmItem":
+    return _lib.LmItem(x.data_ptr(), ld, None if rows is None else rows.data_ptr(), None if wt is None else wt.data_ptr(), n,
+                       *(outs[k].data_ptr() if k in outs else None for k in _lib.LM_OUTPUTS))
+
+
+@_on_operand_device
+def lm_head_rows(x: torch.Tensor, rows, wt, weights: LMWeights, want=None) -> dict:
+    """The LM head on chosen rows (rnamsm_lm_head): x [N, D] fp32 (a slice of a wider buffer is read in place), rows: the n rows to
+    run on (None: all N in order; repeats and any order allowed), wt: the wild-type token of each of the n rows (None: no scores /
+    nll), weights: lm_weights(...).  -> {name: tensor} for every name in `want` (default: all the inputs allow): logits, logp,
+    scores [n, V], nll [n].  What is not wanted is not computed; a wt outside [0, V) gives a NaN row of scores and nll."""
+    members, device = _members("lm_head_rows", functools.partial(_lm_operands, weights.D), 1, _lib.LM_MAX_ROWS,
+                               ("feature buffers", "row tables", "members"), {"x": [x], "rows": [rows]}, lone=True)
+    x, rows, ld, n = members[0]
+    wt = _lm_wt("lm_head_rows", wt, n, device, "wt")
+    want = _lm_want("lm_head_rows", want, wt is not None)
+    V = weights.V
+    outs = {k: torch.empty((n,) if k == "nll" else (n, V), device=device, dtype=torch.float32) for k in want}
+    lib = _lib.load()
+    ws = torch.empty(lib.rnamsm_lm_head_workspace_bytes(n, weights.D), dtype=torch.uint8, device=device)
+    item = _lm_item(x, ld, rows, wt, n, outs)
+    _lib.check(lib.rnamsm_lm_head(item, weights.D, V, weights.ptrs, weights.eps, ws.data_ptr(), ws.numel(), _stream()))
+    return outs
+
+
+@_on_operand_device
+def lm_head_packed(xs: Sequence[torch.Tensor], rows: Sequence, wts: Sequence, weights: LMWeights, want=None) -> List[dict]:
+    """The LM head over several members in one launch set (rnamsm_lm_head_packed): the operand rules of lm_head_rows per member
+    (rows[b] / wts[b] may be None; wts all or none) -> a list of {name: tensor}, each tensor bit-identical to lm_head_rows on that
+    member alone.  One workspace and one allocation per output kind: the returned tensors are views."""
+    xs = list(xs)
+    rows = [None] * len(xs) if rows is None else list(rows)
+    wts = [None] * len(xs) if wts is None else list(wts)
+    members, device = _members("lm_head_packed", functools.partial(_lm_operands, weights.D), _lib.LM_MAX_BATCH, _lib.LM_MAX_ROWS,
+                               ("feature buffers", "row tables", "members"), {"x": xs, "rows": rows})
+    if not members:
+        return []
+    B, ns, V = len(members), [m[-1] for m in members], weights.V
+    if len(wts) != B:
+        raise ValueError(f"lm_head_packed: {len(wts)} wild-type rows for {B} members")
+    if sum(ns) > _lib.LM_MAX_ROWS:
+        raise ValueError(f"lm_head_packed: {sum(ns)} rows exceed the limit of {_lib.LM_MAX_ROWS} per call")
+    has_wt = all(w is not None for w in wts)
+    if not has_wt and any(w is not None for w in wts):
+        raise ValueError("lm_head_packed: wts must be given for every member or for none")
+    wts = [_lm_wt("lm_head_packed", w, n, device, f"wt[{b}]") for b, (w, n) in enumerate(zip(wts, ns))]
+    want = _lm_want("lm_head_packed", want, has_wt)
+    carved = {k: _carved([n if k == "nll" else n * V for n in ns], device, torch.float32) for k in want}
+    outs = [{k: carved[k][b] if k == "nll" else carved[k][b].view(ns[b], V) for k in want} for b in range(B)]
+    lib = _lib.load()
+    ws = torch.empty(lib.rnamsm_lm_head_packed_workspace_bytes(B, (_lib.c_int * B)(*ns), weights.D), dtype=torch.uint8, device=device)
+    items = (_lib.LmItem * B)()
+    for b, ((x, r, ld, n), w) in enumerate(zip(members, wts)):
+        items[b] = _lm_item(x, ld, r, w, n, outs[b])
+    _lib.check(lib.rnamsm_lm_head_packed(items, B, weights.D, V, weights.ptrs, weights.eps, ws.data_ptr(), ws.numel(), _stream()))
     return outs
 
 
