@@ -9,6 +9,9 @@ Same `group.key=value` overrides and defaults as the reference (RNA_MSM_Inferenc
 `python -m torch.distributed.run --nproc-per-node N RNA_MSM_Inference.py ...`; ids are sharded over ranks.
 Extra, non-reference override: `data.sample_method=first|diversity-max|diversity-min` (the default `hhfilter`
 needs the external binary and is only accepted when the alignment already has <= max_seqs_per_msa rows).
+An alignment wider than `data.max_seqlen - 1` columns is randomly cropped, as in the reference; `data.long_msa=windows` runs it
+as overlapping windows instead and writes the full-length `<id>_emb.npy` (L, 768) / `<id>_atp.npy` (120, L, L), a pure function of
+the alignment and `data.window_stride` (0 = half a window); heads other than `data.lm_scores=wt` are skipped for such an alignment.
 """
 import os
 import sys

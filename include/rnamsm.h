@@ -430,6 +430,39 @@ size_t rnamsm_lm_head_packed_workspace_bytes(int B, const int* ns, int D);
 int rnamsm_lm_head_packed(const rnamsm_lm_item* items, int B, int D, int V, const float* const* weights, float eps, void* workspace,
                           size_t workspace_bytes, void* stream);
 
+/* Long alignments -- the outputs of overlapping windows blended into full-length emb / atp.  An alignment of
+ * L > W body columns (W = max_seqlen - 1) runs as n = ceil((L - W) / stride) + 1 forwards over windows of W columns: window k
+ * starts at s_k = k * stride, the last one at L - W; stride in [ceil(W / 2), W].  Blend weight of window k at its local column
+ * i in [0, W), ramp = W - stride: u = 1 where ramp == 0, else (float)min(left, right, ramp) / (float)ramp, left = ramp in the
+ * first window, else i + 1, right = ramp in the last window, else W - i (one IEEE fp32 division; never zero).
+ *   rows   out[p, d]    = (sum_k u_k(p) x_k[p - s_k, d]) / (sum_k u_k(p))
+ *   pairs  out[h, p, q] = (sum_k (u_k(p) u_k(q)) a_k[h, p - s_k, q - s_k]) / (sum_k u_k(p) u_k(q))
+ * over the windows that contain p (pairs: p and q), ascending, starting from the first term; all fp32, every product, sum and
+ * quotient rounded on its own (no fused multiply-add, no reciprocal).  A pair no window contains is +0.0.
+ * One call applies the windows k0 .. k0 + nb - 1, which lie win_stride floats apart: one window of a one-by-one run (nb = 1), or
+ * all windows of a batched forward.  The calls of an alignment come in ascending k0 on one stream and together apply every window
+ * once; between them `out` holds running sums.  After the last call every element of `out` is defined, whatever it held before
+ * the first, and a NaN / inf of a window has reached exactly the elements that window covers.
+ *   rnamsm_stitch_rows   x: window w of the call, local row i at x + w * win_stride + i * ld, D floats (ld >= D: rows inside a
+ *                        wider buffer are read in place); out [L, D].
+ *   rnamsm_stitch_pairs  a: element (h, i, j) of window w at a + w * win_stride + h * plane_stride + (i + off) * ld + (j + off)
+ *                        -- off = 0, ld = W for the stripped atp [H, W, W]; off = 1, ld = W + 1 for maps that still carry <cls>,
+ *                        as rnamsm_contact_head reads them; out [H, L, L].
+ * One launch per call on the caller's stream, no workspace, no allocation, no atomics: every element of `out` is written by at
+ * most one thread, and the same inputs give the same bits on every run.  rnamsm_stitch_num_windows: n, or 0 for an (L, W, stride)
+ * the stitcher refuses.
+ * Refused (RNAMSM_ERR_INVALID) before anything is enqueued: a null pointer, L <= W, W < 1, L above RNAMSM_STITCH_MAX_L, a stride
+ * outside [ceil(W / 2), W] (rnamsm_last_error names the bounds), k0 / nb outside the plan, D < 1, ld < D (pairs: ld < W + off,
+ * off < 0), H outside [1, RNAMSM_STITCH_MAX_H], a plane or window stride below the extent of what it steps over, a pointer that
+ * is not 4-byte aligned. */
+#define RNAMSM_STITCH_MAX_L (1 << 19)
+#define RNAMSM_STITCH_MAX_H (1 << 16)
+int rnamsm_stitch_num_windows(int L, int W, int stride);
+int rnamsm_stitch_rows(const float* x, int64_t win_stride, int64_t ld, int L, int W, int stride, int k0, int nb, int D, float* out,
+                       void* stream);
+int rnamsm_stitch_pairs(const float* a, int64_t win_stride, int64_t plane_stride, int64_t ld, int off, int L, int W, int stride,
+                        int k0, int nb, int H, float* out, void* stream);
+
 /* f4 -- RNA-MSM-SS secondary-structure head (_downstream_tasks/SS: predict.py, code/model.py ResNet._forward_impl with
  * num_blocks BasicBlocks; renet_b16 = 16) on the attention maps of one alignment, exact fp32:
  *   in[c, i, j] = onehot(seq[i])[c] (c < 4), onehot(seq[j])[c-4] (c < 8), atp[c-8, i, j] (c < 128)     i, j < L

@@ -53,6 +53,7 @@ RSA_TEXT_LINE_MAX = 23             # rnamsm_rsa_text_bytes: bytes of the longest
 LM_MAX_D, LM_MAX_V, LM_MAX_BATCH, LM_MAX_ROWS = 1024, 64, 1024, 1 << 24
 W_LM = ("dense.weight", "dense.bias", "layer_norm.weight", "layer_norm.bias", "weight", "bias")     # the weight table's order
 LM_OUTPUTS = ("logits", "logp", "scores", "nll")
+STITCH_MAX_L, STITCH_MAX_H = 1 << 19, 1 << 16      # rnamsm_stitch_rows / _pairs
 
 
 class ModelDims(ctypes.Structure):
@@ -159,6 +160,10 @@ _SIGNATURES = {
     "rnamsm_lm_head": (c_int, [POINTER(LmItem), c_int, c_int, POINTER(c_void_p), c_float, c_void_p, c_size_t, c_void_p]),
     "rnamsm_lm_head_packed_workspace_bytes": (c_size_t, [c_int, POINTER(c_int), c_int]),
     "rnamsm_lm_head_packed": (c_int, [POINTER(LmItem), c_int, c_int, c_int, POINTER(c_void_p), c_float, c_void_p, c_size_t, c_void_p]),
+    "rnamsm_stitch_num_windows": (c_int, [c_int, c_int, c_int]),
+    "rnamsm_stitch_rows": (c_int, [c_void_p, c_int64, c_int64, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "rnamsm_stitch_pairs": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p,
+                                    c_void_p]),
     "rnamsm_ss_head_workspace_bytes": (c_size_t, [c_int]),
     "rnamsm_ss_head": (c_int, [c_void_p, c_int64, c_void_p, c_int, c_int, POINTER(c_void_p), c_void_p, c_void_p, c_void_p, c_size_t,
                                c_void_p]),

@@ -14,6 +14,7 @@ from typing import List, Tuple
 from ._lib import SS_GEMM_DTYPES        # data.ss_gemm_dtype
 
 LM_SCORES_MODES = ("", "wt", "masked")   # data.lm_scores
+LONG_MSA_MODES = ("crop", "windows")     # data.long_msa
 
 
 def check_ss_gemm_dtype(value: str) -> str:
@@ -25,6 +26,12 @@ def check_ss_gemm_dtype(value: str) -> str:
 def check_lm_scores(value: str) -> str:
     if value not in LM_SCORES_MODES:
         raise ValueError(f"data.lm_scores={value!r} is not one of {', '.join(repr(m) for m in LM_SCORES_MODES)}")
+    return value
+
+
+def check_long_msa(value: str) -> str:
+    if value not in LONG_MSA_MODES:
+        raise ValueError(f"data.long_msa={value!r} is not one of {', '.join(repr(m) for m in LONG_MSA_MODES)}")
     return value
 
 
@@ -88,6 +95,14 @@ class DataConfig:                       # RNA_MSM_Inference.py:20-32
     # log p(token) - log p(wild type) per query position, and <id>_lm_nll.npy, (L,) float32, are written next to <id>_emb.npy;
     # log-probabilities are scores - nll[:, None], the pseudo-perplexity exp(mean(nll))
     lm_scores: str = ""
+    # extra (not in the reference): an alignment wider than max_seqlen - 1 columns.  "crop" (default) = the reference's random crop
+    # (RandomCropDataset, dataset.py:142-158: <cls> and one random window; the same draws, the same files).  "windows" = nothing is
+    # cropped or drawn: the alignment runs as overlapping windows of max_seqlen - 1 columns whose outputs are blended on the device
+    # (MSATransformer.forward_windows), and <id>_emb.npy / <id>_atp.npy hold the FULL (L, 768) / (120, L, L).  On such an alignment
+    # lm_scores=wt runs on the stitched emb; the SS, RSA and contact heads and lm_scores=masked are skipped with one printed line.
+    long_msa: str = "crop"
+    # with long_msa=windows: the distance between window starts, within [ceil(W / 2), W] for W = max_seqlen - 1; 0 = ceil(W / 2)
+    window_stride: int = 0
 
 
 @dataclass
@@ -159,4 +174,5 @@ def parse_overrides(argv: List[str], cfg: Config = None) -> Config:
         setattr(node, key, _coerce(value, getattr(node, key)))
     check_ss_gemm_dtype(cfg.data.ss_gemm_dtype)
     check_lm_scores(cfg.data.lm_scores)
+    check_long_msa(cfg.data.long_msa)
     return cfg

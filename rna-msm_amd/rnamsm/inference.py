@@ -21,7 +21,7 @@ import torch
 
 from . import contacts, lm, ops, rsa, sharding, ss
 from .alphabet import RNAAlphabet
-from .config import Config, check_ss_gemm_dtype
+from .config import Config, check_long_msa, check_ss_gemm_dtype
 from .model import MSATransformer
 from .msa import load_msa_tokens
 
@@ -308,6 +308,10 @@ def extract_feat(cfg: Config, model: Optional[MSATransformer] = None, gather_to_
     """async_io: read/tokenise the next alignment on a helper thread while the GPU runs the current one, and move the
     outputs to disk through `_AsyncNpyWriter`; False = the reference's strictly sequential loop (same files)."""
     ss_dtype = check_ss_gemm_dtype(getattr(cfg.data, "ss_gemm_dtype", "f32"))
+    # data.long_msa=windows: an alignment wider than the model's max_seqlen is not cropped (nothing is drawn for it) and runs as
+    # overlapping windows stitched on the device (MSATransformer.forward_windows): its files hold the full L
+    windowing = check_long_msa(getattr(cfg.data, "long_msa", "crop")) == "windows"
+    window_stride = int(getattr(cfg.data, "window_stride", 0))
     device = torch.device(cfg.data.device)
     if device.type != "cuda":
         raise RuntimeError("this build runs on the MI355X HIP path only (data.device=cuda); there is no CPU path")
@@ -391,14 +395,20 @@ def extract_feat(cfg: Config, model: Optional[MSATransformer] = None, gather_to_
         torch.cuda.set_device(device)
         tokens = load_msa_tokens(files[ids[idx]], alphabet, cfg.data.max_seqs_per_msa, cfg.data.sample_method, device=device,
                                  rng=rng)
-        return crop_tokens(tokens, cfg.data.max_seqlen, rng)
+        return tokens if windowing else crop_tokens(tokens, cfg.data.max_seqlen, rng)
 
     writer = _AsyncNpyWriter(device) if async_io and (not gathering or rank == 0) else None
     reader = ThreadPoolExecutor(1, thread_name_prefix="rnamsm-msa-reader") if async_io else None
 
+    def skipped_on(h, L: int) -> bool:
+        """data.long_msa=windows: which heads do not run on a stitched alignment of L body columns -- all but lm_scores=wt, whose
+        kernel has no length limit that matters (the others stop at L <= 1024, or would need per-window semantics)."""
+        return windowing and L > model.max_seqlen - 1 and not (isinstance(h, lm.LMHead) and h.mode == "wt")
+
     def emit(rna_id: str, emb: torch.Tensor, atp: torch.Tensor, after: Optional[torch.cuda.Event] = None, records=()) -> None:
-        """records: this alignment's record of every head that is on, in the order of `heads`; each becomes one writer job."""
-        extra = [h.writer_job(r, rna_id, save_dir) for h, r in zip(heads, records)]
+        """records: this alignment's record of every head that is on, in the order of `heads`; each becomes one writer job (but
+        for the heads skipped on a stitched alignment: their entry is a placeholder)."""
+        extra = [h.writer_job(r, rna_id, save_dir) for h, r in zip(heads, records) if not skipped_on(h, emb.shape[0])]
         if writer is not None:
             writer.submit([(save_dir / f"{rna_id}_atp.npy", atp), (save_dir / f"{rna_id}_emb.npy", emb)] + extra,
                           lambda r=rna_id: written.append(r), after=after)
@@ -442,12 +452,14 @@ def extract_feat(cfg: Config, model: Optional[MSATransformer] = None, gather_to_
                 """records: this alignment's record of every head, where its group's batched heads (deliver_group) have made them;
                 absent, the lone heads run here, on emb and atp where they lie (a packed group's slices included)."""
                 if records is None:
-                    records = [h.one(emb, atp, head_tokens(h, toks)) for h in heads]
+                    records = [None if skipped_on(h, emb.shape[0]) else h.one(emb, atp, head_tokens(h, toks)) for h in heads]
                     if heads and after is not None:             # the copies wait for the heads too
                         after = torch.cuda.Event()
                         after.record(torch.cuda.current_stream())
                 if gatherer is not None:
-                    gatherer.submit(idx, (emb, atp) + tuple(t for h, r in zip(heads, records) for t in h.flatten(r)))
+                    # (a skipped head's share of the item: n_tensors one-element placeholders, dropped again by emit on rank 0)
+                    gatherer.submit(idx, (emb, atp) + tuple(t for h, r in zip(heads, records) for t in (
+                        h.flatten(r) if r is not None else [emb.new_zeros(1) for _ in range(h.n_tensors)])))
                 else:
                     emit(ids[idx], emb, atp, after, records)
 
@@ -585,7 +597,8 @@ def extract_feat(cfg: Config, model: Optional[MSATransformer] = None, gather_to_
                     tokens = pending.result() if reader else read(idx)
                     if reader and n + 1 < len(mine):
                         pending = reader.submit(read, mine[n + 1])       # parsed while the GPU runs this MSA
-                    if (batching and tokens.size <= small_limit and 2 * tokens.shape[1] ** 2 <= FRAME_MAP_ELEMS
+                    wide = windowing and tokens.shape[1] > model.max_seqlen
+                    if (batching and not wide and tokens.size <= small_limit and 2 * tokens.shape[1] ** 2 <= FRAME_MAP_ELEMS
                             and not (tokens == alphabet.padding_idx).any()):
                         if pooled:
                             pool.append((idx, tokens))
@@ -599,6 +612,17 @@ def extract_feat(cfg: Config, model: Optional[MSATransformer] = None, gather_to_
                         group.append((idx, torch.from_numpy(tokens).to(device)))
                         continue
                     flush()
+                    if wide:
+                        # data.long_msa=windows: the lone route, never a group; behind whatever is in flight (its workspace is the model's)
+                        settle()
+                        t_dev = torch.from_numpy(tokens).to(device)
+                        out = model.forward_windows(t_dev, window_stride, what=rna_id)
+                        for h in heads:
+                            if skipped_on(h, tokens.shape[1] - 1):
+                                print(f"{rna_id}: L={tokens.shape[1] - 1} is stitched from windows (data.long_msa=windows); "
+                                      f"{type(h).__name__}{'(masked)' if isinstance(h, lm.LMHead) else ''} is skipped for it")
+                        deliver(idx, out["emb"], out["atp"], toks=t_dev)
+                        continue
                     has_pad = bool((tokens == alphabet.padding_idx).any())          # on the host: no device round trip before the launches
                     t_dev = torch.from_numpy(tokens).to(device)
                     if gatherer is not None:       # (the gather orders its transfers behind the compute stream: one by one there, as before)

@@ -621,6 +621,61 @@ class MSATransformer(nn.Module):
                 raise IndexError(f"{what}: token or position index out of range")
         return out
 
+    def forward_windows(self, tokens2d: torch.Tensor, stride: Optional[int] = None, batched: Optional[bool] = None,
+                        what: str = "MSA") -> Dict[str, torch.Tensor]:
+        """An alignment of ANY width: tokens int64 [R, C] on the HIP device -> {"emb" [C-1, D], "atp" [NL*H, C-1, C-1]}.
+        C <= max_seqlen: checked_forward_one(need_repr=False), the same call and the same bits.  Wider: the L = C - 1 body columns
+        run as the windows of rnamsm.windows.plan_windows(L, W = max_seqlen - 1, stride) -- window k is <cls> and the columns
+        s_k .. s_k + W of every row -- in the model's arithmetic mode, and their outputs are blended in fp32 on the device
+        (ops.stitch_rows / stitch_pairs).  stride: None / 0 = ceil(W / 2); else within [ceil(W / 2), W].
+        The windows share one checked_forward_batch when n * R * max_seqlen fits batch_token_budget and forward()'s own conditions
+        for a batch hold (batched=False: never), else they run one by one through checked_forward_one(need_repr=False) and each
+        is stitched before the next one runs: one call's windows and the stitched outputs are all that is resident.  Exact mode:
+        both routes give the same bits.  A pure function of the tokens and the stride: nothing is drawn."""
+        from . import windows
+        R, C = tokens2d.shape
+        if C <= self.max_seqlen:
+            out = self.checked_forward_one(tokens2d, need_repr=False, what=what)
+            return {"emb": out["emb"], "atp": out["atp"]}
+        if not tokens2d.is_cuda:
+            raise _lib.RnamsmError("tokens must be on the HIP device (no CPU path exists)")
+        W, L = self.max_seqlen - 1, C - 1
+        stride = windows.check_stride(W, int(stride)) if stride else windows.default_stride(W)
+        plan = windows.plan_windows(L, W, stride)
+        n = len(plan)
+        dev = tokens2d.device
+        toks = tokens2d.to(torch.int64)
+        NLH, D = self.num_layers * self.num_attention_heads, self.embed_dim
+
+        def window(k: int) -> torch.Tensor:
+            s = plan[k][0]
+            return torch.cat([toks[:, :1], toks[:, 1 + s:1 + s + W]], 1)
+
+        with torch.cuda.device(dev):
+            # (one mask decision for the alignment, as forward() makes one per batch: both routes then run the same launches per window)
+            has_padding = bool((toks == self.vocab.pad_idx).any())
+            chunked = has_padding and _lib.load().rnamsm_row_chunks(R, W + 1, min(int(self.max_tokens_per_msa), 2 ** 31 - 1)) > 0
+            # (rnamsm_forward_batch reads every member's maps as 16-byte vectors: a member's NL*H*C*C floats must keep that alignment --
+            # always so at 120 maps; a model of fewer maps and an odd C runs its windows one by one)
+            fits = (n * R * self.max_seqlen <= self.batch_token_budget and not chunked and self.batch_small_msas
+                    and (self.gemm_dtype == "f32" or ops.get_param("attn16") != 0) and (NLH * self.max_seqlen ** 2) % 4 == 0)
+            emb = torch.empty(L, D, device=dev, dtype=torch.float32)
+            atp = torch.empty(NLH, L, L, device=dev, dtype=torch.float32)
+            if fits and batched is not False:
+                try:
+                    out = self.checked_forward_batch(torch.stack([window(k) for k in range(n)]), has_padding)
+                except IndexError:
+                    raise IndexError(f"{what}: token or position index out of range") from None
+                ops.stitch_rows(out["emb"], emb, stride, 0)
+                ops.stitch_pairs(out["atp"], atp, stride, 0)
+            else:
+                for k in range(n):
+                    out = self.checked_forward_one(window(k), has_padding, need_repr=False, what=what)
+                    ops.stitch_rows(out["emb"].unsqueeze(0), emb, stride, k)
+                    ops.stitch_pairs(out["atp"].unsqueeze(0), atp, stride, k)
+                    del out
+        return {"emb": emb, "atp": atp}
+
     def _forward_one_on_device(self, tokens2d: torch.Tensor, has_padding: Optional[bool],
                                need_repr: bool = True, fold: bool = True,
                                gemm_dtype: Optional[str] = None) -> Dict[str, torch.Tensor]:

@@ -1077,6 +1077,47 @@ def lm_head_packed(xs: Sequence[torch.Tensor], rows: Sequence, wts: Sequence, we
     return outs
 
 
+def _stitch_out(fn: str, out: torch.Tensor, shape: tuple) -> None:
+    _dev(out, "out")
+    if tuple(out.shape) != shape or not out.is_contiguous():
+        raise ValueError(f"{fn}: out must be a contiguous {shape} tensor, got {tuple(out.shape)} with strides {out.stride()}")
+
+
+@_on_operand_device
+def stitch_rows(x: torch.Tensor, out: torch.Tensor, stride: int, k0: int = 0) -> torch.Tensor:
+    """rnamsm_stitch_rows: x [nb, W, D] fp32 -- the emb of the windows k0 .. k0 + nb - 1 of the plan (L = out.shape[0], W, stride),
+    read where they lie (rows and windows may be further apart: a slice of a wider buffer) -- blended into out [L, D].  Calls come
+    in ascending k0 and together apply every window once; between them `out` holds running sums."""
+    _dev(x, "x")
+    if x.dim() != 3 or out.dim() != 2 or x.shape[2] != out.shape[1]:
+        raise ValueError(f"stitch_rows: x [nb, W, D] and out [L, D], got {tuple(x.shape)} and {tuple(out.shape)}")
+    if x.stride(2) != 1:
+        x = x.contiguous()
+    nb, W, D = x.shape
+    _stitch_out("stitch_rows", out, (out.shape[0], D))
+    _lib.check(_lib.load().rnamsm_stitch_rows(x.data_ptr(), x.stride(0), x.stride(1), out.shape[0], W, int(stride), int(k0), nb, D,
+                                              out.data_ptr(), _stream()))
+    return out
+
+
+@_on_operand_device
+def stitch_pairs(a: torch.Tensor, out: torch.Tensor, stride: int, k0: int = 0, off: int = 0) -> torch.Tensor:
+    """rnamsm_stitch_pairs: a [nb, H, W + off, W + off] fp32 -- the maps of the windows k0 .. k0 + nb - 1, read where they lie
+    through their own strides, skipping `off` leading rows and columns (0: the stripped atp; 1: maps that still carry <cls>) --
+    blended into out [H, L, L]; pairs no window contains come out +0.0.  Calls as for stitch_rows."""
+    _dev(a, "a")
+    if a.dim() != 4 or out.dim() != 3 or a.shape[1] != out.shape[0] or a.shape[2] != a.shape[3] or out.shape[1] != out.shape[2]:
+        raise ValueError(f"stitch_pairs: a [nb, H, W, W] and out [H, L, L], got {tuple(a.shape)} and {tuple(out.shape)}")
+    if a.stride(3) != 1:
+        a = a.contiguous()
+    nb, H, Wo, _ = a.shape
+    _stitch_out("stitch_pairs", out, (H, out.shape[1], out.shape[1]))
+    plane = a.stride(1) if H > 1 else max(a.stride(1), Wo * a.stride(2))      # (the stride of a dimension of one is not binding)
+    _lib.check(_lib.load().rnamsm_stitch_pairs(a.data_ptr(), a.stride(0), plane, a.stride(2), int(off), out.shape[1],
+                                               Wo - int(off), int(stride), int(k0), nb, H, out.data_ptr(), _stream()))
+    return out
+
+
 @_on_operand_device
 def greedy_select(msa_u8: torch.Tensor, num_seqs: int, mode: str = "max") -> torch.Tensor:
     """msa uint8 [N, L] on the device -> int32 [num_seqs] ascending row indices (utils/align.py:128-148)."""
