@@ -616,6 +616,41 @@ int rnamsm_ss_pairs(const float* probs, const uint8_t* letters, int L, int32_t* 
                     uint8_t* bpseq, void* workspace, size_t workspace_bytes, void* stream);
 int rnamsm_ss_pairs_packed(const rnamsm_ss_pairs_item* items, int B, void* workspace, size_t workspace_bytes, void* stream);
 
+/* f1 / f4 on a LONG alignment -- the pair heads on the stitched atp of rnamsm_stitch_pairs, for L in [1, RNAMSM_LONG_MAX_L].  Lone
+ * calls only (a wide alignment never joins a group).  The entry points above keep their limits; each of these gives, for an L both
+ * accept, the BITS (bytes) of its namesake above.  4096: four decimal digits in .ct / .bpseq; L^2 and 120 L^2 are int32 element
+ * counts; the atp is 8 GB.
+ *   rnamsm_contact_head_long    rnamsm_contact_head_atp's arguments, kernels and summation order.  Symmetrise and APC are taken over
+ *                               the whole [L, L] map: a pair no window holds (+0.0 in every channel) takes part as 0.  workspace:
+ *                               rnamsm_contact_head_long_workspace_bytes(L, nch) = (nch L + nch) floats, 4-byte aligned.
+ *   rnamsm_ss_head_long         rnamsm_ss_head's arguments and kernels (exact fp32; there is no bf16 long head).  workspace:
+ *                               rnamsm_ss_head_long_workspace_bytes(L) = 2 x 48 L^2 floats (6.4 GB at the limit), 16-byte aligned.
+ *   rnamsm_ss_prob_text_long    rnamsm_ss_prob_text's arguments, kernel and fallback word; rnamsm_ss_prob_text_long_bytes(L) = 25 L^2
+ *                               (419 MB at the limit).
+ *   rnamsm_ss_pairs_long        rnamsm_ss_pairs' arguments and contract -- partner [L], counts [4], the .ct and .bpseq bodies, within
+ *                               the bounds of rnamsm_ss_struct_text_long_bytes (32 L and 12 L) -- by a kernel pair of its own: the
+ *                               adjacency bits across the grid, then the rounds and the lines in one workgroup of 1024 threads
+ *                               that own ceil(L / 1024) consecutive bases each.  The bytes are the host writer's for every L in
+ *                               range.  workspace: rnamsm_ss_pairs_long_workspace_bytes(L) = L x ceil(L / 64) 64-bit words rounded
+ *                               up to 256 bytes (2 MB at the limit), 16-byte aligned; its contents on entry do not matter.
+ * Every size is 0 for an L outside [1, RNAMSM_LONG_MAX_L].  Refused (RNAMSM_ERR_INVALID) before anything is enqueued, with the
+ * argument named: L out of range, a null pointer, a misaligned pointer, a plane stride < L * L, a short workspace.
+ * No atomics: the same inputs give the same bits on every run. */
+#define RNAMSM_LONG_MAX_L 4096
+size_t rnamsm_contact_head_long_workspace_bytes(int L, int nch);
+int rnamsm_contact_head_long(const float* atp, int64_t plane_stride, int L, int nch, const float* weight, const float* bias,
+                             float* contacts, void* workspace, size_t workspace_bytes, void* stream);
+size_t rnamsm_ss_head_long_workspace_bytes(int L);
+int rnamsm_ss_head_long(const float* atp, int64_t atp_plane_stride, const uint8_t* base_codes, int L, int num_blocks,
+                        const float* const* weights, float* logits, float* probs, void* workspace, size_t workspace_bytes,
+                        void* stream);
+size_t rnamsm_ss_prob_text_long_bytes(int L);
+int rnamsm_ss_prob_text_long(const float* probs, int L, uint8_t* text, int32_t* fallback, void* stream);
+size_t rnamsm_ss_pairs_long_workspace_bytes(int L);
+int rnamsm_ss_struct_text_long_bytes(int L, size_t* ct_bytes, size_t* bpseq_bytes);
+int rnamsm_ss_pairs_long(const float* probs, const uint8_t* letters, int L, int32_t* partner, int32_t* counts, uint8_t* ct,
+                         uint8_t* bpseq, void* workspace, size_t workspace_bytes, void* stream);
+
 /* f5 -- RNA-MSM RSA (relative solvent accessibility) predictor (_downstream_tasks/RSA: predict.py, model/_0811/model_entry.py
  * FrameModel(Cin, 1, planes 64, depth 1, BatchNorm1d)) for an ensemble of n_models members in one set of four launches, exact fp32:
  *   x[c, p]  = (onehot(code[p])[c] - mu_oh[c]) / std_oh[c]  (c < 4, only with use_onehot),

@@ -207,6 +207,35 @@ extern "C" int rnamsm_contact_head_atp(const float* atp, int64_t plane_stride, i
     return contact_lone(atp, plane_stride, L, 0, L, nch, weight, bias, contacts, workspace, static_cast<hipStream_t>(stream));
 }
 
+// The stitched atp of a long alignment, L up to RNAMSM_LONG_MAX_L: the three kernels of rnamsm_contact_head_atp on the same
+// descriptor, so the same bits where both run.  Beyond 1023: every offset into the maps, the contacts and the slab -- ch *
+// plane_stride, i * ld + j, i * T + j, ch * T + i -- is int64_t in the kernels; the grids are nch x ceil(T / 256) <= nch x 16 and
+// ceil(T / 32)^2 <= 2^14 blocks.
+extern "C" size_t rnamsm_contact_head_long_workspace_bytes(int L, int nch) {
+    if (L < 1 || L > RNAMSM_LONG_MAX_L || nch <= 0) return 0;
+    return contact_slab_floats(L, nch) * sizeof(float);
+}
+
+extern "C" int rnamsm_contact_head_long(const float* atp, int64_t plane_stride, int L, int nch, const float* weight, const float* bias,
+                                        float* contacts, void* workspace, size_t workspace_bytes, void* stream) {
+    // every refusal comes before the first launch: a refused call leaves the stream and the outputs untouched
+    RNAMSM_CHECK_ARG(atp, "contact_head_long: null pointer (atp)");
+    RNAMSM_CHECK_ARG(weight, "contact_head_long: null pointer (weight)");
+    RNAMSM_CHECK_ARG(bias, "contact_head_long: null pointer (bias)");
+    RNAMSM_CHECK_ARG(contacts, "contact_head_long: null pointer (contacts)");
+    RNAMSM_CHECK_ARG(workspace, "contact_head_long: null pointer (workspace)");
+    RNAMSM_CHECK_ARG(L >= 1 && L <= RNAMSM_LONG_MAX_L, "contact_head_long: L=%d outside [1, %d]", L, RNAMSM_LONG_MAX_L);
+    RNAMSM_CHECK_ARG(nch > 0, "contact_head_long: nch=%d", nch);
+    RNAMSM_CHECK_ARG(plane_stride >= (int64_t)L * L, "contact_head_long: plane stride %lld < L * L = %lld", (long long)plane_stride,
+                     (long long)L * L);
+    RNAMSM_CHECK_ARG(((uintptr_t)atp & 3u) == 0, "contact_head_long: atp is not 4-byte aligned");
+    RNAMSM_CHECK_ARG(((uintptr_t)contacts & 3u) == 0, "contact_head_long: contacts is not 4-byte aligned");
+    RNAMSM_CHECK_ARG(((uintptr_t)workspace & 3u) == 0, "contact_head_long: workspace is not 4-byte aligned");
+    RNAMSM_CHECK_ARG(workspace_bytes >= contact_slab_floats(L, nch) * sizeof(float), "contact_head_long: workspace of %zu bytes, %zu needed",
+                     workspace_bytes, contact_slab_floats(L, nch) * sizeof(float));
+    return contact_lone(atp, plane_stride, L, 0, L, nch, weight, bias, contacts, workspace, static_cast<hipStream_t>(stream));
+}
+
 extern "C" size_t rnamsm_contact_head_packed_workspace_bytes(int B, const int* Ls, int nch) {
     if (B < 1 || B > RNAMSM_CONTACT_MAX_BATCH || !Ls || nch <= 0) return 0;
     size_t floats = 0;

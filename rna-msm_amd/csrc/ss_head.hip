@@ -242,27 +242,48 @@ int ss_check_weights_and_lds(const char* prefix, const float* const* weights, in
 
 using namespace rnamsm;
 
-extern "C" size_t rnamsm_ss_head_workspace_bytes(int L) {
-    if (L < 1 || L > RNAMSM_SS_MAX_L) return 0;
+// The lone call under either limit: rnamsm_ss_head (RNAMSM_SS_MAX_L) and rnamsm_ss_head_long (RNAMSM_LONG_MAX_L) run the same
+// kernels on the same descriptor, so the same bits where both run.  Beyond 1024: the grid is ceil(L / 16)^2 <= 2^16 blocks; a pixel's
+// index y * L + x < 2^24 is widened before it is scaled by 48 (store_tile, ss_conv_body, ss_out_kernel) and the stem reads plane
+// p * plane_stride + y * L + x in int64_t -- 120 planes of 2^24 floats are 8 GB.
+static size_t ss_head_bytes(int L, int max_L) {
+    if (L < 1 || L > max_L) return 0;
     return 2 * (size_t)L * L * SS_CH * sizeof(float);
 }
-
-extern "C" int rnamsm_ss_head(const float* atp, int64_t atp_plane_stride, const uint8_t* base_codes, int L, int num_blocks,
-                              const float* const* weights, float* logits, float* probs, void* workspace, size_t workspace_bytes,
-                              void* stream) {
-    RNAMSM_CHECK_ARG(atp && base_codes && weights && workspace, "ss_head: null pointer");
-    RNAMSM_CHECK_ARG(logits || probs, "ss_head: neither logits nor probs given");
-    RNAMSM_CHECK_ARG(L >= 1 && L <= RNAMSM_SS_MAX_L, "ss_head: L=%d outside [1, %d]", L, RNAMSM_SS_MAX_L);
-    RNAMSM_CHECK_ARG(num_blocks >= 1 && num_blocks <= RNAMSM_SS_MAX_BLOCKS, "ss_head: num_blocks=%d outside [1, %d]", num_blocks,
+static int ss_head_lone(const char* who, int max_L, const float* atp, int64_t atp_plane_stride, const uint8_t* base_codes, int L,
+                        int num_blocks, const float* const* weights, float* logits, float* probs, void* workspace,
+                        size_t workspace_bytes, void* stream) {
+    RNAMSM_CHECK_ARG(atp && base_codes && weights && workspace, "%s: null pointer", who);
+    RNAMSM_CHECK_ARG(logits || probs, "%s: neither logits nor probs given", who);
+    RNAMSM_CHECK_ARG(L >= 1 && L <= max_L, "%s: L=%d outside [1, %d]", who, L, max_L);
+    RNAMSM_CHECK_ARG(num_blocks >= 1 && num_blocks <= RNAMSM_SS_MAX_BLOCKS, "%s: num_blocks=%d outside [1, %d]", who, num_blocks,
                      RNAMSM_SS_MAX_BLOCKS);
-    RNAMSM_CHECK_ARG(atp_plane_stride >= (int64_t)L * L, "ss_head: atp plane stride %lld < L*L", (long long)atp_plane_stride);
-    RNAMSM_CHECK_ARG(workspace_bytes >= rnamsm_ss_head_workspace_bytes(L), "ss_head: workspace too small");
-    RNAMSM_CHECK_ARG(aligned16(workspace), "ss_head: 16-byte alignment of the workspace");
-    if (int rc = ss_check_weights_and_lds<false>("ss_head", weights, num_blocks)) return rc;
+    RNAMSM_CHECK_ARG(atp_plane_stride >= (int64_t)L * L, "%s: atp plane stride %lld < L*L", who, (long long)atp_plane_stride);
+    RNAMSM_CHECK_ARG(workspace_bytes >= ss_head_bytes(L, max_L), "%s: workspace too small", who);
+    RNAMSM_CHECK_ARG(aligned16(workspace), "%s: 16-byte alignment of the workspace", who);
+    if (int rc = ss_check_weights_and_lds<false>(who, weights, num_blocks)) return rc;
     const int tiles = (L + SS_TILE - 1) / SS_TILE;
     const SsMember lone = {atp, atp_plane_stride, base_codes, logits, probs, 0, L, tiles, 0, 0};
     return ss_launch<false>(nullptr, 1, lone, (int64_t)tiles * tiles, (int64_t)L * L, num_blocks, weights, static_cast<float*>(workspace),
                             static_cast<hipStream_t>(stream));
+}
+
+extern "C" size_t rnamsm_ss_head_workspace_bytes(int L) { return ss_head_bytes(L, RNAMSM_SS_MAX_L); }
+
+extern "C" int rnamsm_ss_head(const float* atp, int64_t atp_plane_stride, const uint8_t* base_codes, int L, int num_blocks,
+                              const float* const* weights, float* logits, float* probs, void* workspace, size_t workspace_bytes,
+                              void* stream) {
+    return ss_head_lone("ss_head", RNAMSM_SS_MAX_L, atp, atp_plane_stride, base_codes, L, num_blocks, weights, logits, probs, workspace,
+                        workspace_bytes, stream);
+}
+
+extern "C" size_t rnamsm_ss_head_long_workspace_bytes(int L) { return ss_head_bytes(L, RNAMSM_LONG_MAX_L); }
+
+extern "C" int rnamsm_ss_head_long(const float* atp, int64_t atp_plane_stride, const uint8_t* base_codes, int L, int num_blocks,
+                                   const float* const* weights, float* logits, float* probs, void* workspace,
+                                   size_t workspace_bytes, void* stream) {
+    return ss_head_lone("ss_head_long", RNAMSM_LONG_MAX_L, atp, atp_plane_stride, base_codes, L, num_blocks, weights, logits, probs,
+                        workspace, workspace_bytes, stream);
 }
 
 extern "C" size_t rnamsm_ss_head_packed_workspace_bytes(int B, const int* Ls) {

@@ -28,7 +28,7 @@ struct SsTextMember {        // 64 bytes
     const float* probs;      // [L, L]
     uint8_t* text;           // [25 L^2], 16-byte aligned
     int32_t* fallback;
-    int32_t L, elems;        // elems = L^2 <= 2^20
+    int32_t L, elems;        // elems = L^2 <= 2^20 (rnamsm_ss_prob_text_long: 2^24)
     int32_t block0;          // blocks of the chunk's members before it
     int32_t pad_[7];
 };
@@ -66,12 +66,14 @@ __global__ __launch_bounds__(ST_THREADS) void ss_text_kernel(const MemberChunk<S
 }
 
 // Every refusal, then the launches.  who: the entry point's name; lone: the one item is the call's own arguments, not "member 0".
-int ss_text_run(const char* who, bool lone, const rnamsm_ss_text_item* items, int B, hipStream_t s) {
+// max_L: the entry point's limit (rnamsm_ss_prob_text_long: RNAMSM_LONG_MAX_L -- elems = L^2 <= 2^24 and the 2^16 blocks of 256
+// elements stay int32; a block's byte offset e0 * 25, up to 419 MB, is taken in size_t).
+int ss_text_run(const char* who, bool lone, const rnamsm_ss_text_item* items, int B, hipStream_t s, int max_L = RNAMSM_SS_MAX_L) {
     char where[32] = "";
     for (int b = 0; b < B; ++b) {
         const rnamsm_ss_text_item& it = items[b];
         if (!lone) snprintf(where, sizeof(where), "member %d: ", b);
-        RNAMSM_CHECK_ARG(it.L >= 1 && it.L <= RNAMSM_SS_MAX_L, "%s: %sL=%d outside [1, %d]", who, where, it.L, RNAMSM_SS_MAX_L);
+        RNAMSM_CHECK_ARG(it.L >= 1 && it.L <= max_L, "%s: %sL=%d outside [1, %d]", who, where, it.L, max_L);
         RNAMSM_CHECK_ARG(it.probs && it.text && it.fallback, "%s: %snull pointer", who, where);
         RNAMSM_CHECK_ARG(((uintptr_t)it.probs & 3u) == 0 && ((uintptr_t)it.fallback & 3u) == 0,
                          "%s: %sprobs or fallback is not 4-byte aligned", who, where);
@@ -115,6 +117,17 @@ extern "C" size_t rnamsm_ss_prob_text_bytes(int L) {
 extern "C" int rnamsm_ss_prob_text(const float* probs, int L, uint8_t* text, int32_t* fallback, void* stream) {
     const rnamsm_ss_text_item item = {probs, L, text, fallback};
     return ss_text_run("ss_prob_text", true, &item, 1, static_cast<hipStream_t>(stream));
+}
+
+// The lone call for L up to RNAMSM_LONG_MAX_L: the same kernel, so the same bytes where both run.
+extern "C" size_t rnamsm_ss_prob_text_long_bytes(int L) {
+    if (L < 1 || L > RNAMSM_LONG_MAX_L) return 0;
+    return (size_t)ST_RECORD * L * L;
+}
+
+extern "C" int rnamsm_ss_prob_text_long(const float* probs, int L, uint8_t* text, int32_t* fallback, void* stream) {
+    const rnamsm_ss_text_item item = {probs, L, text, fallback};
+    return ss_text_run("ss_prob_text_long", true, &item, 1, static_cast<hipStream_t>(stream), RNAMSM_LONG_MAX_L);
 }
 
 extern "C" int rnamsm_ss_prob_text_packed(const rnamsm_ss_text_item* items, int B, void* stream) {

@@ -58,6 +58,11 @@ class ContactHead:
         signature)."""
         return ContactResult(ops.contact_head_atp(atp, self.weight, self.bias))
 
+    def one_long(self, emb: torch.Tensor, atp: torch.Tensor, tokens: torch.Tensor) -> ContactResult:
+        """one() on the stitched atp of a long alignment (data.long_heads=stitched), L up to LONG_MAX_L = 4096: the same record
+        through rnamsm_contact_head_long.  Symmetrise and APC run over the whole map; a pair no window holds takes part as 0."""
+        return ContactResult(ops.contact_head_long(atp, self.weight, self.bias))
+
     def many(self, embs: Sequence[torch.Tensor], atps: Sequence[torch.Tensor], tokens: Sequence[torch.Tensor]) -> List[ContactResult]:
         """A group in one launch set per chunk (predict_many): every member's record holds the bits of one()."""
         return [ContactResult(c) for c in predict_many(atps, self.weight, self.bias)]

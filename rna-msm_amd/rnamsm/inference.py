@@ -19,9 +19,9 @@ from typing import Dict, List, Optional
 import numpy as np
 import torch
 
-from . import contacts, lm, ops, rsa, sharding, ss
+from . import _lib, contacts, lm, ops, rsa, sharding, ss
 from .alphabet import RNAAlphabet
-from .config import Config, check_long_msa, check_ss_gemm_dtype
+from .config import Config, check_long_heads, check_long_msa, check_ss_gemm_dtype
 from .model import MSATransformer
 from .msa import load_msa_tokens
 
@@ -312,6 +312,9 @@ def extract_feat(cfg: Config, model: Optional[MSATransformer] = None, gather_to_
     # overlapping windows stitched on the device (MSATransformer.forward_windows): its files hold the full L
     windowing = check_long_msa(getattr(cfg.data, "long_msa", "crop")) == "windows"
     window_stride = int(getattr(cfg.data, "window_stride", 0))
+    # data.long_heads=stitched: on such an alignment the contact head and the exact-fp32 SS head run on the stitched atp through the
+    # long entry points (L <= _lib.LONG_MAX_L); "skip" leaves everything as it was, the printed lines included
+    long_heads = check_long_heads(getattr(cfg.data, "long_heads", "skip")) == "stitched"
     device = torch.device(cfg.data.device)
     if device.type != "cuda":
         raise RuntimeError("this build runs on the MI355X HIP path only (data.device=cuda); there is no CPU path")
@@ -403,7 +406,25 @@ def extract_feat(cfg: Config, model: Optional[MSATransformer] = None, gather_to_
     def skipped_on(h, L: int) -> bool:
         """data.long_msa=windows: which heads do not run on a stitched alignment of L body columns -- all but lm_scores=wt, whose
         kernel has no length limit that matters (the others stop at L <= 1024, or would need per-window semantics)."""
-        return windowing and L > model.max_seqlen - 1 and not (isinstance(h, lm.LMHead) and h.mode == "wt")
+        return stitched(L) and not (isinstance(h, lm.LMHead) and h.mode == "wt") and long_skip_reason(h, L) is not None
+
+    def stitched(L: int) -> bool:
+        return windowing and L > model.max_seqlen - 1
+
+    def long_skip_reason(h, L: int) -> Optional[str]:
+        """Why head h does not run on a stitched alignment of L columns; None where data.long_heads=stitched lets it through.  ""
+        with the key off: the line printed then names no reason, as before."""
+        if not long_heads:
+            return ""
+        if isinstance(h, rsa.RSAHead):
+            return f"the RSA head's attention is tiled to L <= {_lib.RSA_MAX_L}"
+        if isinstance(h, lm.LMHead):
+            return "the masked scan would run L forwards per window"
+        if L > _lib.LONG_MAX_L:
+            return f"L exceeds the long heads' limit of {_lib.LONG_MAX_L}"
+        if isinstance(h, ss.SSHead) and h.model.gemm_dtype != "f32":
+            return f"there is no long SS head under data.ss_gemm_dtype={h.model.gemm_dtype}"
+        return None if isinstance(h, (ss.SSHead, contacts.ContactHead)) else "it has no long entry point"
 
     def emit(rna_id: str, emb: torch.Tensor, atp: torch.Tensor, after: Optional[torch.cuda.Event] = None, records=()) -> None:
         """records: this alignment's record of every head that is on, in the order of `heads`; each becomes one writer job (but
@@ -452,7 +473,11 @@ def extract_feat(cfg: Config, model: Optional[MSATransformer] = None, gather_to_
                 """records: this alignment's record of every head, where its group's batched heads (deliver_group) have made them;
                 absent, the lone heads run here, on emb and atp where they lie (a packed group's slices included)."""
                 if records is None:
-                    records = [None if skipped_on(h, emb.shape[0]) else h.one(emb, atp, head_tokens(h, toks)) for h in heads]
+                    # (a stitched alignment: the heads data.long_heads=stitched lets through run their long route; lm_scores=wt has
+                    # no length limit and keeps its own)
+                    wide = stitched(emb.shape[0])
+                    records = [None if skipped_on(h, emb.shape[0])
+                               else (getattr(h, "one_long", h.one) if wide else h.one)(emb, atp, head_tokens(h, toks)) for h in heads]
                     if heads and after is not None:             # the copies wait for the heads too
                         after = torch.cuda.Event()
                         after.record(torch.cuda.current_stream())
@@ -619,8 +644,10 @@ def extract_feat(cfg: Config, model: Optional[MSATransformer] = None, gather_to_
                         out = model.forward_windows(t_dev, window_stride, what=rna_id)
                         for h in heads:
                             if skipped_on(h, tokens.shape[1] - 1):
+                                why = long_skip_reason(h, tokens.shape[1] - 1)
                                 print(f"{rna_id}: L={tokens.shape[1] - 1} is stitched from windows (data.long_msa=windows); "
-                                      f"{type(h).__name__}{'(masked)' if isinstance(h, lm.LMHead) else ''} is skipped for it")
+                                      f"{type(h).__name__}{'(masked)' if isinstance(h, lm.LMHead) else ''} is skipped for it"
+                                      + (f" ({why})" if why else ""))
                         deliver(idx, out["emb"], out["atp"], toks=t_dev)
                         continue
                     has_pad = bool((tokens == alphabet.padding_idx).any())          # on the host: no device round trip before the launches

@@ -740,14 +740,14 @@ def ss_head_packed(atps: Sequence[torch.Tensor], codes: Sequence[torch.Tensor], 
     return outs
 
 
-def _ss_text_operand(fn: str, probs: torch.Tensor, name: str):
+def _ss_text_operand(fn: str, probs: torch.Tensor, name: str, max_L: int = _lib.SS_MAX_L):
     """One [L, L] matrix of ss_prob_text / ss_prob_text_packed as the library reads it -> (probs, L)."""
     _dev(probs, name)
     if probs.dim() != 2 or probs.shape[0] != probs.shape[1]:
         raise ValueError(f"{fn}: {name} must be [L, L], got {tuple(probs.shape)}")
     L = probs.shape[0]
-    if not 1 <= L <= _lib.SS_MAX_L:
-        raise ValueError(f"{fn}: {name}: L = {L} outside [1, {_lib.SS_MAX_L}]")
+    if not 1 <= L <= max_L:
+        raise ValueError(f"{fn}: {name}: L = {L} outside [1, {max_L}]")
     return probs.contiguous(), L
 
 
@@ -829,6 +829,71 @@ def _ss_pairs_run(_fn: str, probs, letters):
     items = (_lib.SsPairsItem * B)(*(_lib.SsPairsItem(*a) for a in args))
     _lib.check(lib.rnamsm_ss_pairs_packed(items, B, ws.data_ptr(), ws.numel(), _stream()))
     return outs
+
+
+# ---- the pair heads on a stitched long alignment (include/rnamsm.h: RNAMSM_LONG_MAX_L): lone calls for L up to _lib.LONG_MAX_L, each
+# with the bits of its namesake above where both accept the L
+@_on_operand_device
+def contact_head_long(atp: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor) -> torch.Tensor:
+    """contact_head_atp for L up to LONG_MAX_L (rnamsm_contact_head_long): atp [nch, L, L] fp32, planes read in place -> contacts
+    [L, L]; symmetrise and APC run over the whole map."""
+    members, _ = _members("contact_head_long", _contact_operand, 1, _lib.LONG_MAX_L, (None, None, "alignments"), {"atp": [atp]}, lone=True)
+    atp, L = members[0]
+    nch = atp.shape[0]
+    weight, bias = _contact_regression(weight, bias, nch, "contact_head_long")
+    lib = _lib.load()
+    ws = torch.empty(lib.rnamsm_contact_head_long_workspace_bytes(L, nch), dtype=torch.uint8, device=atp.device)
+    out = torch.empty(L, L, device=atp.device, dtype=torch.float32)
+    _lib.check(lib.rnamsm_contact_head_long(atp.data_ptr(), atp.stride(0), L, nch, weight.data_ptr(), bias.data_ptr(), out.data_ptr(),
+                                            ws.data_ptr(), ws.numel(), _stream()))
+    return out
+
+
+@_on_operand_device
+def ss_head_long(atp: torch.Tensor, base_codes: torch.Tensor, ptrs, num_blocks: int, want: str = "probs") -> torch.Tensor:
+    """ss_head for L up to LONG_MAX_L (rnamsm_ss_head_long, exact fp32 only: ptrs is the fp32 weight table) -> [L, L] probabilities
+    or logits.  The workspace is 384 L^2 bytes: 6.4 GB at the limit."""
+    _want("ss_head_long", want)
+    atp, base_codes, L = _ss_operands("ss_head_long", atp, base_codes, "atp", "base_codes")
+    lib = _lib.load()
+    ws = torch.empty(max(lib.rnamsm_ss_head_long_workspace_bytes(L), 16), dtype=torch.uint8, device=atp.device)
+    out = torch.empty(L, L, device=atp.device, dtype=torch.float32)
+    ptr = out.data_ptr()
+    _lib.check(lib.rnamsm_ss_head_long(atp.data_ptr(), atp.stride(0), base_codes.data_ptr(), L, num_blocks, ptrs,
+                                       ptr if want == "logits" else None, ptr if want == "probs" else None, ws.data_ptr(),
+                                       ws.numel(), _stream()))
+    return out
+
+
+@_on_operand_device
+def ss_prob_text_long(probs: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """ss_prob_text for L up to LONG_MAX_L (rnamsm_ss_prob_text_long) -> (uint8 [25 L^2], the fallback word)."""
+    probs, L = _ss_text_operand("ss_prob_text_long", probs, "probs", _lib.LONG_MAX_L)
+    lib = _lib.load()
+    text = torch.empty(lib.rnamsm_ss_prob_text_long_bytes(L), dtype=torch.uint8, device=probs.device)
+    fallback = torch.empty(1, dtype=torch.int32, device=probs.device)
+    _lib.check(lib.rnamsm_ss_prob_text_long(probs.data_ptr(), L, text.data_ptr(), fallback.data_ptr(), _stream()))
+    return text, fallback
+
+
+@_on_operand_device
+def ss_pairs_long(probs: torch.Tensor, letters: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """ss_pairs for L up to LONG_MAX_L (rnamsm_ss_pairs_long: several bases per thread) -> (partner int32 [L], counts int32 [4], the
+    .ct body uint8 [32 L], the .bpseq body uint8 [12 L]), read as ss_pairs' results are."""
+    probs, L = _ss_text_operand("ss_pairs_long", probs, "probs", _lib.LONG_MAX_L)
+    _dev(letters, "letters", torch.uint8)
+    if letters.dim() != 1 or letters.shape[0] != L:
+        raise ValueError(f"ss_pairs_long: {letters.shape[0] if letters.dim() == 1 else tuple(letters.shape)} letters for probs of L = {L}")
+    if letters.device != probs.device:
+        raise ValueError(f"ss_pairs_long: probs / letters lie on {probs.device} / {letters.device}")
+    letters = letters.contiguous()
+    lib = _lib.load()
+    ws = torch.empty(lib.rnamsm_ss_pairs_long_workspace_bytes(L), dtype=torch.uint8, device=probs.device)
+    partner, counts = (torch.empty(n, dtype=torch.int32, device=probs.device) for n in (L, 4))
+    ct, bpseq = (torch.empty(n * L, dtype=torch.uint8, device=probs.device) for n in (_lib.SS_CT_LINE_MAX, _lib.SS_BPSEQ_LINE_MAX))
+    _lib.check(lib.rnamsm_ss_pairs_long(probs.data_ptr(), letters.data_ptr(), L, partner.data_ptr(), counts.data_ptr(), ct.data_ptr(),
+                                        bpseq.data_ptr(), ws.data_ptr(), ws.numel(), _stream()))
+    return partner, counts, ct, bpseq
 
 
 def _rsa_operands(fn: str, emb: torch.Tensor, bc: torch.Tensor, name: str, bc_name: str):

@@ -160,7 +160,7 @@ class SSPredictor(nn.Module):
         return super()._apply(fn, *args, **kwargs)
 
     @staticmethod
-    def _codes_of(atp, seq, name: str, seq_name: str, on_device: bool) -> torch.Tensor:
+    def _codes_of(atp, seq, name: str, seq_name: str, on_device: bool, max_L: int = _lib.SS_MAX_L) -> torch.Tensor:
         """The checks of one (maps, sequence) pair, named as the caller's arguments (`atp` / `atps[3]`) -> its base codes, flat.
         on_device: refuse maps off the HIP device here, before their shape (False: the caller does that for every item afterwards)."""
         if not isinstance(atp, torch.Tensor) or (on_device and not atp.is_cuda):
@@ -168,8 +168,8 @@ class SSPredictor(nn.Module):
         if atp.dim() != 3 or atp.shape[0] != NUM_MAPS or atp.shape[1] != atp.shape[2]:
             raise ValueError(f"SSPredictor: {name} must be [{NUM_MAPS}, L, L], got {tuple(atp.shape)}")
         L = atp.shape[-1]
-        if L > _lib.SS_MAX_L:
-            raise ValueError(f"SSPredictor: {name}: L = {L} exceeds the head's limit of {_lib.SS_MAX_L}")
+        if L > max_L:
+            raise ValueError(f"SSPredictor: {name}: L = {L} exceeds the head's limit of {max_L}")
         if isinstance(seq, str):
             seq = base_codes(seq)
         codes = torch.as_tensor(seq).reshape(-1)
@@ -189,6 +189,21 @@ class SSPredictor(nn.Module):
         return self._run(atp, seq, "logits")
 
     forward = predict
+
+    def _run_long(self, atp: torch.Tensor, seq, want: str) -> torch.Tensor:
+        if self._gemm_dtype != "f32":
+            raise ValueError(f"SSPredictor: the long head runs in exact fp32 only, not in gemm_dtype={self._gemm_dtype!r}")
+        codes = self._codes_of(atp, seq, "atp", "seq", True, _lib.LONG_MAX_L).to(device=atp.device, dtype=torch.uint8)
+        ptrs, _ = self._packed_weights()
+        return ops.ss_head_long(atp, codes, ptrs, self.num_blocks, want)
+
+    def predict_long(self, atp: torch.Tensor, seq) -> torch.Tensor:
+        """predict() on the stitched maps of a long alignment, L up to LONG_MAX_L = 4096 (rnamsm_ss_head_long: the same kernels, so
+        predict()'s bits where both run); exact fp32 only."""
+        return self._run_long(atp, seq, "probs")
+
+    def logits_long(self, atp: torch.Tensor, seq) -> torch.Tensor:
+        return self._run_long(atp, seq, "logits")
 
     def _run_many(self, atps: Sequence[torch.Tensor], seqs: Sequence, want: str) -> List[torch.Tensor]:
         atps, seqs = list(atps), list(seqs)
@@ -288,6 +303,17 @@ def structure_many(probs: Sequence[torch.Tensor], letters: Sequence[torch.Tensor
     for i in range(0, len(probs), _lib.SS_MAX_BATCH):
         out += ops.ss_pairs_packed(probs[i:i + _lib.SS_MAX_BATCH], letters[i:i + _lib.SS_MAX_BATCH])
     return out
+
+
+def prob_text_long(probs: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """prob_text() for L up to LONG_MAX_L (rnamsm_ss_prob_text_long): the same bytes where both run."""
+    return ops.ss_prob_text_long(probs)
+
+
+def structure_long(probs: torch.Tensor, letters: torch.Tensor):
+    """structure() for L up to LONG_MAX_L (rnamsm_ss_pairs_long: several bases per thread): the same four results, the host path's
+    bytes for every L in range."""
+    return ops.ss_pairs_long(probs, letters)
 
 
 def pairs_from_partner(partner) -> List[Tuple[int, int]]:
@@ -451,6 +477,13 @@ class SSHead:
         probs = self.model.predict(atp, self.base_lut[tokens])
         return SSResult(probs, tokens, tuple(prob_text(probs)) if self.text_on else None,
                         tuple(structure(probs, self.letters_lut[tokens])) if self.pairs_on else None)
+
+    def one_long(self, emb: torch.Tensor, atp: torch.Tensor, tokens: torch.Tensor) -> SSResult:
+        """one() on a stitched long alignment (data.long_heads=stitched), L up to LONG_MAX_L: the same record through the long entry
+        points; with a switch off, that part is left to the host writer, which has no length limit."""
+        probs = self.model.predict_long(atp, self.base_lut[tokens])
+        return SSResult(probs, tokens, tuple(prob_text_long(probs)) if self.text_on else None,
+                        tuple(structure_long(probs, self.letters_lut[tokens])) if self.pairs_on else None)
 
     def many(self, embs: Sequence[torch.Tensor], atps: Sequence[torch.Tensor], tokens: Sequence[torch.Tensor]) -> List[SSResult]:
         """A group in one launch set per stage (predict_many, prob_text_many, structure_many): every member's record holds the bits
