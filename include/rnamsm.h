@@ -334,7 +334,10 @@ int rnamsm_pack_outputs(const float* x_final, const float* probs_all, float* emb
 
 /* f1 -- contact head on the stacked row attentions (ContactPredictionHead.forward, modules.py:344-366 with
  * symmetrize/apc, utils/tensor.py:98-113; model.py:412-414): row_attn [nch = L*H, C, C] (with <cls>) ->
- * contacts [C-1, C-1] = sigmoid(regression(apc(symmetrize(row_attn[:, 1:, 1:])))).  weight [nch], bias [1]. */
+ * contacts [C-1, C-1] = sigmoid(regression(apc(symmetrize(row_attn[:, 1:, 1:])))).  weight [nch], bias [1].
+ * The workspace after the call, for this entry, rnamsm_contact_head_atp and rnamsm_contact_head_long alike (T = C - 1 or L): floats
+ * rs [nch, T] -- rs[ch, i] = sum_j (X[i, j] + X[j, i]), the row sum of the symmetrised channel -- then tot [nch] = sum_i rs[ch, i],
+ * and nothing else; a packed call leaves each member's rs and tot in that member's slab (below).  The tests read the stages there. */
 size_t rnamsm_contact_head_workspace_bytes(int C, int nch);
 int rnamsm_contact_head(const float* row_attn, const float* weight, const float* bias, float* contacts,
                         void* workspace, size_t workspace_bytes, int C, int nch, void* stream);

@@ -18,6 +18,7 @@ namespace {
 
 constexpr int CT_ROWS = 256;       // rows of one block of the sums (= the stride of the total's partial sums)
 constexpr int CT_TILE = 32;        // output tile of the regression: 32 x 32
+constexpr int CT_CHAIN = 64;       // terms of one sequential chain of a row / column sum (as lm_dense's K blocks)
 
 // ---- the member of a block ------------------------------------------------------------------------------------------------------
 // One kernel per stage serves the lone calls and the batched one, as in ss_head.hip / rsa_head.hip: batched, mem is the device
@@ -57,8 +58,9 @@ __device__ __forceinline__ void contact_tree(float* red) {
 }
 
 // ---------------------------------------------------------------------------------------------------------------- launch 1
-// rs[ch, i] = sum_j X[i,j]  +  sum_j X[j,i]  (each a sequential sum over j = 0 .. T-1).  Block (channel, 256 rows): the rows of a
-// channel are spread over ceil(T / 256) blocks, where one block per channel walked them 256 at a time (120 blocks on 256 CUs,
+// rs[ch, i] = sum_j X[i,j]  +  sum_j X[j,i], each summed in fixed blocks of CT_CHAIN: a chain from zero over j = 64 b .. 64 b + 63,
+// the block sums added in ascending b.  One chain over all T terms lost 3.7 x (T = 255) to 7 x (T = 1023) what the library's fp32
+// sum loses on rows of unlike elements.  Block (channel, 256 rows): the rows of a channel are spread over ceil(T / 256) blocks, where one block per channel walked them 256 at a time (120 blocks on 256 CUs,
 // whatever T).  A member of T <= 256 has one block per channel, which then holds every partial sum of the total and finishes
 // it here; a longer member's total is launch 2.
 template <bool PACKED>
@@ -73,9 +75,25 @@ __global__ __launch_bounds__(CT_ROWS) void contact_sums_kernel(const ContactMemb
     float total = 0.f;
     if (i < T) {
         float r = 0.f, c = 0.f;
-        for (int j = 0; j < T; ++j) {
-            r += X[(int64_t)i * ld + j];      // row i of X      (lanes stride rows: L2-resident re-reads)
-            c += X[(int64_t)j * ld + i];      // column i of X   (coalesced across lanes)
+        int j0 = 0;
+        for (; j0 + CT_CHAIN <= T; j0 += CT_CHAIN) {                // the whole chains: a constant trip count
+            float rb = 0.f, cb = 0.f;
+#pragma unroll 8
+            for (int j = j0; j < j0 + CT_CHAIN; ++j) {
+                rb += X[(int64_t)i * ld + j];  // row i of X      (lanes stride rows: L2-resident re-reads)
+                cb += X[(int64_t)j * ld + i];  // column i of X   (coalesced across lanes)
+            }
+            r += rb;
+            c += cb;
+        }
+        if (j0 < T) {                                               // the last, shorter chain (T % 64 terms)
+            float rb = 0.f, cb = 0.f;
+            for (int j = j0; j < T; ++j) {
+                rb += X[(int64_t)i * ld + j];
+                cb += X[(int64_t)j * ld + i];
+            }
+            r += rb;
+            c += cb;
         }
         const float s = r + c;
         rs[(int64_t)ch * T + i] = s;
@@ -107,8 +125,10 @@ __global__ __launch_bounds__(CT_ROWS) void contact_tot_kernel(const ContactMembe
 
 // ---------------------------------------------------------------------------------------------------------------- launch 3
 // 32x32 output tile per block; the transposed operand X[J, I] goes through LDS so both global reads are coalesced.
-// The channel's term is two explicit fused multiply-adds, s - (r_i r_j) / tot and acc + w (...): what hipcc's default contraction
-// made of `acc += w * (s - (r_i * r_j) * inv)` while the kernel had one layout, written out so that no instance can differ.
+// The channel's term is s - (r_i r_j) / tot with a correctly rounded fp32 division, as the reference divides (tensor.py:107-108): a
+// product with a rounded 1 / tot costs a second rounding, which at T = 1, where the quotient is exactly s, left an ulp of s per
+// channel in a logit that is the bias alone.  The accumulation acc + w (...) is an explicit fmaf, so that no
+// instance's layout can change the contraction.  The head is HBM-bound; the division does not show in its time.
 template <bool PACKED>
 __global__ __launch_bounds__(256) void contact_regress_kernel(const ContactMember* __restrict__ mem, int B, const ContactMember lone,
                                                               const float* __restrict__ ws, const float* __restrict__ weight,
@@ -124,7 +144,7 @@ __global__ __launch_bounds__(256) void contact_regress_kernel(const ContactMembe
     float acc[4] = {0.f, 0.f, 0.f, 0.f};
     for (int ch = 0; ch < nch; ++ch) {
         const float* X = contact_plane(m, ch);
-        const float w = weight[ch], inv = 1.f / tot[ch];
+        const float w = weight[ch], t = tot[ch];
         const float* r = rs + (int64_t)ch * T;
         __syncthreads();
 #pragma unroll
@@ -139,7 +159,7 @@ __global__ __launch_bounds__(256) void contact_regress_kernel(const ContactMembe
             if (i < T && j < T) {
                 const float s = X[(int64_t)i * ld + j] + tr[tx][a];
                 const float a12 = r[i] * r[j];                      // a1 * a2 / a12, same order as tensor.py:107-108
-                acc[p] = fmaf(w, fmaf(-inv, a12, s), acc[p]);
+                acc[p] = fmaf(w, s - a12 / t, acc[p]);
             }
         }
     }
