@@ -8,7 +8,8 @@ RNA_MSM_Inference.py writes), runs the ensemble of `<rootdir>/models/OH+RNA-MSM_
 statistic_dict_*.pickle files) on the HIP device (rnamsm.rsa.RSAEnsemble: all members in one set of launches) and writes
 `<featdir>/RSA_result/<name>_<k>/<name>.txt` per member and `<featdir>/RSA_result/<name>_ensemble/<name>.txt` as the reference
 does.  `random` is seeded with 2022 as there.  --text-device (default): the tables are computed and formatted on the device
-(rnamsm_rsa_text) and written as one block each; --no-text-device: the host arithmetic and np.savetxt, the same bytes.  Not written: the reference's two PNG plots; no device but the HIP one.
+(rnamsm_rsa_text) and written as one block each; an embedding of 1025 to 4096 rows, which a stitched long alignment leaves behind,
+goes through rnamsm_rsa_head_long / rnamsm_rsa_text_long; --no-text-device: the host arithmetic and np.savetxt, the same bytes.  Not written: the reference's two PNG plots; no device but the HIP one.
 """
 import os
 import random
@@ -37,7 +38,7 @@ def main(argv=None):
         sys.exit(f"RSA_predict.py: --device {args.device}: this build runs on the HIP device only (--device cuda)")
     import numpy as np
     import torch
-    from rnamsm import rsa
+    from rnamsm import _lib, rsa
     from rnamsm.msa import read_fasta_records
 
     fasta = os.path.join(args.featdir, args.rnaid + ".fasta")
@@ -58,11 +59,13 @@ def main(argv=None):
             sys.exit(f"RSA_predict.py: {name}: sequence of length {len(seq)} but an embedding of shape {emb.shape} in {emb_path}")
         with torch.no_grad():
             emb_dev = torch.from_numpy(np.ascontiguousarray(emb, dtype=np.float32)).to(device)
+            # an embedding of more than 1024 rows (a stitched long alignment's, data.long_msa=windows) takes the long entry points
+            long_ = emb.shape[0] > _lib.RSA_MAX_L
             if args.text_device:
-                values, text = ens.predict_text(emb_dev, seq)
+                values, text = (ens.predict_text_long if long_ else ens.predict_text)(emb_dev, seq)
                 text = tuple(t.cpu().numpy() for t in text)
             else:
-                values, text = ens.predict(emb_dev, seq), None
+                values, text = (ens.predict_long if long_ else ens.predict)(emb_dev, seq), None
         rsa.write_rsa_files(values.cpu().numpy(), seq, name, args.featdir, ens.model_names, random, text=text)
         print(f"{name}: {os.path.join(args.featdir, 'RSA_result', name)}_{{0..{len(ens) - 1},ensemble}}/{name}.txt")
 

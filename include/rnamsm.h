@@ -771,6 +771,31 @@ int rnamsm_rsa_text(const float* rsa, const uint8_t* letters, int L, int n_model
                     void* stream);
 int rnamsm_rsa_text_packed(const rnamsm_rsa_text_item* items, int B, int n_models, void* stream);
 
+/* f5 on a LONG alignment -- the RSA ensemble and its tables on the stitched embedding of rnamsm_stitch_rows, for L in
+ * [1, RNAMSM_LONG_MAX_L].  Lone calls only (a wide alignment never joins a group).  rnamsm_rsa_head and rnamsm_rsa_text keep their
+ * limits and their workspace layout; each of these gives, for an L both accept, the BITS (bytes) of its namesake above: logits,
+ * probs, text, counts, ens and the two flag words.
+ *   rnamsm_rsa_head_long   rnamsm_rsa_head's arguments, weight table, alignment and emb_row_stride rules, and its four stage bodies
+ *                          on a second workspace layout: per model 7 L 64 floats (h1, shortcut, h2, y, q, k, v) and then
+ *                          RNAMSM_LONG_MAX_L / 32 = 128 rows of 64 tile sums, of which the first ceil(L / 32) are written --
+ *                          rnamsm_rsa_head_long_workspace_bytes(L, n_models) = n_models (7 L 64 + 128 x 64) x 4 bytes (7.4 MB per
+ *                          model at the limit), 16-byte aligned.  The squeeze mean adds the tile sums in one ascending chain per
+ *                          group of 32 tiles and the group sums ascending (one group: rnamsm_rsa_head's chain), the same order
+ *                          in every block; the attention sums 64 keys a chunk and the chunks ascending, as for any L.
+ *   rnamsm_rsa_text_long   rnamsm_rsa_text's arguments, kernel, counts, ens, fallback word and zero word; the bytes are the host
+ *                          writer's for every L in range.  rnamsm_rsa_text_long_bytes(L, n_models) = (n_models + 1) x
+ *                          RNAMSM_RSA_TEXT_LINE_MAX x L: 23 bytes still hold the longest line, "4096\t\tG\t\t400.00\t\t1.000\n".
+ * Every size is 0 for an L outside [1, RNAMSM_LONG_MAX_L] or n_models outside [1, RNAMSM_RSA_MAX_MODELS].  Refused
+ * (RNAMSM_ERR_INVALID) before anything is launched, with the value or the argument named: L or n_models out of range, a null or
+ * misaligned pointer, emb_row_stride < 768, a short workspace.  No atomics: the same inputs give the same bits on every run. */
+size_t rnamsm_rsa_head_long_workspace_bytes(int L, int n_models);
+int rnamsm_rsa_head_long(const float* emb, int64_t emb_row_stride, const uint8_t* base_codes, int L, int n_models, int use_onehot,
+                         const void* const* weights, float* probs, float* logits, void* workspace, size_t workspace_bytes,
+                         void* stream);
+size_t rnamsm_rsa_text_long_bytes(int L, int n_models);
+int rnamsm_rsa_text_long(const float* rsa, const uint8_t* letters, int L, int n_models, uint8_t* text, int32_t* counts, double* ens,
+                         void* stream);
+
 /* a7 -- the residual add of NormalizedResidualBlock around a layer that is NOT one of this library's (modules.py:396,
  * `x = residual + x`; around the library's own layers the add is fused into the layer's last GEMM): out[i] = a[i] + b[i], fp32,
  * out may alias a or b. */

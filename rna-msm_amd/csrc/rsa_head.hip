@@ -25,10 +25,16 @@ constexpr int RSA_THREADS = 256;
 constexpr int RSA_HID = 256;
 constexpr int RSA_KEYS = 64;           // keys per streamed K / V chunk
 constexpr int RSA_MAX_TILES = RNAMSM_RSA_MAX_L / RSA_TILE;
+constexpr int RSA_LONG_TILES = RNAMSM_LONG_MAX_L / RSA_TILE;      // tile-sum rows of the long layout (rnamsm_rsa_head_long)
+constexpr int RSA_SUM_GROUP = 32;      // tile sums per chain of the squeeze mean beyond RSA_MAX_TILES tiles
+static_assert(RSA_SUM_GROUP == RSA_MAX_TILES, "one group of tile sums is the existing layout's one chain");
 constexpr float RSA_LN_EPS = 1e-5f;
 
-// per-model workspace: h1, shortcut, h2, y, q, k, v ([L][64] each) and the tile sums [32][64]
-__host__ __device__ inline size_t rsa_model_floats(int L) { return (size_t)7 * L * RSA_CH + (size_t)RSA_MAX_TILES * RSA_CH; }
+// per-model workspace: h1, shortcut, h2, y, q, k, v ([L][64] each) and the tile sums [TR][64] -- TR = 32 rows in the layout of
+// rnamsm_rsa_head / _packed, 128 in the one of rnamsm_rsa_head_long.  TR is a template argument of the four bodies: the slab size
+// stays a compile-time function of L in every instance, as it was.
+template <int TR = RSA_MAX_TILES>
+__host__ __device__ inline size_t rsa_model_floats(int L) { return (size_t)7 * L * RSA_CH + (size_t)TR * RSA_CH; }
 
 // The caller's weight table lives on the host (as rnamsm_ss_head's): it travels to every launch by value, in the kernel arguments.
 constexpr int RSA_TABLE_MAX = RNAMSM_RSA_GLOBAL_WEIGHTS + RNAMSM_RSA_WEIGHTS_PER_MODEL * RNAMSM_RSA_MAX_MODELS;
@@ -88,6 +94,7 @@ __device__ __forceinline__ RsaMember rsa_member(const RsaMember* __restrict__ me
 // In the four bodies ws is the MEMBER's base (its K model slabs); LDS is the calling kernel's.
 constexpr int RSA_STEM_XS = RSA_KC * RSA_XP;
 constexpr int RSA_STEM_RED = 3 * 2 * 2 * 16 * 64;
+template <int TR>
 __device__ __forceinline__ void rsa_stem_body(float* Xs, float* Red, const float* __restrict__ emb, int64_t emb_stride,
                                               const uint8_t* __restrict__ codes, int L, int use_onehot, const RsaTable& table,
                                               float* __restrict__ ws, int m, int p0) {
@@ -169,7 +176,7 @@ __device__ __forceinline__ void rsa_stem_body(float* Xs, float* Red, const float
         }
         const int co = half * 32 + r;
         const float s1 = M.w[W_BN1_S][co], b1 = M.w[W_BN1_B][co], ss = M.w[W_BNS_S][co], bs = M.w[W_BNS_B][co];
-        float* h1 = ws + (size_t)m * rsa_model_floats(L);
+        float* h1 = ws + (size_t)m * rsa_model_floats<TR>(L);
         float* sh = h1 + (size_t)L * RSA_CH;
 #pragma unroll
         for (int i = 0; i < 16; ++i) {
@@ -187,8 +194,16 @@ __global__ __launch_bounds__(RSA_STEM_THREADS) void rsa_stem_kernel(const RsaMem
     __shared__ float Xs[RSA_STEM_XS];
     __shared__ float Red[RSA_STEM_RED];
     const RsaMember m = rsa_member<PACKED>(mem, B, lone);
-    rsa_stem_body(Xs, Red, m.emb, m.emb_stride, m.codes, m.L, use_onehot, table, ws + m.ws_off, blockIdx.y,
+    rsa_stem_body<RSA_MAX_TILES>(Xs, Red, m.emb, m.emb_stride, m.codes, m.L, use_onehot, table, ws + m.ws_off, blockIdx.y,
                   ((int)blockIdx.x - m.tile0) * RSA_TILE);
+}
+// The long form of a stage (rnamsm_rsa_head_long): the same body on the layout with RSA_LONG_TILES tile-sum rows, lone only.
+__global__ __launch_bounds__(RSA_STEM_THREADS) void rsa_stem_long_kernel(const RsaMember lone, int use_onehot, const RsaTable table,
+                                                                         float* __restrict__ ws) {
+    __shared__ float Xs[RSA_STEM_XS];
+    __shared__ float Red[RSA_STEM_RED];
+    rsa_stem_body<RSA_LONG_TILES>(Xs, Red, lone.emb, lone.emb_stride, lone.codes, lone.L, use_onehot, table, ws, blockIdx.y,
+                                  (int)blockIdx.x * RSA_TILE);
 }
 
 // out[j] += sum_ci Wt[ci][co] * Xs[(pb + j)][ci], ci ascending: thread (co, 8 positions); Xs rows are read as wave-wide broadcasts
@@ -226,11 +241,12 @@ __device__ __forceinline__ void ln_tile(const float* Src, float* Dst, const floa
 }
 
 // ---------------------------------------------------------------------------------------------------------------- launch 2
+template <int TR>
 __device__ __forceinline__ void rsa_conv2_body(float* Xs, float* Ps, int L, const RsaTable& table, float* __restrict__ ws, int m,
                                                int p0) {
     const int t = threadIdx.x, co = t & 63, pg = t >> 6;
     const RsaModel M = rsa_model(table, m);
-    float* base = ws + (size_t)m * rsa_model_floats(L);
+    float* base = ws + (size_t)m * rsa_model_floats<TR>(L);
     const float* h1 = base;
     float* h2 = base + (size_t)2 * L * RSA_CH;
     float* part = base + (size_t)7 * L * RSA_CH;
@@ -265,12 +281,18 @@ __global__ __launch_bounds__(RSA_THREADS) void rsa_conv2_kernel(const RsaMember*
     __shared__ __attribute__((aligned(16))) float Xs[(RSA_TILE + 2) * RSA_CH];
     __shared__ float Ps[4 * RSA_CH];
     const RsaMember m = rsa_member<PACKED>(mem, B, lone);
-    rsa_conv2_body(Xs, Ps, m.L, table, ws + m.ws_off, blockIdx.y, ((int)blockIdx.x - m.tile0) * RSA_TILE);
+    rsa_conv2_body<RSA_MAX_TILES>(Xs, Ps, m.L, table, ws + m.ws_off, blockIdx.y, ((int)blockIdx.x - m.tile0) * RSA_TILE);
+}
+__global__ __launch_bounds__(RSA_THREADS) void rsa_conv2_long_kernel(const RsaMember lone, const RsaTable table, float* __restrict__ ws) {
+    __shared__ __attribute__((aligned(16))) float Xs[(RSA_TILE + 2) * RSA_CH];
+    __shared__ float Ps[4 * RSA_CH];
+    rsa_conv2_body<RSA_LONG_TILES>(Xs, Ps, lone.L, table, ws, blockIdx.y, (int)blockIdx.x * RSA_TILE);
 }
 
 // ---------------------------------------------------------------------------------------------------------------- launch 3
 // Sc: the squeeze-excite's scratch -- the channel means [64], the hidden units [4], the gate [64]
 constexpr int RSA_MIX_SC = 2 * RSA_CH + 4;
+template <int TR>
 __device__ __forceinline__ void rsa_mix_body(float* Ys, float* Xs, float* Sc, int L, const RsaTable& table, float* __restrict__ ws,
                                              int m, int p0) {
     float* Mean = Sc;
@@ -278,7 +300,7 @@ __device__ __forceinline__ void rsa_mix_body(float* Ys, float* Xs, float* Sc, in
     float* Gate = Sc + RSA_CH + 4;
     const int t = threadIdx.x, co = t & 63, pg = t >> 6;
     const RsaModel M = rsa_model(table, m);
-    float* base = ws + (size_t)m * rsa_model_floats(L);
+    float* base = ws + (size_t)m * rsa_model_floats<TR>(L);
     const float* sh = base + (size_t)L * RSA_CH;
     const float* h2 = base + (size_t)2 * L * RSA_CH;
     float* y = base + (size_t)3 * L * RSA_CH;
@@ -288,7 +310,17 @@ __device__ __forceinline__ void rsa_mix_body(float* Ys, float* Xs, float* Sc, in
     if (t < RSA_CH) {
         const int tiles = (L + RSA_TILE - 1) / RSA_TILE;
         float s = 0.f;
-        for (int i = 0; i < tiles; ++i) s += part[(size_t)i * RSA_CH + t];
+        if (TR <= RSA_SUM_GROUP) {
+            for (int i = 0; i < tiles; ++i) s += part[(size_t)i * RSA_CH + t];
+        } else {
+            // one ascending chain per group of 32 tiles, the group sums added ascending: the chain above when there is one group
+            for (int g0 = 0; g0 < tiles; g0 += RSA_SUM_GROUP) {
+                const int gn = min(tiles, g0 + RSA_SUM_GROUP);
+                float gs = 0.f;
+                for (int i = g0; i < gn; ++i) gs += part[(size_t)i * RSA_CH + t];
+                s = g0 ? s + gs : gs;
+            }
+        }
         Mean[t] = s / (float)L;
     }
     __syncthreads();
@@ -340,7 +372,13 @@ __global__ __launch_bounds__(RSA_THREADS) void rsa_mix_kernel(const RsaMember* _
     __shared__ __attribute__((aligned(16))) float Xs[RSA_TILE * RSA_CH];
     __shared__ float Sc[RSA_MIX_SC];
     const RsaMember m = rsa_member<PACKED>(mem, B, lone);
-    rsa_mix_body(Ys, Xs, Sc, m.L, table, ws + m.ws_off, blockIdx.y, ((int)blockIdx.x - m.tile0) * RSA_TILE);
+    rsa_mix_body<RSA_MAX_TILES>(Ys, Xs, Sc, m.L, table, ws + m.ws_off, blockIdx.y, ((int)blockIdx.x - m.tile0) * RSA_TILE);
+}
+__global__ __launch_bounds__(RSA_THREADS) void rsa_mix_long_kernel(const RsaMember lone, const RsaTable table, float* __restrict__ ws) {
+    __shared__ __attribute__((aligned(16))) float Ys[RSA_TILE * RSA_CH];
+    __shared__ __attribute__((aligned(16))) float Xs[RSA_TILE * RSA_CH];
+    __shared__ float Sc[RSA_MIX_SC];
+    rsa_mix_body<RSA_LONG_TILES>(Ys, Xs, Sc, lone.L, table, ws, blockIdx.y, (int)blockIdx.x * RSA_TILE);
 }
 
 // ---------------------------------------------------------------------------------------------------------------- launch 4
@@ -348,12 +386,13 @@ __global__ __launch_bounds__(RSA_THREADS) void rsa_mix_kernel(const RsaMember* _
 // exponentials, their sum and the weighted values (the softmax of the reference, no running rescale).  Sums over the keys are
 // two-level: inside a 64-key chunk, then over the chunks.
 // The keys are [0, L) of the member's own K / V and nothing else; logits / probs: the member's [K, L] (either may be null).
+template <int TR>
 __device__ __forceinline__ void rsa_attn_body(float* KV, float* Ys, float* Xs, int L, const RsaTable& table,
                                               const float* __restrict__ ws, int m, int p0, float* __restrict__ logits,
                                               float* __restrict__ probs) {
     const int t = threadIdx.x, co = t & 63, pg = t >> 6;
     const RsaModel M = rsa_model(table, m);
-    const float* base = ws + (size_t)m * rsa_model_floats(L);
+    const float* base = ws + (size_t)m * rsa_model_floats<TR>(L);
     const float* y = base + (size_t)3 * L * RSA_CH;
     const float* qg = base + (size_t)4 * L * RSA_CH;
     const float* kg = base + (size_t)5 * L * RSA_CH;
@@ -497,7 +536,14 @@ __global__ __launch_bounds__(RSA_THREADS) void rsa_attn_kernel(const RsaMember* 
     __shared__ __attribute__((aligned(16))) float Ys[RSA_TILE * RSA_CH];
     __shared__ __attribute__((aligned(16))) float Xs[RSA_TILE * RSA_CH];
     const RsaMember m = rsa_member<PACKED>(mem, B, lone);
-    rsa_attn_body(KV, Ys, Xs, m.L, table, ws + m.ws_off, blockIdx.y, ((int)blockIdx.x - m.tile0) * RSA_TILE, m.logits, m.probs);
+    rsa_attn_body<RSA_MAX_TILES>(KV, Ys, Xs, m.L, table, ws + m.ws_off, blockIdx.y, ((int)blockIdx.x - m.tile0) * RSA_TILE, m.logits, m.probs);
+}
+__global__ __launch_bounds__(RSA_THREADS) void rsa_attn_long_kernel(const RsaMember lone, const RsaTable table,
+                                                                    const float* __restrict__ ws) {
+    __shared__ __attribute__((aligned(16))) float KV[2 * RSA_KEYS * RSA_CH];
+    __shared__ __attribute__((aligned(16))) float Ys[RSA_TILE * RSA_CH];
+    __shared__ __attribute__((aligned(16))) float Xs[RSA_TILE * RSA_CH];
+    rsa_attn_body<RSA_LONG_TILES>(KV, Ys, Xs, lone.L, table, ws, blockIdx.y, (int)blockIdx.x * RSA_TILE, lone.logits, lone.probs);
 }
 
 constexpr size_t rsa_members_bytes(int B) { return ((size_t)B * sizeof(RsaMember) + 255) & ~(size_t)255; }
@@ -519,6 +565,23 @@ int rsa_launch(const RsaMember* mem, int B, const RsaMember& lone, int64_t tiles
     RNAMSM_CHECK_LAUNCH(PACKED ? "rsa_mix (packed)" : "rsa_mix");
     hipLaunchKernelGGL(rsa_attn_kernel<PACKED>, grid, dim3(RSA_THREADS), 0, s, mem, B, lone, table, ws);
     RNAMSM_CHECK_LAUNCH(PACKED ? "rsa_attn (packed)" : "rsa_attn");
+    return RNAMSM_OK;
+}
+
+// The four long launches of one member: ceil(L / 32) tiles, L up to RNAMSM_LONG_MAX_L.  weights: checked by the caller.
+int rsa_launch_long(const RsaMember& lone, int n_models, int use_onehot, const void* const* weights, float* ws, hipStream_t s) {
+    const int nw = RNAMSM_RSA_GLOBAL_WEIGHTS + RNAMSM_RSA_WEIGHTS_PER_MODEL * n_models;
+    RsaTable table;
+    for (int i = 0; i < RSA_TABLE_MAX; ++i) table.p[i] = i < nw ? weights[i] : nullptr;
+    const dim3 grid((unsigned)((lone.L + RSA_TILE - 1) / RSA_TILE), (unsigned)n_models);
+    hipLaunchKernelGGL(rsa_stem_long_kernel, grid, dim3(RSA_STEM_THREADS), 0, s, lone, use_onehot ? 1 : 0, table, ws);
+    RNAMSM_CHECK_LAUNCH("rsa_stem (long)");
+    hipLaunchKernelGGL(rsa_conv2_long_kernel, grid, dim3(RSA_THREADS), 0, s, lone, table, ws);
+    RNAMSM_CHECK_LAUNCH("rsa_conv2 (long)");
+    hipLaunchKernelGGL(rsa_mix_long_kernel, grid, dim3(RSA_THREADS), 0, s, lone, table, ws);
+    RNAMSM_CHECK_LAUNCH("rsa_mix (long)");
+    hipLaunchKernelGGL(rsa_attn_long_kernel, grid, dim3(RSA_THREADS), 0, s, lone, table, ws);
+    RNAMSM_CHECK_LAUNCH("rsa_attn (long)");
     return RNAMSM_OK;
 }
 
@@ -555,6 +618,35 @@ extern "C" int rnamsm_rsa_head(const float* emb, int64_t emb_row_stride, const u
     const RsaMember lone = {emb, emb_row_stride, base_codes, logits, probs, 0, L, 0, {0, 0}};
     return rsa_launch<false>(nullptr, 1, lone, (L + RSA_TILE - 1) / RSA_TILE, n_models, use_onehot, weights, static_cast<float*>(workspace),
                              static_cast<hipStream_t>(stream));
+}
+
+extern "C" size_t rnamsm_rsa_head_long_workspace_bytes(int L, int n_models) {
+    if (L < 1 || L > RNAMSM_LONG_MAX_L || n_models < 1 || n_models > RNAMSM_RSA_MAX_MODELS) return 0;
+    return (size_t)n_models * rsa_model_floats<RSA_LONG_TILES>(L) * sizeof(float);
+}
+
+extern "C" int rnamsm_rsa_head_long(const float* emb, int64_t emb_row_stride, const uint8_t* base_codes, int L, int n_models,
+                                    int use_onehot, const void* const* weights, float* probs, float* logits, void* workspace,
+                                    size_t workspace_bytes, void* stream) {
+    // every refusal comes before the first launch
+    RNAMSM_CHECK_ARG(emb, "rsa_head_long: null pointer (emb)");
+    RNAMSM_CHECK_ARG(base_codes, "rsa_head_long: null pointer (base_codes)");
+    RNAMSM_CHECK_ARG(weights, "rsa_head_long: null pointer (weights)");
+    RNAMSM_CHECK_ARG(workspace, "rsa_head_long: null pointer (workspace)");
+    RNAMSM_CHECK_ARG(logits || probs, "rsa_head_long: neither probs nor logits given");
+    RNAMSM_CHECK_ARG(L >= 1 && L <= RNAMSM_LONG_MAX_L, "rsa_head_long: L=%d outside [1, %d]", L, RNAMSM_LONG_MAX_L);
+    RNAMSM_CHECK_ARG(n_models >= 1 && n_models <= RNAMSM_RSA_MAX_MODELS, "rsa_head_long: n_models=%d outside [1, %d]", n_models,
+                     RNAMSM_RSA_MAX_MODELS);
+    RNAMSM_CHECK_ARG(emb_row_stride >= RSA_EMB, "rsa_head_long: embedding row stride %lld < %d", (long long)emb_row_stride, RSA_EMB);
+    const size_t need = rnamsm_rsa_head_long_workspace_bytes(L, n_models);
+    RNAMSM_CHECK_ARG(workspace_bytes >= need, "rsa_head_long: workspace of %zu bytes, %zu needed", workspace_bytes, need);
+    RNAMSM_CHECK_ARG(aligned16(emb), "rsa_head_long: emb is not 16-byte aligned");
+    RNAMSM_CHECK_ARG(aligned16(workspace), "rsa_head_long: workspace is not 16-byte aligned");
+    RNAMSM_CHECK_ARG((reinterpret_cast<uintptr_t>(probs) & 3u) == 0, "rsa_head_long: probs is not 4-byte aligned");
+    RNAMSM_CHECK_ARG((reinterpret_cast<uintptr_t>(logits) & 3u) == 0, "rsa_head_long: logits is not 4-byte aligned");
+    if (int rc = rsa_check_weights("rsa_head_long", weights, n_models, use_onehot)) return rc;
+    const RsaMember lone = {emb, emb_row_stride, base_codes, logits, probs, 0, L, 0, {0, 0}};
+    return rsa_launch_long(lone, n_models, use_onehot, weights, static_cast<float*>(workspace), static_cast<hipStream_t>(stream));
 }
 
 extern "C" size_t rnamsm_rsa_head_packed_workspace_bytes(int B, const int* Ls, int n_models) {

@@ -21,7 +21,9 @@
 namespace rsatext {
 
 constexpr int MAX_L = 1024, MAX_MODELS = 8;
+constexpr int LONG_MAX_L = 4096;                  // the long entry (rnamsm_rsa_text_long): still four index digits
 constexpr int LINE_BYTES = 23;                    // "1024\t\tG\t\t400.00\t\t1.000\n": bytes of the longest line at L = MAX_L
+static_assert(LONG_MAX_L <= 9999, "a line of LINE_BYTES bytes holds four index digits");
 constexpr uint32_t ONE_BITS = 0x3f800000u;      // 1.0f: a member value's domain is the bit patterns [0, ONE_BITS]
 
 // the per-base scale of the letter as the table prints it (T scales as U); 0: a letter the host path replaces by a drawn base

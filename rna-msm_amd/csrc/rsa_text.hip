@@ -19,6 +19,10 @@ namespace {
 
 static_assert(rsatext::MAX_L == RNAMSM_RSA_MAX_L && rsatext::MAX_MODELS == RNAMSM_RSA_MAX_MODELS, "one set of limits");
 static_assert(rsatext::LINE_BYTES == RNAMSM_RSA_TEXT_LINE_MAX, "one bound");
+static_assert(rsatext::LONG_MAX_L == RNAMSM_LONG_MAX_L, "one long limit");
+// the kernel's running base and prefix scan are uint32 byte counts within one body, and k * L + p an int index of the values
+static_assert((uint64_t)rsatext::LINE_BYTES * rsatext::LONG_MAX_L < (1ull << 31) &&
+              (uint64_t)rsatext::MAX_MODELS * rsatext::LONG_MAX_L < (1ull << 31), "32-bit offsets at the long limit");
 
 constexpr int RT_THREADS = 256;
 
@@ -109,15 +113,17 @@ __global__ __launch_bounds__(RT_THREADS) void rsa_text_kernel(const MemberChunk<
     }
 }
 
-// Every refusal, then the launches.  who: the entry point's name; lone: the one item is the call's own arguments, not "member 0".
-int rsa_text_run(const char* who, bool lone, const rnamsm_rsa_text_item* items, int B, int n_models, hipStream_t s) {
+// Every refusal, then the launches.  who: the entry point's name; lone: the one item is the call's own arguments, not "member 0";
+// max_L: the entry point's limit (the kernel is one for every L: as many passes of 256 positions as L needs).
+int rsa_text_run(const char* who, bool lone, const rnamsm_rsa_text_item* items, int B, int n_models, hipStream_t s,
+                 int max_L = RNAMSM_RSA_MAX_L) {
     RNAMSM_CHECK_ARG(n_models >= 1 && n_models <= RNAMSM_RSA_MAX_MODELS, "%s: n_models=%d outside [1, %d]", who, n_models,
                      RNAMSM_RSA_MAX_MODELS);
     char where[32] = "";
     for (int b = 0; b < B; ++b) {
         const rnamsm_rsa_text_item& it = items[b];
         if (!lone) snprintf(where, sizeof(where), "member %d: ", b);
-        RNAMSM_CHECK_ARG(it.L >= 1 && it.L <= RNAMSM_RSA_MAX_L, "%s: %sL=%d outside [1, %d]", who, where, it.L, RNAMSM_RSA_MAX_L);
+        RNAMSM_CHECK_ARG(it.L >= 1 && it.L <= max_L, "%s: %sL=%d outside [1, %d]", who, where, it.L, max_L);
         RNAMSM_CHECK_ARG(it.rsa && it.letters && it.text && it.counts, "%s: %snull pointer", who, where);
         RNAMSM_CHECK_ARG(((uintptr_t)it.rsa & 3u) == 0 && ((uintptr_t)it.counts & 3u) == 0, "%s: %srsa or counts is not 4-byte aligned",
                          who, where);
@@ -151,6 +157,17 @@ extern "C" int rnamsm_rsa_text(const float* rsa, const uint8_t* letters, int L, 
                                double* ens, void* stream) {
     const rnamsm_rsa_text_item item = {rsa, letters, L, text, counts, ens};
     return rsa_text_run("rsa_text", true, &item, 1, n_models, static_cast<hipStream_t>(stream));
+}
+
+extern "C" size_t rnamsm_rsa_text_long_bytes(int L, int n_models) {
+    if (L < 1 || L > RNAMSM_LONG_MAX_L || n_models < 1 || n_models > RNAMSM_RSA_MAX_MODELS) return 0;
+    return (size_t)(n_models + 1) * RNAMSM_RSA_TEXT_LINE_MAX * L;
+}
+
+extern "C" int rnamsm_rsa_text_long(const float* rsa, const uint8_t* letters, int L, int n_models, uint8_t* text, int32_t* counts,
+                                    double* ens, void* stream) {
+    const rnamsm_rsa_text_item item = {rsa, letters, L, text, counts, ens};
+    return rsa_text_run("rsa_text_long", true, &item, 1, n_models, static_cast<hipStream_t>(stream), RNAMSM_LONG_MAX_L);
 }
 
 extern "C" int rnamsm_rsa_text_packed(const rnamsm_rsa_text_item* items, int B, int n_models, void* stream) {

@@ -54,7 +54,8 @@ LM_MAX_D, LM_MAX_V, LM_MAX_BATCH, LM_MAX_ROWS = 1024, 64, 1024, 1 << 24
 W_LM = ("dense.weight", "dense.bias", "layer_norm.weight", "layer_norm.bias", "weight", "bias")     # the weight table's order
 LM_OUTPUTS = ("logits", "logp", "scores", "nll")
 STITCH_MAX_L, STITCH_MAX_H = 1 << 19, 1 << 16      # rnamsm_stitch_rows / _pairs
-LONG_MAX_L = 4096                  # rnamsm_contact_head_long / _ss_head_long / _ss_prob_text_long / _ss_pairs_long: a stitched alignment
+LONG_MAX_L = 4096                  # rnamsm_contact_head_long / _ss_head_long / _ss_prob_text_long / _ss_pairs_long / _rsa_head_long /
+                                   # _rsa_text_long: a stitched alignment
 
 
 class ModelDims(ctypes.Structure):
@@ -201,6 +202,11 @@ _SIGNATURES = {
     "rnamsm_rsa_text_bytes": (c_size_t, [c_int, c_int]),
     "rnamsm_rsa_text": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     "rnamsm_rsa_text_packed": (c_int, [POINTER(RsaTextItem), c_int, c_int, c_void_p]),
+    "rnamsm_rsa_head_long_workspace_bytes": (c_size_t, [c_int, c_int]),
+    "rnamsm_rsa_head_long": (c_int, [c_void_p, c_int64, c_void_p, c_int, c_int, c_int, POINTER(c_void_p), c_void_p, c_void_p, c_void_p,
+                                     c_size_t, c_void_p]),
+    "rnamsm_rsa_text_long_bytes": (c_size_t, [c_int, c_int]),
+    "rnamsm_rsa_text_long": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     "rnamsm_greedy_select_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
     "rnamsm_greedy_select": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
     "rnamsm_msa_weights": (c_int, [c_void_p, c_int, c_int, c_double, c_void_p, c_void_p]),

@@ -106,14 +106,15 @@ class DataConfig:                       # RNA_MSM_Inference.py:20-32
     # (RandomCropDataset, dataset.py:142-158: <cls> and one random window; the same draws, the same files).  "windows" = nothing is
     # cropped or drawn: the alignment runs as overlapping windows of max_seqlen - 1 columns whose outputs are blended on the device
     # (MSATransformer.forward_windows), and <id>_emb.npy / <id>_atp.npy hold the FULL (L, 768) / (120, L, L).  On such an alignment
-    # lm_scores=wt runs on the stitched emb; the SS, RSA and contact heads and lm_scores=masked are skipped with one printed line (data.long_heads below lets the SS and contact heads through).
+    # lm_scores=wt runs on the stitched emb; the SS, RSA and contact heads and lm_scores=masked are skipped with one printed line (data.long_heads below lets the SS, RSA and contact heads through).
     long_msa: str = "crop"
     # with long_msa=windows: the distance between window starts, within [ceil(W / 2), W] for W = max_seqlen - 1; 0 = ceil(W / 2)
     window_stride: int = 0
-    # with long_msa=windows: what the pair heads do on a stitched alignment.  "skip" (default) = as before, one printed line per
-    # head.  "stitched" = the contact head and the SS head (exact fp32 only) run on the stitched atp through the long entry points
-    # (rnamsm_contact_head_long, rnamsm_ss_head_long, rnamsm_ss_prob_text_long, rnamsm_ss_pairs_long) for L up to 4096 and write
-    # their usual files at the full L; the RSA head, lm_scores=masked, an SS head under ss_gemm_dtype=bf16 and any longer alignment
+    # with long_msa=windows: what the downstream heads do on a stitched alignment.  "skip" (default) = as before, one printed line per
+    # head.  "stitched" = the contact head and the SS head (exact fp32 only) run on the stitched atp and the RSA head on the stitched
+    # emb through the long entry points (rnamsm_contact_head_long, rnamsm_ss_head_long, rnamsm_ss_prob_text_long,
+    # rnamsm_ss_pairs_long, rnamsm_rsa_head_long, rnamsm_rsa_text_long) for L up to 4096 and write their usual files at the full L;
+    # lm_scores=masked, an SS head under ss_gemm_dtype=bf16 and any longer alignment
     # stay skipped, each with a line that names the reason.  Alignments that are not stitched are untouched by the key.
     long_heads: str = "skip"
 

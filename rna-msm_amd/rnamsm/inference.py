@@ -312,8 +312,8 @@ def extract_feat(cfg: Config, model: Optional[MSATransformer] = None, gather_to_
     # overlapping windows stitched on the device (MSATransformer.forward_windows): its files hold the full L
     windowing = check_long_msa(getattr(cfg.data, "long_msa", "crop")) == "windows"
     window_stride = int(getattr(cfg.data, "window_stride", 0))
-    # data.long_heads=stitched: on such an alignment the contact head and the exact-fp32 SS head run on the stitched atp through the
-    # long entry points (L <= _lib.LONG_MAX_L); "skip" leaves everything as it was, the printed lines included
+    # data.long_heads=stitched: on such an alignment the contact head and the exact-fp32 SS head run on the stitched atp, and the RSA
+    # head on the stitched emb, through the long entry points (L <= _lib.LONG_MAX_L); "skip" leaves everything as it was, the printed lines included
     long_heads = check_long_heads(getattr(cfg.data, "long_heads", "skip")) == "stitched"
     device = torch.device(cfg.data.device)
     if device.type != "cuda":
@@ -416,15 +416,13 @@ def extract_feat(cfg: Config, model: Optional[MSATransformer] = None, gather_to_
         with the key off: the line printed then names no reason, as before."""
         if not long_heads:
             return ""
-        if isinstance(h, rsa.RSAHead):
-            return f"the RSA head's attention is tiled to L <= {_lib.RSA_MAX_L}"
         if isinstance(h, lm.LMHead):
             return "the masked scan would run L forwards per window"
         if L > _lib.LONG_MAX_L:
             return f"L exceeds the long heads' limit of {_lib.LONG_MAX_L}"
         if isinstance(h, ss.SSHead) and h.model.gemm_dtype != "f32":
             return f"there is no long SS head under data.ss_gemm_dtype={h.model.gemm_dtype}"
-        return None if isinstance(h, (ss.SSHead, contacts.ContactHead)) else "it has no long entry point"
+        return None if isinstance(h, (ss.SSHead, rsa.RSAHead, contacts.ContactHead)) else "it has no long entry point"
 
     def emit(rna_id: str, emb: torch.Tensor, atp: torch.Tensor, after: Optional[torch.cuda.Event] = None, records=()) -> None:
         """records: this alignment's record of every head that is on, in the order of `heads`; each becomes one writer job (but

@@ -953,16 +953,39 @@ def rsa_head_packed(embs: Sequence[torch.Tensor], codes: Sequence[torch.Tensor],
     return outs
 
 
-def _rsa_text_operands(fn: str, rsa: torch.Tensor, letters: torch.Tensor, name: str, letters_name: str):
-    """One alignment of rsa_text / rsa_text_packed as the library reads it -> (rsa, letters, K, L)."""
+def _long_range(fn: str, t, name: str, dim: int) -> None:
+    """The range of a long RSA call, before anything else is asked of the operand: a length out of range is wrong on any device."""
+    if isinstance(t, torch.Tensor) and t.dim() == 2 and not 1 <= t.shape[dim] <= _lib.LONG_MAX_L:
+        raise ValueError(f"{fn}: {name}: L = {t.shape[dim]} outside [1, {_lib.LONG_MAX_L}]")
+
+
+@_on_operand_device
+def rsa_head_long(emb: torch.Tensor, base_codes: torch.Tensor, ptrs, n_models: int, use_onehot: bool, want: str = "probs") -> torch.Tensor:
+    """rsa_head for L up to LONG_MAX_L (rnamsm_rsa_head_long: the same four stages on a workspace with 128 tile-sum rows per
+    model) -> [n_models, L]; the bits of rsa_head for an L both accept."""
+    _want("rsa_head_long", want)
+    _long_range("rsa_head_long", emb, "emb", 0)
+    emb, stride, base_codes, L = _rsa_operands("rsa_head_long", emb, base_codes, "emb", "base_codes")
+    lib = _lib.load()
+    ws = torch.empty(max(lib.rnamsm_rsa_head_long_workspace_bytes(L, n_models), 16), dtype=torch.uint8, device=emb.device)
+    out = torch.empty(n_models, L, device=emb.device, dtype=torch.float32)
+    ptr = out.data_ptr()
+    _lib.check(lib.rnamsm_rsa_head_long(emb.data_ptr(), stride, base_codes.data_ptr(), L, n_models, 1 if use_onehot else 0, ptrs,
+                                        ptr if want == "probs" else None, ptr if want == "logits" else None, ws.data_ptr(),
+                                        ws.numel(), _stream()))
+    return out
+
+
+def _rsa_text_operands(fn: str, rsa: torch.Tensor, letters: torch.Tensor, name: str, letters_name: str, max_L: int = _lib.RSA_MAX_L):
+    """One alignment of rsa_text / rsa_text_packed / rsa_text_long as the library reads it -> (rsa, letters, K, L)."""
     _dev(rsa, name)
     if rsa.dim() != 2:
         raise ValueError(f"{fn}: {name} must be [n_models, L], got {tuple(rsa.shape)}")
     K, L = rsa.shape
     if not 1 <= K <= _lib.RSA_MAX_MODELS:
         raise ValueError(f"{fn}: {name}: {K} members outside [1, {_lib.RSA_MAX_MODELS}]")
-    if not 1 <= L <= _lib.RSA_MAX_L:
-        raise ValueError(f"{fn}: {name}: L = {L} outside [1, {_lib.RSA_MAX_L}]")
+    if not 1 <= L <= max_L:
+        raise ValueError(f"{fn}: {name}: L = {L} outside [1, {max_L}]")
     _dev(letters, letters_name, torch.uint8)
     if letters.dim() != 1 or letters.shape[0] != L:
         raise ValueError(f"{fn}: {letters.shape[0] if letters.dim() == 1 else tuple(letters.shape)} letters for {name} of L = {L}")
@@ -1009,6 +1032,23 @@ def _rsa_text_run(_fn: str, rsa, letters):
     items = (_lib.RsaTextItem * B)(*(_lib.RsaTextItem(*a) for a in args))
     _lib.check(lib.rnamsm_rsa_text_packed(items, B, K, _stream()))
     return outs
+
+
+@_on_operand_device
+def rsa_text_long(rsa: torch.Tensor, letters: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """rsa_text for L up to LONG_MAX_L (rnamsm_rsa_text_long: the same kernel, as many passes of 256 positions as L needs) -> (text
+    uint8 [(K + 1) x 23 L], counts int32 [K + 3], ens float64 [2, L]), read as rsa_text's results are."""
+    _long_range("rsa_text_long", rsa, "rsa", 1)
+    rsa, letters, K, L = _rsa_text_operands("rsa_text_long", rsa, letters, "rsa", "letters", _lib.LONG_MAX_L)
+    if letters.device != rsa.device:
+        raise ValueError(f"rsa_text_long: rsa / letters lie on {rsa.device} / {letters.device}")
+    lib = _lib.load()
+    text = torch.empty(lib.rnamsm_rsa_text_long_bytes(L, K), dtype=torch.uint8, device=rsa.device)
+    counts = torch.empty(K + 3, dtype=torch.int32, device=rsa.device)
+    ens = torch.empty(2, L, dtype=torch.float64, device=rsa.device)
+    _lib.check(lib.rnamsm_rsa_text_long(rsa.data_ptr(), letters.data_ptr(), L, K, text.data_ptr(), counts.data_ptr(), ens.data_ptr(),
+                                        _stream()))
+    return text, counts, ens
 
 
 class LMWeights(NamedTuple):

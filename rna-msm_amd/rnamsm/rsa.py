@@ -3,7 +3,8 @@
 `RSAPredictor` carries the parameters of one of the reference's `FrameModel(Cin, 1, planes=64, depth=1)` networks under the same
 names and shapes, so a state_dict taken from an upstream model loads with strict=True; `RSAEnsemble` holds K of them and the
 normalisation statistics, and its arithmetic is one HIP entry point (rnamsm_rsa_head: all members in four launches, exact fp32)
-that reads the [L, 768] embedding where it lies on the device; `predict_many` runs a list of alignments through the same four
+that reads the [L, 768] embedding where it lies on the device; `predict_long` does the same up to L = 4096 (rnamsm_rsa_head_long,
+for a stitched long alignment); `predict_many` runs a list of alignments through the same four
 launches (rnamsm_rsa_head_packed), every result the lone call's bits; `predict_text[_many]` adds the bodies of the result tables,
 formatted on the device (rnamsm_rsa_text: `table_text`).  `load_ensemble` reads an upstream model directory -- its `.pt`
 files are pickled whole modules and are opened with no upstream code importable -- and `write_rsa_files` is the reference's
@@ -211,7 +212,7 @@ class RSAEnsemble(nn.Module):
         return super()._apply(fn, *args, **kwargs)
 
     @staticmethod
-    def _codes_of(emb, seq, name: str, seq_name: str, on_device: bool) -> torch.Tensor:
+    def _codes_of(emb, seq, name: str, seq_name: str, on_device: bool, max_L: int = _lib.RSA_MAX_L) -> torch.Tensor:
         """The checks of one (embedding, sequence) pair, named as the caller's arguments (`emb` / `embs[3]`) -> its base codes, flat.
         on_device: refuse an embedding off the HIP device here, before its shape (False: the caller does that for every item
         afterwards)."""
@@ -220,8 +221,8 @@ class RSAEnsemble(nn.Module):
         if emb.dim() != 2 or emb.shape[1] != EMBED_DIM:
             raise ValueError(f"RSAEnsemble: {name} must be [L, {EMBED_DIM}], got {tuple(emb.shape)}")
         L = emb.shape[0]
-        if not 1 <= L <= _lib.RSA_MAX_L:
-            raise ValueError(f"RSAEnsemble: {name}: L = {L} outside the head's range [1, {_lib.RSA_MAX_L}]")
+        if not 1 <= L <= max_L:
+            raise ValueError(f"RSAEnsemble: {name}: L = {L} outside the head's range [1, {max_L}]")
         if isinstance(seq, str):
             seq = base_codes(seq)
         codes = torch.as_tensor(seq).reshape(-1)
@@ -241,6 +242,27 @@ class RSAEnsemble(nn.Module):
         return self._run(emb, seq, "logits")
 
     forward = predict
+
+    def _run_long(self, emb: torch.Tensor, seq, want: str) -> torch.Tensor:
+        # the shape and the length first: they are wrong on any device
+        codes = self._codes_of(emb, seq, "emb", "seq", False, _lib.LONG_MAX_L)
+        if not emb.is_cuda:
+            raise _lib.RnamsmError("RSAEnsemble: emb must be a tensor on the HIP device (no CPU path exists)")
+        ptrs, _ = self._packed_weights()
+        return ops.rsa_head_long(emb, codes.to(device=emb.device, dtype=torch.uint8), ptrs, len(self.members), self.use_onehot, want)
+
+    def predict_long(self, emb: torch.Tensor, seq) -> torch.Tensor:
+        """predict() for L up to LONG_MAX_L (rnamsm_rsa_head_long: a stitched long alignment's embedding); the bits of predict()
+        for an L both accept."""
+        return self._run_long(emb, seq, "probs")
+
+    def logits_long(self, emb: torch.Tensor, seq) -> torch.Tensor:
+        return self._run_long(emb, seq, "logits")
+
+    def predict_text_long(self, emb: torch.Tensor, seq, letters=None):
+        """predict_text() for L up to LONG_MAX_L -> ([K, L] RSA, table_text_long of it)."""
+        values = self.predict_long(emb, seq)
+        return values, table_text_long(values, _letters_for(seq, letters, values.device))
 
     def _run_many(self, embs: Sequence[torch.Tensor], seqs: Sequence, want: str) -> List[torch.Tensor]:
         embs, seqs = list(embs), list(seqs)
@@ -391,6 +413,11 @@ def table_text(values: torch.Tensor, letters: torch.Tensor):
     return ops.rsa_text(values, letters)
 
 
+def table_text_long(values: torch.Tensor, letters: torch.Tensor):
+    """table_text() for L up to LONG_MAX_L (rnamsm_rsa_text_long): the same record, the host writer's bytes for every L in range."""
+    return ops.rsa_text_long(values, letters)
+
+
 def table_text_many(values: Sequence[torch.Tensor], letters: Sequence[torch.Tensor]):
     """table_text() of every (values[b], letters[b]) in as few calls as the batch limit allows; each result is the lone call's."""
     values, letters = list(values), list(letters)
@@ -522,6 +549,12 @@ class RSAHead:
         formatter runs behind the head."""
         values = self.model.predict(emb, self.base_lut[tokens])
         return RSAResult(values, tokens, tuple(table_text(values, self.letters_lut[tokens])) if self.text_on else None)
+
+    def one_long(self, emb: torch.Tensor, atp: torch.Tensor, tokens: torch.Tensor) -> RSAResult:
+        """one() on the stitched embedding of a long alignment (data.long_heads=stitched), L up to LONG_MAX_L: the same record through
+        the long entry points; with the formatter off the tables are left to the host writer, which has no length limit."""
+        values = self.model.predict_long(emb, self.base_lut[tokens])
+        return RSAResult(values, tokens, tuple(table_text_long(values, self.letters_lut[tokens])) if self.text_on else None)
 
     def many(self, embs: Sequence[torch.Tensor], atps: Sequence[torch.Tensor], tokens: Sequence[torch.Tensor]) -> List[RSAResult]:
         """A group in one launch set per stage (predict_many, table_text_many): every member's record holds the bits and bytes of
