@@ -349,7 +349,9 @@ int rnamsm_contact_head(const float* row_attn, const float* weight, const float*
  * The kernels are those of rnamsm_contact_head with the layout as a parameter, and every sum keeps its order, so contacts are
  * BIT-IDENTICAL to rnamsm_contact_head on the [nch, L+1, L+1] maps whose [1:, 1:] part holds the same values.
  * Refused (RNAMSM_ERR_INVALID) before anything is enqueued: a null pointer, L outside [1, RNAMSM_CONTACT_MAX_L], nch <= 0,
- * plane_stride < L * L, a short workspace. */
+ * plane_stride < L * L, atp, contacts or workspace not 4-byte aligned (the checks of rnamsm_contact_head_long, in its order: the
+ * two entries are one function under two names and limits; a pointer the library or an allocator hands out is always aligned), a
+ * short workspace. */
 #define RNAMSM_CONTACT_MAX_L 1023
 int rnamsm_contact_head_atp(const float* atp, int64_t plane_stride, int L, int nch, const float* weight, const float* bias,
                             float* contacts, void* workspace, size_t workspace_bytes, void* stream);
@@ -623,10 +625,11 @@ int rnamsm_ss_pairs_packed(const rnamsm_ss_pairs_item* items, int B, void* works
  * calls only (a wide alignment never joins a group).  The entry points above keep their limits; each of these gives, for an L both
  * accept, the BITS (bytes) of its namesake above.  4096: four decimal digits in .ct / .bpseq; L^2 and 120 L^2 are int32 element
  * counts; the atp is 8 GB.
- *   rnamsm_contact_head_long    rnamsm_contact_head_atp's arguments, kernels and summation order.  Symmetrise and APC are taken over
+ *   rnamsm_contact_head_long    rnamsm_contact_head_atp under another limit: the same function, so the same checks, kernels and
+ *                               summation order.  Symmetrise and APC are taken over
  *                               the whole [L, L] map: a pair no window holds (+0.0 in every channel) takes part as 0.  workspace:
  *                               rnamsm_contact_head_long_workspace_bytes(L, nch) = (nch L + nch) floats, 4-byte aligned.
- *   rnamsm_ss_head_long         rnamsm_ss_head's arguments and kernels (exact fp32; there is no bf16 long head).  workspace:
+ *   rnamsm_ss_head_long         rnamsm_ss_head under another limit, the same function (exact fp32; there is no bf16 long head).  workspace:
  *                               rnamsm_ss_head_long_workspace_bytes(L) = 2 x 48 L^2 floats (6.4 GB at the limit), 16-byte aligned.
  *   rnamsm_ss_prob_text_long    rnamsm_ss_prob_text's arguments, kernel and fallback word; rnamsm_ss_prob_text_long_bytes(L) = 25 L^2
  *                               (419 MB at the limit).
@@ -775,8 +778,9 @@ int rnamsm_rsa_text_packed(const rnamsm_rsa_text_item* items, int B, int n_model
  * [1, RNAMSM_LONG_MAX_L].  Lone calls only (a wide alignment never joins a group).  rnamsm_rsa_head and rnamsm_rsa_text keep their
  * limits and their workspace layout; each of these gives, for an L both accept, the BITS (bytes) of its namesake above: logits,
  * probs, text, counts, ens and the two flag words.
- *   rnamsm_rsa_head_long   rnamsm_rsa_head's arguments, weight table, alignment and emb_row_stride rules, and its four stage bodies
- *                          on a second workspace layout: per model 7 L 64 floats (h1, shortcut, h2, y, q, k, v) and then
+ *   rnamsm_rsa_head_long   rnamsm_rsa_head's arguments, weight table and checks (one function under two names and limits), and the
+ *                          same kernel template per stage, instantiated for a second workspace layout: per model 7 L 64 floats
+ *                          (h1, shortcut, h2, y, q, k, v) and then
  *                          RNAMSM_LONG_MAX_L / 32 = 128 rows of 64 tile sums, of which the first ceil(L / 32) are written --
  *                          rnamsm_rsa_head_long_workspace_bytes(L, n_models) = n_models (7 L 64 + 128 x 64) x 4 bytes (7.4 MB per
  *                          model at the limit), 16-byte aligned.  The squeeze mean adds the tile sums in one ascending chain per

@@ -216,21 +216,37 @@ extern "C" int rnamsm_contact_head(const float* row_attn, const float* weight, c
     return contact_lone(row_attn, (int64_t)C * C, C, 1, C - 1, nch, weight, bias, contacts, workspace, static_cast<hipStream_t>(stream));
 }
 
-extern "C" int rnamsm_contact_head_atp(const float* atp, int64_t plane_stride, int L, int nch, const float* weight, const float* bias,
-                                       float* contacts, void* workspace, size_t workspace_bytes, void* stream) {
-    RNAMSM_CHECK_ARG(atp && weight && bias && contacts && workspace, "contact_head_atp: null pointer");
-    RNAMSM_CHECK_ARG(L >= 1 && L <= RNAMSM_CONTACT_MAX_L, "contact_head_atp: L=%d outside [1, %d]", L, RNAMSM_CONTACT_MAX_L);
-    RNAMSM_CHECK_ARG(nch > 0, "contact_head_atp: nch=%d", nch);
-    RNAMSM_CHECK_ARG(plane_stride >= (int64_t)L * L, "contact_head_atp: plane stride %lld < L * L = %lld", (long long)plane_stride,
+// The lone call on stripped maps, written once for rnamsm_contact_head_atp (who = "contact_head_atp", max_L = RNAMSM_CONTACT_MAX_L)
+// and rnamsm_contact_head_long ("contact_head_long", RNAMSM_LONG_MAX_L: the stitched atp of a long alignment), as ss_head_lone
+// is: one list of refusals under the entry's own name and limit, then the three kernels on the same descriptor, so the same bits
+// where both run.  Every refusal comes before the first launch: a refused call leaves the stream and the outputs untouched.
+// Beyond 1023: every offset into the maps, the contacts and the slab -- ch * plane_stride, i * ld + j, i * T + j, ch * T + i -- is
+// int64_t in the kernels; the grids are nch x ceil(T / 256) <= nch x 16 and ceil(T / 32)^2 <= 2^14 blocks.
+static int contact_atp_lone(const char* who, int max_L, const float* atp, int64_t plane_stride, int L, int nch, const float* weight,
+                            const float* bias, float* contacts, void* workspace, size_t workspace_bytes, void* stream) {
+    RNAMSM_CHECK_ARG(atp, "%s: null pointer (atp)", who);
+    RNAMSM_CHECK_ARG(weight, "%s: null pointer (weight)", who);
+    RNAMSM_CHECK_ARG(bias, "%s: null pointer (bias)", who);
+    RNAMSM_CHECK_ARG(contacts, "%s: null pointer (contacts)", who);
+    RNAMSM_CHECK_ARG(workspace, "%s: null pointer (workspace)", who);
+    RNAMSM_CHECK_ARG(L >= 1 && L <= max_L, "%s: L=%d outside [1, %d]", who, L, max_L);
+    RNAMSM_CHECK_ARG(nch > 0, "%s: nch=%d", who, nch);
+    RNAMSM_CHECK_ARG(plane_stride >= (int64_t)L * L, "%s: plane stride %lld < L * L = %lld", who, (long long)plane_stride,
                      (long long)L * L);
-    RNAMSM_CHECK_ARG(workspace_bytes >= contact_slab_floats(L, nch) * sizeof(float), "contact_head_atp: workspace too small");
+    RNAMSM_CHECK_ARG(((uintptr_t)atp & 3u) == 0, "%s: atp is not 4-byte aligned", who);
+    RNAMSM_CHECK_ARG(((uintptr_t)contacts & 3u) == 0, "%s: contacts is not 4-byte aligned", who);
+    RNAMSM_CHECK_ARG(((uintptr_t)workspace & 3u) == 0, "%s: workspace is not 4-byte aligned", who);
+    const size_t need = contact_slab_floats(L, nch) * sizeof(float);
+    RNAMSM_CHECK_ARG(workspace_bytes >= need, "%s: workspace too small (workspace of %zu bytes, %zu needed)", who, workspace_bytes, need);
     return contact_lone(atp, plane_stride, L, 0, L, nch, weight, bias, contacts, workspace, static_cast<hipStream_t>(stream));
 }
 
-// The stitched atp of a long alignment, L up to RNAMSM_LONG_MAX_L: the three kernels of rnamsm_contact_head_atp on the same
-// descriptor, so the same bits where both run.  Beyond 1023: every offset into the maps, the contacts and the slab -- ch *
-// plane_stride, i * ld + j, i * T + j, ch * T + i -- is int64_t in the kernels; the grids are nch x ceil(T / 256) <= nch x 16 and
-// ceil(T / 32)^2 <= 2^14 blocks.
+extern "C" int rnamsm_contact_head_atp(const float* atp, int64_t plane_stride, int L, int nch, const float* weight, const float* bias,
+                                       float* contacts, void* workspace, size_t workspace_bytes, void* stream) {
+    return contact_atp_lone("contact_head_atp", RNAMSM_CONTACT_MAX_L, atp, plane_stride, L, nch, weight, bias, contacts, workspace,
+                            workspace_bytes, stream);
+}
+
 extern "C" size_t rnamsm_contact_head_long_workspace_bytes(int L, int nch) {
     if (L < 1 || L > RNAMSM_LONG_MAX_L || nch <= 0) return 0;
     return contact_slab_floats(L, nch) * sizeof(float);
@@ -238,22 +254,8 @@ extern "C" size_t rnamsm_contact_head_long_workspace_bytes(int L, int nch) {
 
 extern "C" int rnamsm_contact_head_long(const float* atp, int64_t plane_stride, int L, int nch, const float* weight, const float* bias,
                                         float* contacts, void* workspace, size_t workspace_bytes, void* stream) {
-    // every refusal comes before the first launch: a refused call leaves the stream and the outputs untouched
-    RNAMSM_CHECK_ARG(atp, "contact_head_long: null pointer (atp)");
-    RNAMSM_CHECK_ARG(weight, "contact_head_long: null pointer (weight)");
-    RNAMSM_CHECK_ARG(bias, "contact_head_long: null pointer (bias)");
-    RNAMSM_CHECK_ARG(contacts, "contact_head_long: null pointer (contacts)");
-    RNAMSM_CHECK_ARG(workspace, "contact_head_long: null pointer (workspace)");
-    RNAMSM_CHECK_ARG(L >= 1 && L <= RNAMSM_LONG_MAX_L, "contact_head_long: L=%d outside [1, %d]", L, RNAMSM_LONG_MAX_L);
-    RNAMSM_CHECK_ARG(nch > 0, "contact_head_long: nch=%d", nch);
-    RNAMSM_CHECK_ARG(plane_stride >= (int64_t)L * L, "contact_head_long: plane stride %lld < L * L = %lld", (long long)plane_stride,
-                     (long long)L * L);
-    RNAMSM_CHECK_ARG(((uintptr_t)atp & 3u) == 0, "contact_head_long: atp is not 4-byte aligned");
-    RNAMSM_CHECK_ARG(((uintptr_t)contacts & 3u) == 0, "contact_head_long: contacts is not 4-byte aligned");
-    RNAMSM_CHECK_ARG(((uintptr_t)workspace & 3u) == 0, "contact_head_long: workspace is not 4-byte aligned");
-    RNAMSM_CHECK_ARG(workspace_bytes >= contact_slab_floats(L, nch) * sizeof(float), "contact_head_long: workspace of %zu bytes, %zu needed",
-                     workspace_bytes, contact_slab_floats(L, nch) * sizeof(float));
-    return contact_lone(atp, plane_stride, L, 0, L, nch, weight, bias, contacts, workspace, static_cast<hipStream_t>(stream));
+    return contact_atp_lone("contact_head_long", RNAMSM_LONG_MAX_L, atp, plane_stride, L, nch, weight, bias, contacts, workspace,
+                            workspace_bytes, stream);
 }
 
 extern "C" size_t rnamsm_contact_head_packed_workspace_bytes(int B, const int* Ls, int nch) {

@@ -188,22 +188,14 @@ __device__ __forceinline__ void rsa_stem_body(float* Xs, float* Red, const float
         }
     }
 }
-template <bool PACKED>
+template <bool PACKED, int TR>
 __global__ __launch_bounds__(RSA_STEM_THREADS) void rsa_stem_kernel(const RsaMember* __restrict__ mem, int B, const RsaMember lone,
                                                                     int use_onehot, const RsaTable table, float* __restrict__ ws) {
     __shared__ float Xs[RSA_STEM_XS];
     __shared__ float Red[RSA_STEM_RED];
     const RsaMember m = rsa_member<PACKED>(mem, B, lone);
-    rsa_stem_body<RSA_MAX_TILES>(Xs, Red, m.emb, m.emb_stride, m.codes, m.L, use_onehot, table, ws + m.ws_off, blockIdx.y,
-                  ((int)blockIdx.x - m.tile0) * RSA_TILE);
-}
-// The long form of a stage (rnamsm_rsa_head_long): the same body on the layout with RSA_LONG_TILES tile-sum rows, lone only.
-__global__ __launch_bounds__(RSA_STEM_THREADS) void rsa_stem_long_kernel(const RsaMember lone, int use_onehot, const RsaTable table,
-                                                                         float* __restrict__ ws) {
-    __shared__ float Xs[RSA_STEM_XS];
-    __shared__ float Red[RSA_STEM_RED];
-    rsa_stem_body<RSA_LONG_TILES>(Xs, Red, lone.emb, lone.emb_stride, lone.codes, lone.L, use_onehot, table, ws, blockIdx.y,
-                                  (int)blockIdx.x * RSA_TILE);
+    rsa_stem_body<TR>(Xs, Red, m.emb, m.emb_stride, m.codes, m.L, use_onehot, table, ws + m.ws_off, blockIdx.y,
+                      ((int)blockIdx.x - m.tile0) * RSA_TILE);
 }
 
 // out[j] += sum_ci Wt[ci][co] * Xs[(pb + j)][ci], ci ascending: thread (co, 8 positions); Xs rows are read as wave-wide broadcasts
@@ -275,18 +267,13 @@ __device__ __forceinline__ void rsa_conv2_body(float* Xs, float* Ps, int L, cons
     __syncthreads();
     if (t < RSA_CH) part[(size_t)(p0 / RSA_TILE) * RSA_CH + t] = ((Ps[t] + Ps[RSA_CH + t]) + Ps[2 * RSA_CH + t]) + Ps[3 * RSA_CH + t];
 }
-template <bool PACKED>
+template <bool PACKED, int TR>
 __global__ __launch_bounds__(RSA_THREADS) void rsa_conv2_kernel(const RsaMember* __restrict__ mem, int B, const RsaMember lone,
                                                                 const RsaTable table, float* __restrict__ ws) {
     __shared__ __attribute__((aligned(16))) float Xs[(RSA_TILE + 2) * RSA_CH];
     __shared__ float Ps[4 * RSA_CH];
     const RsaMember m = rsa_member<PACKED>(mem, B, lone);
-    rsa_conv2_body<RSA_MAX_TILES>(Xs, Ps, m.L, table, ws + m.ws_off, blockIdx.y, ((int)blockIdx.x - m.tile0) * RSA_TILE);
-}
-__global__ __launch_bounds__(RSA_THREADS) void rsa_conv2_long_kernel(const RsaMember lone, const RsaTable table, float* __restrict__ ws) {
-    __shared__ __attribute__((aligned(16))) float Xs[(RSA_TILE + 2) * RSA_CH];
-    __shared__ float Ps[4 * RSA_CH];
-    rsa_conv2_body<RSA_LONG_TILES>(Xs, Ps, lone.L, table, ws, blockIdx.y, (int)blockIdx.x * RSA_TILE);
+    rsa_conv2_body<TR>(Xs, Ps, m.L, table, ws + m.ws_off, blockIdx.y, ((int)blockIdx.x - m.tile0) * RSA_TILE);
 }
 
 // ---------------------------------------------------------------------------------------------------------------- launch 3
@@ -365,20 +352,14 @@ __device__ __forceinline__ void rsa_mix_body(float* Ys, float* Xs, float* Sc, in
         }
     }
 }
-template <bool PACKED>
+template <bool PACKED, int TR>
 __global__ __launch_bounds__(RSA_THREADS) void rsa_mix_kernel(const RsaMember* __restrict__ mem, int B, const RsaMember lone,
                                                               const RsaTable table, float* __restrict__ ws) {
     __shared__ __attribute__((aligned(16))) float Ys[RSA_TILE * RSA_CH];
     __shared__ __attribute__((aligned(16))) float Xs[RSA_TILE * RSA_CH];
     __shared__ float Sc[RSA_MIX_SC];
     const RsaMember m = rsa_member<PACKED>(mem, B, lone);
-    rsa_mix_body<RSA_MAX_TILES>(Ys, Xs, Sc, m.L, table, ws + m.ws_off, blockIdx.y, ((int)blockIdx.x - m.tile0) * RSA_TILE);
-}
-__global__ __launch_bounds__(RSA_THREADS) void rsa_mix_long_kernel(const RsaMember lone, const RsaTable table, float* __restrict__ ws) {
-    __shared__ __attribute__((aligned(16))) float Ys[RSA_TILE * RSA_CH];
-    __shared__ __attribute__((aligned(16))) float Xs[RSA_TILE * RSA_CH];
-    __shared__ float Sc[RSA_MIX_SC];
-    rsa_mix_body<RSA_LONG_TILES>(Ys, Xs, Sc, lone.L, table, ws, blockIdx.y, (int)blockIdx.x * RSA_TILE);
+    rsa_mix_body<TR>(Ys, Xs, Sc, m.L, table, ws + m.ws_off, blockIdx.y, ((int)blockIdx.x - m.tile0) * RSA_TILE);
 }
 
 // ---------------------------------------------------------------------------------------------------------------- launch 4
@@ -529,59 +510,37 @@ __device__ __forceinline__ void rsa_attn_body(float* KV, float* Ys, float* Xs, i
         }
     }
 }
-template <bool PACKED>
+template <bool PACKED, int TR>
 __global__ __launch_bounds__(RSA_THREADS) void rsa_attn_kernel(const RsaMember* __restrict__ mem, int B, const RsaMember lone,
                                                                const RsaTable table, const float* __restrict__ ws) {
     __shared__ __attribute__((aligned(16))) float KV[2 * RSA_KEYS * RSA_CH];      // K / V chunk; later the MLP's hidden tile [32][256]
     __shared__ __attribute__((aligned(16))) float Ys[RSA_TILE * RSA_CH];
     __shared__ __attribute__((aligned(16))) float Xs[RSA_TILE * RSA_CH];
     const RsaMember m = rsa_member<PACKED>(mem, B, lone);
-    rsa_attn_body<RSA_MAX_TILES>(KV, Ys, Xs, m.L, table, ws + m.ws_off, blockIdx.y, ((int)blockIdx.x - m.tile0) * RSA_TILE, m.logits, m.probs);
-}
-__global__ __launch_bounds__(RSA_THREADS) void rsa_attn_long_kernel(const RsaMember lone, const RsaTable table,
-                                                                    const float* __restrict__ ws) {
-    __shared__ __attribute__((aligned(16))) float KV[2 * RSA_KEYS * RSA_CH];
-    __shared__ __attribute__((aligned(16))) float Ys[RSA_TILE * RSA_CH];
-    __shared__ __attribute__((aligned(16))) float Xs[RSA_TILE * RSA_CH];
-    rsa_attn_body<RSA_LONG_TILES>(KV, Ys, Xs, lone.L, table, ws, blockIdx.y, (int)blockIdx.x * RSA_TILE, lone.logits, lone.probs);
+    rsa_attn_body<TR>(KV, Ys, Xs, m.L, table, ws + m.ws_off, blockIdx.y, ((int)blockIdx.x - m.tile0) * RSA_TILE, m.logits, m.probs);
 }
 
 constexpr size_t rsa_members_bytes(int B) { return ((size_t)B * sizeof(RsaMember) + 255) & ~(size_t)255; }
 
-// The four launches over `tiles` tiles of n_models models each: PACKED with mem / B the uploaded table of a batch, else null / 1
-// and the lone member.  weights: checked by the caller.
-template <bool PACKED>
+// The four launches over `tiles` tiles of n_models models each, on the layout with TR tile-sum rows: PACKED with mem / B the
+// uploaded table of a batch, else null / 1 and the lone member.  The instances are <false, RSA_MAX_TILES> (rnamsm_rsa_head),
+// <true, RSA_MAX_TILES> (_packed) and <false, RSA_LONG_TILES> (_long).  weights: checked by the caller.
+template <bool PACKED, int TR>
 int rsa_launch(const RsaMember* mem, int B, const RsaMember& lone, int64_t tiles, int n_models, int use_onehot,
                const void* const* weights, float* ws, hipStream_t s) {
     const int nw = RNAMSM_RSA_GLOBAL_WEIGHTS + RNAMSM_RSA_WEIGHTS_PER_MODEL * n_models;
     RsaTable table;
     for (int i = 0; i < RSA_TABLE_MAX; ++i) table.p[i] = i < nw ? weights[i] : nullptr;
     const dim3 grid((unsigned)tiles, (unsigned)n_models);      // the members' own tiles, nothing for a short member beside a long one
-    hipLaunchKernelGGL(rsa_stem_kernel<PACKED>, grid, dim3(RSA_STEM_THREADS), 0, s, mem, B, lone, use_onehot ? 1 : 0, table, ws);
-    RNAMSM_CHECK_LAUNCH(PACKED ? "rsa_stem (packed)" : "rsa_stem");
-    hipLaunchKernelGGL(rsa_conv2_kernel<PACKED>, grid, dim3(RSA_THREADS), 0, s, mem, B, lone, table, ws);
-    RNAMSM_CHECK_LAUNCH(PACKED ? "rsa_conv2 (packed)" : "rsa_conv2");
-    hipLaunchKernelGGL(rsa_mix_kernel<PACKED>, grid, dim3(RSA_THREADS), 0, s, mem, B, lone, table, ws);
-    RNAMSM_CHECK_LAUNCH(PACKED ? "rsa_mix (packed)" : "rsa_mix");
-    hipLaunchKernelGGL(rsa_attn_kernel<PACKED>, grid, dim3(RSA_THREADS), 0, s, mem, B, lone, table, ws);
-    RNAMSM_CHECK_LAUNCH(PACKED ? "rsa_attn (packed)" : "rsa_attn");
-    return RNAMSM_OK;
-}
-
-// The four long launches of one member: ceil(L / 32) tiles, L up to RNAMSM_LONG_MAX_L.  weights: checked by the caller.
-int rsa_launch_long(const RsaMember& lone, int n_models, int use_onehot, const void* const* weights, float* ws, hipStream_t s) {
-    const int nw = RNAMSM_RSA_GLOBAL_WEIGHTS + RNAMSM_RSA_WEIGHTS_PER_MODEL * n_models;
-    RsaTable table;
-    for (int i = 0; i < RSA_TABLE_MAX; ++i) table.p[i] = i < nw ? weights[i] : nullptr;
-    const dim3 grid((unsigned)((lone.L + RSA_TILE - 1) / RSA_TILE), (unsigned)n_models);
-    hipLaunchKernelGGL(rsa_stem_long_kernel, grid, dim3(RSA_STEM_THREADS), 0, s, lone, use_onehot ? 1 : 0, table, ws);
-    RNAMSM_CHECK_LAUNCH("rsa_stem (long)");
-    hipLaunchKernelGGL(rsa_conv2_long_kernel, grid, dim3(RSA_THREADS), 0, s, lone, table, ws);
-    RNAMSM_CHECK_LAUNCH("rsa_conv2 (long)");
-    hipLaunchKernelGGL(rsa_mix_long_kernel, grid, dim3(RSA_THREADS), 0, s, lone, table, ws);
-    RNAMSM_CHECK_LAUNCH("rsa_mix (long)");
-    hipLaunchKernelGGL(rsa_attn_long_kernel, grid, dim3(RSA_THREADS), 0, s, lone, table, ws);
-    RNAMSM_CHECK_LAUNCH("rsa_attn (long)");
+    constexpr bool LONG = TR > RSA_MAX_TILES;
+    hipLaunchKernelGGL((rsa_stem_kernel<PACKED, TR>), grid, dim3(RSA_STEM_THREADS), 0, s, mem, B, lone, use_onehot ? 1 : 0, table, ws);
+    RNAMSM_CHECK_LAUNCH(PACKED ? "rsa_stem (packed)" : LONG ? "rsa_stem (long)" : "rsa_stem");
+    hipLaunchKernelGGL((rsa_conv2_kernel<PACKED, TR>), grid, dim3(RSA_THREADS), 0, s, mem, B, lone, table, ws);
+    RNAMSM_CHECK_LAUNCH(PACKED ? "rsa_conv2 (packed)" : LONG ? "rsa_conv2 (long)" : "rsa_conv2");
+    hipLaunchKernelGGL((rsa_mix_kernel<PACKED, TR>), grid, dim3(RSA_THREADS), 0, s, mem, B, lone, table, ws);
+    RNAMSM_CHECK_LAUNCH(PACKED ? "rsa_mix (packed)" : LONG ? "rsa_mix (long)" : "rsa_mix");
+    hipLaunchKernelGGL((rsa_attn_kernel<PACKED, TR>), grid, dim3(RSA_THREADS), 0, s, mem, B, lone, table, ws);
+    RNAMSM_CHECK_LAUNCH(PACKED ? "rsa_attn (packed)" : LONG ? "rsa_attn (long)" : "rsa_attn");
     return RNAMSM_OK;
 }
 
@@ -601,23 +560,39 @@ extern "C" size_t rnamsm_rsa_head_workspace_bytes(int L, int n_models) {
     return (size_t)n_models * rsa_model_floats(L) * sizeof(float);
 }
 
+// The lone call, written once for rnamsm_rsa_head (who = "rsa_head", TR = RSA_MAX_TILES, max_L = RNAMSM_RSA_MAX_L) and
+// rnamsm_rsa_head_long ("rsa_head_long", RSA_LONG_TILES, RNAMSM_LONG_MAX_L), as ss_head_lone is: one list of refusals under the
+// entry's own name and limit, every one before the first launch, then the four launches on the layout with TR tile-sum rows.
+template <int TR>
+static int rsa_head_lone(const char* who, int max_L, const float* emb, int64_t emb_row_stride, const uint8_t* base_codes, int L,
+                         int n_models, int use_onehot, const void* const* weights, float* probs, float* logits, void* workspace,
+                         size_t workspace_bytes, void* stream) {
+    RNAMSM_CHECK_ARG(emb, "%s: null pointer (emb)", who);
+    RNAMSM_CHECK_ARG(base_codes, "%s: null pointer (base_codes)", who);
+    RNAMSM_CHECK_ARG(weights, "%s: null pointer (weights)", who);
+    RNAMSM_CHECK_ARG(workspace, "%s: null pointer (workspace)", who);
+    RNAMSM_CHECK_ARG(logits || probs, "%s: neither probs nor logits given", who);
+    RNAMSM_CHECK_ARG(L >= 1 && L <= max_L, "%s: L=%d outside [1, %d]", who, L, max_L);
+    RNAMSM_CHECK_ARG(n_models >= 1 && n_models <= RNAMSM_RSA_MAX_MODELS, "%s: n_models=%d outside [1, %d]", who, n_models,
+                     RNAMSM_RSA_MAX_MODELS);
+    RNAMSM_CHECK_ARG(emb_row_stride >= RSA_EMB, "%s: embedding row stride %lld < %d", who, (long long)emb_row_stride, RSA_EMB);
+    const size_t need = (size_t)n_models * rsa_model_floats<TR>(L) * sizeof(float);
+    RNAMSM_CHECK_ARG(workspace_bytes >= need, "%s: workspace of %zu bytes, %zu needed", who, workspace_bytes, need);
+    RNAMSM_CHECK_ARG(aligned16(emb), "%s: emb is not 16-byte aligned", who);
+    RNAMSM_CHECK_ARG(aligned16(workspace), "%s: workspace is not 16-byte aligned", who);
+    RNAMSM_CHECK_ARG((reinterpret_cast<uintptr_t>(probs) & 3u) == 0, "%s: probs is not 4-byte aligned", who);
+    RNAMSM_CHECK_ARG((reinterpret_cast<uintptr_t>(logits) & 3u) == 0, "%s: logits is not 4-byte aligned", who);
+    if (int rc = rsa_check_weights(who, weights, n_models, use_onehot)) return rc;
+    const RsaMember lone = {emb, emb_row_stride, base_codes, logits, probs, 0, L, 0, {0, 0}};
+    return rsa_launch<false, TR>(nullptr, 1, lone, (L + RSA_TILE - 1) / RSA_TILE, n_models, use_onehot, weights,
+                                 static_cast<float*>(workspace), static_cast<hipStream_t>(stream));
+}
+
 extern "C" int rnamsm_rsa_head(const float* emb, int64_t emb_row_stride, const uint8_t* base_codes, int L, int n_models,
                                int use_onehot, const void* const* weights, float* probs, float* logits, void* workspace,
                                size_t workspace_bytes, void* stream) {
-    RNAMSM_CHECK_ARG(emb && base_codes && weights && workspace, "rsa_head: null pointer");
-    RNAMSM_CHECK_ARG(logits || probs, "rsa_head: neither probs nor logits given");
-    RNAMSM_CHECK_ARG(L >= 1 && L <= RNAMSM_RSA_MAX_L, "rsa_head: L=%d outside [1, %d]", L, RNAMSM_RSA_MAX_L);
-    RNAMSM_CHECK_ARG(n_models >= 1 && n_models <= RNAMSM_RSA_MAX_MODELS, "rsa_head: n_models=%d outside [1, %d]", n_models,
-                     RNAMSM_RSA_MAX_MODELS);
-    RNAMSM_CHECK_ARG(emb_row_stride >= RSA_EMB, "rsa_head: embedding row stride %lld < %d", (long long)emb_row_stride, RSA_EMB);
-    RNAMSM_CHECK_ARG(workspace_bytes >= rnamsm_rsa_head_workspace_bytes(L, n_models), "rsa_head: workspace too small");
-    RNAMSM_CHECK_ARG(aligned16(workspace) && aligned16(emb), "rsa_head: 16-byte alignment of the embedding and the workspace");
-    RNAMSM_CHECK_ARG((!probs || (reinterpret_cast<uintptr_t>(probs) & 3u) == 0) && (!logits || (reinterpret_cast<uintptr_t>(logits) & 3u) == 0),
-                     "rsa_head: misaligned output");
-    if (int rc = rsa_check_weights("rsa_head", weights, n_models, use_onehot)) return rc;
-    const RsaMember lone = {emb, emb_row_stride, base_codes, logits, probs, 0, L, 0, {0, 0}};
-    return rsa_launch<false>(nullptr, 1, lone, (L + RSA_TILE - 1) / RSA_TILE, n_models, use_onehot, weights, static_cast<float*>(workspace),
-                             static_cast<hipStream_t>(stream));
+    return rsa_head_lone<RSA_MAX_TILES>("rsa_head", RNAMSM_RSA_MAX_L, emb, emb_row_stride, base_codes, L, n_models, use_onehot, weights,
+                                        probs, logits, workspace, workspace_bytes, stream);
 }
 
 extern "C" size_t rnamsm_rsa_head_long_workspace_bytes(int L, int n_models) {
@@ -628,25 +603,8 @@ extern "C" size_t rnamsm_rsa_head_long_workspace_bytes(int L, int n_models) {
 extern "C" int rnamsm_rsa_head_long(const float* emb, int64_t emb_row_stride, const uint8_t* base_codes, int L, int n_models,
                                     int use_onehot, const void* const* weights, float* probs, float* logits, void* workspace,
                                     size_t workspace_bytes, void* stream) {
-    // every refusal comes before the first launch
-    RNAMSM_CHECK_ARG(emb, "rsa_head_long: null pointer (emb)");
-    RNAMSM_CHECK_ARG(base_codes, "rsa_head_long: null pointer (base_codes)");
-    RNAMSM_CHECK_ARG(weights, "rsa_head_long: null pointer (weights)");
-    RNAMSM_CHECK_ARG(workspace, "rsa_head_long: null pointer (workspace)");
-    RNAMSM_CHECK_ARG(logits || probs, "rsa_head_long: neither probs nor logits given");
-    RNAMSM_CHECK_ARG(L >= 1 && L <= RNAMSM_LONG_MAX_L, "rsa_head_long: L=%d outside [1, %d]", L, RNAMSM_LONG_MAX_L);
-    RNAMSM_CHECK_ARG(n_models >= 1 && n_models <= RNAMSM_RSA_MAX_MODELS, "rsa_head_long: n_models=%d outside [1, %d]", n_models,
-                     RNAMSM_RSA_MAX_MODELS);
-    RNAMSM_CHECK_ARG(emb_row_stride >= RSA_EMB, "rsa_head_long: embedding row stride %lld < %d", (long long)emb_row_stride, RSA_EMB);
-    const size_t need = rnamsm_rsa_head_long_workspace_bytes(L, n_models);
-    RNAMSM_CHECK_ARG(workspace_bytes >= need, "rsa_head_long: workspace of %zu bytes, %zu needed", workspace_bytes, need);
-    RNAMSM_CHECK_ARG(aligned16(emb), "rsa_head_long: emb is not 16-byte aligned");
-    RNAMSM_CHECK_ARG(aligned16(workspace), "rsa_head_long: workspace is not 16-byte aligned");
-    RNAMSM_CHECK_ARG((reinterpret_cast<uintptr_t>(probs) & 3u) == 0, "rsa_head_long: probs is not 4-byte aligned");
-    RNAMSM_CHECK_ARG((reinterpret_cast<uintptr_t>(logits) & 3u) == 0, "rsa_head_long: logits is not 4-byte aligned");
-    if (int rc = rsa_check_weights("rsa_head_long", weights, n_models, use_onehot)) return rc;
-    const RsaMember lone = {emb, emb_row_stride, base_codes, logits, probs, 0, L, 0, {0, 0}};
-    return rsa_launch_long(lone, n_models, use_onehot, weights, static_cast<float*>(workspace), static_cast<hipStream_t>(stream));
+    return rsa_head_lone<RSA_LONG_TILES>("rsa_head_long", RNAMSM_LONG_MAX_L, emb, emb_row_stride, base_codes, L, n_models, use_onehot,
+                                         weights, probs, logits, workspace, workspace_bytes, stream);
 }
 
 extern "C" size_t rnamsm_rsa_head_packed_workspace_bytes(int B, const int* Ls, int n_models) {
@@ -697,6 +655,6 @@ extern "C" int rnamsm_rsa_head_packed(const rnamsm_rsa_item* items, int B, int n
         return m;
     }, s, "rsa_members");
     if (rc != RNAMSM_OK) return rc;
-    return rsa_launch<true>(mem, B, RsaMember{}, tiles_total, n_models, use_onehot, weights,
-                            reinterpret_cast<float*>(static_cast<char*>(workspace) + rsa_members_bytes(B)), s);
+    return rsa_launch<true, RSA_MAX_TILES>(mem, B, RsaMember{}, tiles_total, n_models, use_onehot, weights,
+                                           reinterpret_cast<float*>(static_cast<char*>(workspace) + rsa_members_bytes(B)), s);
 }

@@ -53,15 +53,18 @@ class ContactHead:
     def __init__(self, weight: torch.Tensor, bias: torch.Tensor):
         self.weight, self.bias = weight.detach().contiguous().view(-1), bias.detach().contiguous().view(-1)
 
+    def _one(self, emb: torch.Tensor, atp: torch.Tensor, tokens: torch.Tensor, long: bool) -> ContactResult:
+        return ContactResult((ops.contact_head_long if long else ops.contact_head_atp)(atp, self.weight, self.bias))
+
     def one(self, emb: torch.Tensor, atp: torch.Tensor, tokens: torch.Tensor) -> ContactResult:
         """A lone alignment through the lone call; atp is read where it lies (emb and tokens are not read: the heads share one
         signature)."""
-        return ContactResult(ops.contact_head_atp(atp, self.weight, self.bias))
+        return self._one(emb, atp, tokens, False)
 
     def one_long(self, emb: torch.Tensor, atp: torch.Tensor, tokens: torch.Tensor) -> ContactResult:
         """one() on the stitched atp of a long alignment (data.long_heads=stitched), L up to LONG_MAX_L = 4096: the same record
         through rnamsm_contact_head_long.  Symmetrise and APC run over the whole map; a pair no window holds takes part as 0."""
-        return ContactResult(ops.contact_head_long(atp, self.weight, self.bias))
+        return self._one(emb, atp, tokens, True)
 
     def many(self, embs: Sequence[torch.Tensor], atps: Sequence[torch.Tensor], tokens: Sequence[torch.Tensor]) -> List[ContactResult]:
         """A group in one launch set per chunk (predict_many): every member's record holds the bits of one()."""

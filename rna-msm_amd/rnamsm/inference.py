@@ -472,10 +472,11 @@ def extract_feat(cfg: Config, model: Optional[MSATransformer] = None, gather_to_
                 absent, the lone heads run here, on emb and atp where they lie (a packed group's slices included)."""
                 if records is None:
                     # (a stitched alignment: the heads data.long_heads=stitched lets through run their long route; lm_scores=wt has
-                    # no length limit and keeps its own)
+                    # no length limit and no long route, and keeps its own)
                     wide = stitched(emb.shape[0])
                     records = [None if skipped_on(h, emb.shape[0])
-                               else (getattr(h, "one_long", h.one) if wide else h.one)(emb, atp, head_tokens(h, toks)) for h in heads]
+                               else (h.one_long if wide and not isinstance(h, lm.LMHead) else h.one)(emb, atp, head_tokens(h, toks))
+                               for h in heads]
                     if heads and after is not None:             # the copies wait for the heads too
                         after = torch.cuda.Event()
                         after.record(torch.cuda.current_stream())

@@ -577,22 +577,52 @@ def _contact_regression(weight: torch.Tensor, bias: torch.Tensor, nch: int, fn: 
     return weight, bias
 
 
+class _Route(NamedTuple):
+    """Which entry point a lone call runs through: the call itself or its `_long` sibling for a stitched long alignment
+    (include/rnamsm.h: RNAMSM_LONG_MAX_L), which for an L both accept gives the bits (bytes) of its namesake."""
+    fn: str                        # the public function's name, for the messages; the library's symbol is rnamsm_<fn>
+    max_L: int
+    size: Optional[str] = None     # the symbol of its size function, where the call asks one
+
+    @property
+    def entry(self) -> str:
+        return "rnamsm_" + self.fn
+
+    @property
+    def long(self) -> bool:
+        return self.max_L == _lib.LONG_MAX_L
+
+
+_CONTACT_ATP = _Route("contact_head_atp", _lib.CONTACT_MAX_L, "rnamsm_contact_head_workspace_bytes")
+_CONTACT_LONG = _Route("contact_head_long", _lib.LONG_MAX_L, "rnamsm_contact_head_long_workspace_bytes")
+
+
+def _contact_atp_run(route: _Route, atp: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor) -> torch.Tensor:
+    members, _ = _members(route.fn, _contact_operand, 1, route.max_L, (None, None, "alignments"), {"atp": [atp]}, lone=True)
+    atp, L = members[0]
+    nch = atp.shape[0]
+    weight, bias = _contact_regression(weight, bias, nch, route.fn)
+    lib = _lib.load()
+    # rnamsm_contact_head_workspace_bytes takes the width of the un-stripped maps
+    ws = torch.empty(getattr(lib, route.size)(L if route.long else L + 1, nch), dtype=torch.uint8, device=atp.device)
+    out = torch.empty(L, L, device=atp.device, dtype=torch.float32)
+    _lib.check(getattr(lib, route.entry)(atp.data_ptr(), atp.stride(0), L, nch, weight.data_ptr(), bias.data_ptr(), out.data_ptr(),
+                                         ws.data_ptr(), ws.numel(), _stream()))
+    return out
+
+
 @_on_operand_device
 def contact_head_atp(atp: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor) -> torch.Tensor:
     """The contact head on the stripped maps (rnamsm_contact_head_atp): atp [nch, L, L] fp32 as forward_one / the packed drivers
     leave it (planes may lie further apart than L*L: a slice of a wider buffer is read in place) -> contacts [L, L], the bits of
     contact_head on the [nch, L+1, L+1] maps they were stripped from."""
-    members, _ = _members("contact_head_atp", _contact_operand, 1, _lib.CONTACT_MAX_L, (None, None, "alignments"), {"atp": [atp]},
-                          lone=True)
-    atp, L = members[0]
-    nch = atp.shape[0]
-    weight, bias = _contact_regression(weight, bias, nch, "contact_head_atp")
-    lib = _lib.load()
-    ws = torch.empty(lib.rnamsm_contact_head_workspace_bytes(L + 1, nch), dtype=torch.uint8, device=atp.device)
-    out = torch.empty(L, L, device=atp.device, dtype=torch.float32)
-    _lib.check(lib.rnamsm_contact_head_atp(atp.data_ptr(), atp.stride(0), L, nch, weight.data_ptr(), bias.data_ptr(), out.data_ptr(),
-                                           ws.data_ptr(), ws.numel(), _stream()))
-    return out
+    return _contact_atp_run(_CONTACT_ATP, atp, weight, bias)
+
+
+@_on_operand_device
+def contact_head_long(atp: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor) -> torch.Tensor:
+    """contact_head_atp for L up to LONG_MAX_L (rnamsm_contact_head_long); symmetrise and APC run over the whole map."""
+    return _contact_atp_run(_CONTACT_LONG, atp, weight, bias)
 
 
 @_on_operand_device
@@ -698,6 +728,18 @@ def ss_pack_conv16(w: torch.Tensor) -> torch.Tensor:
     return out
 
 
+def _ss_head_run(fn: str, head, head_bytes, atp: torch.Tensor, base_codes: torch.Tensor, ptrs, num_blocks: int, want: str) -> torch.Tensor:
+    """The lone SS head through the entry point `head` and its size function (the route: fp32, bf16 or long; the library holds each
+    to its own limit of L).  The workspace is 384 L^2 bytes: 6.4 GB at L = 4096."""
+    atp, base_codes, L = _ss_operands(fn, atp, base_codes, "atp", "base_codes")
+    ws = torch.empty(max(head_bytes(L), 16), dtype=torch.uint8, device=atp.device)
+    out = torch.empty(L, L, device=atp.device, dtype=torch.float32)
+    ptr = out.data_ptr()
+    _lib.check(head(atp.data_ptr(), atp.stride(0), base_codes.data_ptr(), L, num_blocks, ptrs,
+                    ptr if want == "logits" else None, ptr if want == "probs" else None, ws.data_ptr(), ws.numel(), _stream()))
+    return out
+
+
 @_on_operand_device
 def ss_head(atp: torch.Tensor, base_codes: torch.Tensor, ptrs, num_blocks: int, want: str = "probs",
             gemm_dtype: str = "f32") -> torch.Tensor:
@@ -707,13 +749,16 @@ def ss_head(atp: torch.Tensor, base_codes: torch.Tensor, ptrs, num_blocks: int, 
     gemm_dtype="bf16": rnamsm_ss_head16, with ptrs the table whose conv entries are bf16 planes (ss_pack_conv16)."""
     _want("ss_head", want)
     head, head_bytes, _, _ = _ss_entries("ss_head", gemm_dtype)
-    atp, base_codes, L = _ss_operands("ss_head", atp, base_codes, "atp", "base_codes")
-    ws = torch.empty(max(head_bytes(L), 16), dtype=torch.uint8, device=atp.device)
-    out = torch.empty(L, L, device=atp.device, dtype=torch.float32)
-    ptr = out.data_ptr()
-    _lib.check(head(atp.data_ptr(), atp.stride(0), base_codes.data_ptr(), L, num_blocks, ptrs,
-                    ptr if want == "logits" else None, ptr if want == "probs" else None, ws.data_ptr(), ws.numel(), _stream()))
-    return out
+    return _ss_head_run("ss_head", head, head_bytes, atp, base_codes, ptrs, num_blocks, want)
+
+
+@_on_operand_device
+def ss_head_long(atp: torch.Tensor, base_codes: torch.Tensor, ptrs, num_blocks: int, want: str = "probs") -> torch.Tensor:
+    """ss_head for L up to LONG_MAX_L (rnamsm_ss_head_long, exact fp32 only: ptrs is the fp32 weight table)."""
+    _want("ss_head_long", want)
+    lib = _lib.load()
+    return _ss_head_run("ss_head_long", lib.rnamsm_ss_head_long, lib.rnamsm_ss_head_long_workspace_bytes, atp, base_codes, ptrs,
+                        num_blocks, want)
 
 
 @_on_operand_device
@@ -751,17 +796,31 @@ def _ss_text_operand(fn: str, probs: torch.Tensor, name: str, max_L: int = _lib.
     return probs.contiguous(), L
 
 
+_SS_TEXT = _Route("ss_prob_text", _lib.SS_MAX_L, "rnamsm_ss_prob_text_bytes")
+_SS_TEXT_LONG = _Route("ss_prob_text_long", _lib.LONG_MAX_L, "rnamsm_ss_prob_text_long_bytes")
+
+
+def _ss_prob_text_run(route: _Route, probs: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    probs, L = _ss_text_operand(route.fn, probs, "probs", route.max_L)
+    lib = _lib.load()
+    text = torch.empty(getattr(lib, route.size)(L), dtype=torch.uint8, device=probs.device)
+    fallback = torch.empty(1, dtype=torch.int32, device=probs.device)
+    _lib.check(getattr(lib, route.entry)(probs.data_ptr(), L, text.data_ptr(), fallback.data_ptr(), _stream()))
+    return text, fallback
+
+
 @_on_operand_device
 def ss_prob_text(probs: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
     """The `.prob` text of [L, L] fp32 probabilities, written on the device (rnamsm_ss_prob_text): -> (uint8 [25 L^2], the
     bytes of np.savetxt(f, probs, delimiter="\\t"); int32 [1], the fallback word: 1 when an element lies outside [0, 1] -- NaN,
     inf and -0.0 included -- and the text is then not to be used)."""
-    probs, L = _ss_text_operand("ss_prob_text", probs, "probs")
-    lib = _lib.load()
-    text = torch.empty(lib.rnamsm_ss_prob_text_bytes(L), dtype=torch.uint8, device=probs.device)
-    fallback = torch.empty(1, dtype=torch.int32, device=probs.device)
-    _lib.check(lib.rnamsm_ss_prob_text(probs.data_ptr(), L, text.data_ptr(), fallback.data_ptr(), _stream()))
-    return text, fallback
+    return _ss_prob_text_run(_SS_TEXT, probs)
+
+
+@_on_operand_device
+def ss_prob_text_long(probs: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """ss_prob_text for L up to LONG_MAX_L (rnamsm_ss_prob_text_long) -> (uint8 [25 L^2], the fallback word)."""
+    return _ss_prob_text_run(_SS_TEXT_LONG, probs)
 
 
 @_on_operand_device
@@ -784,9 +843,9 @@ def ss_prob_text_packed(probs: Sequence[torch.Tensor]) -> List[Tuple[torch.Tenso
     return outs
 
 
-def _ss_pairs_operands(fn: str, probs: torch.Tensor, letters: torch.Tensor, name: str, letters_name: str):
-    """One structure of ss_pairs / ss_pairs_packed as the library reads it -> (probs, letters, L)."""
-    probs, L = _ss_text_operand(fn, probs, name)
+def _ss_pairs_operands(fn: str, probs: torch.Tensor, letters: torch.Tensor, name: str, letters_name: str, max_L: int = _lib.SS_MAX_L):
+    """One structure of ss_pairs / ss_pairs_packed / ss_pairs_long as the library reads it -> (probs, letters, L)."""
+    probs, L = _ss_text_operand(fn, probs, name, max_L)
     _dev(letters, letters_name, torch.uint8)
     if letters.dim() != 1 or letters.shape[0] != L:
         raise ValueError(f"{fn}: {letters.shape[0] if letters.dim() == 1 else tuple(letters.shape)} letters for {name} of L = {L}")
@@ -799,7 +858,13 @@ def ss_pairs(probs: torch.Tensor, letters: torch.Tensor) -> Tuple[torch.Tensor, 
     characters -> (partner int32 [L]: 0 or the partner's 1-based index; counts int32 [4]: pairs, bytes of the .ct body, bytes of
     the .bpseq body, fallback; the .ct body uint8 [32 L]; the .bpseq body uint8 [12 L]).  Only the first counts[1] / counts[2] bytes
     of the bodies are written; with counts[3] == 1 (a letter of 0 or >= 128) they are not to be used."""
-    return _ss_pairs_run("ss_pairs", [probs], [letters])[0]
+    return _ss_pairs_run(_SS_PAIRS, [probs], [letters])[0]
+
+
+@_on_operand_device
+def ss_pairs_long(probs: torch.Tensor, letters: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """ss_pairs for L up to LONG_MAX_L (rnamsm_ss_pairs_long: several bases per thread), read as ss_pairs' results are."""
+    return _ss_pairs_run(_SS_PAIRS_LONG, [probs], [letters])[0]
 
 
 @_on_operand_device
@@ -807,93 +872,36 @@ def ss_pairs_packed(probs: Sequence[torch.Tensor], letters: Sequence[torch.Tenso
     """ss_pairs of every (probs[b], letters[b]) in one call (rnamsm_ss_pairs_packed: one workgroup per structure) -> a list of
     (partner, counts, ct body, bpseq body), each byte-identical to ss_pairs on that structure alone.  One allocation per output kind
     and one workspace per call: the returned tensors are views."""
-    return _ss_pairs_run("ss_pairs_packed", probs, letters)
+    return _ss_pairs_run(None, probs, letters)
 
 
-def _ss_pairs_run(_fn: str, probs, letters):
-    lone = _fn == "ss_pairs"
-    members, device = _members(_fn, _ss_pairs_operands, _lib.SS_MAX_BATCH, None, ("matrices", "letter rows", "structures"),
-                               {"probs": probs, "letters": letters}, checked=2, lone=lone)
+_SS_PAIRS = _Route("ss_pairs", _lib.SS_MAX_L)
+_SS_PAIRS_LONG = _Route("ss_pairs_long", _lib.LONG_MAX_L)
+
+
+def _ss_pairs_run(route: Optional[_Route], probs, letters):
+    """route: the lone call's; None: the packed call."""
+    fn = route.fn if route else "ss_pairs_packed"
+    rule = functools.partial(_ss_pairs_operands, max_L=route.max_L) if route else _ss_pairs_operands
+    members, device = _members(fn, rule, _lib.SS_MAX_BATCH, None, ("matrices", "letter rows", "structures"),
+                               {"probs": probs, "letters": letters}, checked=2, lone=route is not None)
     if not members:
         return []
     B, Ls = len(members), [L for _, _, L in members]
     lib = _lib.load()
-    ws = torch.empty(lib.rnamsm_ss_pairs_workspace_bytes(B, (_lib.c_int * B)(*Ls)), dtype=torch.uint8, device=device)
+    nbytes = (lib.rnamsm_ss_pairs_long_workspace_bytes(Ls[0]) if route and route.long
+              else lib.rnamsm_ss_pairs_workspace_bytes(B, (_lib.c_int * B)(*Ls)))
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=device)
     outs = list(zip(_carved(Ls, device, torch.int32), _carved([4] * B, device, torch.int32),
                     _carved([_lib.SS_CT_LINE_MAX * L for L in Ls], device, torch.uint8),
                     _carved([_lib.SS_BPSEQ_LINE_MAX * L for L in Ls], device, torch.uint8)))
     args = [(p.data_ptr(), l.data_ptr(), L, *(t.data_ptr() for t in o)) for (p, l, L), o in zip(members, outs)]
-    if lone:
-        _lib.check(lib.rnamsm_ss_pairs(*args[0], ws.data_ptr(), ws.numel(), _stream()))
+    if route:
+        _lib.check(getattr(lib, route.entry)(*args[0], ws.data_ptr(), ws.numel(), _stream()))
         return outs
     items = (_lib.SsPairsItem * B)(*(_lib.SsPairsItem(*a) for a in args))
     _lib.check(lib.rnamsm_ss_pairs_packed(items, B, ws.data_ptr(), ws.numel(), _stream()))
     return outs
-
-
-# ---- the pair heads on a stitched long alignment (include/rnamsm.h: RNAMSM_LONG_MAX_L): lone calls for L up to _lib.LONG_MAX_L, each
-# with the bits of its namesake above where both accept the L
-@_on_operand_device
-def contact_head_long(atp: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor) -> torch.Tensor:
-    """contact_head_atp for L up to LONG_MAX_L (rnamsm_contact_head_long): atp [nch, L, L] fp32, planes read in place -> contacts
-    [L, L]; symmetrise and APC run over the whole map."""
-    members, _ = _members("contact_head_long", _contact_operand, 1, _lib.LONG_MAX_L, (None, None, "alignments"), {"atp": [atp]}, lone=True)
-    atp, L = members[0]
-    nch = atp.shape[0]
-    weight, bias = _contact_regression(weight, bias, nch, "contact_head_long")
-    lib = _lib.load()
-    ws = torch.empty(lib.rnamsm_contact_head_long_workspace_bytes(L, nch), dtype=torch.uint8, device=atp.device)
-    out = torch.empty(L, L, device=atp.device, dtype=torch.float32)
-    _lib.check(lib.rnamsm_contact_head_long(atp.data_ptr(), atp.stride(0), L, nch, weight.data_ptr(), bias.data_ptr(), out.data_ptr(),
-                                            ws.data_ptr(), ws.numel(), _stream()))
-    return out
-
-
-@_on_operand_device
-def ss_head_long(atp: torch.Tensor, base_codes: torch.Tensor, ptrs, num_blocks: int, want: str = "probs") -> torch.Tensor:
-    """ss_head for L up to LONG_MAX_L (rnamsm_ss_head_long, exact fp32 only: ptrs is the fp32 weight table) -> [L, L] probabilities
-    or logits.  The workspace is 384 L^2 bytes: 6.4 GB at the limit."""
-    _want("ss_head_long", want)
-    atp, base_codes, L = _ss_operands("ss_head_long", atp, base_codes, "atp", "base_codes")
-    lib = _lib.load()
-    ws = torch.empty(max(lib.rnamsm_ss_head_long_workspace_bytes(L), 16), dtype=torch.uint8, device=atp.device)
-    out = torch.empty(L, L, device=atp.device, dtype=torch.float32)
-    ptr = out.data_ptr()
-    _lib.check(lib.rnamsm_ss_head_long(atp.data_ptr(), atp.stride(0), base_codes.data_ptr(), L, num_blocks, ptrs,
-                                       ptr if want == "logits" else None, ptr if want == "probs" else None, ws.data_ptr(),
-                                       ws.numel(), _stream()))
-    return out
-
-
-@_on_operand_device
-def ss_prob_text_long(probs: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
-    """ss_prob_text for L up to LONG_MAX_L (rnamsm_ss_prob_text_long) -> (uint8 [25 L^2], the fallback word)."""
-    probs, L = _ss_text_operand("ss_prob_text_long", probs, "probs", _lib.LONG_MAX_L)
-    lib = _lib.load()
-    text = torch.empty(lib.rnamsm_ss_prob_text_long_bytes(L), dtype=torch.uint8, device=probs.device)
-    fallback = torch.empty(1, dtype=torch.int32, device=probs.device)
-    _lib.check(lib.rnamsm_ss_prob_text_long(probs.data_ptr(), L, text.data_ptr(), fallback.data_ptr(), _stream()))
-    return text, fallback
-
-
-@_on_operand_device
-def ss_pairs_long(probs: torch.Tensor, letters: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
-    """ss_pairs for L up to LONG_MAX_L (rnamsm_ss_pairs_long: several bases per thread) -> (partner int32 [L], counts int32 [4], the
-    .ct body uint8 [32 L], the .bpseq body uint8 [12 L]), read as ss_pairs' results are."""
-    probs, L = _ss_text_operand("ss_pairs_long", probs, "probs", _lib.LONG_MAX_L)
-    _dev(letters, "letters", torch.uint8)
-    if letters.dim() != 1 or letters.shape[0] != L:
-        raise ValueError(f"ss_pairs_long: {letters.shape[0] if letters.dim() == 1 else tuple(letters.shape)} letters for probs of L = {L}")
-    if letters.device != probs.device:
-        raise ValueError(f"ss_pairs_long: probs / letters lie on {probs.device} / {letters.device}")
-    letters = letters.contiguous()
-    lib = _lib.load()
-    ws = torch.empty(lib.rnamsm_ss_pairs_long_workspace_bytes(L), dtype=torch.uint8, device=probs.device)
-    partner, counts = (torch.empty(n, dtype=torch.int32, device=probs.device) for n in (L, 4))
-    ct, bpseq = (torch.empty(n * L, dtype=torch.uint8, device=probs.device) for n in (_lib.SS_CT_LINE_MAX, _lib.SS_BPSEQ_LINE_MAX))
-    _lib.check(lib.rnamsm_ss_pairs_long(probs.data_ptr(), letters.data_ptr(), L, partner.data_ptr(), counts.data_ptr(), ct.data_ptr(),
-                                        bpseq.data_ptr(), ws.data_ptr(), ws.numel(), _stream()))
-    return partner, counts, ct, bpseq
 
 
 def _rsa_operands(fn: str, emb: torch.Tensor, bc: torch.Tensor, name: str, bc_name: str):
@@ -912,21 +920,43 @@ def _rsa_operands(fn: str, emb: torch.Tensor, bc: torch.Tensor, name: str, bc_na
     return emb, emb.stride(0) if L > 1 else 768, bc.contiguous(), L
 
 
+_RSA_HEAD = _Route("rsa_head", _lib.RSA_MAX_L, "rnamsm_rsa_head_workspace_bytes")
+_RSA_HEAD_LONG = _Route("rsa_head_long", _lib.LONG_MAX_L, "rnamsm_rsa_head_long_workspace_bytes")
+
+
+def _long_range(route: _Route, t, name: str, dim: int) -> None:
+    """The range of a long RSA call, before anything else is asked of the operand: a length out of range is wrong on any device."""
+    if route.long and isinstance(t, torch.Tensor) and t.dim() == 2 and not 1 <= t.shape[dim] <= route.max_L:
+        raise ValueError(f"{route.fn}: {name}: L = {t.shape[dim]} outside [1, {route.max_L}]")
+
+
+def _rsa_head_run(route: _Route, emb: torch.Tensor, base_codes: torch.Tensor, ptrs, n_models: int, use_onehot: bool, want: str) -> torch.Tensor:
+    _want(route.fn, want)
+    _long_range(route, emb, "emb", 0)
+    emb, stride, base_codes, L = _rsa_operands(route.fn, emb, base_codes, "emb", "base_codes")
+    lib = _lib.load()
+    ws = torch.empty(max(getattr(lib, route.size)(L, n_models), 16), dtype=torch.uint8, device=emb.device)
+    out = torch.empty(n_models, L, device=emb.device, dtype=torch.float32)
+    ptr = out.data_ptr()
+    _lib.check(getattr(lib, route.entry)(emb.data_ptr(), stride, base_codes.data_ptr(), L, n_models, 1 if use_onehot else 0, ptrs,
+                                         ptr if want == "probs" else None, ptr if want == "logits" else None, ws.data_ptr(),
+                                         ws.numel(), _stream()))
+    return out
+
+
 @_on_operand_device
 def rsa_head(emb: torch.Tensor, base_codes: torch.Tensor, ptrs, n_models: int, use_onehot: bool, want: str = "probs") -> torch.Tensor:
     """RNA-MSM RSA ensemble (rnamsm_rsa_head): emb [L, 768] fp32 (rows may lie further apart than 768 floats: a slice of the
     final representation is read in place), base_codes uint8 [L], ptrs: the packed weight table of the n_models members
     (rnamsm.rsa.RSAEnsemble) -> [n_models, L] fp32 RSA (want="probs") or the pre-sigmoid values (want="logits")."""
-    _want("rsa_head", want)
-    emb, stride, base_codes, L = _rsa_operands("rsa_head", emb, base_codes, "emb", "base_codes")
-    lib = _lib.load()
-    ws = torch.empty(max(lib.rnamsm_rsa_head_workspace_bytes(L, n_models), 16), dtype=torch.uint8, device=emb.device)
-    out = torch.empty(n_models, L, device=emb.device, dtype=torch.float32)
-    ptr = out.data_ptr()
-    _lib.check(lib.rnamsm_rsa_head(emb.data_ptr(), stride, base_codes.data_ptr(), L, n_models, 1 if use_onehot else 0, ptrs,
-                                   ptr if want == "probs" else None, ptr if want == "logits" else None, ws.data_ptr(), ws.numel(),
-                                   _stream()))
-    return out
+    return _rsa_head_run(_RSA_HEAD, emb, base_codes, ptrs, n_models, use_onehot, want)
+
+
+@_on_operand_device
+def rsa_head_long(emb: torch.Tensor, base_codes: torch.Tensor, ptrs, n_models: int, use_onehot: bool, want: str = "probs") -> torch.Tensor:
+    """rsa_head for L up to LONG_MAX_L (rnamsm_rsa_head_long: the same four stages on a workspace with 128 tile-sum rows per
+    model) -> [n_models, L]; the bits of rsa_head for an L both accept."""
+    return _rsa_head_run(_RSA_HEAD_LONG, emb, base_codes, ptrs, n_models, use_onehot, want)
 
 
 @_on_operand_device
@@ -953,29 +983,6 @@ def rsa_head_packed(embs: Sequence[torch.Tensor], codes: Sequence[torch.Tensor],
     return outs
 
 
-def _long_range(fn: str, t, name: str, dim: int) -> None:
-    """The range of a long RSA call, before anything else is asked of the operand: a length out of range is wrong on any device."""
-    if isinstance(t, torch.Tensor) and t.dim() == 2 and not 1 <= t.shape[dim] <= _lib.LONG_MAX_L:
-        raise ValueError(f"{fn}: {name}: L = {t.shape[dim]} outside [1, {_lib.LONG_MAX_L}]")
-
-
-@_on_operand_device
-def rsa_head_long(emb: torch.Tensor, base_codes: torch.Tensor, ptrs, n_models: int, use_onehot: bool, want: str = "probs") -> torch.Tensor:
-    """rsa_head for L up to LONG_MAX_L (rnamsm_rsa_head_long: the same four stages on a workspace with 128 tile-sum rows per
-    model) -> [n_models, L]; the bits of rsa_head for an L both accept."""
-    _want("rsa_head_long", want)
-    _long_range("rsa_head_long", emb, "emb", 0)
-    emb, stride, base_codes, L = _rsa_operands("rsa_head_long", emb, base_codes, "emb", "base_codes")
-    lib = _lib.load()
-    ws = torch.empty(max(lib.rnamsm_rsa_head_long_workspace_bytes(L, n_models), 16), dtype=torch.uint8, device=emb.device)
-    out = torch.empty(n_models, L, device=emb.device, dtype=torch.float32)
-    ptr = out.data_ptr()
-    _lib.check(lib.rnamsm_rsa_head_long(emb.data_ptr(), stride, base_codes.data_ptr(), L, n_models, 1 if use_onehot else 0, ptrs,
-                                        ptr if want == "probs" else None, ptr if want == "logits" else None, ws.data_ptr(),
-                                        ws.numel(), _stream()))
-    return out
-
-
 def _rsa_text_operands(fn: str, rsa: torch.Tensor, letters: torch.Tensor, name: str, letters_name: str, max_L: int = _lib.RSA_MAX_L):
     """One alignment of rsa_text / rsa_text_packed / rsa_text_long as the library reads it -> (rsa, letters, K, L)."""
     _dev(rsa, name)
@@ -999,7 +1006,14 @@ def rsa_text(rsa: torch.Tensor, letters: torch.Tensor) -> Tuple[torch.Tensor, to
     counts int32 [K + 3]: the bytes of each body, the fallback word, the zero word; ens float64 [2, L]: the ensemble's ASA and
     RSA).  Only the first counts[f] bytes of a body are written; with counts[K + 1] == 1 (a value outside [0, 1] or a letter outside
     ACGUT) text and ens are not to be used, and counts[K + 2] == 1 says that an ASA is exactly 0."""
-    return _rsa_text_run("rsa_text", [rsa], [letters])[0]
+    return _rsa_text_run(_RSA_TEXT, [rsa], [letters])[0]
+
+
+@_on_operand_device
+def rsa_text_long(rsa: torch.Tensor, letters: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """rsa_text for L up to LONG_MAX_L (rnamsm_rsa_text_long: the same kernel, as many passes of 256 positions as L needs), read
+    as rsa_text's results are."""
+    return _rsa_text_run(_RSA_TEXT_LONG, [rsa], [letters])[0]
 
 
 @_on_operand_device
@@ -1007,13 +1021,22 @@ def rsa_text_packed(rsa: Sequence[torch.Tensor], letters: Sequence[torch.Tensor]
     """rsa_text of every (rsa[b], letters[b]) in one call (rnamsm_rsa_text_packed: one workgroup per alignment and table; all the
     members of one K) -> a list of (text, counts, ens), each byte-identical to rsa_text on that alignment alone.  One allocation per
     output kind for the whole group: the returned tensors are views (every text starts on a 16-byte boundary of the buffer)."""
-    return _rsa_text_run("rsa_text_packed", rsa, letters)
+    return _rsa_text_run(None, rsa, letters)
 
 
-def _rsa_text_run(_fn: str, rsa, letters):
-    lone = _fn == "rsa_text"
-    members, device = _members(_fn, _rsa_text_operands, _lib.RSA_MAX_BATCH, None, ("value tables", "letter rows", "alignments"),
-                               {"rsa": rsa, "letters": letters}, checked=2, lone=lone)
+_RSA_TEXT = _Route("rsa_text", _lib.RSA_MAX_L)
+_RSA_TEXT_LONG = _Route("rsa_text_long", _lib.LONG_MAX_L)
+
+
+def _rsa_text_run(route: Optional[_Route], rsa, letters):
+    """route: the lone call's; None: the packed call."""
+    _fn = route.fn if route else "rsa_text_packed"
+    rule = _rsa_text_operands
+    if route:
+        _long_range(route, rsa[0], "rsa", 1)
+        rule = functools.partial(_rsa_text_operands, max_L=route.max_L)
+    members, device = _members(_fn, rule, _lib.RSA_MAX_BATCH, None, ("value tables", "letter rows", "alignments"),
+                               {"rsa": rsa, "letters": letters}, checked=2, lone=route is not None)
     if not members:
         return []
     B, K = len(members), members[0][2]
@@ -1025,30 +1048,13 @@ def _rsa_text_run(_fn: str, rsa, letters):
                     _carved([K + 3] * B, device, torch.int32),
                     (e.view(2, L) for e, L in zip(_carved([2 * L for L in Ls], device, torch.float64), Ls))))
     args = [(r.data_ptr(), l.data_ptr(), L, *(t.data_ptr() for t in o)) for (r, l, _, L), o in zip(members, outs)]
-    if lone:
+    if route:
         r, l, L, text, counts, ens = args[0]
-        _lib.check(lib.rnamsm_rsa_text(r, l, L, K, text, counts, ens, _stream()))
+        _lib.check(getattr(lib, route.entry)(r, l, L, K, text, counts, ens, _stream()))
         return outs
     items = (_lib.RsaTextItem * B)(*(_lib.RsaTextItem(*a) for a in args))
     _lib.check(lib.rnamsm_rsa_text_packed(items, B, K, _stream()))
     return outs
-
-
-@_on_operand_device
-def rsa_text_long(rsa: torch.Tensor, letters: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
-    """rsa_text for L up to LONG_MAX_L (rnamsm_rsa_text_long: the same kernel, as many passes of 256 positions as L needs) -> (text
-    uint8 [(K + 1) x 23 L], counts int32 [K + 3], ens float64 [2, L]), read as rsa_text's results are."""
-    _long_range("rsa_text_long", rsa, "rsa", 1)
-    rsa, letters, K, L = _rsa_text_operands("rsa_text_long", rsa, letters, "rsa", "letters", _lib.LONG_MAX_L)
-    if letters.device != rsa.device:
-        raise ValueError(f"rsa_text_long: rsa / letters lie on {rsa.device} / {letters.device}")
-    lib = _lib.load()
-    text = torch.empty(lib.rnamsm_rsa_text_long_bytes(L, K), dtype=torch.uint8, device=rsa.device)
-    counts = torch.empty(K + 3, dtype=torch.int32, device=rsa.device)
-    ens = torch.empty(2, L, dtype=torch.float64, device=rsa.device)
-    _lib.check(lib.rnamsm_rsa_text_long(rsa.data_ptr(), letters.data_ptr(), L, K, text.data_ptr(), counts.data_ptr(), ens.data_ptr(),
-                                        _stream()))
-    return text, counts, ens
 
 
 class LMWeights(NamedTuple):

@@ -230,10 +230,15 @@ class RSAEnsemble(nn.Module):
             raise ValueError(f"RSAEnsemble: {seq_name} has length {codes.numel()} for an embedding of L = {L}")
         return codes
 
-    def _run(self, emb: torch.Tensor, seq: Union[str, np.ndarray, torch.Tensor], want: str) -> torch.Tensor:
-        codes = self._codes_of(emb, seq, "emb", "seq", True).to(device=emb.device, dtype=torch.uint8)
+    def _run(self, emb: torch.Tensor, seq: Union[str, np.ndarray, torch.Tensor], want: str, long: bool = False) -> torch.Tensor:
+        """long: the route of a stitched long alignment (rnamsm_rsa_head_long, L up to LONG_MAX_L); there the shape and the length
+        are checked before the device: they are wrong on any device."""
+        codes = self._codes_of(emb, seq, "emb", "seq", not long, _lib.LONG_MAX_L if long else _lib.RSA_MAX_L)
+        if not emb.is_cuda:
+            raise _lib.RnamsmError("RSAEnsemble: emb must be a tensor on the HIP device (no CPU path exists)")
         ptrs, _ = self._packed_weights()
-        return ops.rsa_head(emb, codes, ptrs, len(self.members), self.use_onehot, want)
+        head = ops.rsa_head_long if long else ops.rsa_head
+        return head(emb, codes.to(device=emb.device, dtype=torch.uint8), ptrs, len(self.members), self.use_onehot, want)
 
     def predict(self, emb: torch.Tensor, seq) -> torch.Tensor:
         return self._run(emb, seq, "probs")
@@ -243,21 +248,13 @@ class RSAEnsemble(nn.Module):
 
     forward = predict
 
-    def _run_long(self, emb: torch.Tensor, seq, want: str) -> torch.Tensor:
-        # the shape and the length first: they are wrong on any device
-        codes = self._codes_of(emb, seq, "emb", "seq", False, _lib.LONG_MAX_L)
-        if not emb.is_cuda:
-            raise _lib.RnamsmError("RSAEnsemble: emb must be a tensor on the HIP device (no CPU path exists)")
-        ptrs, _ = self._packed_weights()
-        return ops.rsa_head_long(emb, codes.to(device=emb.device, dtype=torch.uint8), ptrs, len(self.members), self.use_onehot, want)
-
     def predict_long(self, emb: torch.Tensor, seq) -> torch.Tensor:
         """predict() for L up to LONG_MAX_L (rnamsm_rsa_head_long: a stitched long alignment's embedding); the bits of predict()
         for an L both accept."""
-        return self._run_long(emb, seq, "probs")
+        return self._run(emb, seq, "probs", long=True)
 
     def logits_long(self, emb: torch.Tensor, seq) -> torch.Tensor:
-        return self._run_long(emb, seq, "logits")
+        return self._run(emb, seq, "logits", long=True)
 
     def predict_text_long(self, emb: torch.Tensor, seq, letters=None):
         """predict_text() for L up to LONG_MAX_L -> ([K, L] RSA, table_text_long of it)."""
@@ -544,17 +541,20 @@ class RSAHead:
                                         dtype=torch.uint8).to(device) if self.text_on else None
         self.n_tensors = 2 + 3 * self.text_on
 
+    def _one(self, emb: torch.Tensor, atp: torch.Tensor, tokens: torch.Tensor, long: bool) -> RSAResult:
+        predict, text = (self.model.predict_long, table_text_long) if long else (self.model.predict, table_text)
+        values = predict(emb, self.base_lut[tokens])
+        return RSAResult(values, tokens, tuple(text(values, self.letters_lut[tokens])) if self.text_on else None)
+
     def one(self, emb: torch.Tensor, atp: torch.Tensor, tokens: torch.Tensor) -> RSAResult:
         """A lone alignment through the lone head; emb is read where it lies (atp is not read: the heads share one signature).  The
         formatter runs behind the head."""
-        values = self.model.predict(emb, self.base_lut[tokens])
-        return RSAResult(values, tokens, tuple(table_text(values, self.letters_lut[tokens])) if self.text_on else None)
+        return self._one(emb, atp, tokens, False)
 
     def one_long(self, emb: torch.Tensor, atp: torch.Tensor, tokens: torch.Tensor) -> RSAResult:
         """one() on the stitched embedding of a long alignment (data.long_heads=stitched), L up to LONG_MAX_L: the same record through
         the long entry points; with the formatter off the tables are left to the host writer, which has no length limit."""
-        values = self.model.predict_long(emb, self.base_lut[tokens])
-        return RSAResult(values, tokens, tuple(table_text_long(values, self.letters_lut[tokens])) if self.text_on else None)
+        return self._one(emb, atp, tokens, True)
 
     def many(self, embs: Sequence[torch.Tensor], atps: Sequence[torch.Tensor], tokens: Sequence[torch.Tensor]) -> List[RSAResult]:
         """A group in one launch set per stage (predict_many, table_text_many): every member's record holds the bits and bytes of

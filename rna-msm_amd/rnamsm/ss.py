@@ -177,9 +177,15 @@ class SSPredictor(nn.Module):
             raise ValueError(f"SSPredictor: {seq_name} has length {codes.numel()} for attention maps of L = {L}")
         return codes
 
-    def _run(self, atp: torch.Tensor, seq: Union[str, np.ndarray, torch.Tensor], want: str) -> torch.Tensor:
-        codes = self._codes_of(atp, seq, "atp", "seq", True).to(device=atp.device, dtype=torch.uint8)
+    def _run(self, atp: torch.Tensor, seq: Union[str, np.ndarray, torch.Tensor], want: str, long: bool = False) -> torch.Tensor:
+        """long: the route of a stitched long alignment (rnamsm_ss_head_long, L up to LONG_MAX_L), exact fp32 only."""
+        if long and self._gemm_dtype != "f32":
+            raise ValueError(f"SSPredictor: the long head runs in exact fp32 only, not in gemm_dtype={self._gemm_dtype!r}")
+        max_L = _lib.LONG_MAX_L if long else _lib.SS_MAX_L
+        codes = self._codes_of(atp, seq, "atp", "seq", True, max_L).to(device=atp.device, dtype=torch.uint8)
         ptrs, _ = self._packed_weights()
+        if long:
+            return ops.ss_head_long(atp, codes, ptrs, self.num_blocks, want)
         return ops.ss_head(atp, codes, ptrs, self.num_blocks, want, self._gemm_dtype)
 
     def predict(self, atp: torch.Tensor, seq) -> torch.Tensor:
@@ -190,20 +196,13 @@ class SSPredictor(nn.Module):
 
     forward = predict
 
-    def _run_long(self, atp: torch.Tensor, seq, want: str) -> torch.Tensor:
-        if self._gemm_dtype != "f32":
-            raise ValueError(f"SSPredictor: the long head runs in exact fp32 only, not in gemm_dtype={self._gemm_dtype!r}")
-        codes = self._codes_of(atp, seq, "atp", "seq", True, _lib.LONG_MAX_L).to(device=atp.device, dtype=torch.uint8)
-        ptrs, _ = self._packed_weights()
-        return ops.ss_head_long(atp, codes, ptrs, self.num_blocks, want)
-
     def predict_long(self, atp: torch.Tensor, seq) -> torch.Tensor:
         """predict() on the stitched maps of a long alignment, L up to LONG_MAX_L = 4096 (rnamsm_ss_head_long: the same kernels, so
         predict()'s bits where both run); exact fp32 only."""
-        return self._run_long(atp, seq, "probs")
+        return self._run(atp, seq, "probs", long=True)
 
     def logits_long(self, atp: torch.Tensor, seq) -> torch.Tensor:
-        return self._run_long(atp, seq, "logits")
+        return self._run(atp, seq, "logits", long=True)
 
     def _run_many(self, atps: Sequence[torch.Tensor], seqs: Sequence, want: str) -> List[torch.Tensor]:
         atps, seqs = list(atps), list(seqs)
@@ -471,19 +470,22 @@ class SSHead:
         self.n_tensors = 2 + 2 * self.text_on + 4 * self.pairs_on
 
     # ------------------------------------------------------------------ records
+    def _one(self, emb: torch.Tensor, atp: torch.Tensor, tokens: torch.Tensor, long: bool) -> SSResult:
+        predict, text, pairs = ((self.model.predict_long, prob_text_long, structure_long) if long
+                                else (self.model.predict, prob_text, structure))
+        probs = predict(atp, self.base_lut[tokens])
+        return SSResult(probs, tokens, tuple(text(probs)) if self.text_on else None,
+                        tuple(pairs(probs, self.letters_lut[tokens])) if self.pairs_on else None)
+
     def one(self, emb: torch.Tensor, atp: torch.Tensor, tokens: torch.Tensor) -> SSResult:
         """A lone alignment through the lone ops; atp is read where it lies (emb is not read: the heads share one signature).  The
         formatter and the decoding run behind the head."""
-        probs = self.model.predict(atp, self.base_lut[tokens])
-        return SSResult(probs, tokens, tuple(prob_text(probs)) if self.text_on else None,
-                        tuple(structure(probs, self.letters_lut[tokens])) if self.pairs_on else None)
+        return self._one(emb, atp, tokens, False)
 
     def one_long(self, emb: torch.Tensor, atp: torch.Tensor, tokens: torch.Tensor) -> SSResult:
         """one() on a stitched long alignment (data.long_heads=stitched), L up to LONG_MAX_L: the same record through the long entry
         points; with a switch off, that part is left to the host writer, which has no length limit."""
-        probs = self.model.predict_long(atp, self.base_lut[tokens])
-        return SSResult(probs, tokens, tuple(prob_text_long(probs)) if self.text_on else None,
-                        tuple(structure_long(probs, self.letters_lut[tokens])) if self.pairs_on else None)
+        return self._one(emb, atp, tokens, True)
 
     def many(self, embs: Sequence[torch.Tensor], atps: Sequence[torch.Tensor], tokens: Sequence[torch.Tensor]) -> List[SSResult]:
         """A group in one launch set per stage (predict_many, prob_text_many, structure_many): every member's record holds the bits

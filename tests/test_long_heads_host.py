@@ -149,6 +149,80 @@ def test_refusals_of_the_ss_head(lib):
              "ss_head:", "L=1025", "[1, 1024]")
 
 
+def test_the_contact_head_on_stripped_maps_refuses_misaligned_pointers(lib):
+    """The lone entry holds the long one's alignment refusals, under its own name."""
+    def call(atp=FAKE, contacts=4 * FAKE, workspace=5 * FAKE):
+        return lib.rnamsm_contact_head_atp(atp, 1 << 20, 8, 120, 2 * FAKE, 3 * FAKE, contacts, workspace, 1 << 22, None)
+
+    for name in ("atp", "contacts", "workspace"):
+        _refused(lib, call(**{name: FAKE * 9 + 2}), "contact_head_atp:", name, "4-byte")
+        _refused(lib, call(**{name: FAKE * 9 + 1}), "contact_head_atp:", name, "4-byte")
+
+
+# Each pair of lone entries is one function under two names and limits: the bad arguments of a pair in the order of its checks, as
+# (overrides of the good call, words of the refusal).  "over" stands for the entry's own limit + 1.
+def _rsa_table(hole=None):
+    t = (ctypes.c_void_p * (4 + 26 * 3))(*[FAKE * (32 + k) for k in range(4 + 26 * 3)])
+    if hole is not None:
+        t[hole] = None
+    return t
+
+
+PAIRS = {
+    "contact": dict(
+        entries=(("contact_head_atp", 1023), ("contact_head_long", 4096)),
+        args=("atp", "stride", "L", "nch", "weight", "bias", "contacts", "workspace", "nbytes"),
+        good=dict(atp=FAKE, stride=1 << 24, L=8, nch=120, weight=2 * FAKE, bias=3 * FAKE, contacts=4 * FAKE, workspace=5 * FAKE,
+                  nbytes=1 << 22),
+        bad=[(dict(atp=None), ("null", "(atp)")), (dict(weight=None), ("null", "(weight)")), (dict(bias=None), ("null", "(bias)")),
+             (dict(contacts=None), ("null", "(contacts)")), (dict(workspace=None), ("null", "(workspace)")),
+             (dict(L=0), ("L=0",)), (dict(L="over"), ("outside [1,",)), (dict(nch=0), ("nch=0",)),
+             (dict(stride=63), ("plane stride 63", "64")), (dict(atp=FAKE + 2), ("atp", "4-byte")),
+             (dict(contacts=4 * FAKE + 2), ("contacts", "4-byte")), (dict(workspace=5 * FAKE + 2), ("workspace", "4-byte")),
+             (dict(nbytes=4 * (120 * 8 + 120) - 1), ("workspace too small", "workspace of 4319 bytes", "4320 needed"))]),
+    "rsa": dict(
+        entries=(("rsa_head", 1024), ("rsa_head_long", 4096)),
+        args=("emb", "stride", "codes", "L", "K", "onehot", "weights", "probs", "logits", "workspace", "nbytes"),
+        good=dict(emb=FAKE, stride=768, codes=2 * FAKE, L=8, K=3, onehot=1, weights=_rsa_table(), probs=3 * FAKE, logits=4 * FAKE,
+                  workspace=5 * FAKE, nbytes=1 << 30),
+        bad=[(dict(emb=None), ("null", "(emb)")), (dict(codes=None), ("null", "(base_codes)")), (dict(weights=None), ("null", "(weights)")),
+             (dict(workspace=None), ("null", "(workspace)")), (dict(probs=None, logits=None), ("neither probs nor logits",)),
+             (dict(L=0), ("L=0",)), (dict(L="over"), ("outside [1,",)), (dict(K=9), ("n_models=9",)),
+             (dict(stride=767), ("row stride 767",)), (dict(nbytes=1023), ("workspace of 1023 bytes", "needed")),
+             (dict(emb=FAKE + 8), ("emb", "16-byte")), (dict(workspace=5 * FAKE + 8), ("workspace", "16-byte")),
+             (dict(probs=3 * FAKE + 2), ("probs", "4-byte")), (dict(logits=4 * FAKE + 2), ("logits", "4-byte")),
+             (dict(weights=_rsa_table(35)), ("weight pointer 35 is null",))]),
+    "ss": dict(
+        entries=(("ss_head", 1024), ("ss_head_long", 4096)),
+        args=("atp", "stride", "codes", "L", "blocks", "weights", "logits", "probs", "workspace", "nbytes"),
+        good=dict(atp=FAKE, stride=1 << 24, codes=2 * FAKE, L=8, blocks=1, weights=(ctypes.c_void_p * 12)(*[FAKE * (16 + k) for k in range(12)]),
+                  logits=3 * FAKE, probs=4 * FAKE, workspace=5 * FAKE, nbytes=1 << 40),
+        bad=[(dict(atp=None), ("null",)), (dict(logits=None, probs=None), ("neither logits nor probs",)), (dict(L=0), ("L=0",)),
+             (dict(L="over"), ("outside [1,",)), (dict(blocks=0), ("num_blocks=0",)), (dict(stride=63), ("plane stride 63",)),
+             (dict(nbytes=1023), ("workspace too small",)), (dict(workspace=5 * FAKE + 8), ("16-byte", "workspace"))]),
+}
+
+
+@pytest.mark.parametrize("pair", sorted(PAIRS))
+def test_both_entries_of_a_pair_refuse_the_same_bad_argument_at_the_same_place(lib, pair):
+    """Every bad argument alone, and together with all that a later check would refuse: both entries answer with the earliest check's
+    refusal, under their own name and with their own limit."""
+    p = PAIRS[pair]
+    for name, max_L in p["entries"]:
+        fn = getattr(lib, "rnamsm_" + name)
+        for i, (bad, words) in enumerate(p["bad"]):
+            later = {}
+            for more, _ in reversed(p["bad"][i + 1:]):
+                later.update(more)
+            for overrides in (bad, {**later, **bad}):
+                kw = {**p["good"], **overrides}
+                if kw["L"] == "over":
+                    kw["L"] = max_L + 1
+                _refused(lib, fn(*(kw[a] for a in p["args"]), None), name + ":", *words)
+                if bad.get("L") == "over":
+                    _refused(lib, fn(*(kw[a] for a in p["args"]), None), f"L={max_L + 1}", f"[1, {max_L}]")
+
+
 # ---------------------------------------------------------------------- ss_pairs_long.h on the host
 @pytest.fixture(scope="module")
 def program(tmp_path_factory):
