@@ -32,7 +32,8 @@ extern "C" {
 #define RNAMSM_VERSION 600 /* major*10000 + minor*100 + patch; 6.0 (round 6): same 63 entry points and signatures; ten knob names of
                               * rnamsm_set_param are gone (INVALID), rnamsm_forward_packed refuses a table mixing the two LayerNorm-fold classes,
                               * rnamsm_pack_outputs requires D % 4 == 0 and 16-byte-aligned x_final / emb.  5.0: rnamsm_forward_packed takes dtype +
-                              * weight_planes, dtype value 2 (bf16x3) answers UNSUPPORTED, + rnamsm_softmax_rows_scaled; 4.0: row_pos_dim, rnamsm_embed_ln_rows */
+                              * weight_planes, dtype value 2 (bf16x3) answers UNSUPPORTED, + rnamsm_softmax_rows_scaled; 4.0: row_pos_dim, rnamsm_embed_ln_rows.
+                              * Entry points added since (the heads, the stitcher, rnamsm_msa_invcov) are additive and left the number where it was. */
 
 typedef enum {
     RNAMSM_OK = 0,
@@ -824,6 +825,28 @@ int rnamsm_greedy_select(const uint8_t* msa, int N, int L, int num_seqs, int min
  * contract).  The reference compares raw character bytes; any one-to-one recoding (the tokenizer's ids for A/C/G/U/X/-)
  * gives the same distances. */
 int rnamsm_msa_weights(const uint8_t* msa, int N, int L, double seqid_cutoff, double* weights, void* stream);
+
+/* Covariance contacts (MSA.invcov, utils/align.py:183-193): out[i, j] = the spectral norm of the K x K block (column i, column j) of
+ * np.cov of the one-hot alignment, float64 [L, L] -- the co-evolution map of the raw alignment, no network involved.  tokens uint8
+ * [N, L] with leading dimension ld >= L; the K symbols are the distinct values other than `gap` that occur, ascending; a gap is all
+ * zeros in the one-hot.  The reference runs over raw character bytes; any one-to-one recoding (the tokenizer's ids) permutes the
+ * rows and columns of every block and leaves its spectral norm unchanged, so token ids give the same map.
+ *   stage 1  n_ab(i,j) = #{rows with symbol a in column i and b in column j}: exact int32 from and + popcount over bit planes of the
+ *            alignment, no atomics, the same bits on every run;
+ *   stage 2  B[a][b] = ((double)n_ab(i,j) - ((double)n_a(i) * (double)n_b(j)) / N) / (N - 1) in exactly this order (n_a(i) =
+ *            n_aa(i,i); the product is exact), then the largest singular value of B by one-sided Jacobi in fp64.  A zero block
+ *            (a constant column) gives exactly 0; no finite input gives NaN.  B(j,i) is the transpose of B(i,j): the upper triangle
+ *            is computed and mirrored, so out is exactly symmetric.
+ * counts: NULL, or int32 [32 + L*L*K*K]: a header (K, then the K symbols ascending, then zeros) followed by n_ab as [L, L, K, K];
+ * the caller sizes it for the K of its alignment (16 is the upper bound).
+ * N in [2, 2^20], L in [1, RNAMSM_LONG_MAX_L], K in [1, 16]: an alignment of gaps only (K = 0) or with more than 16 distinct
+ * non-gap values is refused, the message names the count.  workspace: 256-byte aligned, rnamsm_msa_invcov_workspace_bytes(N, L)
+ * bytes (0 outside the limits; sized for K = 16: the bit planes, N * L * 2 bytes and padding, and a band of counts of at most
+ * 256 MB).  Unlike the rest of this header the call WAITS for the stream once: K is read back before the planes are laid out.  It
+ * must not be captured into a graph. */
+size_t rnamsm_msa_invcov_workspace_bytes(int N, int L);
+int rnamsm_msa_invcov(const uint8_t* tokens, int N, int L, int64_t ld, int gap, double* out, int32_t* counts, void* workspace,
+                      size_t workspace_bytes, void* stream);
 
 /* Whole forward, K0..K10 for one MSA, driven from C++ so that one call enqueues every launch
  * (MSATransformer.forward, model.py:338-416, with repr_layers=[num_layers], need_head_weights=True,

@@ -1,0 +1,319 @@
+// Covariance contacts of an alignment on the device (MSA.invcov, utils/align.py:183-193): the classical co-evolution map,
+//   out[i, j] = || cov(onehot column i, onehot column j) ||_2     float64 [L, L],
+// from the raw alignment, without the network.  The reference one-hot encodes the N x L characters over the K distinct non-gap
+// values that occur (ascending; a gap is all zeros), takes np.cov of the [N, L*K] matrix (N - 1 in the denominator) and the
+// spectral norm of every K x K block.  An entry of that covariance is a rational function of INTEGER counts,
+//   c[(i,a),(j,b)] = (n_ab(i,j) - n_a(i) * n_b(j) / N) / (N - 1),      n_ab(i,j) = #{rows with a in column i and b in column j},
+// n_a(i) = n_aa(i,i), so the O(L^2 N) part is exact integer work and the N x L x K one-hot never exists.
+//
+// Data flow (all on the caller's stream; every buffer in the caller's workspace):
+//   presence   which of the 256 byte values occur                                       invcov_presence_kernel
+//   table      byte -> symbol index (0xFF: the gap or absent), K and the K symbols      invcov_table_kernel   -> host reads K
+//   planes     P[w][i*K + a]: bit n % 64 of word n / 64 says "row n has symbol a in column i"; word-major, rows padded with
+//              zero words to a multiple of 64, words to a multiple of 16; bits past N are zero       invcov_planes_kernel
+//   marginals  n_a(i) = sum_w popcount(P[w][i*K + a])                                    invcov_marginals_kernel
+//   counts     n_ab(i,j) = sum_w popcount(P[w][i*K+a] & P[w][j*K+b]), int32, a band of columns i at a time    invcov_count_kernel
+//   norm       the block in fp64, one-sided Jacobi, the upper triangle mirrored         invcov_norm_kernel
+// The count kernel sees the planes as a bit matrix of R = L*K rows and computes R x R popcount inner products like a GEMM: a
+// block of 256 threads owns 64 x 64 of them (64 / K alignment columns each way: the tile is counted in (column, symbol) rows, so any
+// K in 1..16 runs the same code), a thread 4 x 4 in 16 int32 registers; 16 words of the 64 + 64 rows are staged in LDS (2 x 8 KB,
+// word-major, so both the global reads and the LDS reads are contiguous 16-byte vectors).  Each sum is over one thread's words in
+// ascending order in integers: no atomics, the same bits on every run.  Tiles wholly below the diagonal are skipped unless the
+// caller asked for the counts.
+#include "common.h"
+
+namespace rnamsm {
+
+constexpr int IC_TILE = 64;        // (column, symbol) rows of a count tile, each way
+constexpr int IC_WK = 16;          // words staged per step
+constexpr int IC_MAX_K = 16;
+constexpr int IC_META = 32;        // int32 header: K, then the symbols ascending (the first 16 of them)
+constexpr int IC_MAX_N = 1 << 20;
+constexpr size_t IC_BAND_BYTES = (size_t)1 << 28;      // counts of one band of columns i
+
+// ---- which byte values occur ------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void invcov_presence_kernel(const uint8_t* __restrict__ tok, int N, int L, int64_t ld,
+                                                              uint32_t* __restrict__ present) {
+    __shared__ uint32_t seen[256];
+    seen[threadIdx.x] = 0;
+    __syncthreads();
+    for (int n = blockIdx.x; n < N; n += gridDim.x)
+        for (int c = threadIdx.x; c < L; c += 256) seen[tok[(int64_t)n * ld + c]] = 1u;      // racing stores of the same value
+    __syncthreads();
+    if (seen[threadIdx.x]) present[threadIdx.x] = 1u;
+}
+
+// one block of 256: rank of every present non-gap byte among them = its symbol index
+__global__ __launch_bounds__(256) void invcov_table_kernel(const uint32_t* __restrict__ present, int gap, uint8_t* __restrict__ lut,
+                                                           int32_t* __restrict__ meta) {
+    __shared__ int flag[256];
+    const int b = threadIdx.x;
+    flag[b] = (present[b] != 0u && b != gap) ? 1 : 0;
+    if (b < IC_META) meta[b] = 0;
+    __syncthreads();
+    int rank = 0, total = 0;
+    for (int q = 0; q < 256; ++q) {
+        rank += q < b ? flag[q] : 0;
+        total += flag[q];
+    }
+    lut[b] = (flag[b] && rank < IC_MAX_K) ? (uint8_t)rank : (uint8_t)0xFF;
+    if (flag[b] && rank < IC_MAX_K) meta[1 + rank] = b;
+    if (b == 0) meta[0] = total;
+}
+
+// ---- bit planes: block = word w (64 alignment rows) x 256 columns; lane = row, one ballot per symbol ---------------
+constexpr int IP_COLS = 256, IP_PITCH = 260;         // pitch 65 dwords: a wave's 64 rows of one column hit 64 banks
+__global__ __launch_bounds__(256) void invcov_planes_kernel(const uint8_t* __restrict__ tok, int N, int L, int64_t ld,
+                                                            const uint8_t* __restrict__ lut, int K, int64_t Rp,
+                                                            uint64_t* __restrict__ P) {
+    __shared__ uint8_t sym[64 * IP_PITCH];
+    __shared__ uint8_t slut[256];
+    const int w = blockIdx.y, c0 = blockIdx.x * IP_COLS;
+    slut[threadIdx.x] = lut[threadIdx.x];
+    __syncthreads();
+    for (int r = 0; r < 64; ++r) {
+        const int64_t n = (int64_t)w * 64 + r;
+        const int c = c0 + threadIdx.x;
+        sym[r * IP_PITCH + threadIdx.x] = (n < N && c < L) ? slut[tok[n * ld + c]] : (uint8_t)0xFF;
+    }
+    __syncthreads();
+    const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    for (int c = wv; c < IP_COLS && c0 + c < L; c += 4) {        // wave-uniform
+        const int s = sym[lane * IP_PITCH + c];
+        uint64_t mine = 0;
+        for (int a = 0; a < K; ++a) {
+            const uint64_t m = __ballot(s == a);
+            if (lane == a) mine = m;
+        }
+        if (lane < K) P[(int64_t)w * Rp + (int64_t)(c0 + c) * K + lane] = mine;
+    }
+}
+
+__global__ __launch_bounds__(256) void invcov_marginals_kernel(const uint64_t* __restrict__ P, int W, int64_t Rp, int R,
+                                                               int32_t* __restrict__ marg) {
+    const int r = blockIdx.x * 256 + threadIdx.x;
+    if (r >= R) return;
+    int m = 0;
+    for (int w = 0; w < W; ++w) m += __popcll(P[(int64_t)w * Rp + r]);
+    marg[r] = m;
+}
+
+// ---- stage 1: pair counts ---------------------------------------------------------------------------------------------
+// grid (column tiles, row tiles of the band).  row0: first (column, symbol) row of the band, a multiple of 64; rows_end: one
+// past its last.  cnt: the band's counts, [i - i0][j][a][b].  Wp: words, a multiple of IC_WK.  Rp: padded rows, a multiple of 64.
+__global__ __launch_bounds__(256) void invcov_count_kernel(const uint64_t* __restrict__ P, int Wp, int64_t Rp, int R, int K, int L,
+                                                           int64_t row0, int64_t rows_end, int i0, int full,
+                                                           int32_t* __restrict__ cnt) {
+    __shared__ __attribute__((aligned(16))) uint64_t sA[IC_WK][IC_TILE];
+    __shared__ __attribute__((aligned(16))) uint64_t sB[IC_WK][IC_TILE];
+    const int64_t rb = row0 + (int64_t)blockIdx.y * IC_TILE, cb = (int64_t)blockIdx.x * IC_TILE;
+    if (!full) {                                       // every pair of the tile has j < i: the norm reads the upper triangle only
+        const int64_t last_c = cb + IC_TILE - 1 < R - 1 ? cb + IC_TILE - 1 : R - 1;
+        if (last_c / K < rb / K) return;
+    }
+    const int ty = threadIdx.x >> 4, tx = threadIdx.x & 15;
+    int c[4][4];
+#pragma unroll
+    for (int x = 0; x < 4; ++x)
+#pragma unroll
+        for (int y = 0; y < 4; ++y) c[x][y] = 0;
+
+    for (int w0 = 0; w0 < Wp; w0 += IC_WK) {
+        // 16 words x 64 rows per operand = 512 vectors of two rows; the rows of one word are contiguous in P
+#pragma unroll
+        for (int v = threadIdx.x; v < IC_WK * IC_TILE / 2; v += 256) {
+            const int w = v >> 5, p = (v & 31) * 2;
+            const uint64_t* base = P + (int64_t)(w0 + w) * Rp;
+            *reinterpret_cast<uint4*>(&sA[w][p]) = *reinterpret_cast<const uint4*>(base + rb + p);
+            *reinterpret_cast<uint4*>(&sB[w][p]) = *reinterpret_cast<const uint4*>(base + cb + p);
+        }
+        __syncthreads();
+#pragma unroll
+        for (int w = 0; w < IC_WK; ++w) {
+            uint64_t a[4], b[4];
+#pragma unroll
+            for (int x = 0; x < 4; ++x) { a[x] = sA[w][ty * 4 + x]; b[x] = sB[w][tx * 4 + x]; }
+#pragma unroll
+            for (int x = 0; x < 4; ++x)
+#pragma unroll
+                for (int y = 0; y < 4; ++y) c[x][y] += __popcll(a[x] & b[y]);
+        }
+        __syncthreads();
+    }
+#pragma unroll
+    for (int x = 0; x < 4; ++x) {
+        const int64_t r = rb + ty * 4 + x;
+        if (r >= rows_end) continue;
+        const int i = (int)(r / K), a = (int)(r - (int64_t)i * K);
+#pragma unroll
+        for (int y = 0; y < 4; ++y) {
+            const int64_t col = cb + tx * 4 + y;
+            if (col >= R) continue;
+            const int j = (int)(col / K), b = (int)(col - (int64_t)j * K);
+            cnt[(((int64_t)(i - i0) * L + j) * K + a) * K + b] = c[x][y];
+        }
+    }
+}
+
+// ---- stage 2: the covariance block and its spectral norm --------------------------------------------------------------------
+// One thread per (i, j >= i).  B[a][b] = ((double)n_ab - ((double)n_a * (double)n_b) / N) / (N - 1), in that order: the product is
+// exact (N <= 2^20), then one division, one subtraction, one division (compiled without contraction).  The largest singular value
+// by one-sided Jacobi (Hestenes) on the columns of B, held in LDS element-major ([a*K + b][thread]: conflict-free): cyclic sweeps
+// over the column pairs, a pair is rotated while |<p, q>| > 2^-52 |p| |q|; it stops after a sweep without a rotation, or after
+// IC_SWEEPS.  A zero block rotates nothing and gives exactly 0; no finite block gives NaN (the rotation divides by 2 <p, q> != 0
+// only, and an overflowing cotangent gives t = 0).  ||B(j,i)|| = ||B(i,j)^T|| = ||B(i,j)||: the value is written to both places.
+constexpr int IC_SWEEPS = 40;
+__global__ __launch_bounds__(256) void invcov_norm_kernel(const int32_t* __restrict__ cnt, const int32_t* __restrict__ marg, int N,
+                                                          int L, int K, int i0, int i1, double* __restrict__ out) {
+    extern __shared__ __attribute__((aligned(16))) double sm[];
+    const int T = blockDim.x, t = threadIdx.x;
+    const int j = blockIdx.x * T + t, i = i0 + blockIdx.y;
+    if (i >= i1 || j >= L || j < i) return;                       // (no barrier below: a thread's matrix is its own)
+    double* B = sm + t;
+    const int32_t* cb = cnt + ((int64_t)(i - i0) * L + j) * K * K;
+    const double dn = (double)N, dn1 = (double)(N - 1);
+    for (int a = 0; a < K; ++a) {
+        const double na = (double)marg[i * K + a];
+        for (int b = 0; b < K; ++b) {
+            const double nb = (double)marg[j * K + b];
+            const double prod = na * nb;
+            const double mean = prod / dn;
+            const double diff = (double)cb[a * K + b] - mean;
+            B[(a * K + b) * T] = diff / dn1;
+        }
+    }
+    for (int sweep = 0; sweep < IC_SWEEPS; ++sweep) {
+        bool rotated = false;
+        for (int p = 0; p < K - 1; ++p)
+            for (int q = p + 1; q < K; ++q) {
+                double alpha = 0.0, beta = 0.0, gamma = 0.0;
+                for (int k = 0; k < K; ++k) {
+                    const double x = B[(k * K + p) * T], y = B[(k * K + q) * T];
+                    alpha += x * x;
+                    beta += y * y;
+                    gamma += x * y;
+                }
+                if (!(fabs(gamma) > 2.220446049250313e-16 * sqrt(alpha * beta))) continue;
+                rotated = true;
+                const double zeta = (beta - alpha) / (2.0 * gamma);
+                const double tn = (zeta >= 0.0 ? 1.0 : -1.0) / (fabs(zeta) + sqrt(1.0 + zeta * zeta));
+                const double cs = 1.0 / sqrt(1.0 + tn * tn), sn = cs * tn;
+                for (int k = 0; k < K; ++k) {
+                    const double x = B[(k * K + p) * T], y = B[(k * K + q) * T];
+                    B[(k * K + p) * T] = cs * x - sn * y;
+                    B[(k * K + q) * T] = sn * x + cs * y;
+                }
+            }
+        if (!rotated) break;
+    }
+    double best = 0.0;
+    for (int p = 0; p < K; ++p) {
+        double s = 0.0;
+        for (int k = 0; k < K; ++k) {
+            const double x = B[(k * K + p) * T];
+            s += x * x;
+        }
+        best = s > best ? s : best;
+    }
+    const double v = sqrt(best);
+    out[(int64_t)i * L + j] = v;
+    out[(int64_t)j * L + i] = v;
+}
+
+struct InvcovWs {
+    size_t present, lut, meta, marg, planes, band, total;
+    int W, Wp;
+    int64_t Rp;
+};
+// K: the symbols the layout is made for (the size function knows no K and takes IC_MAX_K; the call lays the planes out for the K
+// it found, inside the same bytes)
+static InvcovWs invcov_ws(int N, int L, int K) {
+    InvcovWs w;
+    w.W = (N + 63) / 64;
+    w.Wp = (w.W + IC_WK - 1) / IC_WK * IC_WK;
+    w.Rp = ((int64_t)L * K + IC_TILE - 1) / IC_TILE * IC_TILE;
+    size_t off = 0;
+    w.present = off; off += 256 * 4;
+    w.lut = off;     off += 256;
+    w.meta = off;    off += IC_META * 4;
+    w.marg = off;    off += (((size_t)L * IC_MAX_K * 4) + 255) & ~(size_t)255;
+    off = (off + 255) & ~(size_t)255;
+    w.planes = off;  off += (size_t)w.Wp * (size_t)w.Rp * 8;
+    off = (off + 255) & ~(size_t)255;
+    const size_t whole = (size_t)L * L * IC_MAX_K * IC_MAX_K * 4;
+    w.band = off;    off += whole < IC_BAND_BYTES ? whole : IC_BAND_BYTES;
+    w.total = off;
+    return w;
+}
+
+}  // namespace rnamsm
+
+using namespace rnamsm;
+
+extern "C" size_t rnamsm_msa_invcov_workspace_bytes(int N, int L) {
+    if (N < 2 || N > IC_MAX_N || L < 1 || L > RNAMSM_LONG_MAX_L) return 0;
+    return invcov_ws(N, L, IC_MAX_K).total;
+}
+
+extern "C" int rnamsm_msa_invcov(const uint8_t* tokens, int N, int L, int64_t ld, int gap, double* out, int32_t* counts,
+                                 void* workspace, size_t workspace_bytes, void* stream) {
+    RNAMSM_CHECK_ARG(tokens && out && workspace, "msa_invcov: null pointer");
+    RNAMSM_CHECK_ARG(N >= 2 && N <= IC_MAX_N, "msa_invcov: N=%d outside [2, %d]", N, IC_MAX_N);
+    RNAMSM_CHECK_ARG(L >= 1 && L <= RNAMSM_LONG_MAX_L, "msa_invcov: L=%d outside [1, %d]", L, RNAMSM_LONG_MAX_L);
+    RNAMSM_CHECK_ARG(ld >= L, "msa_invcov: ld=%lld is smaller than L=%d", (long long)ld, L);
+    RNAMSM_CHECK_ARG(gap >= 0 && gap <= 255, "msa_invcov: gap=%d is not a byte value", gap);
+    const InvcovWs full_ws = invcov_ws(N, L, IC_MAX_K);
+    RNAMSM_CHECK_ARG(workspace_bytes >= full_ws.total && (reinterpret_cast<uintptr_t>(workspace) & 255u) == 0,
+                     "msa_invcov: workspace too small or misaligned (256 bytes)");
+    RNAMSM_CHECK_ARG((reinterpret_cast<uintptr_t>(out) & 7u) == 0 && (reinterpret_cast<uintptr_t>(counts) & 3u) == 0,
+                     "msa_invcov: out / counts misaligned");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    char* ws = static_cast<char*>(workspace);
+    uint32_t* present = reinterpret_cast<uint32_t*>(ws + full_ws.present);
+    uint8_t* lut = reinterpret_cast<uint8_t*>(ws + full_ws.lut);
+    int32_t* meta = reinterpret_cast<int32_t*>(ws + full_ws.meta);
+    int32_t* marg = reinterpret_cast<int32_t*>(ws + full_ws.marg);
+
+    // ---- the symbols that occur: the one place where the host waits for the stream (K decides the layout and two refusals)
+    if (hipMemsetAsync(present, 0, 256 * 4, s) != hipSuccess) return fail(RNAMSM_ERR_HIP, "msa_invcov: hipMemsetAsync failed");
+    hipLaunchKernelGGL(invcov_presence_kernel, dim3(N < 2048 ? N : 2048), dim3(256), 0, s, tokens, N, L, ld, present);
+    hipLaunchKernelGGL(invcov_table_kernel, dim3(1), dim3(256), 0, s, present, gap, lut, meta);
+    RNAMSM_CHECK_LAUNCH("msa_invcov");
+    int32_t host_meta[IC_META];
+    if (hipMemcpyAsync(host_meta, meta, sizeof(host_meta), hipMemcpyDeviceToHost, s) != hipSuccess ||
+        hipStreamSynchronize(s) != hipSuccess)
+        return fail(RNAMSM_ERR_HIP, "msa_invcov: reading the symbol table back failed: %s", hipGetErrorString(hipGetLastError()));
+    const int K = host_meta[0];
+    RNAMSM_CHECK_ARG(K >= 1, "msa_invcov: the alignment holds nothing but the gap value %d (K = 0)", gap);
+    RNAMSM_CHECK_ARG(K <= IC_MAX_K, "msa_invcov: %d distinct non-gap values, more than %d", K, IC_MAX_K);
+
+    const InvcovWs w = invcov_ws(N, L, K);               // (every offset up to the planes is independent of K)
+    uint64_t* P = reinterpret_cast<uint64_t*>(ws + w.planes);
+    const int R = L * K;
+    if (hipMemsetAsync(P, 0, (size_t)w.Wp * (size_t)w.Rp * 8, s) != hipSuccess)
+        return fail(RNAMSM_ERR_HIP, "msa_invcov: hipMemsetAsync failed");
+    hipLaunchKernelGGL(invcov_planes_kernel, dim3((L + IP_COLS - 1) / IP_COLS, w.W), dim3(256), 0, s, tokens, N, L, ld, lut, K, w.Rp, P);
+    hipLaunchKernelGGL(invcov_marginals_kernel, dim3((R + 255) / 256), dim3(256), 0, s, P, w.W, w.Rp, R, marg);
+    int32_t* body = reinterpret_cast<int32_t*>(ws + full_ws.band);
+    int band = L;                                        // columns i per band: all of them, or a multiple of 64 (tile-aligned rows)
+    if (counts) {
+        if (hipMemcpyAsync(counts, meta, IC_META * 4, hipMemcpyDeviceToDevice, s) != hipSuccess)
+            return fail(RNAMSM_ERR_HIP, "msa_invcov: hipMemcpyAsync failed");
+        body = counts + IC_META;
+    } else {
+        const size_t per_col = (size_t)L * K * K * 4;
+        if (per_col * L > IC_BAND_BYTES) band = (int)(IC_BAND_BYTES / per_col / 64) * 64;      // >= 64: per_col <= 2^22
+    }
+    const int T = K <= 4 ? 256 : (K <= 8 ? 64 : 32);     // K^2 doubles per thread in LDS: at most 64 KB a block
+    for (int i0 = 0; i0 < L; i0 += band) {
+        const int i1 = i0 + band < L ? i0 + band : L;
+        const int64_t row0 = (int64_t)i0 * K, rows_end = (int64_t)i1 * K;
+        int32_t* cnt = counts ? body + (int64_t)i0 * L * K * K : body;
+        hipLaunchKernelGGL(invcov_count_kernel, dim3((unsigned)(w.Rp / IC_TILE), (unsigned)((rows_end - row0 + IC_TILE - 1) / IC_TILE)),
+                           dim3(256), 0, s, P, w.Wp, w.Rp, R, K, L, row0, rows_end, i0, counts ? 1 : 0, cnt);
+        hipLaunchKernelGGL(invcov_norm_kernel, dim3((L + T - 1) / T, i1 - i0), dim3(T), (size_t)K * K * T * 8, s, cnt, marg, N, L, K,
+                           i0, i1, out);
+    }
+    RNAMSM_CHECK_LAUNCH("msa_invcov");
+    return RNAMSM_OK;
+}

@@ -56,6 +56,8 @@ LM_OUTPUTS = ("logits", "logp", "scores", "nll")
 STITCH_MAX_L, STITCH_MAX_H = 1 << 19, 1 << 16      # rnamsm_stitch_rows / _pairs
 LONG_MAX_L = 4096                  # rnamsm_contact_head_long / _ss_head_long / _ss_prob_text_long / _ss_pairs_long / _rsa_head_long /
                                    # _rsa_text_long: a stitched alignment
+# rnamsm_msa_invcov: rows, symbols, and the int32 header in front of the optional counts (K, then the symbols)
+INVCOV_MAX_N, INVCOV_MAX_K, INVCOV_META = 1 << 20, 16, 32
 
 
 class ModelDims(ctypes.Structure):
@@ -210,6 +212,8 @@ _SIGNATURES = {
     "rnamsm_greedy_select_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
     "rnamsm_greedy_select": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
     "rnamsm_msa_weights": (c_int, [c_void_p, c_int, c_int, c_double, c_void_p, c_void_p]),
+    "rnamsm_msa_invcov_workspace_bytes": (c_size_t, [c_int, c_int]),
+    "rnamsm_msa_invcov": (c_int, [c_void_p, c_int, c_int, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "rnamsm_forward_workspace_bytes": (c_size_t, [POINTER(ModelDims), c_int, c_int, c_int, c_int]),
     "rnamsm_forward": (c_int, [POINTER(ModelDims), POINTER(c_void_p), c_void_p, c_int, c_int, c_void_p, c_size_t,
                                c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int,

@@ -42,6 +42,12 @@ def check_long_heads(value: str) -> str:
     return value
 
 
+def check_invcov(value) -> bool:
+    if not isinstance(value, bool):
+        raise ValueError(f"data.invcov={value!r} is not one of false, true")
+    return value
+
+
 @dataclass
 class DataConfig:                       # RNA_MSM_Inference.py:20-32
     device: str = "cuda"
@@ -117,6 +123,11 @@ class DataConfig:                       # RNA_MSM_Inference.py:20-32
     # lm_scores=masked, an SS head under ss_gemm_dtype=bf16 and any longer alignment
     # stay skipped, each with a line that names the reason.  Alignments that are not stitched are untouched by the key.
     long_heads: str = "skip"
+    # extra (not in the reference's CLI; its utils/align.py MSA.invcov): the covariance contact map of the alignment AS READ -- every
+    # row, before row sub-sampling, and every column, whatever max_seqlen, long_msa and long_heads say -- computed on the device
+    # (rnamsm.msa.msa_invcov) and written as <id>_invcov.npy, (L, L) float64, next to <id>_emb.npy.  An alignment the kernel refuses
+    # (more than 4096 columns, more than 16 distinct non-gap tokens, fewer than 2 rows) gets one printed line and its other files.
+    invcov: bool = False
 
 
 @dataclass
@@ -190,4 +201,5 @@ def parse_overrides(argv: List[str], cfg: Config = None) -> Config:
     check_lm_scores(cfg.data.lm_scores)
     check_long_msa(cfg.data.long_msa)
     check_long_heads(cfg.data.long_heads)
+    check_invcov(cfg.data.invcov)
     return cfg

@@ -21,9 +21,9 @@ import torch
 
 from . import _lib, contacts, lm, ops, rsa, sharding, ss
 from .alphabet import RNAAlphabet
-from .config import Config, check_long_heads, check_long_msa, check_ss_gemm_dtype
+from .config import Config, check_invcov, check_long_heads, check_long_msa, check_ss_gemm_dtype
 from .model import MSATransformer
-from .msa import load_msa_tokens
+from .msa import load_msa_tokens, msa_invcov_device
 
 
 def load_checkpoint(model: MSATransformer, path: str, device) -> None:
@@ -315,6 +315,10 @@ def extract_feat(cfg: Config, model: Optional[MSATransformer] = None, gather_to_
     # data.long_heads=stitched: on such an alignment the contact head and the exact-fp32 SS head run on the stitched atp, and the RSA
     # head on the stitched emb, through the long entry points (L <= _lib.LONG_MAX_L); "skip" leaves everything as it was, the printed lines included
     long_heads = check_long_heads(getattr(cfg.data, "long_heads", "skip")) == "stitched"
+    # data.invcov: the covariance contact map of every alignment as read -- all rows, all columns -- made on the reader's side and
+    # written as <id>_invcov.npy by one more writer job; off, nothing below differs
+    invcov_on = check_invcov(getattr(cfg.data, "invcov", False))
+    invcov_maps: Dict[str, torch.Tensor] = {}           # id -> the map on the device, from read() until the alignment is emitted
     device = torch.device(cfg.data.device)
     if device.type != "cuda":
         raise RuntimeError("this build runs on the MI355X HIP path only (data.device=cuda); there is no CPU path")
@@ -397,8 +401,18 @@ def extract_feat(cfg: Config, model: Optional[MSATransformer] = None, gather_to_
         process reproduces the reference's choices; under sharding every rank draws for its own items."""
         torch.cuda.set_device(device)
         tokens = load_msa_tokens(files[ids[idx]], alphabet, cfg.data.max_seqs_per_msa, cfg.data.sample_method, device=device,
-                                 rng=rng)
+                                 rng=rng, on_full=(lambda full: covariance_map(ids[idx], full)) if invcov_on else None)
         return tokens if windowing else crop_tokens(tokens, cfg.data.max_seqlen, rng)
+
+    def covariance_map(rna_id: str, full: np.ndarray) -> None:
+        """data.invcov: the map of the alignment as read (before row sub-sampling and any crop), left on the device for emit(); an
+        alignment the kernel refuses gets one line that names the reason, and its other files as usual."""
+        try:
+            invcov_maps[rna_id] = msa_invcov_device(full, alphabet.tok_to_idx["-"], device)
+            torch.cuda.current_stream().synchronize()       # (the reader's stream: the map is complete whichever stream copies it)
+        except _lib.RnamsmError as e:
+            print(f"{rna_id}: no covariance map (data.invcov) for this alignment of {full.shape[0]} rows x {full.shape[1] - 1} "
+                  f"columns: {e}")
 
     writer = _AsyncNpyWriter(device) if async_io and (not gathering or rank == 0) else None
     reader = ThreadPoolExecutor(1, thread_name_prefix="rnamsm-msa-reader") if async_io else None
@@ -424,16 +438,22 @@ def extract_feat(cfg: Config, model: Optional[MSATransformer] = None, gather_to_
             return f"there is no long SS head under data.ss_gemm_dtype={h.model.gemm_dtype}"
         return None if isinstance(h, (ss.SSHead, rsa.RSAHead, contacts.ContactHead)) else "it has no long entry point"
 
-    def emit(rna_id: str, emb: torch.Tensor, atp: torch.Tensor, after: Optional[torch.cuda.Event] = None, records=()) -> None:
+    def emit(rna_id: str, emb: torch.Tensor, atp: torch.Tensor, after: Optional[torch.cuda.Event] = None, records=(),
+             cov: Optional[torch.Tensor] = None) -> None:
         """records: this alignment's record of every head that is on, in the order of `heads`; each becomes one writer job (but
-        for the heads skipped on a stitched alignment: their entry is a placeholder)."""
+        for the heads skipped on a stitched alignment: their entry is a placeholder).  cov: a gathered item's covariance map (or
+        its one-element placeholder); absent, the one read() left for this id, if any."""
         extra = [h.writer_job(r, rna_id, save_dir) for h, r in zip(heads, records) if not skipped_on(h, emb.shape[0])]
+        cov = invcov_maps.pop(rna_id, None) if cov is None else (cov if cov.dim() == 2 else None)
+        cov_job = [(save_dir / f"{rna_id}_invcov.npy", cov)] if cov is not None else []
         if writer is not None:
-            writer.submit([(save_dir / f"{rna_id}_atp.npy", atp), (save_dir / f"{rna_id}_emb.npy", emb)] + extra,
+            writer.submit([(save_dir / f"{rna_id}_atp.npy", atp), (save_dir / f"{rna_id}_emb.npy", emb)] + extra + cov_job,
                           lambda r=rna_id: written.append(r), after=after)
         else:
             for fn, tensors in extra:
                 fn(*(t.cpu().numpy() for t in tensors))
+            for path, t in cov_job:
+                np.save(path, t.cpu().numpy())
             write(rna_id, emb.cpu().numpy(), atp.cpu().numpy())
 
     def records_of(flat) -> list:
@@ -454,8 +474,9 @@ def extract_feat(cfg: Config, model: Optional[MSATransformer] = None, gather_to_
                                f"(every rank then writes its own files)")
         if label != "primary" and rank == 0:
             print(f"gather to rank 0: {label}")
-    item_tensors = 2 + sum(h.n_tensors for h in heads)                # emb, atp, then every head's flattened record
-    gatherer = sharding.RoundGatherer(len(ids), on_item=lambda i, ts: emit(ids[i], ts[0], ts[1], records=records_of(ts[2:])),
+    item_tensors = 2 + sum(h.n_tensors for h in heads) + int(invcov_on)      # emb, atp, every head's flattened record, the covariance map
+    gatherer = sharding.RoundGatherer(len(ids), on_item=lambda i, ts: emit(ids[i], ts[0], ts[1], records=records_of(ts[2:]),
+                                                                         cov=ts[-1] if invcov_on else None),
                                       tensors_per_item=item_tensors,
                                       dst=0, device=device, group=gather_group) if gathering else None
     try:
@@ -483,7 +504,9 @@ def extract_feat(cfg: Config, model: Optional[MSATransformer] = None, gather_to_
                 if gatherer is not None:
                     # (a skipped head's share of the item: n_tensors one-element placeholders, dropped again by emit on rank 0)
                     gatherer.submit(idx, (emb, atp) + tuple(t for h, r in zip(heads, records) for t in (
-                        h.flatten(r) if r is not None else [emb.new_zeros(1) for _ in range(h.n_tensors)])))
+                        h.flatten(r) if r is not None else [emb.new_zeros(1) for _ in range(h.n_tensors)]))
+                        # (data.invcov: the map travels as the item's last tensor; a refused alignment sends a placeholder)
+                        + ((invcov_maps.pop(ids[idx], None) if ids[idx] in invcov_maps else emb.new_zeros(1),) if invcov_on else ()))
                 else:
                     emit(ids[idx], emb, atp, after, records)
 

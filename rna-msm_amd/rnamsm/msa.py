@@ -103,6 +103,28 @@ def msa_weights(tokens: np.ndarray, seqid_cutoff: float = 0.2, device=None) -> n
     return 1 / counts
 
 
+def msa_invcov_device(tokens: np.ndarray, gap_idx: int, device):
+    """msa_invcov with the map left on the device (a float64 [L, L] tensor): what the CLI's writer copies from."""
+    import torch
+    from . import _lib, ops
+    dev = torch.device(device) if device is not None else None
+    if dev is None or dev.type != "cuda":
+        raise _lib.RnamsmError(f"msa_invcov: device={device!r} is not a HIP device (no CPU path exists)")
+    body = tokens[:, 1:] if tokens.shape[1] > 1 else tokens
+    if body.size and (int(body.min()) < 0 or int(body.max()) > 255):
+        raise ValueError("msa_invcov: token ids outside [0, 255]")
+    return ops.msa_invcov(torch.from_numpy(np.ascontiguousarray(body.astype(np.uint8))).to(dev), int(gap_idx))
+
+
+def msa_invcov(tokens: np.ndarray, gap_idx: int, device) -> np.ndarray:
+    """MSA.invcov (utils/align.py:183-193), the covariance contact map of an alignment: float64 [L, L], the spectral norm of every
+    K x K block of the covariance of its one-hot columns (K = the distinct non-gap tokens that occur; a gap is all zeros).  The
+    columns are the alignment's (no <cls>, as in msa_weights); token ids stand for the reference's character bytes -- a one-to-one
+    recoding permutes every block's rows and columns and leaves its norm unchanged.  On the HIP device only (rnamsm_msa_invcov):
+    there is no CPU path, a device that is not one is refused.  N in [2, 2^20], L <= 4096, K in [1, 16]."""
+    return msa_invcov_device(tokens, gap_idx, device).cpu().numpy()
+
+
 def sample_weights(tokens: np.ndarray, num_seqs: int, rng=None, seqid_cutoff: float = 0.2, device=None) -> np.ndarray:
     """Row indices drawn like MSA.sample_weights (utils/align.py:150-163): row 0 plus num_seqs - 1 of the others without
     replacement with probability proportional to their sequence weight, ascending.  `rng`: a numpy RandomState; None =
@@ -118,13 +140,16 @@ def sample_weights(tokens: np.ndarray, num_seqs: int, rng=None, seqid_cutoff: fl
 
 
 def load_msa_tokens(path: Union[str, Path], alphabet: RNAAlphabet, max_seqs_per_msa: int = 512,
-                    sample_method: str = "hhfilter", device=None, rng=None) -> np.ndarray:
+                    sample_method: str = "hhfilter", device=None, rng=None, on_full=None) -> np.ndarray:
     """.a2m_msa2 file -> int64 tokens [R <= max_seqs, L+1].  With `device` (a HIP device) the sub-sampling arithmetic
-    (greedy selection, sequence weights) runs on the GPU.  `rng` feeds `sample-pretrained` (see sample_weights)."""
+    (greedy selection, sequence weights) runs on the GPU.  `rng` feeds `sample-pretrained` (see sample_weights).  `on_full`: called
+    with the tokens of the alignment as read, every row, before anything is sub-sampled."""
     if sample_method not in SAMPLE_METHODS:
         raise AssertionError(f"unknown sample_method {sample_method!r}")
     records = read_fasta_records(path)
     tokens = alphabet.encode_a2m_records([seq for _, seq in records])
+    if on_full is not None:
+        on_full(tokens)
     if max_seqs_per_msa is None or tokens.shape[0] <= max_seqs_per_msa:
         return tokens
     if sample_method == "first":

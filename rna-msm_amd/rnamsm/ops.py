@@ -1257,6 +1257,34 @@ def msa_weights(msa_u8: torch.Tensor, seqid_cutoff: float = 0.2) -> torch.Tensor
     return out
 
 
+@_on_operand_device
+def msa_invcov(tokens_u8: torch.Tensor, gap: int, want_counts: bool = False):
+    """Covariance contacts (MSA.invcov, utils/align.py:183-193; rnamsm_msa_invcov): tokens uint8 [N, L] on the device (rows may be
+    strided: a view with contiguous rows is read where it lies) -> float64 [L, L], exactly symmetric.  N in [2, 2^20], L in [1, 4096],
+    at most 16 distinct values other than `gap`; the library refuses anything else and the message names the reason.
+    want_counts: also stage 1 -- (map, counts int32 [L, L, K, K], symbols int32 [K] ascending), counts[i, j, a, b] = the number of rows
+    with symbols[a] in column i and symbols[b] in column j.  The call waits for the device once (K is read back)."""
+    _dev(tokens_u8, "tokens", torch.uint8)
+    if tokens_u8.dim() != 2 or (tokens_u8.shape[1] > 1 and tokens_u8.stride(1) != 1) or tokens_u8.stride(0) < tokens_u8.shape[1]:
+        tokens_u8 = tokens_u8.contiguous()
+    N, L = tokens_u8.shape
+    ld = tokens_u8.stride(0) if N > 1 else L
+    lib = _lib.load()
+    dev = tokens_u8.device
+    ws = torch.empty(max(lib.rnamsm_msa_invcov_workspace_bytes(N, L), 256), dtype=torch.uint8, device=dev)
+    out = torch.empty((L, L), dtype=torch.float64, device=dev)
+    counts = None
+    if want_counts:
+        vals = torch.unique(tokens_u8[:, :L])
+        K = int((vals != int(gap)).sum())
+        counts = torch.empty(_lib.INVCOV_META + L * L * K * K * (1 <= K <= _lib.INVCOV_MAX_K), dtype=torch.int32, device=dev)
+    _lib.check(lib.rnamsm_msa_invcov(tokens_u8.data_ptr(), N, L, ld, int(gap), out.data_ptr(),
+                                     counts.data_ptr() if want_counts else None, ws.data_ptr(), ws.numel(), _stream()))
+    if not want_counts:
+        return out
+    return out, counts[_lib.INVCOV_META:].view(L, L, K, K), counts[1:1 + K]
+
+
 def depth_scaling(R: int) -> float:
     """1/sqrt(R) as the C++ drivers form it -- `1.0f / sqrtf((float)R)` in fp32, both steps correctly rounded -- so that the
     layer-wise mirror modules hand K5 the very same factor (forming it in double and rounding once can differ in the last bit)."""
