@@ -15,7 +15,7 @@ import numpy as np
 import torch
 
 from . import _lib, ops
-from .ss import plan_chunks
+from .ss import long_refusal, plan_chunks
 
 # pixels (sum of L^2) of one packed call: the SS head's budget.  The head's own workspace is 121 floats per position and its
 # outputs 4 MB at the budget, so the budget bounds nothing but the size of one output allocation (a condition, not a measurement).
@@ -65,6 +65,11 @@ class ContactHead:
         """one() on the stitched atp of a long alignment (data.long_heads=stitched), L up to LONG_MAX_L = 4096: the same record
         through rnamsm_contact_head_long.  Symmetrise and APC run over the whole map; a pair no window holds takes part as 0."""
         return self._one(emb, atp, tokens, True)
+
+    def stitched_route(self, L: int, long_on: bool):
+        """On a stitched alignment of L body columns: the method that runs this head, or the reason (a str) it is skipped."""
+        why = long_refusal(L, long_on)
+        return self.one_long if why is None else why
 
     def many(self, embs: Sequence[torch.Tensor], atps: Sequence[torch.Tensor], tokens: Sequence[torch.Tensor]) -> List[ContactResult]:
         """A group in one launch set per chunk (predict_many): every member's record holds the bits of one()."""

@@ -14,7 +14,7 @@ import random
 import threading
 from concurrent.futures import ThreadPoolExecutor
 from pathlib import Path
-from typing import Dict, List, Optional
+from typing import Dict, List, NamedTuple, Optional
 
 import numpy as np
 import torch
@@ -303,10 +303,31 @@ def plan_packed_groups(shapes: List[tuple], fold_min_tokens: int = 0, split_toke
         k = len(groups)             # the hard bounds cut earlier than planned: aim for that many, evenly filled
 
 
-def extract_feat(cfg: Config, model: Optional[MSATransformer] = None, gather_to_rank0: bool = False,
-                 async_io: bool = True) -> List[str]:
-    """async_io: read/tokenise the next alignment on a helper thread while the GPU runs the current one, and move the
-    outputs to disk through `_AsyncNpyWriter`; False = the reference's strictly sequential loop (same files)."""
+class _Switches(NamedTuple):
+    """Every optional cfg.data.* / cfg.model.* key the CLI loop reads, and what follows from them (read_switches)."""
+    gemm_dtype: str             # model.gemm_dtype
+    ss_dtype: str               # data.ss_gemm_dtype
+    windowing: bool             # data.long_msa=windows
+    window_stride: int          # data.window_stride
+    long_heads: bool            # data.long_heads=stitched
+    invcov_on: bool             # data.invcov
+    gathering: bool             # gather_to_rank0 with more than one rank
+    ss_path: str                # data.ss_model_path
+    rsa_dir: str                # data.rsa_model_dir
+    ss_text: bool               # data.ss_prob_text, data.ss_pairs_device, data.rsa_text_device: off under a gather
+    ss_pairs: bool
+    rsa_text: bool
+    contacts: bool              # data.contacts
+    lm_mode: str                # data.lm_scores
+    exact: bool                 # the model runs in fp32
+    packing: bool               # small alignments share token-packed groups (else: padded frames)
+    batching: bool              # small alignments share groups at all
+    pooled: bool                # ... formed from the pool, by shape, instead of in list order
+    small_limit: int            # tokens up to which an alignment waits for company
+
+
+def read_switches(cfg: Config, gathering: bool) -> _Switches:
+    """The keys are read and checked here, once, before anything is loaded; the module's limits as they stand at this call."""
     ss_dtype = check_ss_gemm_dtype(getattr(cfg.data, "ss_gemm_dtype", "f32"))
     # data.long_msa=windows: an alignment wider than the model's max_seqlen is not cropped (nothing is drawn for it) and runs as
     # overlapping windows stitched on the device (MSATransformer.forward_windows): its files hold the full L
@@ -318,13 +339,438 @@ def extract_feat(cfg: Config, model: Optional[MSATransformer] = None, gather_to_
     # data.invcov: the covariance contact map of every alignment as read -- all rows, all columns -- made on the reader's side and
     # written as <id>_invcov.npy by one more writer job; off, nothing below differs
     invcov_on = check_invcov(getattr(cfg.data, "invcov", False))
-    invcov_maps: Dict[str, torch.Tensor] = {}           # id -> the map on the device, from read() until the alignment is emitted
-    device = torch.device(cfg.data.device)
-    if device.type != "cuda":
-        raise RuntimeError("this build runs on the MI355X HIP path only (data.device=cuda); there is no CPU path")
+    # data.batch_small_msas: small alignments go through ONE launch set per group (forward_ragged: padded into one
+    # frame, every MSA scaled by its own depth); a lone forward of a few hundred tokens costs 5.5 ms on a mostly
+    # idle chip.  Groups: by shape from the pool (plan_groups); under gather_to_rank0 the RoundGatherer needs this
+    # rank's items in list order, so there only CONSECUTIVE small alignments share a group.
+    # (16-bit modes: only with data.batch_small_msas_16bit -- a batch's token count selects the GEMM kernels there, so
+    # an alignment's files would depend on its neighbours in the list at the mode's rounding level)
+    exact = cfg.model.gemm_dtype == "f32"
+    framed16 = bool(getattr(cfg.data, "batch_small_msas_16bit", False)) and ops.get_param("attn16") != 0
+    # groups are token-packed (no frame, no padding -- rnamsm_forward_packed, in the model's arithmetic mode), so any small
+    # alignments share one -- unless 16-bit framed batches were asked for (data.batch_small_msas_16bit)
+    packing = (bool(getattr(cfg.data, "batch_small_msas", True)) and bool(getattr(cfg.data, "pack_small_msas", True))
+               and (exact or not framed16))
+    batching = bool(getattr(cfg.data, "batch_small_msas", True)) and (exact or framed16 or packing)
+    small_limit = (PACKED_SMALL_TOKENS if exact else PACKED_SMALL_TOKENS_16BIT.get(cfg.model.gemm_dtype, 1024)) if packing else SMALL_MSA_TOKENS
+    return _Switches(
+        gemm_dtype=cfg.model.gemm_dtype, ss_dtype=ss_dtype, windowing=windowing, window_stride=window_stride, long_heads=long_heads,
+        invcov_on=invcov_on, gathering=gathering, ss_path=getattr(cfg.data, "ss_model_path", ""),
+        rsa_dir=getattr(cfg.data, "rsa_model_dir", ""), ss_text=bool(getattr(cfg.data, "ss_prob_text", True)) and not gathering,
+        ss_pairs=bool(getattr(cfg.data, "ss_pairs_device", True)) and not gathering,
+        rsa_text=bool(getattr(cfg.data, "rsa_text_device", True)) and not gathering, contacts=bool(getattr(cfg.data, "contacts", False)),
+        lm_mode=lm.check_lm_scores(getattr(cfg.data, "lm_scores", "")), exact=exact, packing=packing, batching=batching,
+        pooled=batching and not gathering, small_limit=small_limit)
+
+
+def _load_model(cfg: Config, model: Optional[MSATransformer], alphabet, device) -> MSATransformer:
+    if model is None:
+        model = MSATransformer(alphabet, embed_dim=cfg.model.embed_dim, num_attention_heads=cfg.model.num_attention_heads,
+                               num_layers=cfg.model.num_layers, embed_positions_msa=cfg.model.embed_positions_msa,
+                               dropout=cfg.model.dropout, attention_dropout=cfg.model.attention_dropout,
+                               activation_dropout=cfg.model.activation_dropout, max_tokens_per_msa=cfg.data.max_tokens,
+                               max_seqlen=cfg.data.max_seqlen)
+        load_checkpoint(model, cfg.data.model_path, device)
+    model = model.eval().to(device)
+    model.gemm_dtype = cfg.model.gemm_dtype
+    return model
+
+
+def _load_heads(sw: _Switches, model: MSATransformer, alphabet, device, rank: int) -> list:
+    """The heads that are on, SS before RSA before the contacts before the LM scores: each reads an alignment's device-resident outputs and makes one record
+    of it (rnamsm.ss.SSHead: data.ss_model_path, the maps; rnamsm.rsa.RSAHead: data.rsa_model_dir, the embedding;
+    rnamsm.contacts.ContactHead: data.contacts, the maps; rnamsm.lm.LMHead: data.lm_scores, the embedding and the tokens).
+    data.ss_prob_text (default on): the `.prob` text is formatted on the device behind the head (rnamsm.ss.prob_text) and the
+    writer thread's share of it is one binary write, where np.savetxt formats L^2 numbers under the GIL; the files are the same
+    bytes.  data.ss_pairs_device (default on): the pairs are decoded and the bodies of `.ct` / `.bpseq` written on the device too
+    (rnamsm.ss.structure), so the writer thread no longer runs secondary_structure and two np.savetxt tables per structure; with
+    the formatter on as well no [L, L] float tensor is copied to the host at all.  data.rsa_text_device (default on): the RSA
+    head's K + 1 tables are computed and formatted on the device behind the head (rnamsm.rsa.table_text), so the writer thread no
+    longer runs K + 1 np.savetxt tables per alignment.  Under gather_to_rank0 all three stay off (the host path): the gathered items
+    are the heads' values and the tokens."""
+    base_lut = ss.token_base_codes(alphabet, device) if sw.ss_path or sw.rsa_dir else None
+    heads: list = []
+    if sw.ss_path:
+        if rank == 0:
+            print(f"SS head arithmetic: {sw.ss_dtype} (data.ss_gemm_dtype; independent of model.gemm_dtype={sw.gemm_dtype})")
+        predictor = ss.load_predictor(sw.ss_path, device)
+        predictor.gemm_dtype = sw.ss_dtype
+        heads.append(ss.SSHead(predictor, alphabet, base_lut, device, text_on=sw.ss_text, pairs_on=sw.ss_pairs))
+    if sw.rsa_dir:      # (the reference program's seed; every alignment's draws are taken as its writer job is made, in delivery order)
+        heads.append(rsa.RSAHead(rsa.load_ensemble(sw.rsa_dir, device), alphabet, base_lut, random.Random(2022),
+                                 text_on=sw.rsa_text, device=device))
+    if sw.contacts:     # the trunk's own contact_head.regression.*: no further file to load
+        reg = model.contact_head.regression
+        heads.append(contacts.ContactHead(reg.weight, reg.bias))
+    if sw.lm_mode:      # the trunk's own lm_head.*: "wt" reads every alignment's emb where it lies, "masked" runs L further forwards
+        heads.append(lm.LMHead(model, sw.lm_mode))
+    return heads
+
+
+def _route(h, L: int, sw: _Switches, max_seqlen: int):
+    """The method that runs head h on an alignment of L body columns, or the reason (a str) it is skipped.  Only an alignment stitched
+    from windows (data.long_msa=windows, wider than the model) asks the head (stitched_route): the others stop at L <= 1024, or
+    would need per-window semantics."""
+    return h.stitched_route(L, sw.long_heads) if sw.windowing and L > max_seqlen - 1 else h.one
+
+
+def _head_tokens(h, toks: torch.Tensor) -> torch.Tensor:
+    """What a head is handed of an alignment's tokens [R, C]: the query behind <cls>; the whole matrix where the head asks
+    for it (rnamsm.lm.LMHead: the masked scan runs further forwards on it)."""
+    return toks if getattr(h, "whole_tokens", False) else toks[0, 1:]
+
+
+def _record_event() -> torch.cuda.Event:
+    ev = torch.cuda.Event()
+    ev.record(torch.cuda.current_stream())
+    return ev
+
+
+class _Reader:
+    """Reader + row sub-sampling + crop of one alignment.  All randomness of the CLI lives here, drawn from ONE stream
+    in the reference's order -- per item `sample-pretrained`'s weighted draw (dataset.py:88-90), then the crop
+    (dataset.py:147) -- seeded 42 like the reference's global numpy state (RNA_MSM_Inference.py:17), so a single
+    process reproduces the reference's choices; under sharding every rank draws for its own items."""
+
+    def __init__(self, cfg: Config, sw: _Switches, ids: List[str], files: Dict[str, Path], alphabet, device, put_map):
+        self.cfg, self.sw, self.ids, self.files, self.alphabet, self.device, self.put_map = cfg, sw, ids, files, alphabet, device, put_map
+        self.rng = np.random.RandomState(42)
+
+    def __call__(self, idx: int) -> np.ndarray:
+        torch.cuda.set_device(self.device)
+        rna_id = self.ids[idx]
+        tokens = load_msa_tokens(self.files[rna_id], self.alphabet, self.cfg.data.max_seqs_per_msa, self.cfg.data.sample_method,
+                                 device=self.device, rng=self.rng,
+                                 on_full=(lambda full: self.covariance_map(rna_id, full)) if self.sw.invcov_on else None)
+        return tokens if self.sw.windowing else crop_tokens(tokens, self.cfg.data.max_seqlen, self.rng)
+
+    def covariance_map(self, rna_id: str, full: np.ndarray) -> None:
+        """data.invcov: the map of the alignment as read (before row sub-sampling and any crop), left on the device for the sink; an
+        alignment the kernel refuses gets one line that names the reason, and its other files as usual."""
+        try:
+            self.put_map(rna_id, msa_invcov_device(full, self.alphabet.tok_to_idx["-"], self.device))
+            torch.cuda.current_stream().synchronize()       # (the reader's stream: the map is complete whichever stream copies it)
+        except _lib.RnamsmError as e:
+            print(f"{rna_id}: no covariance map (data.invcov) for this alignment of {full.shape[0]} rows x {full.shape[1] - 1} "
+                  f"columns: {e}")
+
+
+def _gather_group(device, rank: int):
+    """Transport: RCCL point-to-point where it comes up; otherwise the ranks agree (over the default gloo group) to stage the same
+    gather through host memory -- the outputs arrive on rank 0 either way (sharding.negotiate_gather_transport).  A default group
+    that is not gloo (a caller's own nccl world) is used as it is, as before."""
+    import torch.distributed as dist
+    if dist.get_backend() != "gloo":
+        return None
+    group, label, _ = sharding.negotiate_gather_transport(device, want_backend=os.environ.get("RNAMSM_GATHER_BACKEND", "nccl"))
+    if group is False:
+        raise RuntimeError(f"gather_to_rank0: no transport to rank 0 ({label}); run without RNAMSM_GATHER_TO_RANK0 "
+                           f"(every rank then writes its own files)")
+    if label != "primary" and rank == 0:
+        print(f"gather to rank 0: {label}")
+    return group
+
+
+class _Sink:
+    """The delivery side of the CLI loop: an alignment's outputs and its heads' records become files -- through the
+    _AsyncNpyWriter, or on the spot (async_io=False) -- on this rank or, under gather_to_rank0, on rank 0."""
+
+    def __init__(self, ids: List[str], heads: list, save_dir: Path, sw: _Switches, max_seqlen: int, device, rank: int, async_io: bool):
+        self.ids, self.heads, self.save_dir, self.sw, self.max_seqlen = ids, heads, save_dir, sw, max_seqlen
+        self.written: List[str] = []
+        self.invcov_maps: Dict[str, torch.Tensor] = {}      # id -> the map on the device, from the reader until the alignment is delivered
+        self.writer = _AsyncNpyWriter(device) if async_io and (not sw.gathering or rank == 0) else None
+        # gather_to_rank0: outputs travel to rank 0 one ROUND (one MSA per rank) at a time, round k's RCCL transfers
+        # overlapping round k+1's forward, and are handed to the writer as they arrive -- at most one round is resident
+        # (an item: emb, atp, every head's flattened record, the covariance map)
+        self.gatherer = sharding.RoundGatherer(len(ids), on_item=self.on_item,
+                                               tensors_per_item=2 + sum(h.n_tensors for h in heads) + int(sw.invcov_on),
+                                               dst=0, device=device, group=_gather_group(device, rank)) if sw.gathering else None
+
+    def put_map(self, rna_id: str, cov: torch.Tensor) -> None:
+        self.invcov_maps[rna_id] = cov
+
+    def deliver(self, idx: int, emb: torch.Tensor, atp: torch.Tensor, after: Optional[torch.cuda.Event], records: list) -> None:
+        """records: the alignment's record of every head, None for a head skipped on it."""
+        if self.gatherer is None:
+            self.emit(self.ids[idx], emb, atp, after, records)
+            return
+        # (a skipped head's share of the item: n_tensors one-element placeholders, dropped again by records_of on rank 0)
+        item = (emb, atp) + tuple(t for h, r in zip(self.heads, records) for t in (
+            h.flatten(r) if r is not None else [emb.new_zeros(1) for _ in range(h.n_tensors)]))
+        if self.sw.invcov_on:           # (the map travels as the item's last tensor; a refused alignment sends a placeholder)
+            cov = self.invcov_maps.pop(self.ids[idx], None)
+            item += (cov if cov is not None else emb.new_zeros(1),)
+        self.gatherer.submit(idx, item)
+
+    def on_item(self, i: int, ts) -> None:
+        self.emit(self.ids[i], ts[0], ts[1], records=self.records_of(ts[2:], ts[0].shape[0]), cov=ts[-1] if self.sw.invcov_on else None)
+
+    def records_of(self, flat, L: int) -> list:
+        """A gathered item's tensors behind emb and atp -> the heads' records (the inverse of deliver()'s flattening)."""
+        flat = iter(flat)
+        shares = [(h, [next(flat) for _ in range(h.n_tensors)]) for h in self.heads]
+        return [None if isinstance(_route(h, L, self.sw, self.max_seqlen), str) else h.unflatten(ts) for h, ts in shares]
+
+    def emit(self, rna_id: str, emb: torch.Tensor, atp: torch.Tensor, after: Optional[torch.cuda.Event] = None, records=(),
+             cov: Optional[torch.Tensor] = None) -> None:
+        """records: this alignment's record of every head that is on, in the order of `heads`; each becomes one writer job (but
+        for the heads skipped on a stitched alignment: their entry is None).  cov: a gathered item's covariance map (or
+        its one-element placeholder); absent, the one the reader left for this id, if any."""
+        extra = [h.writer_job(r, rna_id, self.save_dir) for h, r in zip(self.heads, records) if r is not None]
+        cov = self.invcov_maps.pop(rna_id, None) if cov is None else (cov if cov.dim() == 2 else None)
+        cov_job = [(self.save_dir / f"{rna_id}_invcov.npy", cov)] if cov is not None else []
+        if self.writer is not None:
+            self.writer.submit([(self.save_dir / f"{rna_id}_atp.npy", atp), (self.save_dir / f"{rna_id}_emb.npy", emb)] + extra + cov_job,
+                               lambda r=rna_id: self.written.append(r), after=after)
+            return
+        for fn, tensors in extra:
+            fn(*(t.cpu().numpy() for t in tensors))
+        for path, t in cov_job:
+            np.save(path, t.cpu().numpy())
+        emb_host, atp_host = emb.cpu().numpy(), atp.cpu().numpy()
+        np.save(self.save_dir / f"{rna_id}_atp.npy", atp_host)
+        np.save(self.save_dir / f"{rna_id}_emb.npy", emb_host)
+        self.written.append(rna_id)
+
+    def finish(self) -> None:
+        if self.gatherer is not None:
+            self.gatherer.finish()
+
+    def close(self) -> None:
+        if self.writer is not None:
+            self.writer.close()
+
+    def written_in_list_order(self) -> List[str]:
+        position = {rna_id: n for n, rna_id in enumerate(self.ids)}
+        return sorted(self.written, key=position.__getitem__)              # whatever order the groups ran in
+
+
+class _Scheduler:
+    """The compute side of the CLI loop: which alignments share a launch set, in which order the forwards are enqueued and read back,
+    and the heads behind them.  It reaches the device through the model's entry points, the heads' one / one_long / many and the two
+    callables it is given -- to_device(host tokens) and record_event() on the current stream -- and nothing else."""
+
+    def __init__(self, model, heads: list, sink, sw: _Switches, ids: List[str], mine: List[int], read, reader, padding_idx: int,
+                 to_device, record_event):
+        self.model, self.heads, self.sink, self.sw, self.ids, self.mine = model, heads, sink, sw, ids, mine
+        self.read, self.reader, self.padding_idx, self.to_device, self.record_event = read, reader, padding_idx, to_device, record_event
+        self.group: List = []           # (idx, tokens on the device)
+        self.pool: List = []            # (idx, tokens on the host)
+        self.inflight = None            # the pipelined forward whose results are still on the device: (the method that finishes it, its arguments...)
+        self.pending = None             # the reader's future: the next alignment of the list
+
+    def run(self) -> None:
+        self.pending = self.reader.submit(self.read, self.mine[0]) if self.reader and len(self.mine) else None
+        try:
+            self.read_and_run()
+        except Exception:
+            # a bad alignment late in the list must not cost the results already computed or read: what waits in the
+            # group / pool is run and written (as the one-by-one loop would have done before reaching it), then the
+            # error goes up.  KeyboardInterrupt / SystemExit are not caught: they propagate at once.  Under a gatherer the
+            # peers are not known to be in the same state (a deliver() could block on them): no salvage there.  A second
+            # failure in here is reported and dropped in favour of the first.
+            if not self.sw.gathering:
+                try:
+                    self.drain()
+                except Exception as second:                       # noqa: BLE001
+                    import warnings
+                    warnings.warn(f"while writing the results computed before the error: {type(second).__name__}: {second}")
+            raise
+        self.drain()
+        self.sink.finish()
+
+    def drain(self) -> None:
+        self.flush()
+        self.run_pool()
+        self.settle()
+
+    def read_and_run(self) -> None:
+        for n, idx in enumerate(self.mine):
+            tokens = self.pending.result() if self.reader else self.read(idx)
+            if self.reader and n + 1 < len(self.mine):
+                self.pending = self.reader.submit(self.read, self.mine[n + 1])       # parsed while the GPU runs this MSA
+            self.step(idx, tokens)
+
+    def step(self, idx: int, tokens: np.ndarray) -> None:
+        """One alignment of the list: into the pool or the group where it is small, else by itself."""
+        sw, model = self.sw, self.model
+        wide = sw.windowing and tokens.shape[1] > model.max_seqlen
+        if (sw.batching and not wide and tokens.size <= sw.small_limit and 2 * tokens.shape[1] ** 2 <= FRAME_MAP_ELEMS
+                and not (tokens == self.padding_idx).any()):
+            if sw.pooled:
+                self.pool.append((idx, tokens))
+                # (packing: a full group's worth of tokens starts NOW -- the reader goes on under its forward -- instead of
+                # waiting for POOL_MSAS alignments or the end of the list)
+                if len(self.pool) >= POOL_MSAS or (sw.packing and sum(t.size for _, t in self.pool) >= PACKED_TOKENS):
+                    self.run_pool()
+                return
+            if not (joins_packed if sw.packing else joins_group)([tuple(t.shape) for _, t in self.group], tuple(tokens.shape)):
+                self.flush()                                  # the group is full (framed: this one would pad too much)
+            self.group.append((idx, self.to_device(tokens)))
+            return
+        self.flush()
+        if wide:
+            self.run_wide(idx, tokens)
+            return
+        has_pad = bool((tokens == self.padding_idx).any())          # on the host: no device round trip before the launches
+        t_dev = self.to_device(tokens)
+        if sw.gathering:            # (the gather orders its transfers behind the compute stream: one by one there, as before)
+            self.settle()
+            out = model.checked_forward_one(t_dev, has_pad, need_repr=False, what=self.ids[idx])   # emb + atp are all that is written
+            self.deliver(idx, out["emb"], out["atp"], toks=t_dev)
+            return
+        # PIPELINED (round 6): this forward is enqueued BEFORE the previous one's error word and outputs are read -- the ~3 ms
+        # of host work per alignment (weight-table check, ~140 launches, delivery) no longer idle the GPU between forwards
+        out = model.forward_one(t_dev, has_pad, need_repr=False)
+        ev = self.record_event()
+        self.settle()                   # the previous forward is finished first; only then is this one the one in flight
+        self.inflight = (self.finish_one, idx, t_dev, has_pad, out, ev)
+
+    def run_wide(self, idx: int, tokens: np.ndarray) -> None:
+        """data.long_msa=windows: the lone route, never a group; behind whatever is in flight (its workspace is the model's)."""
+        self.settle()
+        rna_id, L = self.ids[idx], tokens.shape[1] - 1
+        t_dev = self.to_device(tokens)
+        out = self.model.forward_windows(t_dev, self.sw.window_stride, what=rna_id)
+        for h in self.heads:
+            why = _route(h, L, self.sw, self.model.max_seqlen)
+            if isinstance(why, str):
+                print(f"{rna_id}: L={L} is stitched from windows (data.long_msa=windows); "
+                      f"{type(h).__name__}{getattr(h, 'skip_suffix', '')} is skipped for it" + (f" ({why})" if why else ""))
+        self.deliver(idx, out["emb"], out["atp"], toks=t_dev)
+
+    def deliver(self, idx: int, emb: torch.Tensor, atp: torch.Tensor, after: Optional[torch.cuda.Event] = None,
+                toks: Optional[torch.Tensor] = None, records: Optional[list] = None) -> None:
+        """records: this alignment's record of every head, where its group's batched heads (deliver_group) have made them;
+        absent, the lone heads run here, on emb and atp where they lie (a packed group's slices included)."""
+        if records is None:
+            # (a stitched alignment: the heads data.long_heads=stitched lets through run their long route; lm_scores=wt has
+            # no length limit and no long route, and keeps its own; a head that names a reason instead is skipped)
+            routes = [_route(h, emb.shape[0], self.sw, self.model.max_seqlen) for h in self.heads]
+            records = [None if isinstance(run, str) else run(emb, atp, _head_tokens(h, toks)) for h, run in zip(self.heads, routes)]
+            if self.heads and after is not None:            # the copies wait for the heads too
+                after = self.record_event()
+        self.sink.deliver(idx, emb, atp, after, records)
+
+    def deliver_group(self, members_, outs, ev: Optional[torch.cuda.Event] = None) -> None:
+        """Every head once over the whole group (one launch set per stage; each member's record is the lone head's bits), then
+        the members one by one."""
+        embs, atps = [o["emb"].contiguous() for o in outs], [o["atp"].contiguous() for o in outs]
+        per_head = [h.many(embs, atps, [_head_tokens(h, t) for _, t in members_]) for h in self.heads]
+        if self.heads and ev is not None:                   # the copies wait for the batched heads too
+            ev = self.record_event()
+        for n, ((i, t), emb, atp) in enumerate(zip(members_, embs, atps)):
+            self.deliver(i, emb, atp, ev, t, records=[recs[n] for recs in per_head])
+
+    def finish_packed(self, members_, begun, ev) -> None:
+        """Second half of a pipelined packed group: its error word and outputs, read behind the event recorded after its launches."""
+        res, mode = begun
+        toks_ = [t for _, t in members_]
+        try:
+            outs = self.model.forward_ragged_finish(toks_, res, mode, after=ev)
+            if outs is not res:
+                ev = None                                 # a rerun: its outputs are behind everything enqueued so far
+            if outs is None:                              # <pad> inside the batch: the framed rerun of forward_ragged
+                outs = self.model.forward_ragged(toks_, packed=False)
+        except IndexError:                                # name the offending alignment: one by one
+            outs, ev = [self.alone(i, t) for i, t in members_], None
+        if not all(o["emb"].is_contiguous() and o["atp"].is_contiguous() for o in outs):
+            ev = None                                     # .contiguous() below would launch copies on the compute stream
+        self.deliver_group(members_, outs, ev)
+
+    def finish_one(self, idx: int, t_dev, has_pad: bool, out, ev) -> None:
+        """Second half of a pipelined lone forward (the one-by-one loop of alignments too large to wait for company)."""
+        done = self.model.finish_forward_one(t_dev, out, has_pad, need_repr=False, what=self.ids[idx], after=ev)
+        self.deliver(idx, done["emb"], done["atp"], ev if done is out else None, t_dev)
+
+    def settle(self) -> None:
+        """Read back and deliver what is still in flight, if anything: a packed group or a lone forward."""
+        if self.inflight is not None:
+            entry, self.inflight = self.inflight, None
+            self.finish(entry)
+
+    @staticmethod
+    def finish(entry) -> None:
+        entry[0](*entry[1:])
+
+    def run_pool(self) -> None:
+        sw, pool = self.sw, self.pool
+        shapes_ = [tuple(t.shape) for _, t in pool]
+        fold_min = ops.get_param("ln_fold_min_tokens") if (sw.exact and self.model.fold_layernorm and ops.get_param("ln_fold") == 1) else 0
+        if not sw.packing:
+            for members in plan_groups(shapes_):
+                self.group.extend((pool[j][0], self.to_device(pool[j][1])) for j in members)
+                self.flush()
+            pool.clear()
+            return
+        # Token-packed groups, PIPELINED (round 6): group g+1 is enqueued before group g's error word is read, so g's
+        # device-to-host copies and file writes run under g+1's forward instead of after it with the GPU idle (64 small
+        # alignments used to be one blocking 117 ms forward followed by 26 ms of deliveries).  A pool that would be ONE group
+        # of at least PIPELINE_SPLIT_TOKENS tokens is dealt into two for that.  Same launch sets per group as before: every
+        # member's files are byte for byte those of its own forward (exact mode).
+        # (one stream carries every forward: what belongs to group g -- its error word, its outputs -- is read behind an EVENT
+        # recorded right after g's launches, on side streams, or it would wait for g+1's forward as well)
+        # The last group of a pool STAYS in flight when run_pool returns (self.inflight): the reader goes on, the next pool's first group
+        # is enqueued behind it, and only then is it read back; settle() ends the pipeline (before a forward outside the pool, at the
+        # end of the list).
+        waiting, self.inflight = self.inflight, None        # the group in flight (or a lone forward, from before the pool)
+        try:
+            for members in plan_packed_groups(shapes_, fold_min, split_tokens=PIPELINE_SPLIT_TOKENS):
+                members_ = [(pool[j][0], self.to_device(pool[j][1])) for j in members]
+                if len(members_) == 1:
+                    if waiting is not None:
+                        self.finish(waiting)
+                        waiting = None
+                    self.group.extend(members_)
+                    self.flush()
+                    continue
+                begun = self.model.forward_ragged_begin([t for _, t in members_])
+                ev = self.record_event()
+                if waiting is not None:
+                    self.finish(waiting)
+                waiting = (self.finish_packed, members_, begun, ev)
+        finally:
+            self.inflight = waiting                         # also when a group raised: what is in flight is still delivered (salvage)
+        pool.clear()
+
+    def alone(self, i: int, t: torch.Tensor) -> dict:
+        """One member of a group by itself, in the arithmetic the GROUP runs in (what a small alignment's
+        files hold must not depend on whether it had company).  Exact mode: its own forward IS the packed batch's
+        arithmetic, bit for bit.  16-bit modes: a packed batch's attention runs on the exact kernels, a lone forward's on
+        the 16-bit ones -- so there a lone small alignment is a packed batch of one."""
+        if self.sw.packing and not self.sw.exact:
+            try:
+                return self.model.forward_ragged([t], packed=True)[0]
+            except IndexError:
+                raise IndexError(f"{self.ids[i]}: token or position index out of range") from None
+        return self.model.checked_forward_one(t, need_repr=False, what=self.ids[i])
+
+    def flush(self) -> None:
+        group = self.group
+        if len(group) == 1:
+            idx0, t0 = group[0]
+            self.deliver_group(group, [self.alone(idx0, t0)])
+        elif group:
+            try:
+                outs = self.model.forward_ragged([t for _, t in group], packed=self.sw.packing)
+            except IndexError:                                # name the offending alignment: one by one
+                outs = [self.alone(i, t) for i, t in group]
+            self.deliver_group(group, outs)
+        group.clear()
+
+
+def extract_feat(cfg: Config, model: Optional[MSATransformer] = None, gather_to_rank0: bool = False,
+                 async_io: bool = True) -> List[str]:
+    """async_io: read/tokenise the next alignment on a helper thread while the GPU runs the current one, and move the
+    outputs to disk through `_AsyncNpyWriter`; False = the reference's strictly sequential loop (same files)."""
     import torch.distributed as dist
     rank = dist.get_rank() if dist.is_initialized() else 0
     world = dist.get_world_size() if dist.is_initialized() else 1
+    sw = read_switches(cfg, gather_to_rank0 and world > 1)
+    device = torch.device(cfg.data.device)
+    if device.type != "cuda":
+        raise RuntimeError("this build runs on the MI355X HIP path only (data.device=cuda); there is no CPU path")
     if device.index is None:          # "cuda": this rank's GPU under a launcher, else the process's current device
         device = torch.device("cuda", int(os.environ.get("LOCAL_RANK", rank)) if world > 1 else torch.cuda.current_device())
     alphabet = RNAAlphabet.from_architecture(cfg.data.architecture)
@@ -337,384 +783,28 @@ def extract_feat(cfg: Config, model: Optional[MSATransformer] = None, gather_to_
         ids = sorted(f.read().splitlines())
     ids = [i for i in ids if i]
     files = find_msa_files(root / cfg.data.MSA_path, ids)
-
-    if model is None:
-        model = MSATransformer(alphabet, embed_dim=cfg.model.embed_dim, num_attention_heads=cfg.model.num_attention_heads,
-                               num_layers=cfg.model.num_layers, embed_positions_msa=cfg.model.embed_positions_msa,
-                               dropout=cfg.model.dropout, attention_dropout=cfg.model.attention_dropout,
-                               activation_dropout=cfg.model.activation_dropout, max_tokens_per_msa=cfg.data.max_tokens,
-                               max_seqlen=cfg.data.max_seqlen)
-        load_checkpoint(model, cfg.data.model_path, device)
-    model = model.eval().to(device)
-    model.gemm_dtype = cfg.model.gemm_dtype
-
+    model = _load_model(cfg, model, alphabet, device)
     save_dir = root / cfg.data.MSA_path
     save_dir.mkdir(parents=True, exist_ok=True)
-    # The heads that are on, SS before RSA before the contacts before the LM scores: each reads an alignment's device-resident outputs and makes one record
-    # of it (rnamsm.ss.SSHead: data.ss_model_path, the maps; rnamsm.rsa.RSAHead: data.rsa_model_dir, the embedding;
-    # rnamsm.contacts.ContactHead: data.contacts, the maps; rnamsm.lm.LMHead: data.lm_scores, the embedding and the tokens).
-    # data.ss_prob_text (default on): the `.prob` text is formatted on the device behind the head (rnamsm.ss.prob_text) and the
-    # writer thread's share of it is one binary write, where np.savetxt formats L^2 numbers under the GIL; the files are the same
-    # bytes.  data.ss_pairs_device (default on): the pairs are decoded and the bodies of `.ct` / `.bpseq` written on the device too
-    # (rnamsm.ss.structure), so the writer thread no longer runs secondary_structure and two np.savetxt tables per structure; with
-    # the formatter on as well no [L, L] float tensor is copied to the host at all.  data.rsa_text_device (default on): the RSA
-    # head's K + 1 tables are computed and formatted on the device behind the head (rnamsm.rsa.table_text), so the writer thread no
-    # longer runs K + 1 np.savetxt tables per alignment.  Under gather_to_rank0 all three stay off (the host path): the gathered items
-    # are the heads' values and the tokens.
-    gathering = gather_to_rank0 and world > 1
-    ss_path, rsa_dir = getattr(cfg.data, "ss_model_path", ""), getattr(cfg.data, "rsa_model_dir", "")
-    base_lut = ss.token_base_codes(alphabet, device) if ss_path or rsa_dir else None
-    heads: list = []
-    if ss_path:
-        if rank == 0:
-            print(f"SS head arithmetic: {ss_dtype} (data.ss_gemm_dtype; independent of model.gemm_dtype={cfg.model.gemm_dtype})")
-        predictor = ss.load_predictor(ss_path, device)
-        predictor.gemm_dtype = ss_dtype
-        heads.append(ss.SSHead(predictor, alphabet, base_lut, device,
-                               text_on=bool(getattr(cfg.data, "ss_prob_text", True)) and not gathering,
-                               pairs_on=bool(getattr(cfg.data, "ss_pairs_device", True)) and not gathering))
-    if rsa_dir:         # (the reference program's seed; every alignment's draws are taken as its writer job is made, in delivery order)
-        heads.append(rsa.RSAHead(rsa.load_ensemble(rsa_dir, device), alphabet, base_lut, random.Random(2022),
-                                 text_on=bool(getattr(cfg.data, "rsa_text_device", True)) and not gathering, device=device))
-    if bool(getattr(cfg.data, "contacts", False)):      # the trunk's own contact_head.regression.*: no further file to load
-        reg = model.contact_head.regression
-        heads.append(contacts.ContactHead(reg.weight, reg.bias))
-    lm_mode = lm.check_lm_scores(getattr(cfg.data, "lm_scores", ""))
-    if lm_mode:         # the trunk's own lm_head.*: "wt" reads every alignment's emb where it lies, "masked" runs L further forwards
-        heads.append(lm.LMHead(model, lm_mode))
-    rng = np.random.RandomState(42)
-    mine = sharding.shard_indices(len(ids), rank, world)
-    written: List[str] = []
+    heads = _load_heads(sw, model, alphabet, device, rank)
     # the library launches on the calling thread's current device: make it this rank's GPU on the main thread and on
     # the reader thread (whose greedy sub-sampling runs on the device)
     torch.cuda.set_device(device)
 
-    def write(rna_id: str, emb: np.ndarray, atp: np.ndarray) -> None:
-        np.save(save_dir / f"{rna_id}_atp.npy", atp)
-        np.save(save_dir / f"{rna_id}_emb.npy", emb)
-        written.append(rna_id)
-
-    def read(idx: int) -> np.ndarray:
-        """Reader + row sub-sampling + crop of one alignment.  All randomness of the CLI lives here, drawn from ONE stream
-        in the reference's order -- per item `sample-pretrained`'s weighted draw (dataset.py:88-90), then the crop
-        (dataset.py:147) -- seeded 42 like the reference's global numpy state (RNA_MSM_Inference.py:17), so a single
-        process reproduces the reference's choices; under sharding every rank draws for its own items."""
-        torch.cuda.set_device(device)
-        tokens = load_msa_tokens(files[ids[idx]], alphabet, cfg.data.max_seqs_per_msa, cfg.data.sample_method, device=device,
-                                 rng=rng, on_full=(lambda full: covariance_map(ids[idx], full)) if invcov_on else None)
-        return tokens if windowing else crop_tokens(tokens, cfg.data.max_seqlen, rng)
-
-    def covariance_map(rna_id: str, full: np.ndarray) -> None:
-        """data.invcov: the map of the alignment as read (before row sub-sampling and any crop), left on the device for emit(); an
-        alignment the kernel refuses gets one line that names the reason, and its other files as usual."""
-        try:
-            invcov_maps[rna_id] = msa_invcov_device(full, alphabet.tok_to_idx["-"], device)
-            torch.cuda.current_stream().synchronize()       # (the reader's stream: the map is complete whichever stream copies it)
-        except _lib.RnamsmError as e:
-            print(f"{rna_id}: no covariance map (data.invcov) for this alignment of {full.shape[0]} rows x {full.shape[1] - 1} "
-                  f"columns: {e}")
-
-    writer = _AsyncNpyWriter(device) if async_io and (not gathering or rank == 0) else None
+    sink = _Sink(ids, heads, save_dir, sw, model.max_seqlen, device, rank, async_io)
     reader = ThreadPoolExecutor(1, thread_name_prefix="rnamsm-msa-reader") if async_io else None
-
-    def skipped_on(h, L: int) -> bool:
-        """data.long_msa=windows: which heads do not run on a stitched alignment of L body columns -- all but lm_scores=wt, whose
-        kernel has no length limit that matters (the others stop at L <= 1024, or would need per-window semantics)."""
-        return stitched(L) and not (isinstance(h, lm.LMHead) and h.mode == "wt") and long_skip_reason(h, L) is not None
-
-    def stitched(L: int) -> bool:
-        return windowing and L > model.max_seqlen - 1
-
-    def long_skip_reason(h, L: int) -> Optional[str]:
-        """Why head h does not run on a stitched alignment of L columns; None where data.long_heads=stitched lets it through.  ""
-        with the key off: the line printed then names no reason, as before."""
-        if not long_heads:
-            return ""
-        if isinstance(h, lm.LMHead):
-            return "the masked scan would run L forwards per window"
-        if L > _lib.LONG_MAX_L:
-            return f"L exceeds the long heads' limit of {_lib.LONG_MAX_L}"
-        if isinstance(h, ss.SSHead) and h.model.gemm_dtype != "f32":
-            return f"there is no long SS head under data.ss_gemm_dtype={h.model.gemm_dtype}"
-        return None if isinstance(h, (ss.SSHead, rsa.RSAHead, contacts.ContactHead)) else "it has no long entry point"
-
-    def emit(rna_id: str, emb: torch.Tensor, atp: torch.Tensor, after: Optional[torch.cuda.Event] = None, records=(),
-             cov: Optional[torch.Tensor] = None) -> None:
-        """records: this alignment's record of every head that is on, in the order of `heads`; each becomes one writer job (but
-        for the heads skipped on a stitched alignment: their entry is a placeholder).  cov: a gathered item's covariance map (or
-        its one-element placeholder); absent, the one read() left for this id, if any."""
-        extra = [h.writer_job(r, rna_id, save_dir) for h, r in zip(heads, records) if not skipped_on(h, emb.shape[0])]
-        cov = invcov_maps.pop(rna_id, None) if cov is None else (cov if cov.dim() == 2 else None)
-        cov_job = [(save_dir / f"{rna_id}_invcov.npy", cov)] if cov is not None else []
-        if writer is not None:
-            writer.submit([(save_dir / f"{rna_id}_atp.npy", atp), (save_dir / f"{rna_id}_emb.npy", emb)] + extra + cov_job,
-                          lambda r=rna_id: written.append(r), after=after)
-        else:
-            for fn, tensors in extra:
-                fn(*(t.cpu().numpy() for t in tensors))
-            for path, t in cov_job:
-                np.save(path, t.cpu().numpy())
-            write(rna_id, emb.cpu().numpy(), atp.cpu().numpy())
-
-    def records_of(flat) -> list:
-        """A gathered item's tensors behind emb and atp -> the heads' records (the inverse of deliver()'s flattening)."""
-        flat = iter(flat)
-        return [h.unflatten([next(flat) for _ in range(h.n_tensors)]) for h in heads]
-
-    # gather_to_rank0: outputs travel to rank 0 one ROUND (one MSA per rank) at a time, round k's RCCL transfers
-    # overlapping round k+1's forward, and are handed to the writer as they arrive -- at most one round is resident
-    # Transport: RCCL point-to-point where it comes up; otherwise the ranks agree (over the default gloo group) to stage the same
-    # gather through host memory -- the outputs arrive on rank 0 either way (sharding.negotiate_gather_transport).  A default group
-    # that is not gloo (a caller's own nccl world) is used as it is, as before.
-    gather_group = None
-    if gathering and dist.get_backend() == "gloo":
-        gather_group, label, _ = sharding.negotiate_gather_transport(device, want_backend=os.environ.get("RNAMSM_GATHER_BACKEND", "nccl"))
-        if gather_group is False:
-            raise RuntimeError(f"gather_to_rank0: no transport to rank 0 ({label}); run without RNAMSM_GATHER_TO_RANK0 "
-                               f"(every rank then writes its own files)")
-        if label != "primary" and rank == 0:
-            print(f"gather to rank 0: {label}")
-    item_tensors = 2 + sum(h.n_tensors for h in heads) + int(invcov_on)      # emb, atp, every head's flattened record, the covariance map
-    gatherer = sharding.RoundGatherer(len(ids), on_item=lambda i, ts: emit(ids[i], ts[0], ts[1], records=records_of(ts[2:]),
-                                                                         cov=ts[-1] if invcov_on else None),
-                                      tensors_per_item=item_tensors,
-                                      dst=0, device=device, group=gather_group) if gathering else None
+    scheduler = _Scheduler(model, heads, sink, sw, ids, sharding.shard_indices(len(ids), rank, world),
+                           _Reader(cfg, sw, ids, files, alphabet, device, sink.put_map), reader, alphabet.padding_idx,
+                           to_device=lambda tokens: torch.from_numpy(tokens).to(device), record_event=_record_event)
     try:
         with torch.no_grad():
-            pending = reader.submit(read, mine[0]) if reader and len(mine) else None
-            def head_tokens(h, toks: torch.Tensor) -> torch.Tensor:
-                """What a head is handed of an alignment's tokens [R, C]: the query behind <cls>; the whole matrix where the head asks
-                for it (rnamsm.lm.LMHead: the masked scan runs further forwards on it)."""
-                return toks if getattr(h, "whole_tokens", False) else toks[0, 1:]
-
-            def deliver(idx: int, emb: torch.Tensor, atp: torch.Tensor, after: Optional[torch.cuda.Event] = None,
-                        toks: Optional[torch.Tensor] = None, records: Optional[list] = None) -> None:
-                """records: this alignment's record of every head, where its group's batched heads (deliver_group) have made them;
-                absent, the lone heads run here, on emb and atp where they lie (a packed group's slices included)."""
-                if records is None:
-                    # (a stitched alignment: the heads data.long_heads=stitched lets through run their long route; lm_scores=wt has
-                    # no length limit and no long route, and keeps its own)
-                    wide = stitched(emb.shape[0])
-                    records = [None if skipped_on(h, emb.shape[0])
-                               else (h.one_long if wide and not isinstance(h, lm.LMHead) else h.one)(emb, atp, head_tokens(h, toks))
-                               for h in heads]
-                    if heads and after is not None:             # the copies wait for the heads too
-                        after = torch.cuda.Event()
-                        after.record(torch.cuda.current_stream())
-                if gatherer is not None:
-                    # (a skipped head's share of the item: n_tensors one-element placeholders, dropped again by emit on rank 0)
-                    gatherer.submit(idx, (emb, atp) + tuple(t for h, r in zip(heads, records) for t in (
-                        h.flatten(r) if r is not None else [emb.new_zeros(1) for _ in range(h.n_tensors)]))
-                        # (data.invcov: the map travels as the item's last tensor; a refused alignment sends a placeholder)
-                        + ((invcov_maps.pop(ids[idx], None) if ids[idx] in invcov_maps else emb.new_zeros(1),) if invcov_on else ()))
-                else:
-                    emit(ids[idx], emb, atp, after, records)
-
-            def deliver_group(members_, outs, ev: Optional[torch.cuda.Event] = None) -> None:
-                """Every head once over the whole group (one launch set per stage; each member's record is the lone head's bits), then
-                the members one by one."""
-                embs, atps = [o["emb"].contiguous() for o in outs], [o["atp"].contiguous() for o in outs]
-                per_head = [h.many(embs, atps, [head_tokens(h, t) for _, t in members_]) for h in heads]
-                if heads and ev is not None:                    # the copies wait for the batched heads too
-                    ev = torch.cuda.Event()
-                    ev.record(torch.cuda.current_stream())
-                for n, ((i, t), emb, atp) in enumerate(zip(members_, embs, atps)):
-                    deliver(i, emb, atp, ev, t, records=[recs[n] for recs in per_head])
-
-            # data.batch_small_msas: small alignments go through ONE launch set per group (forward_ragged: padded into one
-            # frame, every MSA scaled by its own depth); a lone forward of a few hundred tokens costs 5.5 ms on a mostly
-            # idle chip.  Groups: by shape from the pool (plan_groups); under gather_to_rank0 the RoundGatherer needs this
-            # rank's items in list order, so there only CONSECUTIVE small alignments share a group.
-            # (16-bit modes: only with data.batch_small_msas_16bit -- a batch's token count selects the GEMM kernels there, so
-            # an alignment's files would depend on its neighbours in the list at the mode's rounding level)
-            exact = model.gemm_dtype == "f32"
-            framed16 = bool(getattr(cfg.data, "batch_small_msas_16bit", False)) and ops.get_param("attn16") != 0
-            # groups are token-packed (no frame, no padding -- rnamsm_forward_packed, in the model's arithmetic mode), so any small
-            # alignments share one -- unless 16-bit framed batches were asked for (data.batch_small_msas_16bit)
-            packing = (bool(getattr(cfg.data, "batch_small_msas", True)) and bool(getattr(cfg.data, "pack_small_msas", True))
-                       and (exact or not framed16))
-            batching = bool(getattr(cfg.data, "batch_small_msas", True)) and (exact or framed16 or packing)
-            pooled = batching and gatherer is None
-            small_limit = (PACKED_SMALL_TOKENS if exact else PACKED_SMALL_TOKENS_16BIT.get(model.gemm_dtype, 1024)) if packing else SMALL_MSA_TOKENS
-            group: List = []                                          # (idx, tokens on the device)
-            pool: List = []                                           # (idx, tokens on the host)
-            inflight: List = [None]                                   # the pipelined pool's group whose results are still on the device
-
-            def finish_packed(entry) -> None:
-                """Second half of a pipelined packed group: its error word and outputs, read behind the event recorded after its launches."""
-                members_, (res, mode), ev = entry
-                toks_ = [t for _, t in members_]
-                try:
-                    outs = model.forward_ragged_finish(toks_, res, mode, after=ev)
-                    if outs is not res:
-                        ev = None                                 # a rerun: its outputs are behind everything enqueued so far
-                    if outs is None:                              # <pad> inside the batch: the framed rerun of forward_ragged
-                        outs = model.forward_ragged(toks_, packed=False)
-                except IndexError:                                # name the offending alignment: one by one
-                    outs, ev = [alone(i, t) for i, t in members_], None
-                if not all(o["emb"].is_contiguous() and o["atp"].is_contiguous() for o in outs):
-                    ev = None                                     # .contiguous() below would launch copies on the compute stream
-                deliver_group(members_, outs, ev)
-
-            def finish_one(entry) -> None:
-                """Second half of a pipelined lone forward (the one-by-one loop of alignments too large to wait for company)."""
-                _, idx_, t_dev, has_pad, out, ev = entry
-                done = model.finish_forward_one(t_dev, out, has_pad, need_repr=False, what=ids[idx_], after=ev)
-                deliver(idx_, done["emb"], done["atp"], ev if done is out else None, t_dev)
-
-            def finish_any(entry) -> None:
-                (finish_one if entry[0] == "one" else finish_packed)(entry)
-
-            def settle() -> None:
-                """Read back and deliver what is still in flight, if anything: a packed group or a lone forward."""
-                if inflight[0] is not None:
-                    entry, inflight[0] = inflight[0], None
-                    finish_any(entry)
-
-            def run_pool() -> None:
-                shapes_ = [tuple(t.shape) for _, t in pool]
-                fold_min = ops.get_param("ln_fold_min_tokens") if (exact and model.fold_layernorm and ops.get_param("ln_fold") == 1) else 0
-                if not packing:
-                    for members in plan_groups(shapes_):
-                        group.extend((pool[j][0], torch.from_numpy(pool[j][1]).to(device)) for j in members)
-                        flush()
-                    pool.clear()
-                    return
-                # Token-packed groups, PIPELINED (round 6): group g+1 is enqueued before group g's error word is read, so g's
-                # device-to-host copies and file writes run under g+1's forward instead of after it with the GPU idle (64 small
-                # alignments used to be one blocking 117 ms forward followed by 26 ms of deliveries).  A pool that would be ONE group
-                # of at least PIPELINE_SPLIT_TOKENS tokens is dealt into two for that.  Same launch sets per group as before: every
-                # member's files are byte for byte those of its own forward (exact mode).
-                # (one stream carries every forward: what belongs to group g -- its error word, its outputs -- is read behind an EVENT
-                # recorded right after g's launches, on side streams, or it would wait for g+1's forward as well)
-                # The last group of a pool STAYS in flight when run_pool returns (inflight[0]): the reader goes on, the next pool's first group
-                # is enqueued behind it, and only then is it read back; settle() ends the pipeline (before a forward outside the pool, at the
-                # end of the list).
-                waiting = inflight[0]                                 # (members' (idx, tokens), begun forward, event) of the group in flight
-                inflight[0] = None
-
-                try:
-                    for members in plan_packed_groups(shapes_, fold_min, split_tokens=PIPELINE_SPLIT_TOKENS):
-                        members_ = [(pool[j][0], torch.from_numpy(pool[j][1]).to(device)) for j in members]
-                        if len(members_) == 1:
-                            if waiting is not None:
-                                finish_any(waiting)
-                                waiting = None
-                            group.extend(members_)
-                            flush()
-                            continue
-                        begun = model.forward_ragged_begin([t for _, t in members_])
-                        ev = torch.cuda.Event()
-                        ev.record(torch.cuda.current_stream())
-                        if waiting is not None:
-                            finish_any(waiting)
-                        waiting = (members_, begun, ev)
-                finally:
-                    inflight[0] = waiting                             # also when a group raised: what is in flight is still delivered (salvage)
-                pool.clear()
-
-            def alone(i: int, t: torch.Tensor) -> dict:
-                """One member of a group by itself, in the arithmetic the GROUP runs in (what a small alignment's
-                files hold must not depend on whether it had company).  Exact mode: its own forward IS the packed batch's
-                arithmetic, bit for bit.  16-bit modes: a packed batch's attention runs on the exact kernels, a lone forward's on
-                the 16-bit ones -- so there a lone small alignment is a packed batch of one."""
-                if packing and not exact:
-                    try:
-                        return model.forward_ragged([t], packed=True)[0]
-                    except IndexError:
-                        raise IndexError(f"{ids[i]}: token or position index out of range") from None
-                return model.checked_forward_one(t, need_repr=False, what=ids[i])
-
-            def flush() -> None:
-                if len(group) == 1:
-                    idx0, t0 = group[0]
-                    deliver_group(group, [alone(idx0, t0)])
-                elif group:
-                    try:
-                        outs = model.forward_ragged([t for _, t in group], packed=packing)
-                    except IndexError:                                # name the offending alignment: one by one
-                        outs = [alone(i, t) for i, t in group]
-                    deliver_group(group, outs)
-                group.clear()
-
-            def read_and_run() -> None:
-                nonlocal pending
-                for n, idx in enumerate(mine):
-                    rna_id = ids[idx]
-                    tokens = pending.result() if reader else read(idx)
-                    if reader and n + 1 < len(mine):
-                        pending = reader.submit(read, mine[n + 1])       # parsed while the GPU runs this MSA
-                    wide = windowing and tokens.shape[1] > model.max_seqlen
-                    if (batching and not wide and tokens.size <= small_limit and 2 * tokens.shape[1] ** 2 <= FRAME_MAP_ELEMS
-                            and not (tokens == alphabet.padding_idx).any()):
-                        if pooled:
-                            pool.append((idx, tokens))
-                            # (packing: a full group's worth of tokens starts NOW -- the reader goes on under its forward -- instead of
-                            # waiting for POOL_MSAS alignments or the end of the list)
-                            if len(pool) >= POOL_MSAS or (packing and sum(t.size for _, t in pool) >= PACKED_TOKENS):
-                                run_pool()
-                            continue
-                        if not (joins_packed if packing else joins_group)([tuple(t.shape) for _, t in group], tuple(tokens.shape)):
-                            flush()                                       # the group is full (framed: this one would pad too much)
-                        group.append((idx, torch.from_numpy(tokens).to(device)))
-                        continue
-                    flush()
-                    if wide:
-                        # data.long_msa=windows: the lone route, never a group; behind whatever is in flight (its workspace is the model's)
-                        settle()
-                        t_dev = torch.from_numpy(tokens).to(device)
-                        out = model.forward_windows(t_dev, window_stride, what=rna_id)
-                        for h in heads:
-                            if skipped_on(h, tokens.shape[1] - 1):
-                                why = long_skip_reason(h, tokens.shape[1] - 1)
-                                print(f"{rna_id}: L={tokens.shape[1] - 1} is stitched from windows (data.long_msa=windows); "
-                                      f"{type(h).__name__}{'(masked)' if isinstance(h, lm.LMHead) else ''} is skipped for it"
-                                      + (f" ({why})" if why else ""))
-                        deliver(idx, out["emb"], out["atp"], toks=t_dev)
-                        continue
-                    has_pad = bool((tokens == alphabet.padding_idx).any())          # on the host: no device round trip before the launches
-                    t_dev = torch.from_numpy(tokens).to(device)
-                    if gatherer is not None:       # (the gather orders its transfers behind the compute stream: one by one there, as before)
-                        settle()
-                        out = model.checked_forward_one(t_dev, has_pad, need_repr=False, what=rna_id)   # emb + atp are all that is written
-                        deliver(idx, out["emb"], out["atp"], toks=t_dev)
-                        continue
-                    # PIPELINED (round 6): this forward is enqueued BEFORE the previous one's error word and outputs are read -- the ~3 ms
-                    # of host work per alignment (weight-table check, ~140 launches, delivery) no longer idle the GPU between forwards
-                    out = model.forward_one(t_dev, has_pad, need_repr=False)
-                    ev = torch.cuda.Event()
-                    ev.record(torch.cuda.current_stream())
-                    settle()
-                    inflight[0] = ("one", idx, t_dev, has_pad, out, ev)
-
-            try:
-                read_and_run()
-            except Exception:
-                # a bad alignment late in the list must not cost the results already computed or read: what waits in the
-                # group / pool is run and written (as the one-by-one loop would have done before reaching it), then the
-                # error goes up.  KeyboardInterrupt / SystemExit are not caught: they propagate at once.  Under a gatherer the
-                # peers are not known to be in the same state (a deliver() could block on them): no salvage there.  A second
-                # failure in here is reported and dropped in favour of the first.
-                if gatherer is None:
-                    try:
-                        flush()
-                        run_pool()
-                        settle()
-                    except Exception as second:                       # noqa: BLE001
-                        import warnings
-                        warnings.warn(f"while writing the results computed before the error: {type(second).__name__}: {second}")
-                raise
-            flush()
-            run_pool()
-            settle()
-            if gatherer is not None:
-                gatherer.finish()
+            scheduler.run()
     finally:
         if reader is not None:
             reader.shutdown(wait=True)
-        if writer is not None:
-            writer.close()
+        sink.close()
     if rank == 0:
         print(f"Done! Generated files are saved at {save_dir}")
-    position = {rna_id: n for n, rna_id in enumerate(ids)}
-    return sorted(written, key=position.__getitem__)                  # in list order, whatever order the groups ran in
+    return sink.written_in_list_order()
+
+

@@ -77,6 +77,7 @@ class LMHead:
 
     n_tensors = 2
     whole_tokens = True
+    skip_suffix = "(masked)"            # behind the class name in the line the CLI prints where stitched_route skips this head
 
     def __init__(self, model, mode: str):
         if check_lm_scores(mode) == "":
@@ -95,6 +96,13 @@ class LMHead:
             return self._masked(tokens)
         out = self.kernel.rows(emb, None, tokens[0, 1:], want=("scores", "nll"))
         return LMResult(out["scores"], out["nll"])
+
+    def stitched_route(self, L: int, long_on: bool):
+        """On a stitched alignment of L body columns: "wt" keeps one() -- its kernel has no length limit that matters, and no long
+        route; "masked" is skipped (the reason named with data.long_heads=stitched on only, as for the other heads)."""
+        if self.mode == "wt":
+            return self.one
+        return "the masked scan would run L forwards per window" if long_on else ""
 
     def many(self, embs: Sequence[torch.Tensor], atps: Sequence[torch.Tensor], tokens: Sequence[torch.Tensor]) -> List[LMResult]:
         """A group: "wt" in one launch set per chunk of plan_lm_chunks, every member's record the bits of one()."""

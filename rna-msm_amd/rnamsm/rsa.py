@@ -28,7 +28,7 @@ import torch
 from torch import nn
 
 from . import _lib, ops
-from .ss import base_codes, letter_codes, plan_chunks
+from .ss import base_codes, letter_codes, long_refusal, plan_chunks
 
 EMBED_DIM = 768
 PLANES = 64
@@ -555,6 +555,11 @@ class RSAHead:
         """one() on the stitched embedding of a long alignment (data.long_heads=stitched), L up to LONG_MAX_L: the same record through
         the long entry points; with the formatter off the tables are left to the host writer, which has no length limit."""
         return self._one(emb, atp, tokens, True)
+
+    def stitched_route(self, L: int, long_on: bool):
+        """On a stitched alignment of L body columns: the method that runs this head, or the reason (a str) it is skipped."""
+        why = long_refusal(L, long_on)
+        return self.one_long if why is None else why
 
     def many(self, embs: Sequence[torch.Tensor], atps: Sequence[torch.Tensor], tokens: Sequence[torch.Tensor]) -> List[RSAResult]:
         """A group in one launch set per stage (predict_many, table_text_many): every member's record holds the bits and bytes of

@@ -65,6 +65,16 @@ def plan_chunks(weights: Sequence[int], budget: int, max_batch: int) -> List[Lis
     return chunks
 
 
+def long_refusal(L: int, long_on: bool) -> Optional[str]:
+    """Why the long entry points do not take a stitched alignment of L body columns; None where they do.  "" with
+    data.long_heads=stitched off: the line the CLI prints then names no reason."""
+    if not long_on:
+        return ""
+    if L > _lib.LONG_MAX_L:
+        return f"L exceeds the long heads' limit of {_lib.LONG_MAX_L}"
+    return None
+
+
 class _Block(nn.Module):
     """Parameters of the reference's BasicBlock (code/model.py:32-85)."""
 
@@ -486,6 +496,14 @@ class SSHead:
         """one() on a stitched long alignment (data.long_heads=stitched), L up to LONG_MAX_L: the same record through the long entry
         points; with a switch off, that part is left to the host writer, which has no length limit."""
         return self._one(emb, atp, tokens, True)
+
+    def stitched_route(self, L: int, long_on: bool):
+        """On a stitched alignment of L body columns (data.long_msa=windows): the method that runs this head, or the reason (a str)
+        it is skipped; long_on: data.long_heads=stitched."""
+        why = long_refusal(L, long_on)
+        if why is None and self.model.gemm_dtype != "f32":
+            why = f"there is no long SS head under data.ss_gemm_dtype={self.model.gemm_dtype}"
+        return self.one_long if why is None else why
 
     def many(self, embs: Sequence[torch.Tensor], atps: Sequence[torch.Tensor], tokens: Sequence[torch.Tensor]) -> List[SSResult]:
         """A group in one launch set per stage (predict_many, prob_text_many, structure_many): every member's record holds the bits
