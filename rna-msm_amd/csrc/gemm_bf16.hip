@@ -12,7 +12,7 @@
 // with the row stride padded to 144 B -- byte-for-byte the layout of the fp32 kernel's [128][32 f32] tile, so the
 // conflict-free ds_read_b128 pattern carries over: 16 B at row*144 + 32*kk + 16*half = k 16kk + 8*half + j, exactly
 // the operand map of the 32x32x16 MFMA (lane (r, half) holds k = 8*half + j).
-#include "half16.h"
+#include "mma16_core.h"
 
 namespace rnamsm {
 
@@ -419,19 +419,15 @@ __global__ __launch_bounds__(HB_THREADS, SPLIT == 3 ? 1 : 2) void gemm16_dma_ker
         aoff[j] = (int64_t)m * lda + dchunk * 8;
         woff[j] = (int64_t)(n0 + row) * K + dchunk * 8;
     }
-    typedef const __attribute__((address_space(1))) void* gptr_t;
-    typedef __attribute__((address_space(3))) void* lptr_t;
     auto issue = [&](int kt, int buf) {
         char* base = smem_b + buf * Cfg::BUF;
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             const int loff = (8 * (wv + 4 * j)) * 128;                          // wave-uniform LDS row-group offset
-            __builtin_amdgcn_global_load_lds((gptr_t)(Ahi + aoff[j] + kt * HB_BK), (lptr_t)(base + loff), 16, 0, 0);
-            if (SPLIT == 3)
-                __builtin_amdgcn_global_load_lds((gptr_t)(Alo + aoff[j] + kt * HB_BK), (lptr_t)(base + HD_PLANE + loff), 16, 0, 0);
-            __builtin_amdgcn_global_load_lds((gptr_t)(Whi + woff[j] + kt * HB_BK), (lptr_t)(base + NPL * HD_PLANE + loff), 16, 0, 0);
-            if (SPLIT == 3)
-                __builtin_amdgcn_global_load_lds((gptr_t)(Wlo + woff[j] + kt * HB_BK), (lptr_t)(base + (NPL + 1) * HD_PLANE + loff), 16, 0, 0);
+            dma16(Ahi + aoff[j] + kt * HB_BK, base + loff);
+            if (SPLIT == 3) dma16(Alo + aoff[j] + kt * HB_BK, base + HD_PLANE + loff);
+            dma16(Whi + woff[j] + kt * HB_BK, base + NPL * HD_PLANE + loff);
+            if (SPLIT == 3) dma16(Wlo + woff[j] + kt * HB_BK, base + (NPL + 1) * HD_PLANE + loff);
         }
     };
 
@@ -491,68 +487,18 @@ static int launch_hd(const uint16_t* Whi, const uint16_t* Wlo, const float* bias
 // to land, so bytes-in-flight must cover rate x latency.  The 128x128 tile eats 42 B/clk (126 KB needed, 64 KB in
 // flight); a 256x256 tile with BK = 32 eats 21 B/clk (64 KB needed = exactly the one 64 KB buffer in flight).
 // 8 waves as 2(M) x 4(N), wave tile 128x64 = 4x2 MFMA tiles (128 accumulator VGPRs), two waves per SIMD.
-// Rows are 64 B (32 halves): physical 16-B chunk = logical chunk ^ ((row >> 2) & 3), again 16 distinct slots per
-// ds_read_b128 lane group.
-constexpr int HX_BM = 256, HX_BN = 256, HX_BK = 32, HX_THREADS = 512;
+constexpr int HX_BM = 256, HX_BN = 256, HX_THREADS = 512;
 constexpr unsigned GEMM16_PERSISTENT_BLOCKS = 256;     // one per CU; a multiple of 8 keeps the XCD affinity of xcd_panel_map_grouped
-constexpr int HX_ROWB = HX_BK * 2;                     // 64 bytes per row
-constexpr int HX_PLANE = 256 * HX_ROWB;                // 16 KB
-template <int SPLIT>
-struct HxCfg {
-    static constexpr int NPL = SPLIT == 3 ? 2 : 1;
-    static constexpr int BUF = 2 * NPL * HX_PLANE;
-    static constexpr int EPI = 8 * 64 * 68 * 4;        // epilogue staging: 8 waves x [64][68] f32
-    static constexpr int LDS = (2 * BUF) > EPI ? (2 * BUF) : EPI;
+// dynamic LDS of the 256x256 GEMM kernels: the ring's two stages (mma16_core.h), or the epilogue staging of 8 waves x [64][68] f32
+template <int SPLIT, int BK>
+struct HsCfg : Ring16Cfg<SPLIT, BK> {
+    static constexpr int EPI = 8 * 64 * 68 * 4;
+    static constexpr int LDS = (2 * Ring16Cfg<SPLIT, BK>::BUF) > EPI ? (2 * Ring16Cfg<SPLIT, BK>::BUF) : EPI;
 };
-template <int SPLIT, int FMT>
-struct HxFrag {
-    typename Half16<FMT>::V8 a[HxCfg<SPLIT>::NPL][4], b[HxCfg<SPLIT>::NPL][2];
-};
-template <int SPLIT, int FMT>
-__device__ __forceinline__ void hx_frag_mma(const HxFrag<SPLIT, FMT>& f, f32x16 (&acc)[4][2]) {
-#pragma unroll
-    for (int mt = 0; mt < 4; ++mt)
-#pragma unroll
-        for (int nt = 0; nt < 2; ++nt) {
-            if (SPLIT == 3) {
-                acc[mt][nt] = Half16<FMT>::mfma(f.a[1][mt], f.b[0][nt], acc[mt][nt]);
-                acc[mt][nt] = Half16<FMT>::mfma(f.a[0][mt], f.b[1][nt], acc[mt][nt]);
-            }
-            acc[mt][nt] = Half16<FMT>::mfma(f.a[0][mt], f.b[0][nt], acc[mt][nt]);
-        }
-}
 
 // ---- 256x256 tile, two buffers, software-pipelined fragments -------------------------------------------------------
-// A kernel that reads a k-step's fragments and waits for them right before the MFMAs that use them (round 1-3: gemm16_dma256_kernel, removed in round 4) has its two
-// waves per SIMD are barrier-synchronised, so they tend to sit in those waits together and the matrix pipe idles
-// (PMC, split 3 QKV: 56% MFMA busy at the actual clock, waves 32% of their time in s_waitcnt).  Here a k-step's
-// fragments are requested while the PREVIOUS step's MFMAs issue (two fragment sets, interleave pinned with
-// sched_group_barrier), also across the tile boundary: the barrier sits in the middle of a tile, right after the tile's
-// last fragment read -- at that point every wave is done READING the buffer, so the DMA of tile kt+2 can start
-// overwriting it while the MFMAs of tile kt are still issuing, and the first fragments of tile kt+1 load under them.
-// Measured against the kernel above in one process (cfg3 shapes): +3..5% for split 3 (QKV 337 -> 356 TF algorithmic,
-// matrix pipe 56% -> 60% busy at the ~1.7 GHz the chip sustains here) and +4..10% for split 1.  What remains is not
-// fragment latency: a 4-stage DMA pipeline with counted vmcnt (three tiles in flight, BK = 16 for split 3) was also
-// built and measured -- split 1 +5..10%, split 3 -7..12% (twice the barriers for the same bytes) -- and dropped.
-// What-if builds: skipping the B fragment reads gains <= 2% (LDS read bandwidth is not the limiter);
-// skipping the DMA gains 23-45%; a DMA-only loop takes 60-75% of the kernel time.  Data movement and MFMA each need
-// most of the time and overlap imperfectly -- contention of the LDS-DMA path or the power budget, still open.
-// BK = 32 (64-B tile rows) or 64 (128-B rows = whole cache lines per DMA row, twice the bytes in flight, half the
-// barriers; only split 1 fits: 2 buffers x 64 KB).  Split 1 with BK = 64 against BK = 32, one process, cfg3 shapes:
-// QKV 775 -> 882 TF, out_proj 515 -> 553, fc1 714 -> 759, fc2 830 -> 996 TF ("gemm16_dma" = 4 forces BK = 32).
-template <int SPLIT, int BK>
-struct HsCfg {
-    static constexpr int NPL = SPLIT == 3 ? 2 : 1;
-    static constexpr int ROWB = BK * 2;
-    static constexpr int PLANE = 256 * ROWB;
-    static constexpr int BUF = 2 * NPL * PLANE;
-    static constexpr int EPI = 8 * 64 * 68 * 4;
-    static constexpr int LDS = (2 * BUF) > EPI ? (2 * BUF) : EPI;
-    static constexpr int RPI = 1024 / ROWB;                 // tile rows per wave DMA instruction
-    static constexpr int IPW = 256 / RPI / 8;               // DMA instructions per wave per plane tile
-    static constexpr int KS = BK / 16;                      // MFMA k steps per tile
-};
-
+// The ring of mma16_core.h (swp_kloop16: the reasoning and the measurements stand there) on A / W planes; BK = 32, or 64 for
+// split 1 ("gemm16_dma" = 4 forces BK = 32).
 template <int ACT, bool HAS_RES, int SPLIT, int FMT, bool O_PL, int BK>
 __global__ __launch_bounds__(HX_THREADS, 1) void gemm16_swp_kernel(
     const uint16_t* __restrict__ Ahi, const uint16_t* __restrict__ Alo, int64_t lda, const uint16_t* __restrict__ Whi,
@@ -560,11 +506,9 @@ __global__ __launch_bounds__(HX_THREADS, 1) void gemm16_swp_kernel(
     int64_t ldc, int M, int N, int K, float scale, int scale_cols, uint16_t* __restrict__ Ohi, uint16_t* __restrict__ Olo,
     int group, unsigned total_tiles, Fold16 fa) {
     using Cfg = HsCfg<SPLIT, BK>;
-    constexpr int NPL = Cfg::NPL, ROWB = Cfg::ROWB, PLANE = Cfg::PLANE, KS = Cfg::KS;
+    constexpr int NPL = Cfg::NPL, ROWB = Cfg::ROWB, PLANE = Cfg::PLANE;
     constexpr int NMF = 8 * (SPLIT == 3 ? 3 : 1);          // MFMAs per k step per wave
     constexpr int NDS = 6 * NPL;                           // fragment reads per k step per wave
-    typedef typename Half16<FMT>::V8 V8;
-    static_assert(BK == 32 || BK == 64, "tile depth");
     extern __shared__ __attribute__((aligned(16))) char smem_b[];
 
     const unsigned nb = N / HX_BN, mp = (M + HX_BM - 1) / HX_BM;
@@ -590,8 +534,7 @@ __global__ __launch_bounds__(HX_THREADS, 1) void gemm16_swp_kernel(
     // chunks-per-row), fetching the logical chunk the read-side swizzle expects there.  g = wv + 8j.
     constexpr int CPR = ROWB / 16;
     const int drow = lane / CPR;
-    const int dchunk = BK == 32 ? ((lane & 3) ^ ((lane >> 4) & 3))                      // (row >> 2) & 3
-                                : ((lane & 7) ^ ((4 * (wv & 1) + (lane >> 4)) & 7));    // (row >> 1) & 7, row = 8g + lane/8
+    const int dchunk = dma_chunk16_k<BK>(lane, wv);
     // source offsets: one 64-bit base per operand and lane; a lane's further rows lie 8 RPI rows apart -- a uniform stride for W
     // (N % 256 == 0), a 32-bit delta per row for A (rows past M are clamped to the last one: <= 255 rows, fits an int).  Eight 64-bit
     // offsets per lane used to live here: with 128 accumulators and two fragment sets that spilled 1-7 registers.
@@ -602,97 +545,24 @@ __global__ __launch_bounds__(HX_THREADS, 1) void gemm16_swp_kernel(
     int adelta[Cfg::IPW];
 #pragma unroll
     for (int j = 0; j < Cfg::IPW; ++j) adelta[j] = (min(m0 + row0 + 8 * Cfg::RPI * j, M - 1) - ma0) * (int)lda;
-    typedef const __attribute__((address_space(1))) void* gptr_t;
-    typedef __attribute__((address_space(3))) void* lptr_t;
     auto issue = [&](int kt, int buf) {
         char* base = smem_b + buf * Cfg::BUF;
 #pragma unroll
         for (int j = 0; j < Cfg::IPW; ++j) {
             const int loff = (Cfg::RPI * (wv + 8 * j)) * ROWB;
             const int64_t ao = aoff0 + adelta[j] + kt * BK, wo = woff0 + j * wstride + kt * BK;
-            __builtin_amdgcn_global_load_lds((gptr_t)(Ahi + ao), (lptr_t)(base + loff), 16, 0, 0);
-            if (SPLIT == 3)
-                __builtin_amdgcn_global_load_lds((gptr_t)(Alo + ao), (lptr_t)(base + PLANE + loff), 16, 0, 0);
-            __builtin_amdgcn_global_load_lds((gptr_t)(Whi + wo), (lptr_t)(base + NPL * PLANE + loff), 16, 0, 0);
-            if (SPLIT == 3)
-                __builtin_amdgcn_global_load_lds((gptr_t)(Wlo + wo), (lptr_t)(base + (NPL + 1) * PLANE + loff), 16, 0, 0);
+            dma16(Ahi + ao, base + loff);
+            if (SPLIT == 3) dma16(Alo + ao, base + PLANE + loff);
+            dma16(Whi + wo, base + NPL * PLANE + loff);
+            if (SPLIT == 3) dma16(Wlo + wo, base + (NPL + 1) * PLANE + loff);
         }
     };
-    auto frag_load = [&](const char* buf, int kk, HxFrag<SPLIT, FMT>& f) {
-        const int chunk = (BK == 32 ? ((2 * kk + lh) ^ ((li >> 2) & 3)) : ((2 * kk + lh) ^ ((li >> 1) & 7))) * 16;
-#pragma unroll
-        for (int p = 0; p < NPL; ++p) {
-#pragma unroll
-            for (int t = 0; t < 4; ++t)
-                f.a[p][t] = *reinterpret_cast<const V8*>(buf + p * PLANE + (wm * 128 + t * 32 + li) * ROWB + chunk);
-#pragma unroll
-            for (int t = 0; t < 2; ++t)
-                f.b[p][t] = *reinterpret_cast<const V8*>(buf + (NPL + p) * PLANE + (wn * 64 + t * 32 + li) * ROWB + chunk);
-        }
-    };
-    // pin "NMF MFMAs with NDS fragment reads between them": one read per MFMA from the start, so the last read has the
-    // rest of the run to land before the next phase waits for it
-    auto interleave = [&]() {
-#pragma unroll
-        for (int i = 0; i < NDS; ++i) {
-            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-            __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-        }
-        __builtin_amdgcn_sched_group_barrier(0x008, NMF - NDS, 0);
-        __builtin_amdgcn_sched_barrier(0);
-    };
+    auto frag_load = [&](const char* buf, int kk, Frag16<SPLIT, FMT>& f) { frag16_load_k<SPLIT, FMT, BK>(buf, kk, wm, wn, li, lh, f); };
+    auto frag_mma = [&](const Frag16<SPLIT, FMT>& f, f32x16 (&acc)[4][2], auto) { frag16_mma<SPLIT, FMT>(f, acc); };
 
     f32x16 acc[4][2];
-#pragma unroll
-    for (int mt = 0; mt < 4; ++mt)
-#pragma unroll
-        for (int nt = 0; nt < 2; ++nt)
-#pragma unroll
-            for (int t = 0; t < 16; ++t) acc[mt][nt][t] = 0.f;
-
-    const int nk = K / BK;
-    issue(0, 0);
-    wait_dma_then_barrier<0>();                               // tile 0 landed
-    issue(nk > 1 ? 1 : 0, 1);                                 // (a redundant reload when nk == 1: never read)
-    HxFrag<SPLIT, FMT> f[2];                                  // step kk lives in f[kk & 1]; KS is even
-    frag_load(smem_b, 0, f[0]);
-    for (int kt = 0; kt + 1 < nk; ++kt) {
-        const char* cur = smem_b + (kt & 1) * Cfg::BUF;
-        const char* nxt = smem_b + ((kt & 1) ^ 1) * Cfg::BUF;
-#pragma unroll
-        for (int kk = 0; kk + 1 < KS; ++kk) {                 // step kk on f[kk&1], step kk+1's fragments arriving
-            frag_load(cur, kk + 1, f[(kk + 1) & 1]);
-            hx_frag_mma<SPLIT, FMT>(f[kk & 1], acc);
-            interleave();
-        }
-        // every wave is done reading `cur` once its last fragments have arrived; tile kt+1 (issued one tile ago) must
-        // have landed
-        wait_dma_then_barrier<0>();
-        const int k2 = kt + 2 < nk ? kt + 2 : nk - 1;         // clamped: the last reload is never read
-        // DEPHASED ISSUE: a wave is stuck for ~100 cycles per LDS-DMA request it issues (8 per tile); when the two waves of a SIMD issue
-        // theirs at the same moment -- right after this barrier -- nobody feeds the matrix pipe meanwhile, so the upper wave group issues
-        // one step later.  (Staging by operand as in gemm16_q16s_kernel -- row-half-major micro-steps,
-        // W requested half a tile before A -- was built for this kernel too and measured no better than this delay: f16x3 six
-        // GEMMs x1.026 against x1.035, plain bf16 QKV x1.01 and fc1 x0.93; EXPERIMENTS.md R3.3.)
-        if (wm == 0) issue(k2, kt & 1);
-        __builtin_amdgcn_sched_barrier(0);
-        // last step of tile kt, step 0 of tile kt+1 arriving
-        frag_load(nxt, 0, f[0]);
-        hx_frag_mma<SPLIT, FMT>(f[(KS - 1) & 1], acc);
-        interleave();
-        if (wm == 1) issue(k2, kt & 1);
-        __builtin_amdgcn_sched_barrier(0);
-    }
-    {   // last tile
-        const char* cur = smem_b + ((nk - 1) & 1) * Cfg::BUF;
-#pragma unroll
-        for (int kk = 0; kk + 1 < KS; ++kk) {
-            frag_load(cur, kk + 1, f[(kk + 1) & 1]);
-            hx_frag_mma<SPLIT, FMT>(f[kk & 1], acc);
-            interleave();
-        }
-        hx_frag_mma<SPLIT, FMT>(f[(KS - 1) & 1], acc);
-    }
+    zero_acc16(acc);
+    swp_kloop16<Frag16<SPLIT, FMT>, Cfg::BUF, Cfg::KS, NMF, NDS>(K / BK, smem_b, wm, acc, issue, frag_load, frag_mma);
     wait_dma_then_barrier<0>();                               // the clamped reload has landed: LDS is free for the epilogue
     // The epilogue's lane geometry is re-derived from an OPAQUE copy of the lane id inside the tile loop: values computed from
     // the loop-invariant `lane` are hoisted to kernel entry, live across the whole K loop next to 128 accumulators and two
@@ -733,7 +603,7 @@ static int launch_hs(const uint16_t* Whi, const uint16_t* Wlo, const float* bias
     const unsigned grid = GEMM16_PERSISTENT_BLOCKS < total ? GEMM16_PERSISTENT_BLOCKS : total;
     // (a folded-LayerNorm producer also writes the new residual stream as planes: the next consumer's A operand)
     KernelTimer timer(TC_GEMM, 2.0 * M * N * K,
-                      gemm16_bytes(M, N, K, HxCfg<SPLIT>::NPL, HAS_RES, O_PL) + (fa.xhi ? 2.0 * HxCfg<SPLIT>::NPL * (double)M * N : 0.0),
+                      gemm16_bytes(M, N, K, HsCfg<SPLIT, BK>::NPL, HAS_RES, O_PL) + (fa.xhi ? 2.0 * HsCfg<SPLIT, BK>::NPL * (double)M * N : 0.0),
                       stream, PEAK_F16_MFMA_TFLOPS, SPLIT);
     hipLaunchKernelGGL(kern, dim3(grid), dim3(HX_THREADS), lds, stream, a_hi, a_lo, lda, Whi, Wlo, bias, residual, ldr, Cout,
                        ldc, M, N, K, scale, scale_cols, o_hi, o_lo, group, total, fa);
@@ -742,14 +612,9 @@ static int launch_hs(const uint16_t* Whi, const uint16_t* Wlo, const float* bias
 }
 
 // ---- 256x256 tile, plain bf16, 16x16x32 MFMAs ------------------------------------------------------------------------
-// The loop of gemm16_swp_kernel<.., SPLIT 1, BK 64> with v_mfma_f32_16x16x32_bf16 instead of 32x32x16: the same flops per
-// cycle on paper, but the chip holds a higher clock on the 16x16 shape under sustained matrix load (MI355X_MICROARCH.md,
-// DVFS give-back item 7: ~1.12-1.15x the FLOP/s of the 32x32 loop at equal cycles) -- and everything else in the kernel
-// (DMA issue, LDS reads) speeds up with the clock.  Same tiles, same DMA map and swizzle (the 16 lanes of a ds_read_b128
-// group hold rows distinct mod 16 and two k-groups: 16 distinct 16-B slots), wave tile 128x64 = 8x4 MFMA tiles (128
-// accumulator VGPRs), a k-step is 32 deep: 32 MFMAs of 16 cycles against 12 fragment reads.  Products are identical to the
-// 32x32 kernel's and are summed in a different order inside a k-step: results agree to fp32 rounding (exact on integers).
-typedef float f32x4a __attribute__((ext_vector_type(4)));
+// The staged-by-operand loop of mma16_core.h (staged_kloop16: the reasoning and the measurements stand there) on A / W planes.
+// Products are identical to the 32x32 kernel's and are summed in a different order inside a k-step: results agree to fp32
+// rounding (exact on integers).
 // Epilogue of the 16x16x32 kernel, straight from the accumulators (no LDS transpose, no barrier).  With the MFMA operands
 // swapped the tile comes out transposed in the registers, and with the W rows permuted by the DMA map lane (fr, fq) holds,
 // of row 16 mt + fr of the wave's 128 x 64 tile, the columns 8 fq .. 8 fq + 7 (tiles t = 0, 1) and 32 + 8 fq .. + 7
@@ -775,7 +640,7 @@ __device__ __forceinline__ void hq_epilogue_loads(HqEpiRegs& r, int gm0, int gnb
     for (int mt = 0; mt < 8; ++mt) r.st[mt] = fold ? fa.stats[min(gm0 + mt * 16 + fr, M - 1)] : float2{0.f, 1.f};
 }
 template <int ACT, bool HAS_RES, bool O_PL>
-__device__ __forceinline__ void hq_epilogue(f32x4a (&acc)[8][4], const HqEpiRegs& r, int gm0, int gnb, int lane,
+__device__ __forceinline__ void hq_epilogue(f32x4 (&acc)[8][4], const HqEpiRegs& r, int gm0, int gnb, int lane,
                                             const float* residual, int64_t ldr, float* Cout, int64_t ldc, int M, float scale,
                                             int scale_cols, uint16_t* __restrict__ Ohi) {
     const int fr = lane & 15, fq = lane >> 4;
@@ -832,27 +697,18 @@ __global__ __launch_bounds__(HX_THREADS, 1) void gemm16_q16s_kernel(
     const float* residual, int64_t ldr, float* Cout, int64_t ldc, int M, int N, int K, float scale, int scale_cols,
     uint16_t* __restrict__ Ohi, int group, unsigned total_tiles, Fold16 fa) {
     using Cfg = HsCfg<1, 64>;
-    constexpr int BK = 64, ROWB = Cfg::ROWB, PLANE = Cfg::PLANE;
-    typedef typename Half16<0>::V8 V8;
+    constexpr int BK = 64, PLANE = Cfg::PLANE;
     extern __shared__ __attribute__((aligned(16))) char smem_b[];
 
     const unsigned nb = N / HX_BN, mp = (M + HX_BM - 1) / HX_BM;
     const int lane = threadIdx.x & 63, wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int wm = wv >> 2, wn = wv & 3, fr = lane & 15, fq = lane >> 4;
-    typedef const __attribute__((address_space(1))) void* gptr_t;
-    typedef __attribute__((address_space(3))) void* lptr_t;
+    const int wm = wv >> 2, wn = wv & 3;
     // Persistent tile walk with the epilogue OFF the memory critical path.  The epilogue needs no LDS (hq_epilogue), so the
     // next tile's first operand tile is requested BEFORE the current tile's stores: vector memory operations retire in
     // order, and the first wait of the next tile then allows exactly the stores to stay in flight (vmcnt(HQ_STORES)) instead
     // of draining them (a what-if: 27 % of the QKV launch, 34 % of fc1's, was the wait for the previous tile's stores).
     constexpr int HQ_STORES = O_PL ? 16 : 32;                 // store instructions of one epilogue, per lane
-    // STAGING BY OPERAND.  A wave is stuck for ~100 cycles per LDS-DMA request it issues, and while both waves of a SIMD issue
-    // theirs at the same moment nobody feeds the matrix pipe.  Here the lower wave group (wm = 0) moves the whole W tile and
-    // the upper one the whole A tile -- 8 requests per wave and K tile either way -- and the micro-steps run in the order
-    // (ks 0, h 0), (ks 1, h 0), (ks 0, h 1), (ks 1, h 1): the W tile has been read completely after the FIRST micro-step's
-    // fragment reads, the A tile after the third's.  So W of tile kt+2 is requested behind a barrier at the start of
-    // micro-step 1 and A of tile kt+2 behind the barrier at the start of micro-step 3: the two bursts lie half a tile apart,
-    // each overlapped by the other group's MFMAs, and both have at least a whole tile of flight time.
+    // Staging by operand (mma16_core.h): the lower wave group (wm = 0) moves the whole W tile, the upper one the whole A tile.
     const int w4 = wv & 3;
     const int drow = lane >> 3;
     const int dchunk = (lane & 7) ^ ((4 * (w4 & 1) + (lane >> 4)) & 7);      // (row >> 1) & 7, row = 8 (w4 + 4 j) + lane / 8
@@ -887,7 +743,7 @@ __global__ __launch_bounds__(HX_THREADS, 1) void gemm16_q16s_kernel(
         char* base = smem_b + buf * Cfg::BUF + (wm ? 0 : PLANE) + 1024 * w4;
 #pragma unroll
         for (int j = 0; j < 8; ++j)
-            __builtin_amdgcn_global_load_lds((gptr_t)(src + off[j] + kt * BK), (lptr_t)(base + 4096 * j), 16, 0, 0);
+            dma16(src + off[j] + kt * BK, base + 4096 * j);
     };
     unsigned vid = blockIdx.x;
     int m0, n0;
@@ -896,95 +752,8 @@ __global__ __launch_bounds__(HX_THREADS, 1) void gemm16_q16s_kernel(
     issue_mine(0, 0);
     bool stores_in_flight = false;                            // uniform
     for (;;) {
-    // lane (row fr, k-group fq) of a 16-row tile reads logical chunk 4*ks + fq of its row; (row >> 1) & 7 = (fr >> 1) & 7.
-    // A tile is consumed in four micro-steps u = (k-step ks = u >> 1, row half h = u & 1) of 16 MFMAs: the A fragments of
-    // one half (4 x V8) ping-pong by micro-step, the B fragments of a k-step (4 x V8) by k-step -- 64 fragment registers
-    // instead of the 96 of two whole k-step sets, which with 128 accumulators would not fit 256.
-    V8 ah[2][4], bq[2][4];
-    auto load_a = [&](const char* buf, int ks, int h, V8 (&a)[4]) {
-        const int chunk = ((4 * ks + fq) ^ ((fr >> 1) & 7)) * 16;
-#pragma unroll
-        for (int t = 0; t < 4; ++t) a[t] = *reinterpret_cast<const V8*>(buf + (wm * 128 + (4 * h + t) * 16 + fr) * ROWB + chunk);
-    };
-    auto load_b = [&](const char* buf, int ks, V8 (&b)[4]) {
-        const int chunk = ((4 * ks + fq) ^ ((fr >> 1) & 7)) * 16;
-#pragma unroll
-        for (int t = 0; t < 4; ++t) b[t] = *reinterpret_cast<const V8*>(buf + PLANE + (wn * 64 + t * 16 + fr) * ROWB + chunk);
-    };
-    f32x4a acc[8][4];
-#pragma unroll
-    for (int mt = 0; mt < 8; ++mt)
-#pragma unroll
-        for (int nt = 0; nt < 4; ++nt) acc[mt][nt] = f32x4a{0.f, 0.f, 0.f, 0.f};
-    auto mma = [&](int h, const V8 (&a)[4], const V8 (&b)[4]) {
-#pragma unroll
-        for (int mt = 0; mt < 4; ++mt)
-#pragma unroll
-            for (int nt = 0; nt < 4; ++nt)
-                // operands swapped: the tile comes out TRANSPOSED in the registers -- lane (fr, fq) holds row fr, columns
-                // 4 fq .. 4 fq + 3 of the 16x16 tile -- so the epilogue stores row pieces straight from the accumulators
-                acc[4 * h + mt][nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(b[nt], a[mt], acc[4 * h + mt][nt], 0, 0, 0);
-    };
-
-    const int nk = K / BK;
-    // tile 0 was requested before the previous tile's stores (or at kernel start): it has landed once at most those
-    // stores are still outstanding
-    if (stores_in_flight) wait_dma_then_barrier<HQ_STORES>();
-    else wait_dma_then_barrier<0>();
-    issue_mine(nk > 1 ? 1 : 0, 1);
-    load_a(smem_b, 0, 0, ah[0]);
-    load_b(smem_b, 0, bq[0]);
-#define HQ_PIN(NDS_)                                                                  \
-    _Pragma("unroll") for (int i_ = 0; i_ < NDS_; ++i_) {                             \
-        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);                            \
-        __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);                            \
-    }                                                                                 \
-    __builtin_amdgcn_sched_group_barrier(0x008, 16 - NDS_, 0);                        \
-    __builtin_amdgcn_sched_barrier(0)
-    for (int kt = 0; kt + 1 < nk; ++kt) {
-        const char* cur = smem_b + (kt & 1) * Cfg::BUF;
-        const char* nxt = smem_b + ((kt & 1) ^ 1) * Cfg::BUF;
-        const int k2 = kt + 2 < nk ? kt + 2 : nk - 1;         // clamped: the last reload is never read (keeps the counts below fixed)
-        load_a(cur, 1, 0, ah[1]);                             // u0 = (ks 0, h 0) computes; u1 = (ks 1, h 0) arriving: the last reads of W
-        load_b(cur, 1, bq[1]);
-        mma(0, ah[0], bq[0]);
-        HQ_PIN(8);
-        asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");     // every wave has read the W tile of `cur`
-        if (wm == 0) issue_mine(k2, kt & 1);                  // W of tile kt+2 -> the W plane of `cur`
-        __builtin_amdgcn_sched_barrier(0);
-        load_a(cur, 0, 1, ah[0]);                             // u1 computes; u2 = (ks 0, h 1) arriving
-        mma(0, ah[1], bq[1]);
-        HQ_PIN(4);
-        load_a(cur, 1, 1, ah[1]);                             // u2 computes; u3 = (ks 1, h 1) arriving: the last reads of A
-        mma(1, ah[0], bq[0]);
-        HQ_PIN(4);
-        // every wave has read the A tile of `cur`, and tile kt+1 has landed: the A group waits for all of its requests, the W
-        // group leaves its newest 8 (W of tile kt+2, requested half a tile ago) in flight
-        if (wm == 0) wait_dma_then_barrier<8>();
-        else wait_dma_then_barrier<0>();
-        if (wm == 1) issue_mine(k2, kt & 1);                  // A of tile kt+2 -> the A plane of `cur`
-        __builtin_amdgcn_sched_barrier(0);
-        load_a(nxt, 0, 0, ah[0]);                             // u3 computes; the next tile's u0 operands arriving
-        load_b(nxt, 0, bq[0]);
-        mma(1, ah[1], bq[1]);
-        HQ_PIN(8);
-    }
-    {
-        const char* cur = smem_b + ((nk - 1) & 1) * Cfg::BUF;
-        load_a(cur, 1, 0, ah[1]);
-        load_b(cur, 1, bq[1]);
-        mma(0, ah[0], bq[0]);
-        HQ_PIN(8);
-        load_a(cur, 0, 1, ah[0]);
-        mma(0, ah[1], bq[1]);
-        HQ_PIN(4);
-        load_a(cur, 1, 1, ah[1]);
-        mma(1, ah[0], bq[0]);
-        HQ_PIN(4);
-        mma(1, ah[1], bq[1]);
-    }
-#undef HQ_PIN
-    wait_dma_then_barrier<0>();                               // every wave is done with LDS; the clamped reload has landed
+    f32x4 acc[8][4];
+    staged_kloop16<HQ_STORES>(K / BK, smem_b, wm, wn, lane, stores_in_flight, acc, issue_mine);
     // what the epilogue reads (bias / fold vectors, row statistics) first, then the next tile's tile 0, then the stores
     HqEpiRegs er;
     hq_epilogue_loads<HAS_RES>(er, m0 + wm * 128, n0 + wn * 64, lane, bias, M, fa);

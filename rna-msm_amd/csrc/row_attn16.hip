@@ -16,8 +16,8 @@
 // Roofline: MFMA-bound like the fp32 kernels (same flops, 16-bit rate x 1 or / 3).
 #include <type_traits>
 
+#include "mma16_core.h"
 #include "row_split.h"
-#include "tile16.h"
 
 namespace rnamsm {
 
@@ -279,27 +279,11 @@ __global__ __launch_bounds__(R16_THREADS, SPLIT == 3 ? 1 : 2) void row_apply16_k
 }
 
 // ---------------------------------------------------------------------------------------------- K4' (large C)
-// 256x256 tile version of row_logits16 for C >= 256 (half the operand bytes per flop, see K6' (large C) below): both
-// operands are "k" tiles, i.e. exactly the loop of gemm16_swp_kernel with q / k planes for A / W.  One block per CU, so the
-// row split is chosen for 256 slots.  K tile: BK = 32 -- half of one alignment row's head dims, 64-B tile rows (the hi/lo
-// modes: four planes per stage) -- or BK = 64 -- one whole alignment row, 128-B tile rows = whole cache lines per DMA row,
-// half the barriers (plain bf16 only: two 64 KB stages; round 3).
-template <int SPLIT, int BK>
-struct R16LCfg {
-    static constexpr int NPL = SPLIT == 3 ? 2 : 1;
-    static constexpr int ROWB = BK * 2;
-    static constexpr int PLANE = 256 * ROWB;            // [256 rows][BK halves]
-    static constexpr int BUF = 2 * NPL * PLANE;
-    static constexpr int LDS = 2 * BUF;
-    static constexpr int RPI = 1024 / ROWB;              // tile rows per wave DMA instruction
-    static constexpr int IPW = 256 / RPI / 8;            // DMA instructions per wave per plane tile
-    static constexpr int KS = BK / 16;                   // MFMA k steps per tile
-};
-template <int SPLIT, int FMT>
-struct R16LFrag {
-    typename Half16<FMT>::V8 a[SPLIT == 3 ? 2 : 1][4], b[SPLIT == 3 ? 2 : 1][2];
-};
-
+// 256x256 tile version of row_logits16 for C >= 256 (half the operand bytes per flop, see K6' (large C) below) in the hi/lo modes:
+// both operands are "k" tiles, so this is the ring of mma16_core.h (swp_kloop16) with q / k planes for A / B.  One block per CU, so
+// the row split is chosen for 256 slots.  K tile: BK = 32 -- half of one alignment row's head dims, 64-B tile rows, four planes
+// per stage.  (Plain bf16 on 256x256 tiles is row_logits16q_kernel; the 64-deep instance of this kernel measured level with the
+// 128x128 kernel and went in round 6; the BK argument stays because the kernel's symbol is exported with it.)
 template <int SPLIT, int FMT, int BK>
 __global__ __launch_bounds__(512, 1) void row_logits16x_kernel(
     const uint16_t* __restrict__ qhi, const uint16_t* __restrict__ qlo, const uint16_t* __restrict__ khi,
@@ -312,12 +296,11 @@ __global__ __launch_bounds__(512, 1) void row_logits16x_kernel(
     if (klo) klo += blockIdx.y * qk_bstride;
     partial += blockIdx.y * part_bstride;
     if (true_rows) scale = scale / sqrtf((float)max(true_rows[blockIdx.y], 1));
-    using Cfg = R16LCfg<SPLIT, BK>;
-    constexpr int NPL = Cfg::NPL, ROWB = Cfg::ROWB, PLANE = Cfg::PLANE, KS = Cfg::KS;
+    static_assert(BK == 32, "the 64-deep branches went in round 6");
+    using Cfg = Ring16Cfg<SPLIT, BK>;
+    constexpr int NPL = Cfg::NPL, ROWB = Cfg::ROWB, PLANE = Cfg::PLANE;
     constexpr int NMF = 8 * (SPLIT == 3 ? 3 : 1);
     constexpr int NDS = 6 * NPL;
-    static_assert(BK == 32 || (BK == 64 && SPLIT == 1), "64-deep K tiles: two 64 KB stages fit for one plane per operand only");
-    typedef typename Half16<FMT>::V8 V8;
     extern __shared__ __attribute__((aligned(16))) char smem_b[];
 
     const unsigned tiles_c = (C + 255) / 256;
@@ -331,11 +314,10 @@ __global__ __launch_bounds__(512, 1) void row_logits16x_kernel(
     const int lane = threadIdx.x & 63, wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int wm = wv >> 2, wn = wv & 3, li = lane & 31, lh = lane >> 5;
 
-    // DMA map: a wave instruction covers RPI tile rows (16 of 64 B, or 8 of 128 B); lane -> (row RPI g + lane / chunks-per-row,
-    // physical chunk lane % chunks-per-row) fetching the logical chunk the read-side swizzle expects there; g = wv + 8 j
+    // DMA map: a wave instruction covers RPI = 16 tile rows of 64 B; lane -> (row RPI g + lane / chunks-per-row, physical chunk
+    // lane % chunks-per-row) fetching the logical chunk the read-side swizzle expects there; g = wv + 8 j
     constexpr int CPR = ROWB / 16;
-    const int dchunk = BK == 32 ? ((lane & 3) ^ ((lane >> 4) & 3))                      // (row >> 2) & 3
-                                : ((lane & 7) ^ ((4 * (wv & 1) + (lane >> 4)) & 7));    // (row >> 1) & 7, row = 8 g + lane / 8
+    const int dchunk = dma_chunk16_k<BK>(lane, wv);
     int64_t qoff[Cfg::IPW], koff[Cfg::IPW];
 #pragma unroll
     for (int j = 0; j < Cfg::IPW; ++j) {
@@ -343,10 +325,10 @@ __global__ __launch_bounds__(512, 1) void row_logits16x_kernel(
         qoff[j] = (int64_t)min(i0 + row, C - 1) * ld + h * 64 + dchunk * 8;     // clamped columns feed discarded outputs
         koff[j] = (int64_t)min(j0 + row, C - 1) * ld + h * 64 + dchunk * 8;
     }
-    // K tile kt: BK = 32 -> (alignment row r_begin + kt/2, d half kt&1); BK = 64 -> alignment row r_begin + kt
+    // K tile kt = (alignment row r_begin + kt / 2, d half kt & 1)
     auto issue = [&](int kt, int buf) {
         char* base = smem_b + buf * Cfg::BUF;
-        const int64_t rb = BK == 32 ? (int64_t)(r_begin + (kt >> 1)) * C * ld + (kt & 1) * 32 : (int64_t)(r_begin + kt) * C * ld;
+        const int64_t rb = (int64_t)(r_begin + (kt >> 1)) * C * ld + (kt & 1) * 32;
 #pragma unroll
         for (int j = 0; j < Cfg::IPW; ++j) {
             const int loff = (Cfg::RPI * (wv + 8 * j)) * ROWB;
@@ -356,84 +338,13 @@ __global__ __launch_bounds__(512, 1) void row_logits16x_kernel(
             if (SPLIT == 3) dma16(klo + rb + koff[j], base + (NPL + 1) * PLANE + loff);
         }
     };
-    auto frag_load = [&](const char* buf, int kk, R16LFrag<SPLIT, FMT>& f) {
-        const int chunk = (BK == 32 ? ((2 * kk + lh) ^ ((li >> 2) & 3)) : ((2 * kk + lh) ^ ((li >> 1) & 7))) * 16;
-#pragma unroll
-        for (int p = 0; p < NPL; ++p) {
-#pragma unroll
-            for (int t = 0; t < 4; ++t)
-                f.a[p][t] = *reinterpret_cast<const V8*>(buf + p * PLANE + (wm * 128 + t * 32 + li) * ROWB + chunk);
-#pragma unroll
-            for (int t = 0; t < 2; ++t)
-                f.b[p][t] = *reinterpret_cast<const V8*>(buf + (NPL + p) * PLANE + (wn * 64 + t * 32 + li) * ROWB + chunk);
-        }
-    };
-    auto frag_mma = [&](const R16LFrag<SPLIT, FMT>& f, f32x16 (&acc)[4][2]) {
-#pragma unroll
-        for (int mt = 0; mt < 4; ++mt)
-#pragma unroll
-            for (int nt = 0; nt < 2; ++nt) {
-                if (SPLIT == 3) {
-                    acc[mt][nt] = Half16<FMT>::mfma(f.a[1][mt], f.b[0][nt], acc[mt][nt]);
-                    acc[mt][nt] = Half16<FMT>::mfma(f.a[0][mt], f.b[1][nt], acc[mt][nt]);
-                }
-                acc[mt][nt] = Half16<FMT>::mfma(f.a[0][mt], f.b[0][nt], acc[mt][nt]);
-            }
-    };
-    auto interleave = [&]() {
-#pragma unroll
-        for (int i = 0; i < NDS; ++i) {
-            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-            __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-        }
-        __builtin_amdgcn_sched_group_barrier(0x008, NMF - NDS, 0);
-        __builtin_amdgcn_sched_barrier(0);
-    };
+    auto frag_load = [&](const char* buf, int kk, Frag16<SPLIT, FMT>& f) { frag16_load_k<SPLIT, FMT, BK>(buf, kk, wm, wn, li, lh, f); };
+    auto frag_mma = [&](const Frag16<SPLIT, FMT>& f, f32x16 (&acc)[4][2], auto) { frag16_mma<SPLIT, FMT>(f, acc); };
 
     f32x16 acc[4][2];
-#pragma unroll
-    for (int mt = 0; mt < 4; ++mt)
-#pragma unroll
-        for (int nt = 0; nt < 2; ++nt)
-#pragma unroll
-            for (int t = 0; t < 16; ++t) acc[mt][nt][t] = 0.f;
-
-    const int nk = (BK == 32 ? 2 : 1) * (r_end - r_begin);
-    issue(0, 0);
-    wait_dma_then_barrier<0>();
-    issue(nk > 1 ? 1 : 0, 1);                                // (a redundant reload when nk == 1: never read)
-    R16LFrag<SPLIT, FMT> f[2];                               // step kk lives in f[kk & 1]; KS is even
-    frag_load(smem_b, 0, f[0]);
-    for (int kt = 0; kt + 1 < nk; ++kt) {
-        const char* cur = smem_b + (kt & 1) * Cfg::BUF;
-        const char* nxt = smem_b + ((kt & 1) ^ 1) * Cfg::BUF;
-#pragma unroll
-        for (int kk = 0; kk + 1 < KS; ++kk) {
-            frag_load(cur, kk + 1, f[(kk + 1) & 1]);
-            frag_mma(f[kk & 1], acc);
-            interleave();
-        }
-        // every wave is done reading `cur` once its last fragments have arrived; tile kt+1 (issued one tile ago) must have landed
-        wait_dma_then_barrier<0>();
-        const int k2 = kt + 2 < nk ? kt + 2 : nk - 1;        // clamped: the last reload is never read
-        if (wm == 0) issue(k2, kt & 1);                      // dephased issue: the upper wave group issues one step later (gemm_bf16.hip)
-        __builtin_amdgcn_sched_barrier(0);
-        frag_load(nxt, 0, f[0]);
-        frag_mma(f[(KS - 1) & 1], acc);
-        interleave();
-        if (wm == 1) issue(k2, kt & 1);
-        __builtin_amdgcn_sched_barrier(0);
-    }
-    {
-        const char* cur = smem_b + ((nk - 1) & 1) * Cfg::BUF;
-#pragma unroll
-        for (int kk = 0; kk + 1 < KS; ++kk) {
-            frag_load(cur, kk + 1, f[(kk + 1) & 1]);
-            frag_mma(f[kk & 1], acc);
-            interleave();
-        }
-        frag_mma(f[(KS - 1) & 1], acc);
-    }
+    zero_acc16(acc);
+    // two K tiles per alignment row: nk >= 2
+    swp_kloop16<Frag16<SPLIT, FMT>, Cfg::BUF, Cfg::KS, NMF, NDS>(2 * (r_end - r_begin), smem_b, wm, acc, issue, frag_load, frag_mma);
     asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");      // the clamped reload has landed before the block exits
 
     float* out = partial + ((int64_t)split * H + h) * C * C;
@@ -451,11 +362,10 @@ __global__ __launch_bounds__(512, 1) void row_logits16x_kernel(
 }
 
 // ---------------------------------------------------------------------------------------------- K4' (large C, plain bf16)
-// The K loop of gemm16_q16s_kernel (gemm_bf16.hip) on the tied-row logits: per head a [C x R*64] . [R*64 x C] product whose K
-// tile is one alignment row r (64 head dims = one 128-byte run per alignment column).  256x256 output tile, 8 waves (2 x 4),
-// wave tile 128 x 64 = 8 x 4 tiles of v_mfma_f32_16x16x32_bf16, two 64 KB stages.  STAGING BY OPERAND: the lower wave group
-// moves the k tile (the "W" operand), the upper one the q tile, half a tile apart, each burst under the other group's MFMAs
-// and with a whole tile of flight time (see gemm16_q16s_kernel for the reasoning and the measurements); persistent blocks walk
+// The staged-by-operand loop (mma16_core.h: staged_kloop16 describes it; this kernel keeps its own copy of the text, which compiles
+// to one VGPR less than the call -- profiles/gemm16_core_code_objects.md) on the tied-row logits: per head a [C x R*64] . [R*64 x C] product
+// whose K tile is one alignment row r (64 head dims = one 128-byte run per alignment column).  256x256 output tile, two 64 KB
+// stages; the lower wave group moves the k tile (the "B" operand), the upper one the q tile; persistent blocks walk
 // (MSA, head, row slab, tile) and request the next tile's first stage before the current tile's stores.  The k rows are
 // permuted on their way into LDS so that a lane's (transposed) accumulators are 8 + 8 consecutive output columns: the
 // epilogue stores 16-byte pieces straight from the registers.  Needs C % 8 == 0 (16-byte stores into rows of C floats); other
@@ -560,13 +470,6 @@ __global__ __launch_bounds__(512, 1) void row_logits16q_kernel(
     issue_mine(nk > 1 ? 1 : 0, 1);
     load_a(smem_b, 0, 0, ah[0]);
     load_b(smem_b, 0, bq[0]);
-#define RQ_PIN(NDS_)                                                                  \
-    _Pragma("unroll") for (int i_ = 0; i_ < NDS_; ++i_) {                             \
-        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);                            \
-        __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);                            \
-    }                                                                                 \
-    __builtin_amdgcn_sched_group_barrier(0x008, 16 - NDS_, 0);                        \
-    __builtin_amdgcn_sched_barrier(0)
     for (int kt = 0; kt + 1 < nk; ++kt) {
         const char* cur = smem_b + (kt & 1) * BUF;
         const char* nxt = smem_b + ((kt & 1) ^ 1) * BUF;
@@ -574,16 +477,16 @@ __global__ __launch_bounds__(512, 1) void row_logits16q_kernel(
         load_a(cur, 1, 0, ah[1]);                             // (ks 0, h 0) computes; (ks 1, h 0) arriving: the last reads of the k tile
         load_b(cur, 1, bq[1]);
         mma(0, ah[0], bq[0]);
-        RQ_PIN(8);
+        pin_mfma_ds<16, 8>();
         asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");     // every wave has read the k tile of `cur`
         if (wm == 0) issue_mine(k2, kt & 1);                  // k of tile kt+2 -> the k plane of `cur`
         __builtin_amdgcn_sched_barrier(0);
         load_a(cur, 0, 1, ah[0]);
         mma(0, ah[1], bq[1]);
-        RQ_PIN(4);
+        pin_mfma_ds<16, 4>();
         load_a(cur, 1, 1, ah[1]);                             // the last reads of the q tile
         mma(1, ah[0], bq[0]);
-        RQ_PIN(4);
+        pin_mfma_ds<16, 4>();
         // every wave has read the q tile of `cur`, and tile kt+1 has landed: the q group waits for all of its requests, the k
         // group leaves its newest 8 (k of tile kt+2, requested half a tile ago) in flight
         if (wm == 0) wait_dma_then_barrier<8>();
@@ -593,23 +496,22 @@ __global__ __launch_bounds__(512, 1) void row_logits16q_kernel(
         load_a(nxt, 0, 0, ah[0]);
         load_b(nxt, 0, bq[0]);
         mma(1, ah[1], bq[1]);
-        RQ_PIN(8);
+        pin_mfma_ds<16, 8>();
     }
     {
         const char* cur = smem_b + ((nk - 1) & 1) * BUF;
         load_a(cur, 1, 0, ah[1]);
         load_b(cur, 1, bq[1]);
         mma(0, ah[0], bq[0]);
-        RQ_PIN(8);
+        pin_mfma_ds<16, 8>();
         load_a(cur, 0, 1, ah[0]);
         mma(0, ah[1], bq[1]);
-        RQ_PIN(4);
+        pin_mfma_ds<16, 4>();
         load_a(cur, 1, 1, ah[1]);
         mma(1, ah[0], bq[0]);
-        RQ_PIN(4);
+        pin_mfma_ds<16, 4>();
         mma(1, ah[1], bq[1]);
     }
-#undef RQ_PIN
     wait_dma_then_barrier<0>();                               // every wave is done with LDS; the clamped reload has landed
     // the epilogue's own data first (the scale of a ragged batch: every MSA's logits by ITS depth), then the next tile's first
     // stage, then the stores
@@ -658,16 +560,17 @@ __global__ __launch_bounds__(512, 1) void row_logits16q_kernel(
 // 256x256 tile version of row_apply16 for C >= 256: M = 256 alignment columns i, N = 4 alignment rows x 64 head dims,
 // K tile = 32 keys.  Per flop it moves half the operand bytes of the 128x128 kernel above -- the 16-bit kernels lose
 // matrix-pipe time in proportion to the bytes they pull into the CU, so the tile size is the lever.
-// 8 waves as 2 (M) x 4 (N): wave tile 128 x 64 = one alignment row; the loop is gemm16_swp_kernel's (two fragment sets,
-// one LDS read per MFMA, barrier in the middle of a tile), with the B fragments coming from "t" tiles by transposed read.
+// 8 waves as 2 (M) x 4 (N): wave tile 128 x 64 = one alignment row; the loop is the ring of mma16_core.h (swp_kloop16 describes it; this
+// kernel keeps its own copy of the text, which compiles to two VGPRs less in the hi/lo mode than the call --
+// profiles/gemm16_core_code_objects.md), with the B fragments coming from "t" tiles by transposed read.
 // Throw-away what-if builds of row_apply16x_kernel (wrong results, timing only; tools/whatif_row_apply16.sh): 1 no MFMAs, 2 no LDS-DMA
 // inside the K loop, 4 one K tile per block, 8 no epilogue stores.  0 in the shipped library (every use folds away).
 #ifndef R16X_WHATIF
 #define R16X_WHATIF 0
 #endif
 constexpr int R16X_THREADS = 512;
-// KT = keys per K tile: 32 (64-B P rows; the hi/lo modes: four planes per stage) or 64 (128-B P rows = whole cache lines per
-// DMA row, half the barriers; plain bf16 only: two 64 KB stages)
+// KT = keys per K tile: 32 (the hi/lo modes) or 64 (plain bf16), as Ring16Cfg's BK.  The A planes have the ring's geometry; the B
+// planes are "t" tiles, so a stage is laid out differently and this kernel keeps its own trait.
 template <int SPLIT, int KT>
 struct R16XCfg {
     static constexpr int NPL = SPLIT == 3 ? 2 : 1;
@@ -797,15 +700,6 @@ __global__ __launch_bounds__(R16X_THREADS, 1) void row_apply16x_kernel(
     };
     typedef std::integral_constant<int, 4 * NPL> next_set_t;
     typedef std::integral_constant<int, 0> none_t;
-    auto interleave = [&]() {
-#pragma unroll
-        for (int i = 0; i < (NDS < NMF ? NDS : NMF); ++i) {
-            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-            __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-        }
-        if (NMF > NDS) __builtin_amdgcn_sched_group_barrier(0x008, NMF - NDS, 0);
-        __builtin_amdgcn_sched_barrier(0);
-    };
 
     f32x16 acc[4][2];
 #pragma unroll
@@ -828,7 +722,7 @@ __global__ __launch_bounds__(R16X_THREADS, 1) void row_apply16x_kernel(
         for (int kk = 0; kk + 1 < KS; ++kk) {
             frag_load(cur, kk + 1, f[(kk + 1) & 1]);
             frag_mma(f[kk & 1], acc, next_set_t());
-            interleave();
+            pin_mfma_ds<NMF, NDS>();
         }
         // every wave is done reading `cur` once its last fragments have arrived; tile kt+1 (issued one tile ago) must have landed
         wait_dma_then_barrier<0>();
@@ -837,7 +731,7 @@ __global__ __launch_bounds__(R16X_THREADS, 1) void row_apply16x_kernel(
         __builtin_amdgcn_sched_barrier(0);
         frag_load(nxt, 0, f[0]);
         frag_mma(f[(KS - 1) & 1], acc, next_set_t());
-        interleave();
+        pin_mfma_ds<NMF, NDS>();
         if (wm == 1 && !(R16X_WHATIF & 2)) issue(k2, kt & 1);
         __builtin_amdgcn_sched_barrier(0);
     }
@@ -847,7 +741,7 @@ __global__ __launch_bounds__(R16X_THREADS, 1) void row_apply16x_kernel(
         for (int kk = 0; kk + 1 < KS; ++kk) {
             frag_load(cur, kk + 1, f[(kk + 1) & 1]);
             frag_mma(f[kk & 1], acc, next_set_t());
-            interleave();
+            pin_mfma_ds<NMF, NDS>();
         }
         frag_mma(f[(KS - 1) & 1], acc, none_t());
     }
@@ -962,14 +856,13 @@ static int row_logits16_launch(const uint16_t* q_hi, const uint16_t* q_lo, const
                       q_lo ? 3.0 : 1.0);
 #define RL_BIG(SP_, FMT_)                                                                                           \
     do {                                                                                                            \
-        constexpr int BKX_ = SP_ == 1 ? 64 : 32;                                                                    \
         static DeviceOnce cfgx_;                                                                                    \
         if (cfgx_.pending()) {                                                                                      \
-            int rc = set_lds16(row_logits16x_kernel<SP_, FMT_, BKX_>, R16LCfg<SP_, BKX_>::LDS, "row_logits16x");    \
+            int rc = set_lds16(row_logits16x_kernel<SP_, FMT_, 32>, 2 * Ring16Cfg<SP_, 32>::BUF, "row_logits16x");  \
             if (rc) return rc;                                                                                      \
             cfgx_.mark();                                                                                           \
         }                                                                                                           \
-        hipLaunchKernelGGL((row_logits16x_kernel<SP_, FMT_, BKX_>), dim3(grid, batch), dim3(512), (R16LCfg<SP_, BKX_>::LDS), s, q_hi, q_lo,  \
+        hipLaunchKernelGGL((row_logits16x_kernel<SP_, FMT_, 32>), dim3(grid, batch), dim3(512), (2 * Ring16Cfg<SP_, 32>::BUF), s, q_hi, q_lo, \
                            k_hi, k_lo, ld, partial, R, C, H, sp.nsplit, sp.rows_per_split, scale, qk_bstride, part_bstride, true_rows); \
     } while (0)
 #define RL_GO(SP_, FMT_)                                                                                            \
