@@ -848,6 +848,41 @@ size_t rnamsm_msa_invcov_workspace_bytes(int N, int L);
 int rnamsm_msa_invcov(const uint8_t* tokens, int N, int L, int64_t ld, int gap, double* out, int32_t* counts, void* workspace,
                       size_t workspace_bytes, void* stream);
 
+/* Alignment statistics built on the pairwise Hamming matrix (utils/align.py: MSA.pdist :121-126, MSA.weights / MSA.neff :250-269, the
+ * coverage property :242-247).  msa uint8 [N, L] with leading dimension ld >= L: any byte values, any number of distinct ones (raw
+ * character bytes or token ids: a one-to-one recoding changes no distance); bytes in [L, ld) are never read as data.  All of it rests
+ * on m(i, j) = the number of columns in which rows i and j differ, an exact int32 from xor + a per-byte non-zero mask + popcount over
+ * the rows kept eight bytes to a 64-bit word (zero past L), 64 x 64 pairs a block, tiles on or above the diagonal only: no atomics,
+ * the same bits on every run.
+ *   rnamsm_msa_pdist     counts int32 [N, N] = m and / or dist float64 [N, N] = (double)m / (double)L (scipy's pdist "hamming", one
+ *                        IEEE division); either may be NULL, not both.  The diagonal is exactly 0, the lower triangle a copy of the
+ *                        upper.  N in [1, 16384] (dist is 2 GB there; every i * N + j is 64-bit), L in [1, 32768].  workspace:
+ *                        rnamsm_msa_pdist_workspace_bytes(N, L) bytes (the packed rows; 0 outside the limits), 256-byte aligned.
+ *   rnamsm_msa_neff      n_neighbors[i] = #{ j : (double)m(i, j) / (double)L < seqid_cutoff } int32 [N] (the reference's strict
+ *                        comparison; the row itself has m = 0 and counts unless the cutoff is 0), weights[i] = 1.0 / n_neighbors[i]
+ *                        float64 [N] (rnamsm_msa_weights' values, bit for bit; inf where nothing counts), neff = the weights' sum,
+ *                        one float64, added in one fixed order: 1024 running sums, sum t over rows t, t + 1024, ... ascending from
+ *                        0.0, then folded in halves (s[t] += s[t + 512], then + 256, ..., + 1).  Each output may be NULL, not all
+ *                        three.  The N x N matrix is never formed: every tile's thresholded row and column sums go to int32 partial
+ *                        slots, one per (row, block of 64 rows), each written once, and are added per row.  N in [1, 2^20], L in
+ *                        [1, 32768], seqid_cutoff in [0, 1].  workspace, 256-byte aligned: any size from
+ *                        rnamsm_msa_neff_min_workspace_bytes(N, L) upward; rnamsm_msa_neff_workspace_bytes(N, L) is the default (the
+ *                        packed rows, N int32 totals and a partial table of at most 256 MB).  A partial table that does not hold
+ *                        every row block is reused band by band of row blocks; the band count follows from workspace_bytes alone,
+ *                        and every accepted size gives the same bits (the totals are integer sums).
+ *   rnamsm_msa_coverage  coverage[c] = (double)#{rows whose byte in column c != gap} / (double)N, float64 [L]: integer counts, one
+ *                        division.  N in [1, 2^20], L in [1, 32768], gap a byte value.
+ * Every refusal comes before the first launch, leaves the outputs untouched and names the offending value.  The calls are
+ * asynchronous: none waits for the stream. */
+size_t rnamsm_msa_pdist_workspace_bytes(int N, int L);
+int rnamsm_msa_pdist(const uint8_t* msa, int N, int L, int64_t ld, int32_t* counts, double* dist, void* workspace,
+                     size_t workspace_bytes, void* stream);
+size_t rnamsm_msa_neff_workspace_bytes(int N, int L);
+size_t rnamsm_msa_neff_min_workspace_bytes(int N, int L);
+int rnamsm_msa_neff(const uint8_t* msa, int N, int L, int64_t ld, double seqid_cutoff, int32_t* n_neighbors, double* weights,
+                    double* neff, void* workspace, size_t workspace_bytes, void* stream);
+int rnamsm_msa_coverage(const uint8_t* msa, int N, int L, int64_t ld, int gap, double* coverage, void* stream);
+
 /* Whole forward, K0..K10 for one MSA, driven from C++ so that one call enqueues every launch
  * (MSATransformer.forward, model.py:338-416, with repr_layers=[num_layers], need_head_weights=True,
  * lm_head / contact head omitted -- their results are unused by the CLI).

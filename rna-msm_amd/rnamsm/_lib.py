@@ -58,6 +58,8 @@ LONG_MAX_L = 4096                  # rnamsm_contact_head_long / _ss_head_long / 
                                    # _rsa_text_long: a stitched alignment
 # rnamsm_msa_invcov: rows, symbols, and the int32 header in front of the optional counts (K, then the symbols)
 INVCOV_MAX_N, INVCOV_MAX_K, INVCOV_META = 1 << 20, 16, 32
+# rnamsm_msa_pdist / _neff / _coverage: columns, rows of the matrix form, rows of the other two
+PDIST_MAX_L, PDIST_MAX_N_MATRIX, PDIST_MAX_N = 32768, 16384, 1 << 20
 
 
 class ModelDims(ctypes.Structure):
@@ -214,6 +216,12 @@ _SIGNATURES = {
     "rnamsm_msa_weights": (c_int, [c_void_p, c_int, c_int, c_double, c_void_p, c_void_p]),
     "rnamsm_msa_invcov_workspace_bytes": (c_size_t, [c_int, c_int]),
     "rnamsm_msa_invcov": (c_int, [c_void_p, c_int, c_int, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "rnamsm_msa_pdist_workspace_bytes": (c_size_t, [c_int, c_int]),
+    "rnamsm_msa_pdist": (c_int, [c_void_p, c_int, c_int, c_int64, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "rnamsm_msa_neff_workspace_bytes": (c_size_t, [c_int, c_int]),
+    "rnamsm_msa_neff_min_workspace_bytes": (c_size_t, [c_int, c_int]),
+    "rnamsm_msa_neff": (c_int, [c_void_p, c_int, c_int, c_int64, c_double, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "rnamsm_msa_coverage": (c_int, [c_void_p, c_int, c_int, c_int64, c_int, c_void_p, c_void_p]),
     "rnamsm_forward_workspace_bytes": (c_size_t, [POINTER(ModelDims), c_int, c_int, c_int, c_int]),
     "rnamsm_forward": (c_int, [POINTER(ModelDims), POINTER(c_void_p), c_void_p, c_int, c_int, c_void_p, c_size_t,
                                c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int,

@@ -48,6 +48,12 @@ def check_invcov(value) -> bool:
     return value
 
 
+def check_msa_stats(value) -> bool:
+    if not isinstance(value, bool):
+        raise ValueError(f"data.msa_stats={value!r} is not one of false, true")
+    return value
+
+
 @dataclass
 class DataConfig:                       # RNA_MSM_Inference.py:20-32
     device: str = "cuda"
@@ -128,6 +134,13 @@ class DataConfig:                       # RNA_MSM_Inference.py:20-32
     # (rnamsm.msa.msa_invcov) and written as <id>_invcov.npy, (L, L) float64, next to <id>_emb.npy.  An alignment the kernel refuses
     # (more than 4096 columns, more than 16 distinct non-gap tokens, fewer than 2 rows) gets one printed line and its other files.
     invcov: bool = False
+    # extra (not in the reference's CLI; its utils/align.py MSA.weights, MSA.neff and coverage): the statistics of the alignment AS
+    # READ -- every row, before row sub-sampling, and every column -- computed on the device (rnamsm_msa_neff, rnamsm_msa_coverage):
+    # <id>_weights.npy, (N,) float64, the sequence weights at a normalised Hamming cutoff of 0.2 (the reference's seqid_cutoff
+    # default), and <id>_coverage.npy, (L,) float64, next to <id>_emb.npy, and one printed line with N, L, Neff, Neff / sqrt(L) and
+    # Neff / L.  An alignment the kernels refuse (more than 32768 columns, more than 2^20 rows) gets one printed line and its other
+    # files.
+    msa_stats: bool = False
 
 
 @dataclass
@@ -202,4 +215,5 @@ def parse_overrides(argv: List[str], cfg: Config = None) -> Config:
     check_long_msa(cfg.data.long_msa)
     check_long_heads(cfg.data.long_heads)
     check_invcov(cfg.data.invcov)
+    check_msa_stats(cfg.data.msa_stats)
     return cfg

@@ -8,6 +8,7 @@ to rank 0 over RCCL first (`gather_to_rank0=True`).
 """
 from __future__ import annotations
 
+import math
 import os
 import queue
 import random
@@ -21,9 +22,9 @@ import torch
 
 from . import _lib, contacts, lm, ops, rsa, sharding, ss
 from .alphabet import RNAAlphabet
-from .config import Config, check_invcov, check_long_heads, check_long_msa, check_ss_gemm_dtype
+from .config import Config, check_invcov, check_long_heads, check_long_msa, check_msa_stats, check_ss_gemm_dtype
 from .model import MSATransformer
-from .msa import load_msa_tokens, msa_invcov_device
+from .msa import load_msa_tokens, msa_invcov_device, msa_stats_device
 
 
 def load_checkpoint(model: MSATransformer, path: str, device) -> None:
@@ -311,6 +312,8 @@ class _Switches(NamedTuple):
     window_stride: int          # data.window_stride
     long_heads: bool            # data.long_heads=stitched
     invcov_on: bool             # data.invcov
+    msa_stats_on: bool          # data.msa_stats
+    seqid_cutoff: float         # data.seqid_cutoff where the configuration has one, else the reference's default
     gathering: bool             # gather_to_rank0 with more than one rank
     ss_path: str                # data.ss_model_path
     rsa_dir: str                # data.rsa_model_dir
@@ -339,6 +342,10 @@ def read_switches(cfg: Config, gathering: bool) -> _Switches:
     # data.invcov: the covariance contact map of every alignment as read -- all rows, all columns -- made on the reader's side and
     # written as <id>_invcov.npy by one more writer job; off, nothing below differs
     invcov_on = check_invcov(getattr(cfg.data, "invcov", False))
+    # data.msa_stats: the sequence weights, the coverage and Neff of every alignment as read, made on the reader's side like the map
+    # above and written as <id>_weights.npy / <id>_coverage.npy by two more writer jobs; off, nothing below differs
+    msa_stats_on = check_msa_stats(getattr(cfg.data, "msa_stats", False))
+    seqid_cutoff = float(getattr(cfg.data, "seqid_cutoff", 0.2))
     # data.batch_small_msas: small alignments go through ONE launch set per group (forward_ragged: padded into one
     # frame, every MSA scaled by its own depth); a lone forward of a few hundred tokens costs 5.5 ms on a mostly
     # idle chip.  Groups: by shape from the pool (plan_groups); under gather_to_rank0 the RoundGatherer needs this
@@ -355,7 +362,7 @@ def read_switches(cfg: Config, gathering: bool) -> _Switches:
     small_limit = (PACKED_SMALL_TOKENS if exact else PACKED_SMALL_TOKENS_16BIT.get(cfg.model.gemm_dtype, 1024)) if packing else SMALL_MSA_TOKENS
     return _Switches(
         gemm_dtype=cfg.model.gemm_dtype, ss_dtype=ss_dtype, windowing=windowing, window_stride=window_stride, long_heads=long_heads,
-        invcov_on=invcov_on, gathering=gathering, ss_path=getattr(cfg.data, "ss_model_path", ""),
+        invcov_on=invcov_on, msa_stats_on=msa_stats_on, seqid_cutoff=seqid_cutoff, gathering=gathering, ss_path=getattr(cfg.data, "ss_model_path", ""),
         rsa_dir=getattr(cfg.data, "rsa_model_dir", ""), ss_text=bool(getattr(cfg.data, "ss_prob_text", True)) and not gathering,
         ss_pairs=bool(getattr(cfg.data, "ss_pairs_device", True)) and not gathering,
         rsa_text=bool(getattr(cfg.data, "rsa_text_device", True)) and not gathering, contacts=bool(getattr(cfg.data, "contacts", False)),
@@ -432,8 +439,9 @@ class _Reader:
     (dataset.py:147) -- seeded 42 like the reference's global numpy state (RNA_MSM_Inference.py:17), so a single
     process reproduces the reference's choices; under sharding every rank draws for its own items."""
 
-    def __init__(self, cfg: Config, sw: _Switches, ids: List[str], files: Dict[str, Path], alphabet, device, put_map):
+    def __init__(self, cfg: Config, sw: _Switches, ids: List[str], files: Dict[str, Path], alphabet, device, put_map, put_stats=None):
         self.cfg, self.sw, self.ids, self.files, self.alphabet, self.device, self.put_map = cfg, sw, ids, files, alphabet, device, put_map
+        self.put_stats = put_stats
         self.rng = np.random.RandomState(42)
 
     def __call__(self, idx: int) -> np.ndarray:
@@ -441,8 +449,27 @@ class _Reader:
         rna_id = self.ids[idx]
         tokens = load_msa_tokens(self.files[rna_id], self.alphabet, self.cfg.data.max_seqs_per_msa, self.cfg.data.sample_method,
                                  device=self.device, rng=self.rng,
-                                 on_full=(lambda full: self.covariance_map(rna_id, full)) if self.sw.invcov_on else None)
+                                 on_full=(lambda full: self.on_full(rna_id, full)) if self.sw.invcov_on or self.sw.msa_stats_on else None)
         return tokens if self.sw.windowing else crop_tokens(tokens, self.cfg.data.max_seqlen, self.rng)
+
+    def on_full(self, rna_id: str, full: np.ndarray) -> None:
+        if self.sw.invcov_on:
+            self.covariance_map(rna_id, full)
+        if self.sw.msa_stats_on:
+            self.alignment_stats(rna_id, full)
+
+    def alignment_stats(self, rna_id: str, full: np.ndarray) -> None:
+        """data.msa_stats: the weights and the coverage of the alignment as read, left on the device for the sink, and the line with
+        Neff; an alignment the kernels refuse gets one line that names the reason, and its other files as usual."""
+        N, L = full.shape[0], max(full.shape[1] - 1, 1)
+        try:
+            rec, coverage = msa_stats_device(full, self.alphabet.tok_to_idx["-"], self.sw.seqid_cutoff, self.device)
+            neff = float(rec.neff.item())                   # (waits for the reader's stream: the vectors are complete)
+        except _lib.RnamsmError as e:
+            print(f"{rna_id}: no alignment statistics (data.msa_stats) for this alignment of {N} rows x {L} columns: {e}")
+            return
+        self.put_stats(rna_id, (rec.weights, coverage))
+        print(f"{rna_id}: {N} rows x {L} columns, Neff {neff:.3f} (Neff/sqrt(L) {neff / math.sqrt(L):.3f}, Neff/L {neff / L:.4f})")
 
     def covariance_map(self, rna_id: str, full: np.ndarray) -> None:
         """data.invcov: the map of the alignment as read (before row sub-sampling and any crop), left on the device for the sink; an
@@ -479,16 +506,20 @@ class _Sink:
         self.ids, self.heads, self.save_dir, self.sw, self.max_seqlen = ids, heads, save_dir, sw, max_seqlen
         self.written: List[str] = []
         self.invcov_maps: Dict[str, torch.Tensor] = {}      # id -> the map on the device, from the reader until the alignment is delivered
+        self.msa_stats: Dict[str, tuple] = {}               # id -> (weights, coverage) on the device, likewise (data.msa_stats)
         self.writer = _AsyncNpyWriter(device) if async_io and (not sw.gathering or rank == 0) else None
         # gather_to_rank0: outputs travel to rank 0 one ROUND (one MSA per rank) at a time, round k's RCCL transfers
         # overlapping round k+1's forward, and are handed to the writer as they arrive -- at most one round is resident
         # (an item: emb, atp, every head's flattened record, the covariance map)
         self.gatherer = sharding.RoundGatherer(len(ids), on_item=self.on_item,
-                                               tensors_per_item=2 + sum(h.n_tensors for h in heads) + int(sw.invcov_on),
+                                               tensors_per_item=2 + sum(h.n_tensors for h in heads) + int(sw.invcov_on) + 2 * int(sw.msa_stats_on),
                                                dst=0, device=device, group=_gather_group(device, rank)) if sw.gathering else None
 
     def put_map(self, rna_id: str, cov: torch.Tensor) -> None:
         self.invcov_maps[rna_id] = cov
+
+    def put_stats(self, rna_id: str, vectors: tuple) -> None:
+        self.msa_stats[rna_id] = vectors
 
     def deliver(self, idx: int, emb: torch.Tensor, atp: torch.Tensor, after: Optional[torch.cuda.Event], records: list) -> None:
         """records: the alignment's record of every head, None for a head skipped on it."""
@@ -501,10 +532,14 @@ class _Sink:
         if self.sw.invcov_on:           # (the map travels as the item's last tensor; a refused alignment sends a placeholder)
             cov = self.invcov_maps.pop(self.ids[idx], None)
             item += (cov if cov is not None else emb.new_zeros(1),)
+        if self.sw.msa_stats_on:        # (the two vectors travel as the item's last tensors, float64; a refused alignment sends fp32 placeholders)
+            item += tuple(self.msa_stats.pop(self.ids[idx], None) or (emb.new_zeros(1, dtype=torch.float32),) * 2)
         self.gatherer.submit(idx, item)
 
     def on_item(self, i: int, ts) -> None:
-        self.emit(self.ids[i], ts[0], ts[1], records=self.records_of(ts[2:], ts[0].shape[0]), cov=ts[-1] if self.sw.invcov_on else None)
+        n_stats = 2 * int(self.sw.msa_stats_on)
+        self.emit(self.ids[i], ts[0], ts[1], records=self.records_of(ts[2:], ts[0].shape[0]),
+                  cov=ts[len(ts) - n_stats - 1] if self.sw.invcov_on else None, stats=tuple(ts[len(ts) - n_stats:]) if n_stats else None)
 
     def records_of(self, flat, L: int) -> list:
         """A gathered item's tensors behind emb and atp -> the heads' records (the inverse of deliver()'s flattening)."""
@@ -513,13 +548,17 @@ class _Sink:
         return [None if isinstance(_route(h, L, self.sw, self.max_seqlen), str) else h.unflatten(ts) for h, ts in shares]
 
     def emit(self, rna_id: str, emb: torch.Tensor, atp: torch.Tensor, after: Optional[torch.cuda.Event] = None, records=(),
-             cov: Optional[torch.Tensor] = None) -> None:
+             cov: Optional[torch.Tensor] = None, stats: Optional[tuple] = None) -> None:
         """records: this alignment's record of every head that is on, in the order of `heads`; each becomes one writer job (but
         for the heads skipped on a stitched alignment: their entry is None).  cov: a gathered item's covariance map (or
         its one-element placeholder); absent, the one the reader left for this id, if any."""
         extra = [h.writer_job(r, rna_id, self.save_dir) for h, r in zip(self.heads, records) if r is not None]
         cov = self.invcov_maps.pop(rna_id, None) if cov is None else (cov if cov.dim() == 2 else None)
         cov_job = [(self.save_dir / f"{rna_id}_invcov.npy", cov)] if cov is not None else []
+        # stats: a gathered item's (weights, coverage) or its placeholders; absent, what the reader left for this id, if anything
+        stats = self.msa_stats.pop(rna_id, None) if stats is None else (stats if stats[0].dtype == torch.float64 else None)
+        if stats is not None:
+            cov_job += [(self.save_dir / f"{rna_id}_weights.npy", stats[0]), (self.save_dir / f"{rna_id}_coverage.npy", stats[1])]
         if self.writer is not None:
             self.writer.submit([(self.save_dir / f"{rna_id}_atp.npy", atp), (self.save_dir / f"{rna_id}_emb.npy", emb)] + extra + cov_job,
                                lambda r=rna_id: self.written.append(r), after=after)
@@ -794,7 +833,7 @@ def extract_feat(cfg: Config, model: Optional[MSATransformer] = None, gather_to_
     sink = _Sink(ids, heads, save_dir, sw, model.max_seqlen, device, rank, async_io)
     reader = ThreadPoolExecutor(1, thread_name_prefix="rnamsm-msa-reader") if async_io else None
     scheduler = _Scheduler(model, heads, sink, sw, ids, sharding.shard_indices(len(ids), rank, world),
-                           _Reader(cfg, sw, ids, files, alphabet, device, sink.put_map), reader, alphabet.padding_idx,
+                           _Reader(cfg, sw, ids, files, alphabet, device, sink.put_map, sink.put_stats), reader, alphabet.padding_idx,
                            to_device=lambda tokens: torch.from_numpy(tokens).to(device), record_event=_record_event)
     try:
         with torch.no_grad():

@@ -125,6 +125,55 @@ def msa_invcov(tokens: np.ndarray, gap_idx: int, device) -> np.ndarray:
     return msa_invcov_device(tokens, gap_idx, device).cpu().numpy()
 
 
+def _stats_body_device(tokens: np.ndarray, device, name: str):
+    """The alignment's columns (no <cls>, as msa_weights slices them) as uint8 on the HIP device; any other device is refused."""
+    import torch
+    from . import _lib
+    dev = torch.device(device) if device is not None else None
+    if dev is None or dev.type != "cuda":
+        raise _lib.RnamsmError(f"{name}: device={device!r} is not a HIP device (no CPU path exists)")
+    body = tokens[:, 1:] if tokens.shape[1] > 1 else tokens
+    if body.size and (int(body.min()) < 0 or int(body.max()) > 255):
+        raise ValueError(f"{name}: token ids outside [0, 255]")
+    return torch.from_numpy(np.ascontiguousarray(body.astype(np.uint8))).to(dev)
+
+
+def msa_pdist(tokens: np.ndarray, device) -> np.ndarray:
+    """MSA.pdist (utils/align.py:121-126): the normalised Hamming distance of every pair of rows, float64 [N, N] (scipy's
+    squareform(pdist(.., "hamming")): mismatches / L), over the alignment's columns (no <cls>).  Token ids stand for the reference's
+    character bytes: a one-to-one recoding changes no distance.  On the HIP device only (rnamsm_msa_pdist); N <= 16384, L <= 32768."""
+    from . import ops
+    return ops.msa_pdist(_stats_body_device(tokens, device, "msa_pdist"), "dist").cpu().numpy()
+
+
+def msa_stats_device(tokens: np.ndarray, gap_idx: int, seqid_cutoff: float, device):
+    """(ops.MsaNeff, coverage float64 [L]) of an alignment, left on the device: what the CLI's data.msa_stats writes and prints."""
+    from . import ops
+    u8 = _stats_body_device(tokens, device, "msa_stats")
+    return ops.msa_neff(u8, seqid_cutoff), ops.msa_coverage(u8, int(gap_idx))
+
+
+def msa_neff(tokens: np.ndarray, seqid_cutoff: float = 0.2, normalization="none", device=None) -> float:
+    """MSA.neff (utils/align.py:259-269): the sum of the sequence weights at `seqid_cutoff`, divided by 1 ("none"), sqrt(L) ("sqrt"),
+    L ("seqlen") or the number given; L = the alignment's columns (no <cls>).  The sum is rnamsm_msa_neff's (one fixed order on the
+    device), the division is done here.  On the HIP device only."""
+    import math
+    from . import ops
+    u8 = _stats_body_device(tokens, device, "msa_neff")
+    if isinstance(normalization, str):
+        if normalization not in ("none", "sqrt", "seqlen"):
+            raise ValueError(f"msa_neff: normalization={normalization!r} is not one of 'none', 'sqrt', 'seqlen' or a number")
+        normalization = {"none": 1, "sqrt": math.sqrt(u8.shape[1]), "seqlen": u8.shape[1]}[normalization]
+    return float(ops.msa_neff(u8, seqid_cutoff).neff.item()) / normalization
+
+
+def msa_coverage(tokens: np.ndarray, gap_idx: int, device) -> np.ndarray:
+    """The coverage property (utils/align.py:242-247): per column the share of rows that hold no gap, float64 [L] (no <cls>).  On the
+    HIP device only (rnamsm_msa_coverage)."""
+    from . import ops
+    return ops.msa_coverage(_stats_body_device(tokens, device, "msa_coverage"), int(gap_idx)).cpu().numpy()
+
+
 def sample_weights(tokens: np.ndarray, num_seqs: int, rng=None, seqid_cutoff: float = 0.2, device=None) -> np.ndarray:
     """Row indices drawn like MSA.sample_weights (utils/align.py:150-163): row 0 plus num_seqs - 1 of the others without
     replacement with probability proportional to their sequence weight, ascending.  `rng`: a numpy RandomState; None =

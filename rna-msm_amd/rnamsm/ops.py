@@ -1285,6 +1285,75 @@ def msa_invcov(tokens_u8: torch.Tensor, gap: int, want_counts: bool = False):
     return out, counts[_lib.INVCOV_META:].view(L, L, K, K), counts[1:1 + K]
 
 
+def _msa_rows(msa_u8: torch.Tensor, name: str):
+    """uint8 [N, L] on the device as the alignment statistics read it: (tensor, N, L, ld).  A view with contiguous rows is read where
+    it lies (ld = its row stride); anything else is copied."""
+    _dev(msa_u8, name, torch.uint8)
+    if msa_u8.dim() != 2:
+        raise ValueError(f"{name}: expected uint8 [N, L], got {tuple(msa_u8.shape)}")
+    if (msa_u8.shape[1] > 1 and msa_u8.stride(1) != 1) or msa_u8.stride(0) < msa_u8.shape[1]:
+        msa_u8 = msa_u8.contiguous()
+    N, L = msa_u8.shape
+    return msa_u8, N, L, (msa_u8.stride(0) if N > 1 else L)
+
+
+def _aligned_workspace(nbytes: int, device) -> torch.Tensor:
+    return torch.empty(max(int(nbytes), 256), dtype=torch.uint8, device=device)
+
+
+@_on_operand_device
+def msa_pdist(msa_u8: torch.Tensor, want: str = "dist"):
+    """MSA.pdist (utils/align.py:121-126; rnamsm_msa_pdist): msa uint8 [N, L] on the device -> want="dist": float64 [N, N] =
+    mismatches / L, scipy's pdist "hamming" in square form; "counts": int32 [N, N], the mismatches; "both": (dist, counts).  Exactly
+    symmetric, the diagonal exactly 0.  N in [1, 16384], L in [1, 32768]; the library refuses anything else."""
+    if want not in ("dist", "counts", "both"):
+        raise ValueError(f"msa_pdist: want={want!r} is not one of 'dist', 'counts', 'both'")
+    msa_u8, N, L, ld = _msa_rows(msa_u8, "msa_pdist")
+    lib = _lib.load()
+    dev = msa_u8.device
+    ws = _aligned_workspace(lib.rnamsm_msa_pdist_workspace_bytes(N, L), dev)
+    dist = torch.empty((N, N), dtype=torch.float64, device=dev) if want != "counts" else None
+    counts = torch.empty((N, N), dtype=torch.int32, device=dev) if want != "dist" else None
+    _lib.check(lib.rnamsm_msa_pdist(msa_u8.data_ptr(), N, L, ld, counts.data_ptr() if counts is not None else None,
+                                    dist.data_ptr() if dist is not None else None, ws.data_ptr(), ws.numel(), _stream()))
+    return {"dist": dist, "counts": counts, "both": (dist, counts)}[want]
+
+
+class MsaNeff(NamedTuple):
+    """What rnamsm_msa_neff writes, on the device."""
+    n_neighbors: torch.Tensor      # int32 [N]: rows within the cutoff, the row itself included
+    weights: torch.Tensor          # float64 [N]: 1 / n_neighbors
+    neff: torch.Tensor             # float64 scalar: the weights' sum
+
+
+@_on_operand_device
+def msa_neff(msa_u8: torch.Tensor, seqid_cutoff: float = 0.2, workspace_bytes: Optional[int] = None) -> MsaNeff:
+    """MSA.weights and MSA.neff("none") (utils/align.py:250-269; rnamsm_msa_neff): msa uint8 [N, L] on the device -> MsaNeff.  The
+    weights are msa_weights' values bit for bit, from the tiled pair kernel, without the N x N matrix.  workspace_bytes: None = the
+    library's default; any size from rnamsm_msa_neff_min_workspace_bytes(N, L) upward gives the same bits in more bands.
+    N in [1, 2^20], L in [1, 32768], seqid_cutoff in [0, 1]."""
+    msa_u8, N, L, ld = _msa_rows(msa_u8, "msa_neff")
+    lib = _lib.load()
+    dev = msa_u8.device
+    ws = _aligned_workspace(lib.rnamsm_msa_neff_workspace_bytes(N, L) if workspace_bytes is None else workspace_bytes, dev)
+    rec = MsaNeff(torch.empty(N, dtype=torch.int32, device=dev), torch.empty(N, dtype=torch.float64, device=dev),
+                  torch.empty((), dtype=torch.float64, device=dev))
+    _lib.check(lib.rnamsm_msa_neff(msa_u8.data_ptr(), N, L, ld, float(seqid_cutoff), rec.n_neighbors.data_ptr(), rec.weights.data_ptr(),
+                                   rec.neff.data_ptr(), ws.data_ptr(), ws.numel() if workspace_bytes is None else int(workspace_bytes),
+                                   _stream()))
+    return rec
+
+
+@_on_operand_device
+def msa_coverage(msa_u8: torch.Tensor, gap: int) -> torch.Tensor:
+    """The coverage property (utils/align.py:242-247; rnamsm_msa_coverage): msa uint8 [N, L] on the device -> float64 [L], the share
+    of rows whose byte in the column is not `gap`.  N in [1, 2^20], L in [1, 32768]."""
+    msa_u8, N, L, ld = _msa_rows(msa_u8, "msa_coverage")
+    out = torch.empty(L, dtype=torch.float64, device=msa_u8.device)
+    _lib.check(_lib.load().rnamsm_msa_coverage(msa_u8.data_ptr(), N, L, ld, int(gap), out.data_ptr(), _stream()))
+    return out
+
+
 def depth_scaling(R: int) -> float:
     """1/sqrt(R) as the C++ drivers form it -- `1.0f / sqrtf((float)R)` in fp32, both steps correctly rounded -- so that the
     layer-wise mirror modules hand K5 the very same factor (forming it in double and rounding once can differ in the last bit)."""
