@@ -848,6 +848,45 @@ size_t rnamsm_msa_invcov_workspace_bytes(int N, int L);
 int rnamsm_msa_invcov(const uint8_t* tokens, int N, int L, int64_t ld, int gap, double* out, int32_t* counts, void* workspace,
                       size_t workspace_bytes, void* stream);
 
+/* Mutual-information contacts: mi[i, j] = the mutual information of alignment columns i and j, and mip = its average-product
+ * corrected form (MIp), float64 [L, L] each; either may be NULL, not both.  tokens, ld, gap, the K symbols, the refusals (K = 0,
+ * K > 16) and the limits (N in [2, 2^20], L in [1, RNAMSM_LONG_MAX_L]) are rnamsm_msa_invcov's, and so is stage 1: the exact integer
+ * pair counts n_ab(i, j) and marginals n_a(i).  The states of a column pair give an integer table c[a][b]; gap_mode says what a gap is:
+ *   RNAMSM_MI_GAPS_PAIRWISE (0)  rows with a gap in column i or j are left out of that pair: c[a][b] = n_ab(i, j) over the K symbols,
+ *                                all of it from the pair's own K x K block;
+ *   RNAMSM_MI_GAPS_STATE (1)     the gap is a (K+1)-th state, its row and column from the marginals in integers:
+ *                                c[a][gap] = n_a(i) - sum_b n_ab, c[gap][b] = n_b(j) - sum_a n_ab, c[gap][gap] = N - the rest; n = N.
+ * With n = sum c, r_a = sum_b c[a][b], s_b = sum_a c[a][b], all integers,
+ *   mi(i, j) = sum over a, b with c[a][b] > 0 of (c[a][b] / n) * log((c[a][b] * n) / (r_a * s_b))        natural log, float64;
+ * a pair with n = 0 gives 0.  Both integer products are below 2^40 and exact in a double, so the argument of the log is one
+ * correctly rounded division of exact integers; the sum runs a-major then b, ascending, in one thread, without contraction, no
+ * atomics: the same bits on every run.  Hence, exactly: a constant column, and in state mode an all-gap column, has ratio 1.0, log 0,
+ * and its whole row and column of mi exactly 0; mi(i, i) is the column's entropy; j >= i is computed and written to both places, so
+ * the map is exactly symmetric.
+ *   mip = rnamsm_apc_f64 of mi with its diagonal read as 0 (below); a total of 0 (L = 1, or every column constant) gives NaN everywhere.
+ * workspace: 256-byte aligned, rnamsm_msa_mi_workspace_bytes(N, L) bytes (0 outside the limits): rnamsm_msa_invcov's, an [L, L]
+ * float64 map (used when mi is NULL) and the correction's sums.  Every refusal comes before the first launch and names the value.
+ * Like rnamsm_msa_invcov the call WAITS for the stream once (K is read back); it must not be captured into a graph. */
+#define RNAMSM_MI_GAPS_PAIRWISE 0
+#define RNAMSM_MI_GAPS_STATE 1
+size_t rnamsm_msa_mi_workspace_bytes(int N, int L);
+int rnamsm_msa_mi(const uint8_t* tokens, int N, int L, int64_t ld, int gap, int gap_mode, double* mi, double* mip, void* workspace,
+                  size_t workspace_bytes, void* stream);
+
+/* Average-product correction of a square float64 map (the reference's apc, utils/tensor.py:103-113), symmetric or not:
+ *   a1 = row sums, a2 = column sums, a12 = the total,  out[i, j] = x[i, j] - (a1[i] * a2[j]) / a12     (product, division, subtraction).
+ * x [L, L] with leading dimension ld >= L, out [L, L] packed.  zero_diagonal = 1: the diagonal of x is read as 0, in the sums and in
+ * the subtraction, so out[i, i] = 0 - (a1[i] * a2[i]) / a12.  A total of 0 gives NaN everywhere, as the reference's 0 / 0 does.
+ * Every sum has one fixed order, no atomics: a1[i]: 256 running sums, sum t over x[i, t], x[i, t + 256], ... ascending from 0.0,
+ * folded in halves (s[t] += s[t + 128], then + 64, ..., + 1); a2[j]: four running sums, sum g over x[g, j], x[g + 4, j], ...
+ * ascending from 0.0, a2[j] = (p0 + p2) + (p1 + p3); a12: the 256-sum-and-fold of a1.  L in [1, 32768].  out == x is allowed where
+ * ld == L (an element is read and written by one thread, after the sums) and refused otherwise; other overlaps are the caller's
+ * error.  workspace: rnamsm_apc_f64_workspace_bytes(L) bytes (2 L + 1 doubles; 0 outside the limits), 8-byte aligned.  Asynchronous:
+ * the call waits for nothing. */
+size_t rnamsm_apc_f64_workspace_bytes(int L);
+int rnamsm_apc_f64(const double* x, int L, int64_t ld, int zero_diagonal, double* out, void* workspace, size_t workspace_bytes,
+                   void* stream);
+
 /* Alignment statistics built on the pairwise Hamming matrix (utils/align.py: MSA.pdist :121-126, MSA.weights / MSA.neff :250-269, the
  * coverage property :242-247).  msa uint8 [N, L] with leading dimension ld >= L: any byte values, any number of distinct ones (raw
  * character bytes or token ids: a one-to-one recoding changes no distance); bytes in [L, ld) are never read as data.  All of it rests

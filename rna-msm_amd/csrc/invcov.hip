@@ -20,6 +20,9 @@
 // word-major, so both the global reads and the LDS reads are contiguous 16-byte vectors).  Each sum is over one thread's words in
 // ascending order in integers: no atomics, the same bits on every run.  Tiles wholly below the diagonal are skipped unless the
 // caller asked for the counts.
+//
+// Mutual information (rnamsm_msa_mi) runs the same stage 1 and replaces the norm by mi_pair_kernel, a per-pair fp64 sum over the
+// integer table; its corrected map is apc.hip's rnamsm_apc_f64 of the map with a zero diagonal.
 #include "common.h"
 
 namespace rnamsm {
@@ -246,6 +249,152 @@ static InvcovWs invcov_ws(int N, int L, int K) {
     return w;
 }
 
+// ---- stage 1 as both entry points (rnamsm_msa_invcov, rnamsm_msa_mi) run it ---------------------------------------------------------
+// `who` is the entry point's name in every message.
+static int stage1_check(const char* who, bool pointers, int N, int L, int64_t ld, int gap) {
+    RNAMSM_CHECK_ARG(pointers, "%s: null pointer", who);
+    RNAMSM_CHECK_ARG(N >= 2 && N <= IC_MAX_N, "%s: N=%d outside [2, %d]", who, N, IC_MAX_N);
+    RNAMSM_CHECK_ARG(L >= 1 && L <= RNAMSM_LONG_MAX_L, "%s: L=%d outside [1, %d]", who, L, RNAMSM_LONG_MAX_L);
+    RNAMSM_CHECK_ARG(ld >= L, "%s: ld=%lld is smaller than L=%d", who, (long long)ld, L);
+    RNAMSM_CHECK_ARG(gap >= 0 && gap <= 255, "%s: gap=%d is not a byte value", who, gap);
+    return RNAMSM_OK;
+}
+
+struct Stage1 {
+    InvcovWs w;                  // the layout for the K that was found
+    int K, R;
+    int32_t *meta, *marg, *band; // the header (K, the symbols), n_a(i) as [L, K], the workspace's band of counts
+    uint64_t* P;
+};
+
+// presence, table (the one wait for the stream: K is read back), planes, marginals
+static int stage1_planes(const char* who, const uint8_t* tokens, int N, int L, int64_t ld, int gap, char* ws, hipStream_t s, Stage1* st) {
+    const InvcovWs full_ws = invcov_ws(N, L, IC_MAX_K);
+    uint32_t* present = reinterpret_cast<uint32_t*>(ws + full_ws.present);
+    uint8_t* lut = reinterpret_cast<uint8_t*>(ws + full_ws.lut);
+    st->meta = reinterpret_cast<int32_t*>(ws + full_ws.meta);
+    st->marg = reinterpret_cast<int32_t*>(ws + full_ws.marg);
+    st->band = reinterpret_cast<int32_t*>(ws + full_ws.band);
+
+    // ---- the symbols that occur: the one place where the host waits for the stream (K decides the layout and two refusals)
+    if (hipMemsetAsync(present, 0, 256 * 4, s) != hipSuccess) return fail(RNAMSM_ERR_HIP, "%s: hipMemsetAsync failed", who);
+    hipLaunchKernelGGL(invcov_presence_kernel, dim3(N < 2048 ? N : 2048), dim3(256), 0, s, tokens, N, L, ld, present);
+    hipLaunchKernelGGL(invcov_table_kernel, dim3(1), dim3(256), 0, s, present, gap, lut, st->meta);
+    RNAMSM_CHECK_LAUNCH(who);
+    int32_t host_meta[IC_META];
+    if (hipMemcpyAsync(host_meta, st->meta, sizeof(host_meta), hipMemcpyDeviceToHost, s) != hipSuccess ||
+        hipStreamSynchronize(s) != hipSuccess)
+        return fail(RNAMSM_ERR_HIP, "%s: reading the symbol table back failed: %s", who, hipGetErrorString(hipGetLastError()));
+    const int K = host_meta[0];
+    RNAMSM_CHECK_ARG(K >= 1, "%s: the alignment holds nothing but the gap value %d (K = 0)", who, gap);
+    RNAMSM_CHECK_ARG(K <= IC_MAX_K, "%s: %d distinct non-gap values, more than %d", who, K, IC_MAX_K);
+
+    st->w = invcov_ws(N, L, K);                          // (every offset up to the planes is independent of K)
+    st->K = K;
+    st->R = L * K;
+    st->P = reinterpret_cast<uint64_t*>(ws + st->w.planes);
+    if (hipMemsetAsync(st->P, 0, (size_t)st->w.Wp * (size_t)st->w.Rp * 8, s) != hipSuccess)
+        return fail(RNAMSM_ERR_HIP, "%s: hipMemsetAsync failed", who);
+    hipLaunchKernelGGL(invcov_planes_kernel, dim3((L + IP_COLS - 1) / IP_COLS, st->w.W), dim3(256), 0, s, tokens, N, L, ld, lut, K,
+                       st->w.Rp, st->P);
+    hipLaunchKernelGGL(invcov_marginals_kernel, dim3((st->R + 255) / 256), dim3(256), 0, s, st->P, st->w.W, st->w.Rp, st->R, st->marg);
+    return RNAMSM_OK;
+}
+
+// columns i per band of counts held in the workspace: all of them, or a multiple of 64 (tile-aligned rows)
+static int stage1_band(int L, int K) {
+    const size_t per_col = (size_t)L * K * K * 4;
+    return per_col * L > IC_BAND_BYTES ? (int)(IC_BAND_BYTES / per_col / 64) * 64 : L;      // >= 64: per_col <= 2^22
+}
+
+// the counts of columns [i0, i1) into cnt as [i - i0][j][a][b]; full = 0: tiles wholly below the diagonal are left out
+static void stage1_count(const Stage1& st, int L, int i0, int i1, int full, int32_t* cnt, hipStream_t s) {
+    const int64_t row0 = (int64_t)i0 * st.K, rows_end = (int64_t)i1 * st.K;
+    hipLaunchKernelGGL(invcov_count_kernel, dim3((unsigned)(st.w.Rp / IC_TILE), (unsigned)((rows_end - row0 + IC_TILE - 1) / IC_TILE)),
+                       dim3(256), 0, s, st.P, st.w.Wp, st.w.Rp, st.R, st.K, L, row0, rows_end, i0, full, cnt);
+}
+
+// ---- mutual information of a band of counts ------------------------------------------------------------------------------------------
+// One thread per (i, j >= i), the counterpart of invcov_norm_kernel.  The pair's integer table c[a][b] over the K symbols is its
+// K x K block of counts; MODE 1 ("state") adds the gap as state K, from the marginals in integers: c[a][K] = n_a(i) - sum_b n_ab,
+// c[K][b] = n_b(j) - sum_a n_ab, c[K][K] = N - the rest, so n = N, r_a = n_a(i), s_b = n_b(j).  MODE 0 ("pairwise") leaves the rows with
+// a gap in either column out: n, r_a, s_b are the block's own sums (s_b is kept in LDS, element-major [b][thread]: conflict-free, and
+// a thread reads only what it wrote, so there is no barrier).
+//   mi = sum over a then b ascending, the entries with c > 0 only, of ((double)c / (double)n) * log((double)(c * n) / (double)(r_a * s_b))
+// both products exact in int64 (below 2^40), one division each, no contraction.  n = 0 gives 0.  The value goes to (i, j) and (j, i).
+__device__ __forceinline__ double mi_term(int c, int64_t n, double dn, int r, int s) {
+    const double ratio = (double)((int64_t)c * n) / (double)((int64_t)r * (int64_t)s);
+    const double w = (double)c / dn;
+    return w * log(ratio);
+}
+
+template <int MODE>
+__global__ __launch_bounds__(256) void mi_pair_kernel(const int32_t* __restrict__ cnt, const int32_t* __restrict__ marg, int N, int L,
+                                                      int K, int i0, int i1, double* __restrict__ mi) {
+    __shared__ int s_col[MODE == 0 ? IC_MAX_K * 256 : 1];
+    const int t = threadIdx.x;
+    const int j = blockIdx.x * 256 + t, i = i0 + blockIdx.y;
+    if (i >= i1 || j >= L || j < i) return;                       // (no barrier below)
+    const int32_t* cb = cnt + ((int64_t)(i - i0) * L + j) * K * K;
+    const int32_t* mi_i = marg + (int64_t)i * K;
+    const int32_t* mj = marg + (int64_t)j * K;
+    int64_t n = N;
+    if (MODE == 0) {
+        n = 0;
+        for (int b = 0; b < K; ++b) {
+            int s = 0;
+            for (int a = 0; a < K; ++a) s += cb[a * K + b];
+            s_col[b * 256 + t] = s;
+            n += s;
+        }
+    }
+    double sum = 0.0;
+    if (n > 0) {
+        const double dn = (double)n;
+        int all = 0, gaps_i = N, gaps_j = N;                      // MODE 1: sum of the block, rows with a gap in column i, in column j
+        if (MODE == 1)
+            for (int b = 0; b < K; ++b) gaps_j -= mj[b];
+        for (int a = 0; a < K; ++a) {
+            int row = 0;
+            for (int b = 0; b < K; ++b) row += cb[a * K + b];
+            const int r = MODE == 1 ? mi_i[a] : row;
+            for (int b = 0; b < K; ++b) {
+                const int c = cb[a * K + b];
+                if (c > 0) sum += mi_term(c, n, dn, r, MODE == 1 ? mj[b] : s_col[b * 256 + t]);
+            }
+            if (MODE == 1) {
+                const int c = r - row;                            // symbol a in column i, a gap in column j
+                if (c > 0) sum += mi_term(c, n, dn, r, gaps_j);
+                all += row;
+                gaps_i -= r;
+            }
+        }
+        if (MODE == 1) {
+            for (int b = 0; b < K; ++b) {
+                int col = 0;
+                for (int a = 0; a < K; ++a) col += cb[a * K + b];
+                const int c = mj[b] - col;                        // a gap in column i, symbol b in column j
+                if (c > 0) sum += mi_term(c, n, dn, gaps_i, mj[b]);
+            }
+            const int c = gaps_i - ((N - gaps_j) - all);          // a gap in both: N - the rest
+            if (c > 0) sum += mi_term(c, n, dn, gaps_i, gaps_j);
+        }
+    }
+    mi[(int64_t)i * L + j] = sum;
+    mi[(int64_t)j * L + i] = sum;
+}
+
+struct MiWs {
+    size_t map, apc, total;          // behind stage 1's bytes, which start at 0
+};
+static MiWs mi_ws(int N, int L) {
+    MiWs w;
+    w.map = (invcov_ws(N, L, IC_MAX_K).total + 255) & ~(size_t)255;                  // mi where the caller wants mip alone
+    w.apc = w.map + ((((size_t)L * L * 8) + 255) & ~(size_t)255);
+    w.total = w.apc + rnamsm_apc_f64_workspace_bytes(L);
+    return w;
+}
+
 }  // namespace rnamsm
 
 using namespace rnamsm;
@@ -257,63 +406,69 @@ extern "C" size_t rnamsm_msa_invcov_workspace_bytes(int N, int L) {
 
 extern "C" int rnamsm_msa_invcov(const uint8_t* tokens, int N, int L, int64_t ld, int gap, double* out, int32_t* counts,
                                  void* workspace, size_t workspace_bytes, void* stream) {
-    RNAMSM_CHECK_ARG(tokens && out && workspace, "msa_invcov: null pointer");
-    RNAMSM_CHECK_ARG(N >= 2 && N <= IC_MAX_N, "msa_invcov: N=%d outside [2, %d]", N, IC_MAX_N);
-    RNAMSM_CHECK_ARG(L >= 1 && L <= RNAMSM_LONG_MAX_L, "msa_invcov: L=%d outside [1, %d]", L, RNAMSM_LONG_MAX_L);
-    RNAMSM_CHECK_ARG(ld >= L, "msa_invcov: ld=%lld is smaller than L=%d", (long long)ld, L);
-    RNAMSM_CHECK_ARG(gap >= 0 && gap <= 255, "msa_invcov: gap=%d is not a byte value", gap);
-    const InvcovWs full_ws = invcov_ws(N, L, IC_MAX_K);
-    RNAMSM_CHECK_ARG(workspace_bytes >= full_ws.total && (reinterpret_cast<uintptr_t>(workspace) & 255u) == 0,
+    if (int rc = stage1_check("msa_invcov", tokens && out && workspace, N, L, ld, gap)) return rc;
+    RNAMSM_CHECK_ARG(workspace_bytes >= invcov_ws(N, L, IC_MAX_K).total && (reinterpret_cast<uintptr_t>(workspace) & 255u) == 0,
                      "msa_invcov: workspace too small or misaligned (256 bytes)");
     RNAMSM_CHECK_ARG((reinterpret_cast<uintptr_t>(out) & 7u) == 0 && (reinterpret_cast<uintptr_t>(counts) & 3u) == 0,
                      "msa_invcov: out / counts misaligned");
     hipStream_t s = static_cast<hipStream_t>(stream);
-    char* ws = static_cast<char*>(workspace);
-    uint32_t* present = reinterpret_cast<uint32_t*>(ws + full_ws.present);
-    uint8_t* lut = reinterpret_cast<uint8_t*>(ws + full_ws.lut);
-    int32_t* meta = reinterpret_cast<int32_t*>(ws + full_ws.meta);
-    int32_t* marg = reinterpret_cast<int32_t*>(ws + full_ws.marg);
-
-    // ---- the symbols that occur: the one place where the host waits for the stream (K decides the layout and two refusals)
-    if (hipMemsetAsync(present, 0, 256 * 4, s) != hipSuccess) return fail(RNAMSM_ERR_HIP, "msa_invcov: hipMemsetAsync failed");
-    hipLaunchKernelGGL(invcov_presence_kernel, dim3(N < 2048 ? N : 2048), dim3(256), 0, s, tokens, N, L, ld, present);
-    hipLaunchKernelGGL(invcov_table_kernel, dim3(1), dim3(256), 0, s, present, gap, lut, meta);
-    RNAMSM_CHECK_LAUNCH("msa_invcov");
-    int32_t host_meta[IC_META];
-    if (hipMemcpyAsync(host_meta, meta, sizeof(host_meta), hipMemcpyDeviceToHost, s) != hipSuccess ||
-        hipStreamSynchronize(s) != hipSuccess)
-        return fail(RNAMSM_ERR_HIP, "msa_invcov: reading the symbol table back failed: %s", hipGetErrorString(hipGetLastError()));
-    const int K = host_meta[0];
-    RNAMSM_CHECK_ARG(K >= 1, "msa_invcov: the alignment holds nothing but the gap value %d (K = 0)", gap);
-    RNAMSM_CHECK_ARG(K <= IC_MAX_K, "msa_invcov: %d distinct non-gap values, more than %d", K, IC_MAX_K);
-
-    const InvcovWs w = invcov_ws(N, L, K);               // (every offset up to the planes is independent of K)
-    uint64_t* P = reinterpret_cast<uint64_t*>(ws + w.planes);
-    const int R = L * K;
-    if (hipMemsetAsync(P, 0, (size_t)w.Wp * (size_t)w.Rp * 8, s) != hipSuccess)
-        return fail(RNAMSM_ERR_HIP, "msa_invcov: hipMemsetAsync failed");
-    hipLaunchKernelGGL(invcov_planes_kernel, dim3((L + IP_COLS - 1) / IP_COLS, w.W), dim3(256), 0, s, tokens, N, L, ld, lut, K, w.Rp, P);
-    hipLaunchKernelGGL(invcov_marginals_kernel, dim3((R + 255) / 256), dim3(256), 0, s, P, w.W, w.Rp, R, marg);
-    int32_t* body = reinterpret_cast<int32_t*>(ws + full_ws.band);
-    int band = L;                                        // columns i per band: all of them, or a multiple of 64 (tile-aligned rows)
+    Stage1 st;
+    if (int rc = stage1_planes("msa_invcov", tokens, N, L, ld, gap, static_cast<char*>(workspace), s, &st)) return rc;
+    const int K = st.K;
+    int32_t* body = st.band;
+    int band = L;
     if (counts) {
-        if (hipMemcpyAsync(counts, meta, IC_META * 4, hipMemcpyDeviceToDevice, s) != hipSuccess)
+        if (hipMemcpyAsync(counts, st.meta, IC_META * 4, hipMemcpyDeviceToDevice, s) != hipSuccess)
             return fail(RNAMSM_ERR_HIP, "msa_invcov: hipMemcpyAsync failed");
         body = counts + IC_META;
     } else {
-        const size_t per_col = (size_t)L * K * K * 4;
-        if (per_col * L > IC_BAND_BYTES) band = (int)(IC_BAND_BYTES / per_col / 64) * 64;      // >= 64: per_col <= 2^22
+        band = stage1_band(L, K);
     }
     const int T = K <= 4 ? 256 : (K <= 8 ? 64 : 32);     // K^2 doubles per thread in LDS: at most 64 KB a block
     for (int i0 = 0; i0 < L; i0 += band) {
         const int i1 = i0 + band < L ? i0 + band : L;
-        const int64_t row0 = (int64_t)i0 * K, rows_end = (int64_t)i1 * K;
         int32_t* cnt = counts ? body + (int64_t)i0 * L * K * K : body;
-        hipLaunchKernelGGL(invcov_count_kernel, dim3((unsigned)(w.Rp / IC_TILE), (unsigned)((rows_end - row0 + IC_TILE - 1) / IC_TILE)),
-                           dim3(256), 0, s, P, w.Wp, w.Rp, R, K, L, row0, rows_end, i0, counts ? 1 : 0, cnt);
-        hipLaunchKernelGGL(invcov_norm_kernel, dim3((L + T - 1) / T, i1 - i0), dim3(T), (size_t)K * K * T * 8, s, cnt, marg, N, L, K,
+        stage1_count(st, L, i0, i1, counts ? 1 : 0, cnt, s);
+        hipLaunchKernelGGL(invcov_norm_kernel, dim3((L + T - 1) / T, i1 - i0), dim3(T), (size_t)K * K * T * 8, s, cnt, st.marg, N, L, K,
                            i0, i1, out);
     }
     RNAMSM_CHECK_LAUNCH("msa_invcov");
     return RNAMSM_OK;
+}
+
+extern "C" size_t rnamsm_msa_mi_workspace_bytes(int N, int L) {
+    if (N < 2 || N > IC_MAX_N || L < 1 || L > RNAMSM_LONG_MAX_L) return 0;
+    return mi_ws(N, L).total;
+}
+
+extern "C" int rnamsm_msa_mi(const uint8_t* tokens, int N, int L, int64_t ld, int gap, int gap_mode, double* mi, double* mip,
+                             void* workspace, size_t workspace_bytes, void* stream) {
+    if (int rc = stage1_check("msa_mi", tokens && workspace, N, L, ld, gap)) return rc;
+    RNAMSM_CHECK_ARG(gap_mode == RNAMSM_MI_GAPS_PAIRWISE || gap_mode == RNAMSM_MI_GAPS_STATE,
+                     "msa_mi: gap_mode=%d is not 0 (pairwise) or 1 (state)", gap_mode);
+    RNAMSM_CHECK_ARG(mi || mip, "msa_mi: mi and mip are both NULL: nothing to compute");
+    const MiWs mw = mi_ws(N, L);
+    RNAMSM_CHECK_ARG(workspace_bytes >= mw.total, "msa_mi: workspace of %zu bytes is smaller than the %zu that N=%d, L=%d need",
+                     workspace_bytes, mw.total, N, L);
+    RNAMSM_CHECK_ARG((reinterpret_cast<uintptr_t>(workspace) & 255u) == 0, "msa_mi: workspace misaligned (256 bytes)");
+    RNAMSM_CHECK_ARG((reinterpret_cast<uintptr_t>(mi) & 7u) == 0 && (reinterpret_cast<uintptr_t>(mip) & 7u) == 0 && (!mi || mi != mip),
+                     "msa_mi: mi / mip misaligned, or one buffer for both");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    char* ws = static_cast<char*>(workspace);
+    Stage1 st;
+    if (int rc = stage1_planes("msa_mi", tokens, N, L, ld, gap, ws, s, &st)) return rc;
+    double* map = mi ? mi : reinterpret_cast<double*>(ws + mw.map);
+    const int band = stage1_band(L, st.K);
+    for (int i0 = 0; i0 < L; i0 += band) {
+        const int i1 = i0 + band < L ? i0 + band : L;
+        stage1_count(st, L, i0, i1, 0, st.band, s);
+        const dim3 grid((L + 255) / 256, i1 - i0);
+        if (gap_mode == RNAMSM_MI_GAPS_STATE)
+            hipLaunchKernelGGL(mi_pair_kernel<1>, grid, dim3(256), 0, s, st.band, st.marg, N, L, st.K, i0, i1, map);
+        else
+            hipLaunchKernelGGL(mi_pair_kernel<0>, grid, dim3(256), 0, s, st.band, st.marg, N, L, st.K, i0, i1, map);
+    }
+    RNAMSM_CHECK_LAUNCH("msa_mi");
+    if (!mip) return RNAMSM_OK;
+    return rnamsm_apc_f64(map, L, L, 1, mip, ws + mw.apc, mw.total - mw.apc, stream);      // mip = apc(mi with a zero diagonal)
 }

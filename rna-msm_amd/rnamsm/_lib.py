@@ -58,6 +58,9 @@ LONG_MAX_L = 4096                  # rnamsm_contact_head_long / _ss_head_long / 
                                    # _rsa_text_long: a stitched alignment
 # rnamsm_msa_invcov: rows, symbols, and the int32 header in front of the optional counts (K, then the symbols)
 INVCOV_MAX_N, INVCOV_MAX_K, INVCOV_META = 1 << 20, 16, 32
+# rnamsm_msa_mi: gap_mode by the name data.mi_gaps and ops.msa_mi take; rnamsm_apc_f64: the widest map
+MI_GAP_MODES = {"pairwise": 0, "state": 1}
+APC_MAX_L = 32768
 # rnamsm_msa_pdist / _neff / _coverage: columns, rows of the matrix form, rows of the other two
 PDIST_MAX_L, PDIST_MAX_N_MATRIX, PDIST_MAX_N = 32768, 16384, 1 << 20
 
@@ -216,6 +219,10 @@ _SIGNATURES = {
     "rnamsm_msa_weights": (c_int, [c_void_p, c_int, c_int, c_double, c_void_p, c_void_p]),
     "rnamsm_msa_invcov_workspace_bytes": (c_size_t, [c_int, c_int]),
     "rnamsm_msa_invcov": (c_int, [c_void_p, c_int, c_int, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "rnamsm_msa_mi_workspace_bytes": (c_size_t, [c_int, c_int]),
+    "rnamsm_msa_mi": (c_int, [c_void_p, c_int, c_int, c_int64, c_int, c_int, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "rnamsm_apc_f64_workspace_bytes": (c_size_t, [c_int]),
+    "rnamsm_apc_f64": (c_int, [c_void_p, c_int, c_int64, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
     "rnamsm_msa_pdist_workspace_bytes": (c_size_t, [c_int, c_int]),
     "rnamsm_msa_pdist": (c_int, [c_void_p, c_int, c_int, c_int64, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "rnamsm_msa_neff_workspace_bytes": (c_size_t, [c_int, c_int]),

@@ -54,6 +54,21 @@ def check_msa_stats(value) -> bool:
     return value
 
 
+MI_GAPS_MODES = ("pairwise", "state")
+
+
+def check_mi(value) -> bool:
+    if not isinstance(value, bool):
+        raise ValueError(f"data.mi={value!r} is not one of false, true")
+    return value
+
+
+def check_mi_gaps(value: str) -> str:
+    if value not in MI_GAPS_MODES:
+        raise ValueError(f"data.mi_gaps={value!r} is not one of {', '.join(repr(m) for m in MI_GAPS_MODES)}")
+    return value
+
+
 @dataclass
 class DataConfig:                       # RNA_MSM_Inference.py:20-32
     device: str = "cuda"
@@ -141,6 +156,14 @@ class DataConfig:                       # RNA_MSM_Inference.py:20-32
     # Neff / L.  An alignment the kernels refuse (more than 32768 columns, more than 2^20 rows) gets one printed line and its other
     # files.
     msa_stats: bool = False
+    # extra (not in the reference's CLI): the mutual-information contacts of the alignment AS READ -- every row, before row
+    # sub-sampling, and every column, like data.invcov -- computed on the device (rnamsm.msa.msa_mi) and written as <id>_mi.npy, the
+    # mutual information of every pair of columns, and <id>_mip.npy, its average-product correction (the reference's apc,
+    # utils/tensor.py:103-113, of the map with a zero diagonal), (L, L) float64 each, next to <id>_emb.npy.  mi_gaps: "pairwise" = rows
+    # with a gap in either column are left out of that pair; "state" = the gap is one more state.  An alignment the kernel refuses (as
+    # for data.invcov) gets one printed line and its other files.
+    mi: bool = False
+    mi_gaps: str = "pairwise"
 
 
 @dataclass
@@ -216,4 +239,6 @@ def parse_overrides(argv: List[str], cfg: Config = None) -> Config:
     check_long_heads(cfg.data.long_heads)
     check_invcov(cfg.data.invcov)
     check_msa_stats(cfg.data.msa_stats)
+    check_mi(cfg.data.mi)
+    check_mi_gaps(cfg.data.mi_gaps)
     return cfg

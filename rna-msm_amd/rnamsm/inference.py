@@ -22,9 +22,9 @@ import torch
 
 from . import _lib, contacts, lm, ops, rsa, sharding, ss
 from .alphabet import RNAAlphabet
-from .config import Config, check_invcov, check_long_heads, check_long_msa, check_msa_stats, check_ss_gemm_dtype
+from .config import Config, check_invcov, check_long_heads, check_long_msa, check_mi, check_mi_gaps, check_msa_stats, check_ss_gemm_dtype
 from .model import MSATransformer
-from .msa import load_msa_tokens, msa_invcov_device, msa_stats_device
+from .msa import load_msa_tokens, msa_invcov_device, msa_mi_device, msa_stats_device
 
 
 def load_checkpoint(model: MSATransformer, path: str, device) -> None:
@@ -313,6 +313,8 @@ class _Switches(NamedTuple):
     long_heads: bool            # data.long_heads=stitched
     invcov_on: bool             # data.invcov
     msa_stats_on: bool          # data.msa_stats
+    mi_on: bool                 # data.mi
+    mi_gaps: str                # data.mi_gaps
     seqid_cutoff: float         # data.seqid_cutoff where the configuration has one, else the reference's default
     gathering: bool             # gather_to_rank0 with more than one rank
     ss_path: str                # data.ss_model_path
@@ -346,6 +348,10 @@ def read_switches(cfg: Config, gathering: bool) -> _Switches:
     # above and written as <id>_weights.npy / <id>_coverage.npy by two more writer jobs; off, nothing below differs
     msa_stats_on = check_msa_stats(getattr(cfg.data, "msa_stats", False))
     seqid_cutoff = float(getattr(cfg.data, "seqid_cutoff", 0.2))
+    # data.mi: the mutual-information maps of every alignment as read, made on the reader's side like the two above and written as
+    # <id>_mi.npy / <id>_mip.npy by two more writer jobs; off, nothing below differs
+    mi_on = check_mi(getattr(cfg.data, "mi", False))
+    mi_gaps = check_mi_gaps(getattr(cfg.data, "mi_gaps", "pairwise"))
     # data.batch_small_msas: small alignments go through ONE launch set per group (forward_ragged: padded into one
     # frame, every MSA scaled by its own depth); a lone forward of a few hundred tokens costs 5.5 ms on a mostly
     # idle chip.  Groups: by shape from the pool (plan_groups); under gather_to_rank0 the RoundGatherer needs this
@@ -362,7 +368,7 @@ def read_switches(cfg: Config, gathering: bool) -> _Switches:
     small_limit = (PACKED_SMALL_TOKENS if exact else PACKED_SMALL_TOKENS_16BIT.get(cfg.model.gemm_dtype, 1024)) if packing else SMALL_MSA_TOKENS
     return _Switches(
         gemm_dtype=cfg.model.gemm_dtype, ss_dtype=ss_dtype, windowing=windowing, window_stride=window_stride, long_heads=long_heads,
-        invcov_on=invcov_on, msa_stats_on=msa_stats_on, seqid_cutoff=seqid_cutoff, gathering=gathering, ss_path=getattr(cfg.data, "ss_model_path", ""),
+        invcov_on=invcov_on, msa_stats_on=msa_stats_on, mi_on=mi_on, mi_gaps=mi_gaps, seqid_cutoff=seqid_cutoff, gathering=gathering, ss_path=getattr(cfg.data, "ss_model_path", ""),
         rsa_dir=getattr(cfg.data, "rsa_model_dir", ""), ss_text=bool(getattr(cfg.data, "ss_prob_text", True)) and not gathering,
         ss_pairs=bool(getattr(cfg.data, "ss_pairs_device", True)) and not gathering,
         rsa_text=bool(getattr(cfg.data, "rsa_text_device", True)) and not gathering, contacts=bool(getattr(cfg.data, "contacts", False)),
@@ -439,9 +445,9 @@ class _Reader:
     (dataset.py:147) -- seeded 42 like the reference's global numpy state (RNA_MSM_Inference.py:17), so a single
     process reproduces the reference's choices; under sharding every rank draws for its own items."""
 
-    def __init__(self, cfg: Config, sw: _Switches, ids: List[str], files: Dict[str, Path], alphabet, device, put_map, put_stats=None):
+    def __init__(self, cfg: Config, sw: _Switches, ids: List[str], files: Dict[str, Path], alphabet, device, put_map, put_stats=None, put_mi=None):
         self.cfg, self.sw, self.ids, self.files, self.alphabet, self.device, self.put_map = cfg, sw, ids, files, alphabet, device, put_map
-        self.put_stats = put_stats
+        self.put_stats, self.put_mi = put_stats, put_mi
         self.rng = np.random.RandomState(42)
 
     def __call__(self, idx: int) -> np.ndarray:
@@ -449,7 +455,7 @@ class _Reader:
         rna_id = self.ids[idx]
         tokens = load_msa_tokens(self.files[rna_id], self.alphabet, self.cfg.data.max_seqs_per_msa, self.cfg.data.sample_method,
                                  device=self.device, rng=self.rng,
-                                 on_full=(lambda full: self.on_full(rna_id, full)) if self.sw.invcov_on or self.sw.msa_stats_on else None)
+                                 on_full=(lambda full: self.on_full(rna_id, full)) if self.sw.invcov_on or self.sw.msa_stats_on or self.sw.mi_on else None)
         return tokens if self.sw.windowing else crop_tokens(tokens, self.cfg.data.max_seqlen, self.rng)
 
     def on_full(self, rna_id: str, full: np.ndarray) -> None:
@@ -457,6 +463,8 @@ class _Reader:
             self.covariance_map(rna_id, full)
         if self.sw.msa_stats_on:
             self.alignment_stats(rna_id, full)
+        if self.sw.mi_on:
+            self.mutual_information(rna_id, full)
 
     def alignment_stats(self, rna_id: str, full: np.ndarray) -> None:
         """data.msa_stats: the weights and the coverage of the alignment as read, left on the device for the sink, and the line with
@@ -470,6 +478,17 @@ class _Reader:
             return
         self.put_stats(rna_id, (rec.weights, coverage))
         print(f"{rna_id}: {N} rows x {L} columns, Neff {neff:.3f} (Neff/sqrt(L) {neff / math.sqrt(L):.3f}, Neff/L {neff / L:.4f})")
+
+    def mutual_information(self, rna_id: str, full: np.ndarray) -> None:
+        """data.mi: the two maps of the alignment as read (before row sub-sampling and any crop), left on the device for the sink; an
+        alignment the kernel refuses gets one line that names the reason, and its other files as usual."""
+        try:
+            rec = msa_mi_device(full, self.alphabet.tok_to_idx["-"], self.device, self.sw.mi_gaps)
+            self.put_mi(rna_id, (rec.mi, rec.mip))
+            torch.cuda.current_stream().synchronize()       # (the reader's stream: the maps are complete whichever stream copies them)
+        except _lib.RnamsmError as e:
+            print(f"{rna_id}: no mutual-information maps (data.mi) for this alignment of {full.shape[0]} rows x {full.shape[1] - 1} "
+                  f"columns: {e}")
 
     def covariance_map(self, rna_id: str, full: np.ndarray) -> None:
         """data.invcov: the map of the alignment as read (before row sub-sampling and any crop), left on the device for the sink; an
@@ -507,12 +526,13 @@ class _Sink:
         self.written: List[str] = []
         self.invcov_maps: Dict[str, torch.Tensor] = {}      # id -> the map on the device, from the reader until the alignment is delivered
         self.msa_stats: Dict[str, tuple] = {}               # id -> (weights, coverage) on the device, likewise (data.msa_stats)
+        self.mi_maps: Dict[str, tuple] = {}                 # id -> (mi, mip) on the device, likewise (data.mi)
         self.writer = _AsyncNpyWriter(device) if async_io and (not sw.gathering or rank == 0) else None
         # gather_to_rank0: outputs travel to rank 0 one ROUND (one MSA per rank) at a time, round k's RCCL transfers
         # overlapping round k+1's forward, and are handed to the writer as they arrive -- at most one round is resident
         # (an item: emb, atp, every head's flattened record, the covariance map)
         self.gatherer = sharding.RoundGatherer(len(ids), on_item=self.on_item,
-                                               tensors_per_item=2 + sum(h.n_tensors for h in heads) + int(sw.invcov_on) + 2 * int(sw.msa_stats_on),
+                                               tensors_per_item=2 + sum(h.n_tensors for h in heads) + int(sw.invcov_on) + 2 * int(sw.msa_stats_on) + 2 * int(sw.mi_on),
                                                dst=0, device=device, group=_gather_group(device, rank)) if sw.gathering else None
 
     def put_map(self, rna_id: str, cov: torch.Tensor) -> None:
@@ -520,6 +540,9 @@ class _Sink:
 
     def put_stats(self, rna_id: str, vectors: tuple) -> None:
         self.msa_stats[rna_id] = vectors
+
+    def put_mi(self, rna_id: str, maps: tuple) -> None:
+        self.mi_maps[rna_id] = maps
 
     def deliver(self, idx: int, emb: torch.Tensor, atp: torch.Tensor, after: Optional[torch.cuda.Event], records: list) -> None:
         """records: the alignment's record of every head, None for a head skipped on it."""
@@ -534,12 +557,17 @@ class _Sink:
             item += (cov if cov is not None else emb.new_zeros(1),)
         if self.sw.msa_stats_on:        # (the two vectors travel as the item's last tensors, float64; a refused alignment sends fp32 placeholders)
             item += tuple(self.msa_stats.pop(self.ids[idx], None) or (emb.new_zeros(1, dtype=torch.float32),) * 2)
+        if self.sw.mi_on:               # (the two maps travel as the item's last tensors; a refused alignment sends placeholders)
+            item += tuple(self.mi_maps.pop(self.ids[idx], None) or (emb.new_zeros(1),) * 2)
         self.gatherer.submit(idx, item)
 
     def on_item(self, i: int, ts) -> None:
+        n_mi = 2 * int(self.sw.mi_on)
+        mi, ts = (tuple(ts[len(ts) - n_mi:]), ts[:len(ts) - n_mi]) if n_mi else (None, ts)
         n_stats = 2 * int(self.sw.msa_stats_on)
         self.emit(self.ids[i], ts[0], ts[1], records=self.records_of(ts[2:], ts[0].shape[0]),
-                  cov=ts[len(ts) - n_stats - 1] if self.sw.invcov_on else None, stats=tuple(ts[len(ts) - n_stats:]) if n_stats else None)
+                  cov=ts[len(ts) - n_stats - 1] if self.sw.invcov_on else None, stats=tuple(ts[len(ts) - n_stats:]) if n_stats else None,
+                  mi=mi)
 
     def records_of(self, flat, L: int) -> list:
         """A gathered item's tensors behind emb and atp -> the heads' records (the inverse of deliver()'s flattening)."""
@@ -548,7 +576,7 @@ class _Sink:
         return [None if isinstance(_route(h, L, self.sw, self.max_seqlen), str) else h.unflatten(ts) for h, ts in shares]
 
     def emit(self, rna_id: str, emb: torch.Tensor, atp: torch.Tensor, after: Optional[torch.cuda.Event] = None, records=(),
-             cov: Optional[torch.Tensor] = None, stats: Optional[tuple] = None) -> None:
+             cov: Optional[torch.Tensor] = None, stats: Optional[tuple] = None, mi: Optional[tuple] = None) -> None:
         """records: this alignment's record of every head that is on, in the order of `heads`; each becomes one writer job (but
         for the heads skipped on a stitched alignment: their entry is None).  cov: a gathered item's covariance map (or
         its one-element placeholder); absent, the one the reader left for this id, if any."""
@@ -559,6 +587,10 @@ class _Sink:
         stats = self.msa_stats.pop(rna_id, None) if stats is None else (stats if stats[0].dtype == torch.float64 else None)
         if stats is not None:
             cov_job += [(self.save_dir / f"{rna_id}_weights.npy", stats[0]), (self.save_dir / f"{rna_id}_coverage.npy", stats[1])]
+        # mi: a gathered item's (mi, mip) or its placeholders; absent, what the reader left for this id, if anything
+        mi = self.mi_maps.pop(rna_id, None) if mi is None else (mi if mi[0].dim() == 2 else None)
+        if mi is not None:
+            cov_job += [(self.save_dir / f"{rna_id}_mi.npy", mi[0]), (self.save_dir / f"{rna_id}_mip.npy", mi[1])]
         if self.writer is not None:
             self.writer.submit([(self.save_dir / f"{rna_id}_atp.npy", atp), (self.save_dir / f"{rna_id}_emb.npy", emb)] + extra + cov_job,
                                lambda r=rna_id: self.written.append(r), after=after)
@@ -833,7 +865,7 @@ def extract_feat(cfg: Config, model: Optional[MSATransformer] = None, gather_to_
     sink = _Sink(ids, heads, save_dir, sw, model.max_seqlen, device, rank, async_io)
     reader = ThreadPoolExecutor(1, thread_name_prefix="rnamsm-msa-reader") if async_io else None
     scheduler = _Scheduler(model, heads, sink, sw, ids, sharding.shard_indices(len(ids), rank, world),
-                           _Reader(cfg, sw, ids, files, alphabet, device, sink.put_map, sink.put_stats), reader, alphabet.padding_idx,
+                           _Reader(cfg, sw, ids, files, alphabet, device, sink.put_map, sink.put_stats, sink.put_mi), reader, alphabet.padding_idx,
                            to_device=lambda tokens: torch.from_numpy(tokens).to(device), record_event=_record_event)
     try:
         with torch.no_grad():

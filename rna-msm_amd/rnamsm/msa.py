@@ -138,6 +138,23 @@ def _stats_body_device(tokens: np.ndarray, device, name: str):
     return torch.from_numpy(np.ascontiguousarray(body.astype(np.uint8))).to(dev)
 
 
+def msa_mi_device(tokens: np.ndarray, gap_idx: int, device, gaps: str = "pairwise"):
+    """msa_mi with the two maps left on the device (an ops.MsaMi of float64 [L, L] tensors): what the CLI's writer copies from."""
+    from . import ops
+    return ops.msa_mi(_stats_body_device(tokens, device, "msa_mi"), int(gap_idx), gaps)
+
+
+def msa_mi(tokens: np.ndarray, gap_idx: int, device, gaps: str = "pairwise"):
+    """Mutual-information contacts of an alignment: (mi, mip), float64 [L, L] each.  mi[i, j] is the mutual information (natural log) of
+    columns i and j over the K distinct non-gap tokens that occur, its diagonal the columns' entropies; mip is its average-product
+    correction, apc(mi with a zero diagonal) (utils/tensor.py:103-113).  gaps="pairwise": rows with a gap in either column are left
+    out of that pair; "state": the gap is a (K+1)-th state.  The columns are the alignment's (no <cls>, as in msa_invcov); a
+    one-to-one recoding of the tokens permutes every pair's table and changes the sum's order only.  On the HIP device only
+    (rnamsm_msa_mi): there is no CPU path.  N in [2, 2^20], L <= 4096, K in [1, 16]."""
+    rec = msa_mi_device(tokens, gap_idx, device, gaps)
+    return rec.mi.cpu().numpy(), rec.mip.cpu().numpy()
+
+
 def msa_pdist(tokens: np.ndarray, device) -> np.ndarray:
     """MSA.pdist (utils/align.py:121-126): the normalised Hamming distance of every pair of rows, float64 [N, N] (scipy's
     squareform(pdist(.., "hamming")): mismatches / L), over the alignment's columns (no <cls>).  Token ids stand for the reference's

@@ -1301,6 +1301,54 @@ def _aligned_workspace(nbytes: int, device) -> torch.Tensor:
     return torch.empty(max(int(nbytes), 256), dtype=torch.uint8, device=device)
 
 
+class MsaMi(NamedTuple):
+    """What rnamsm_msa_mi writes, on the device; a map that was not asked for is None."""
+    mi: Optional[torch.Tensor]     # float64 [L, L]: the mutual information of every pair of columns
+    mip: Optional[torch.Tensor]    # float64 [L, L]: apc of mi with a zero diagonal
+
+
+@_on_operand_device
+def msa_mi(tokens_u8: torch.Tensor, gap: int, gaps: str = "pairwise", want=("mi", "mip")) -> MsaMi:
+    """Mutual-information contacts (rnamsm_msa_mi): tokens uint8 [N, L] on the device (a view with contiguous rows is read where it
+    lies) -> MsaMi.  gaps="pairwise": rows with a gap in either column are left out of that pair; "state": the gap is one more state.
+    want: which of "mi", "mip" to make.  mi is exactly symmetric, its diagonal the columns' entropies; mip = apc(mi with a zero
+    diagonal), NaN everywhere where that map's total is 0.  N in [2, 2^20], L in [1, 4096], at most 16 distinct values other than
+    `gap`; the library refuses anything else.  The call waits for the device once (K is read back)."""
+    if gaps not in _lib.MI_GAP_MODES:
+        raise ValueError(f"msa_mi: gaps={gaps!r} is not one of {', '.join(map(repr, _lib.MI_GAP_MODES))}")
+    want = (want,) if isinstance(want, str) else tuple(want)
+    if not want or any(w not in ("mi", "mip") for w in want):
+        raise ValueError(f"msa_mi: want={want!r} is not a non-empty choice of 'mi', 'mip'")
+    tokens_u8, N, L, ld = _msa_rows(tokens_u8, "msa_mi")
+    lib = _lib.load()
+    dev = tokens_u8.device
+    ws = _aligned_workspace(lib.rnamsm_msa_mi_workspace_bytes(N, L), dev)
+    rec = MsaMi(*(torch.empty((L, L), dtype=torch.float64, device=dev) if w in want else None for w in ("mi", "mip")))
+    _lib.check(lib.rnamsm_msa_mi(tokens_u8.data_ptr(), N, L, ld, int(gap), _lib.MI_GAP_MODES[gaps],
+                                 rec.mi.data_ptr() if rec.mi is not None else None, rec.mip.data_ptr() if rec.mip is not None else None,
+                                 ws.data_ptr(), ws.numel(), _stream()))
+    return rec
+
+
+@_on_operand_device
+def apc(x: torch.Tensor, zero_diagonal: bool = False) -> torch.Tensor:
+    """Average-product correction (the reference's apc, utils/tensor.py:103-113; rnamsm_apc_f64): x float64 [L, L] on the device,
+    symmetric or not (a view with contiguous rows is read where it lies) -> x - row sums * column sums / total, float64 [L, L].
+    zero_diagonal: the diagonal of x is read as 0.  A total of 0 gives NaN everywhere.  L in [1, 32768]."""
+    _dev(x, "x", torch.float64)
+    if x.dim() != 2 or x.shape[0] != x.shape[1]:
+        raise ValueError(f"apc: expected a square float64 map, got {tuple(x.shape)}")
+    L = x.shape[0]
+    if (L > 1 and x.stride(1) != 1) or x.stride(0) < L:
+        x = x.contiguous()
+    lib = _lib.load()
+    ws = _aligned_workspace(lib.rnamsm_apc_f64_workspace_bytes(L), x.device)
+    out = torch.empty((L, L), dtype=torch.float64, device=x.device)
+    _lib.check(lib.rnamsm_apc_f64(x.data_ptr(), L, x.stride(0) if L > 1 else L, int(bool(zero_diagonal)), out.data_ptr(), ws.data_ptr(),
+                                  ws.numel(), _stream()))
+    return out
+
+
 @_on_operand_device
 def msa_pdist(msa_u8: torch.Tensor, want: str = "dist"):
     """MSA.pdist (utils/align.py:121-126; rnamsm_msa_pdist): msa uint8 [N, L] on the device -> want="dist": float64 [N, N] =
