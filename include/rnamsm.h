@@ -873,6 +873,33 @@ size_t rnamsm_msa_mi_workspace_bytes(int N, int L);
 int rnamsm_msa_mi(const uint8_t* tokens, int N, int L, int64_t ld, int gap, int gap_mode, double* mi, double* mip, void* workspace,
                   size_t workspace_bytes, void* stream);
 
+/* Sequence-weighted mutual information (rnamsm_msa_mi with row n counted weights[n] times): the pair's table is
+ *   c[a][b] = sum over rows n of weights[n] * [x(n, i) = a] * [x(n, j) = b]                                  float64,
+ * over S states: the K symbols in RNAMSM_MI_GAPS_PAIRWISE (S = K; a row with a gap in column i or j is in no entry), the K symbols
+ * and the gap as state K, counted like any other, in RNAMSM_MI_GAPS_STATE (S = K + 1 <= 17).  tokens, ld, gap, the K symbols, the
+ * refusals and the limits (N in [2, 2^20], L in [1, RNAMSM_LONG_MAX_L], K in [1, 16]) are rnamsm_msa_invcov's.  weights: float64
+ * [N] on the device, every one finite and > 0 (rnamsm_msa_neff's at a cutoff above 0); they are checked on the device and the
+ * verdict is read back with K: a weight that is NaN, +-inf, zero or negative is refused with RNAMSM_ERR_INVALID, the message names
+ * the first such row, and no output is touched.  The counts are a contraction of one-hot operands on the fp64 matrix pipe: every
+ * product is exact, one thread block adds all N rows of its results in groups of four ascending rows from 0.0 (within a group in
+ * the instruction's order), without atomics: the same bits on every run, and c(i,a; j,b) == c(j,b; i,a) bit for bit.  Then
+ *   s_b = sum_a c[a][b], r_a = sum_b c[a][b], n = sum_b s_b, each ascending from 0.0,
+ *   mi(i, j) = sum over a then b ascending, the entries with c > 0 only, of (c / n) * log((c * n) / (r_a * s_b)); n = 0 gives 0,
+ * one operation at a time: with every weight 1.0 the two maps are rnamsm_msa_mi's bit for bit.  mip = rnamsm_apc_f64 of mi with a
+ * zero diagonal.  mi, mip: float64 [L, L]; either may be NULL, and both where wcounts is given.  wcounts (optional): float64
+ * [L, L, S, S], every table.  wmarg (optional): float64 [L, S], c(i,a; i,a), the weighted column profile.  meta (optional): int32
+ * [32], K and the symbols ascending, as rnamsm_msa_invcov's counts header.  workspace, 256-byte aligned: any size from
+ * rnamsm_msa_wmi_min_workspace_bytes(N, L) upward, rnamsm_msa_wmi_workspace_bytes(N, L) by default (both 0 outside the limits):
+ * stage 1's planes, the state planes, an [L, L] map, the correction's sums and a band of counts, L * S * S * 8 bytes per column i
+ * (at most 256 MB by default, one column at S = 17 at least).  Without wcounts the columns are counted band by band; the band
+ * count follows from workspace_bytes alone and every accepted size gives the same bits.  Every refusal of an argument comes
+ * before the first launch and names the value.  Like its two siblings the call WAITS for the stream once (K and the weights'
+ * verdict are read back); it must not be captured into a graph. */
+size_t rnamsm_msa_wmi_workspace_bytes(int N, int L);
+size_t rnamsm_msa_wmi_min_workspace_bytes(int N, int L);
+int rnamsm_msa_wmi(const uint8_t* tokens, int N, int L, int64_t ld, int gap, int gap_mode, const double* weights, double* mi,
+                   double* mip, double* wcounts, double* wmarg, int32_t* meta, void* workspace, size_t workspace_bytes, void* stream);
+
 /* Average-product correction of a square float64 map (the reference's apc, utils/tensor.py:103-113), symmetric or not:
  *   a1 = row sums, a2 = column sums, a12 = the total,  out[i, j] = x[i, j] - (a1[i] * a2[j]) / a12     (product, division, subtraction).
  * x [L, L] with leading dimension ld >= L, out [L, L] packed.  zero_diagonal = 1: the diagonal of x is read as 0, in the sums and in

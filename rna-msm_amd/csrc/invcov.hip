@@ -23,16 +23,9 @@
 //
 // Mutual information (rnamsm_msa_mi) runs the same stage 1 and replaces the norm by mi_pair_kernel, a per-pair fp64 sum over the
 // integer table; its corrected map is apc.hip's rnamsm_apc_f64 of the map with a zero diagonal.
-#include "common.h"
+#include "invcov_stage1.h"
 
 namespace rnamsm {
-
-constexpr int IC_TILE = 64;        // (column, symbol) rows of a count tile, each way
-constexpr int IC_WK = 16;          // words staged per step
-constexpr int IC_MAX_K = 16;
-constexpr int IC_META = 32;        // int32 header: K, then the symbols ascending (the first 16 of them)
-constexpr int IC_MAX_N = 1 << 20;
-constexpr size_t IC_BAND_BYTES = (size_t)1 << 28;      // counts of one band of columns i
 
 // ---- which byte values occur ------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void invcov_presence_kernel(const uint8_t* __restrict__ tok, int N, int L, int64_t ld,
@@ -223,14 +216,8 @@ __global__ __launch_bounds__(256) void invcov_norm_kernel(const int32_t* __restr
     out[(int64_t)j * L + i] = v;
 }
 
-struct InvcovWs {
-    size_t present, lut, meta, marg, planes, band, total;
-    int W, Wp;
-    int64_t Rp;
-};
-// K: the symbols the layout is made for (the size function knows no K and takes IC_MAX_K; the call lays the planes out for the K
-// it found, inside the same bytes)
-static InvcovWs invcov_ws(int N, int L, int K) {
+// (InvcovWs, Stage1 and the constants: invcov_stage1.h)
+InvcovWs invcov_ws(int N, int L, int K) {
     InvcovWs w;
     w.W = (N + 63) / 64;
     w.Wp = (w.W + IC_WK - 1) / IC_WK * IC_WK;
@@ -249,9 +236,9 @@ static InvcovWs invcov_ws(int N, int L, int K) {
     return w;
 }
 
-// ---- stage 1 as both entry points (rnamsm_msa_invcov, rnamsm_msa_mi) run it ---------------------------------------------------------
+// ---- stage 1 as its entry points (rnamsm_msa_invcov, rnamsm_msa_mi, msa_wmi.hip's rnamsm_msa_wmi) run it ----------------------------
 // `who` is the entry point's name in every message.
-static int stage1_check(const char* who, bool pointers, int N, int L, int64_t ld, int gap) {
+int stage1_check(const char* who, bool pointers, int N, int L, int64_t ld, int gap) {
     RNAMSM_CHECK_ARG(pointers, "%s: null pointer", who);
     RNAMSM_CHECK_ARG(N >= 2 && N <= IC_MAX_N, "%s: N=%d outside [2, %d]", who, N, IC_MAX_N);
     RNAMSM_CHECK_ARG(L >= 1 && L <= RNAMSM_LONG_MAX_L, "%s: L=%d outside [1, %d]", who, L, RNAMSM_LONG_MAX_L);
@@ -260,15 +247,9 @@ static int stage1_check(const char* who, bool pointers, int N, int L, int64_t ld
     return RNAMSM_OK;
 }
 
-struct Stage1 {
-    InvcovWs w;                  // the layout for the K that was found
-    int K, R;
-    int32_t *meta, *marg, *band; // the header (K, the symbols), n_a(i) as [L, K], the workspace's band of counts
-    uint64_t* P;
-};
-
-// presence, table (the one wait for the stream: K is read back), planes, marginals
-static int stage1_planes(const char* who, const uint8_t* tokens, int N, int L, int64_t ld, int gap, char* ws, hipStream_t s, Stage1* st) {
+// presence, table (the one wait for the stream: K is read back, and a caller's verdict with it), planes, marginals
+int stage1_planes(const char* who, const uint8_t* tokens, int N, int L, int64_t ld, int gap, char* ws, hipStream_t s, Stage1* st,
+                  Stage1Verdict* verdict) {
     const InvcovWs full_ws = invcov_ws(N, L, IC_MAX_K);
     uint32_t* present = reinterpret_cast<uint32_t*>(ws + full_ws.present);
     uint8_t* lut = reinterpret_cast<uint8_t*>(ws + full_ws.lut);
@@ -283,6 +264,7 @@ static int stage1_planes(const char* who, const uint8_t* tokens, int N, int L, i
     RNAMSM_CHECK_LAUNCH(who);
     int32_t host_meta[IC_META];
     if (hipMemcpyAsync(host_meta, st->meta, sizeof(host_meta), hipMemcpyDeviceToHost, s) != hipSuccess ||
+        (verdict && hipMemcpyAsync(&verdict->host, verdict->dev, 4, hipMemcpyDeviceToHost, s) != hipSuccess) ||
         hipStreamSynchronize(s) != hipSuccess)
         return fail(RNAMSM_ERR_HIP, "%s: reading the symbol table back failed: %s", who, hipGetErrorString(hipGetLastError()));
     const int K = host_meta[0];
@@ -302,13 +284,13 @@ static int stage1_planes(const char* who, const uint8_t* tokens, int N, int L, i
 }
 
 // columns i per band of counts held in the workspace: all of them, or a multiple of 64 (tile-aligned rows)
-static int stage1_band(int L, int K) {
+int stage1_band(int L, int K) {
     const size_t per_col = (size_t)L * K * K * 4;
     return per_col * L > IC_BAND_BYTES ? (int)(IC_BAND_BYTES / per_col / 64) * 64 : L;      // >= 64: per_col <= 2^22
 }
 
 // the counts of columns [i0, i1) into cnt as [i - i0][j][a][b]; full = 0: tiles wholly below the diagonal are left out
-static void stage1_count(const Stage1& st, int L, int i0, int i1, int full, int32_t* cnt, hipStream_t s) {
+void stage1_count(const Stage1& st, int L, int i0, int i1, int full, int32_t* cnt, hipStream_t s) {
     const int64_t row0 = (int64_t)i0 * st.K, rows_end = (int64_t)i1 * st.K;
     hipLaunchKernelGGL(invcov_count_kernel, dim3((unsigned)(st.w.Rp / IC_TILE), (unsigned)((rows_end - row0 + IC_TILE - 1) / IC_TILE)),
                        dim3(256), 0, s, st.P, st.w.Wp, st.w.Rp, st.R, st.K, L, row0, rows_end, i0, full, cnt);

@@ -221,6 +221,10 @@ _SIGNATURES = {
     "rnamsm_msa_invcov": (c_int, [c_void_p, c_int, c_int, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "rnamsm_msa_mi_workspace_bytes": (c_size_t, [c_int, c_int]),
     "rnamsm_msa_mi": (c_int, [c_void_p, c_int, c_int, c_int64, c_int, c_int, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "rnamsm_msa_wmi_workspace_bytes": (c_size_t, [c_int, c_int]),
+    "rnamsm_msa_wmi_min_workspace_bytes": (c_size_t, [c_int, c_int]),
+    "rnamsm_msa_wmi": (c_int, [c_void_p, c_int, c_int, c_int64, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                               c_void_p, c_size_t, c_void_p]),
     "rnamsm_apc_f64_workspace_bytes": (c_size_t, [c_int]),
     "rnamsm_apc_f64": (c_int, [c_void_p, c_int, c_int64, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
     "rnamsm_msa_pdist_workspace_bytes": (c_size_t, [c_int, c_int]),

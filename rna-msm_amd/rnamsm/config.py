@@ -69,6 +69,18 @@ def check_mi_gaps(value: str) -> str:
     return value
 
 
+MI_WEIGHTS_MODES = ("none", "seqid")
+
+
+def check_mi_weights(value: str, mi_on: bool = True) -> str:
+    """data.mi_weights; "seqid" reweights data.mi's maps, so it is refused where data.mi is off."""
+    if value not in MI_WEIGHTS_MODES:
+        raise ValueError(f"data.mi_weights={value!r} is not one of {', '.join(repr(m) for m in MI_WEIGHTS_MODES)}")
+    if value != "none" and not mi_on:
+        raise ValueError(f"data.mi_weights={value!r} needs data.mi=true: it reweights the maps that key writes")
+    return value
+
+
 @dataclass
 class DataConfig:                       # RNA_MSM_Inference.py:20-32
     device: str = "cuda"
@@ -164,6 +176,11 @@ class DataConfig:                       # RNA_MSM_Inference.py:20-32
     # for data.invcov) gets one printed line and its other files.
     mi: bool = False
     mi_gaps: str = "pairwise"
+    # mi_weights: "none" = every row counts once (the two files above); "seqid" = row n counts MSA.weights[n] times (1 / the rows
+    # within the normalised Hamming cutoff data.msa_stats uses; rnamsm.msa.msa_mi_weighted) and the maps are written as
+    # <id>_wmi.npy and <id>_wmip.npy INSTEAD of the unweighted pair.  "seqid" needs data.mi=true; with data.msa_stats on as well the
+    # weights are computed once.
+    mi_weights: str = "none"
 
 
 @dataclass
@@ -241,4 +258,5 @@ def parse_overrides(argv: List[str], cfg: Config = None) -> Config:
     check_msa_stats(cfg.data.msa_stats)
     check_mi(cfg.data.mi)
     check_mi_gaps(cfg.data.mi_gaps)
+    check_mi_weights(cfg.data.mi_weights, cfg.data.mi)
     return cfg

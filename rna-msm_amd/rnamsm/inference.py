@@ -22,9 +22,9 @@ import torch
 
 from . import _lib, contacts, lm, ops, rsa, sharding, ss
 from .alphabet import RNAAlphabet
-from .config import Config, check_invcov, check_long_heads, check_long_msa, check_mi, check_mi_gaps, check_msa_stats, check_ss_gemm_dtype
+from .config import Config, check_invcov, check_long_heads, check_long_msa, check_mi, check_mi_gaps, check_mi_weights, check_msa_stats, check_ss_gemm_dtype
 from .model import MSATransformer
-from .msa import load_msa_tokens, msa_invcov_device, msa_mi_device, msa_stats_device
+from .msa import load_msa_tokens, msa_invcov_device, msa_mi_device, msa_mi_weighted_device, msa_stats_device
 
 
 def load_checkpoint(model: MSATransformer, path: str, device) -> None:
@@ -315,6 +315,7 @@ class _Switches(NamedTuple):
     msa_stats_on: bool          # data.msa_stats
     mi_on: bool                 # data.mi
     mi_gaps: str                # data.mi_gaps
+    mi_weighted: bool           # data.mi_weights=seqid
     seqid_cutoff: float         # data.seqid_cutoff where the configuration has one, else the reference's default
     gathering: bool             # gather_to_rank0 with more than one rank
     ss_path: str                # data.ss_model_path
@@ -352,6 +353,9 @@ def read_switches(cfg: Config, gathering: bool) -> _Switches:
     # <id>_mi.npy / <id>_mip.npy by two more writer jobs; off, nothing below differs
     mi_on = check_mi(getattr(cfg.data, "mi", False))
     mi_gaps = check_mi_gaps(getattr(cfg.data, "mi_gaps", "pairwise"))
+    # data.mi_weights=seqid: the pair is the sequence-weighted one and goes to <id>_wmi.npy / <id>_wmip.npy instead; the same two
+    # tensors per item travel the same way
+    mi_weighted = check_mi_weights(getattr(cfg.data, "mi_weights", "none"), mi_on) == "seqid"
     # data.batch_small_msas: small alignments go through ONE launch set per group (forward_ragged: padded into one
     # frame, every MSA scaled by its own depth); a lone forward of a few hundred tokens costs 5.5 ms on a mostly
     # idle chip.  Groups: by shape from the pool (plan_groups); under gather_to_rank0 the RoundGatherer needs this
@@ -368,7 +372,7 @@ def read_switches(cfg: Config, gathering: bool) -> _Switches:
     small_limit = (PACKED_SMALL_TOKENS if exact else PACKED_SMALL_TOKENS_16BIT.get(cfg.model.gemm_dtype, 1024)) if packing else SMALL_MSA_TOKENS
     return _Switches(
         gemm_dtype=cfg.model.gemm_dtype, ss_dtype=ss_dtype, windowing=windowing, window_stride=window_stride, long_heads=long_heads,
-        invcov_on=invcov_on, msa_stats_on=msa_stats_on, mi_on=mi_on, mi_gaps=mi_gaps, seqid_cutoff=seqid_cutoff, gathering=gathering, ss_path=getattr(cfg.data, "ss_model_path", ""),
+        invcov_on=invcov_on, msa_stats_on=msa_stats_on, mi_on=mi_on, mi_gaps=mi_gaps, mi_weighted=mi_weighted, seqid_cutoff=seqid_cutoff, gathering=gathering, ss_path=getattr(cfg.data, "ss_model_path", ""),
         rsa_dir=getattr(cfg.data, "rsa_model_dir", ""), ss_text=bool(getattr(cfg.data, "ss_prob_text", True)) and not gathering,
         ss_pairs=bool(getattr(cfg.data, "ss_pairs_device", True)) and not gathering,
         rsa_text=bool(getattr(cfg.data, "rsa_text_device", True)) and not gathering, contacts=bool(getattr(cfg.data, "contacts", False)),
@@ -461,29 +465,34 @@ class _Reader:
     def on_full(self, rna_id: str, full: np.ndarray) -> None:
         if self.sw.invcov_on:
             self.covariance_map(rna_id, full)
-        if self.sw.msa_stats_on:
-            self.alignment_stats(rna_id, full)
+        weights = self.alignment_stats(rna_id, full) if self.sw.msa_stats_on else None
         if self.sw.mi_on:
-            self.mutual_information(rna_id, full)
+            self.mutual_information(rna_id, full, weights)
 
-    def alignment_stats(self, rna_id: str, full: np.ndarray) -> None:
+    def alignment_stats(self, rna_id: str, full: np.ndarray):
         """data.msa_stats: the weights and the coverage of the alignment as read, left on the device for the sink, and the line with
-        Neff; an alignment the kernels refuse gets one line that names the reason, and its other files as usual."""
+        Neff; an alignment the kernels refuse gets one line that names the reason, and its other files as usual.  Returns the
+        weights on the device (data.mi_weights=seqid counts with them), None for a refused alignment."""
         N, L = full.shape[0], max(full.shape[1] - 1, 1)
         try:
             rec, coverage = msa_stats_device(full, self.alphabet.tok_to_idx["-"], self.sw.seqid_cutoff, self.device)
             neff = float(rec.neff.item())                   # (waits for the reader's stream: the vectors are complete)
         except _lib.RnamsmError as e:
             print(f"{rna_id}: no alignment statistics (data.msa_stats) for this alignment of {N} rows x {L} columns: {e}")
-            return
+            return None
         self.put_stats(rna_id, (rec.weights, coverage))
         print(f"{rna_id}: {N} rows x {L} columns, Neff {neff:.3f} (Neff/sqrt(L) {neff / math.sqrt(L):.3f}, Neff/L {neff / L:.4f})")
+        return rec.weights
 
-    def mutual_information(self, rna_id: str, full: np.ndarray) -> None:
+    def mutual_information(self, rna_id: str, full: np.ndarray, weights=None) -> None:
         """data.mi: the two maps of the alignment as read (before row sub-sampling and any crop), left on the device for the sink; an
-        alignment the kernel refuses gets one line that names the reason, and its other files as usual."""
+        alignment the kernel refuses gets one line that names the reason, and its other files as usual.  data.mi_weights=seqid: the
+        sequence-weighted pair, with `weights` (data.msa_stats' own, where that key made them) or the weights at the same cutoff."""
         try:
-            rec = msa_mi_device(full, self.alphabet.tok_to_idx["-"], self.device, self.sw.mi_gaps)
+            if self.sw.mi_weighted:
+                rec = msa_mi_weighted_device(full, self.alphabet.tok_to_idx["-"], self.device, self.sw.mi_gaps, weights, self.sw.seqid_cutoff)
+            else:
+                rec = msa_mi_device(full, self.alphabet.tok_to_idx["-"], self.device, self.sw.mi_gaps)
             self.put_mi(rna_id, (rec.mi, rec.mip))
             torch.cuda.current_stream().synchronize()       # (the reader's stream: the maps are complete whichever stream copies them)
         except _lib.RnamsmError as e:
@@ -590,7 +599,8 @@ class _Sink:
         # mi: a gathered item's (mi, mip) or its placeholders; absent, what the reader left for this id, if anything
         mi = self.mi_maps.pop(rna_id, None) if mi is None else (mi if mi[0].dim() == 2 else None)
         if mi is not None:
-            cov_job += [(self.save_dir / f"{rna_id}_mi.npy", mi[0]), (self.save_dir / f"{rna_id}_mip.npy", mi[1])]
+            names = ("wmi", "wmip") if self.sw.mi_weighted else ("mi", "mip")
+            cov_job += [(self.save_dir / f"{rna_id}_{names[0]}.npy", mi[0]), (self.save_dir / f"{rna_id}_{names[1]}.npy", mi[1])]
         if self.writer is not None:
             self.writer.submit([(self.save_dir / f"{rna_id}_atp.npy", atp), (self.save_dir / f"{rna_id}_emb.npy", emb)] + extra + cov_job,
                                lambda r=rna_id: self.written.append(r), after=after)

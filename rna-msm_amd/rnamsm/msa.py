@@ -155,6 +155,30 @@ def msa_mi(tokens: np.ndarray, gap_idx: int, device, gaps: str = "pairwise"):
     return rec.mi.cpu().numpy(), rec.mip.cpu().numpy()
 
 
+def msa_mi_weighted_device(tokens: np.ndarray, gap_idx: int, device, gaps: str = "pairwise", weights=None, seqid_cutoff: float = 0.2):
+    """msa_mi_weighted with everything left on the device (an ops.MsaWmi): what the CLI's writer copies from.  weights: float64 [N],
+    a numpy array or a tensor on the device; None: ops.msa_neff's at seqid_cutoff."""
+    import torch
+    from . import ops
+    u8 = _stats_body_device(tokens, device, "msa_mi_weighted")
+    if weights is None:
+        weights = ops.msa_neff(u8, seqid_cutoff).weights
+    elif not isinstance(weights, torch.Tensor):
+        weights = torch.from_numpy(np.array(weights, dtype=np.float64))
+    return ops.msa_wmi(u8, int(gap_idx), gaps, weights.to(u8.device))
+
+
+def msa_mi_weighted(tokens: np.ndarray, gap_idx: int, device, gaps: str = "pairwise", weights=None, seqid_cutoff: float = 0.2):
+    """Sequence-weighted mutual-information contacts of an alignment: (mi, mip), float64 [L, L] each -- msa_mi with row n counted
+    weights[n] times in every pair's table, so a thousand near-identical copies of one sequence count about once.  weights: float64
+    [N], every one finite and > 0; None: MSA.weights (utils/align.py:250-253), 1 / the rows within a normalised Hamming distance of
+    seqid_cutoff, from the device (ops.msa_neff, with that call's limits; a cutoff of 0 gives infinite weights, which are refused).
+    With every weight 1.0 the maps are msa_mi's bit for bit.  gaps and the columns (no <cls>) are msa_mi's.  On the HIP device only
+    (rnamsm_msa_wmi): there is no CPU path.  N in [2, 2^20], L <= 4096, K in [1, 16]."""
+    rec = msa_mi_weighted_device(tokens, gap_idx, device, gaps, weights, seqid_cutoff)
+    return rec.mi.cpu().numpy(), rec.mip.cpu().numpy()
+
+
 def msa_pdist(tokens: np.ndarray, device) -> np.ndarray:
     """MSA.pdist (utils/align.py:121-126): the normalised Hamming distance of every pair of rows, float64 [N, N] (scipy's
     squareform(pdist(.., "hamming")): mismatches / L), over the alignment's columns (no <cls>).  Token ids stand for the reference's

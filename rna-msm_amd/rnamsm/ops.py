@@ -1330,6 +1330,57 @@ def msa_mi(tokens_u8: torch.Tensor, gap: int, gaps: str = "pairwise", want=("mi"
     return rec
 
 
+class MsaWmi(NamedTuple):
+    """What rnamsm_msa_wmi writes, on the device; wcounts is None unless it was asked for."""
+    mi: torch.Tensor                   # float64 [L, L]: the sequence-weighted mutual information of every pair of columns
+    mip: torch.Tensor                  # float64 [L, L]: apc of mi with a zero diagonal
+    wcounts: Optional[torch.Tensor]    # float64 [L, L, S, S]: the weighted pair counts; S = K ("pairwise") or K + 1 ("state", the gap last)
+    wmarg: torch.Tensor                # float64 [L, S]: the weighted column profile, wcounts[i, i, a, a]
+    symbols: torch.Tensor              # int32 [K] ascending
+
+
+@_on_operand_device
+def msa_wmi(tokens_u8: torch.Tensor, gap: int, gaps: str = "pairwise", weights: torch.Tensor = None, want_counts: bool = False,
+            workspace_bytes: Optional[int] = None) -> MsaWmi:
+    """Sequence-weighted mutual information (rnamsm_msa_wmi): msa_mi with row n counted weights[n] times.  tokens uint8 [N, L] on the
+    device (a view with contiguous rows is read where it lies), weights float64 [N] on the device, every one finite and > 0 (the
+    library refuses anything else and names the first such row) -> MsaWmi.  With every weight 1.0 mi and mip are msa_mi's bit for
+    bit.  workspace_bytes: None = the library's default; any size from rnamsm_msa_wmi_min_workspace_bytes(N, L) upward gives the
+    same bits in more bands of columns.  want_counts: the counts have to be sized before the call, so K is counted here first
+    (torch.unique over the tokens, as ops.msa_invcov does: one more pass and one more wait).  N in [2, 2^20], L in [1, 4096], at most 16 distinct values other than `gap`.  The call
+    waits for the device once (K and the weights' verdict are read back)."""
+    if gaps not in _lib.MI_GAP_MODES:
+        raise ValueError(f"msa_wmi: gaps={gaps!r} is not one of {', '.join(map(repr, _lib.MI_GAP_MODES))}")
+    if weights is None:
+        raise ValueError("msa_wmi: weights is required (float64 [N] on the device)")
+    tokens_u8, N, L, ld = _msa_rows(tokens_u8, "msa_wmi")
+    _dev(weights, "weights", torch.float64)
+    if weights.dim() != 1 or weights.shape[0] != N:
+        raise ValueError(f"msa_wmi: expected {N} weights, got {tuple(weights.shape)}")
+    weights = weights.contiguous()
+    lib = _lib.load()
+    dev = tokens_u8.device
+    ws = _aligned_workspace(lib.rnamsm_msa_wmi_workspace_bytes(N, L) if workspace_bytes is None else workspace_bytes, dev)
+    S_max = _lib.INVCOV_MAX_K + 1
+    mi, mip = (torch.empty((L, L), dtype=torch.float64, device=dev) for _ in range(2))
+    wmarg = torch.empty(L * S_max, dtype=torch.float64, device=dev)
+    meta = torch.zeros(_lib.INVCOV_META, dtype=torch.int32, device=dev)
+    wcounts = None
+    if want_counts:
+        K = int((torch.unique(tokens_u8[:, :L]) != int(gap)).sum())
+        S = K + (gaps == "state")
+        wcounts = torch.empty(L * L * S * S * (1 <= K <= _lib.INVCOV_MAX_K), dtype=torch.float64, device=dev)
+    _lib.check(lib.rnamsm_msa_wmi(tokens_u8.data_ptr(), N, L, ld, int(gap), _lib.MI_GAP_MODES[gaps], weights.data_ptr(), mi.data_ptr(),
+                                  mip.data_ptr(), wcounts.data_ptr() if want_counts else None, wmarg.data_ptr(), meta.data_ptr(),
+                                  ws.data_ptr(), ws.numel() if workspace_bytes is None else int(workspace_bytes), _stream()))
+    found = int(meta[0].item())
+    if want_counts and found != K:      # (both are "the distinct byte values other than gap": they cannot differ)
+        raise RuntimeError(f"msa_wmi: the library found {found} symbols, the counts were sized for {K}")
+    K = found
+    S = K + (gaps == "state")
+    return MsaWmi(mi, mip, wcounts.view(L, L, S, S) if want_counts else None, wmarg[:L * S].view(L, S), meta[1:1 + K])
+
+
 @_on_operand_device
 def apc(x: torch.Tensor, zero_diagonal: bool = False) -> torch.Tensor:
     """Average-product correction (the reference's apc, utils/tensor.py:103-113; rnamsm_apc_f64): x float64 [L, L] on the device,
