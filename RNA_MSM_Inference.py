@@ -7,8 +7,10 @@
 Same `group.key=value` overrides and defaults as the reference (RNA_MSM_Inference.py:20-87), same outputs
 (`<id>_emb.npy`, `<id>_atp.npy` next to the alignments).  Multi-GPU: launch one process per GPU with
 `python -m torch.distributed.run --nproc-per-node N RNA_MSM_Inference.py ...`; ids are sharded over ranks.
-Extra, non-reference override: `data.sample_method=first|diversity-max|diversity-min` (the default `hhfilter`
-needs the external binary and is only accepted when the alignment already has <= max_seqs_per_msa rows).
+Extra, non-reference override: `data.sample_method=first|diversity-max|diversity-min|sample-pretrained|seqid-filter` (the default
+`hhfilter` needs the external binary and is only accepted when the alignment already has <= max_seqs_per_msa rows;
+`seqid-filter` is this project's own identity redundancy filter with `data.filter_min_seqid` / `filter_max_seqid` / `filter_step`,
+modelled on hhfilter's -id / -diff and not a reproduction of its selection).
 An alignment wider than `data.max_seqlen - 1` columns is randomly cropped, as in the reference; `data.long_msa=windows` runs it
 as overlapping windows instead and writes the full-length `<id>_emb.npy` (L, 768) / `<id>_atp.npy` (120, L, L), a pure function of
 the alignment and `data.window_stride` (0 = half a window); heads other than `data.lm_scores=wt` are skipped for such an alignment.

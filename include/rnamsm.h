@@ -949,6 +949,38 @@ int rnamsm_msa_neff(const uint8_t* msa, int N, int L, int64_t ld, double seqid_c
                     double* neff, void* workspace, size_t workspace_bytes, void* stream);
 int rnamsm_msa_coverage(const uint8_t* msa, int N, int L, int64_t ld, int gap, double* coverage, void* stream);
 
+/* The identity redundancy filter: a row sub-sampling rule of this project's own, modelled on what the reference asks of the external
+ * hhfilter binary (-id 90 -diff num_seqs, utils/align.py:68-102) and NOT that binary's algorithm -- hhfilter's -diff counts sequences
+ * per window of 50 columns and has its own threshold schedule, this rule counts over the whole alignment.  Integers throughout.
+ *   msa uint8 [N, L], leading dimension ld >= L, `gap` one byte value; bytes in [L, ld) are never read as data.  Per pair of rows:
+ *   both(i, j) = the columns where neither row has the gap, same(i, j) = those of them where the bytes are equal, nres(i) = both(i, i).
+ *   Row k is REDUNDANT to row j at threshold t (a percentage) iff both(k, j) > 0 and 100 * same(k, j) >= t * both(k, j)  (int32).
+ *   order: int32 [N] on the device, the rows in the order they are walked (a permutation of 0 .. N - 1; the Python layer passes
+ *   row 0, then the others by descending nres, ties by ascending index), or NULL = rows as given.  An entry outside [0, N) is found
+ *   on the device and refused (RNAMSM_ERR_INVALID, the message names its position; no output is touched); a repeated row is not
+ *   looked for -- it is redundant to its first occurrence, and a row that is missing is never kept.
+ *   thresholds: num_seqs > 0: min_seqid, min_seqid + step, ... while below max_seqid, then max_seqid; num_seqs == 0, or
+ *   min_seqid >= max_seqid: max_seqid alone.  1 <= min_seqid, 1 <= max_seqid <= 100, step >= 1.
+ *   a pass at threshold t walks the rows not kept yet, in order: a row is kept iff it is redundant at t to no kept row (of an earlier
+ *   pass, or earlier in this one); a row with nres = 0 is never kept unless it is the first of the order, which always is; a row
+ *   rejected in one pass is tried again in the next.  The walk stops after the first pass that leaves at least num_seqs rows kept
+ *   (num_seqs > 0), and after the last threshold in any case.
+ * kept_indices: int32 [N] on the device; its first *n_kept entries are the kept row indices, ascending, the rest is untouched.
+ * kept_at: int32 [N] on the device or NULL: per row the threshold of the pass that kept it, -1 for a row never kept.  n_kept: on the
+ * HOST.  Cutting to num_seqs rows (the first num_seqs of the ascending list) is the caller's.
+ * The rows are kept eight bytes to a 64-bit word, the gap recoded to the zero byte (one-to-one); the pairs are counted 64 x 64 a
+ * block like rnamsm_msa_neff's.  The order is walked in chunks of "seqid_filter_chunk" positions (rnamsm_set_param): per chunk one
+ * launch rejects what is redundant to the rows kept so far and one block resolves the chunk's own survivors in order; ANY chunk size
+ * gives the same indices.  No atomics, the same indices on every run.  N in [1, 2^20], L in [1, 32768].  workspace:
+ * rnamsm_seqid_filter_workspace_bytes(N, L) bytes (the packed rows and four int32 per row; 0 outside the limits), 256-byte aligned.
+ * Every argument refusal comes before the first launch and names the value.  Unlike the statistics calls above this call WAITS for
+ * the stream: the kept count is read back once per pass to decide whether to stop, and the call returns with the outputs complete;
+ * it must not be captured into a graph. */
+size_t rnamsm_seqid_filter_workspace_bytes(int N, int L);
+int rnamsm_seqid_filter(const uint8_t* msa, int N, int L, int64_t ld, int gap, const int32_t* order, int num_seqs, int min_seqid,
+                        int max_seqid, int step, int32_t* kept_indices, int32_t* kept_at, int* n_kept, void* workspace,
+                        size_t workspace_bytes, void* stream);
+
 /* Whole forward, K0..K10 for one MSA, driven from C++ so that one call enqueues every launch
  * (MSATransformer.forward, model.py:338-416, with repr_layers=[num_layers], need_head_weights=True,
  * lm_head / contact head omitted -- their results are unused by the CLI).
@@ -1152,6 +1184,9 @@ void rnamsm_timing_reset(void);
  *                 rnamsm_col_attn16 only: 4 = one 32-query block per wave for every R, 5 = the TRACKED (online-softmax) loop for
  *                 every format (A/B, and the reference the FAST loop's fallback is tested against).
  *                 The RNAMSM_F32 path is not affected by either.
+ *   "seqid_filter_chunk"  rnamsm_seqid_filter (added after round 6, the fifteenth name): the positions of the order one block
+ *                 resolves per step of a pass, a multiple of 64 in [64, 512] (anything else is refused), default 256.  Every value
+ *                 gives the same indices; smaller chunks mean more launches, larger ones a longer one-block stage.
  * Threading: the knobs are process-global and are read on the host while a call enqueues its launches.  Change them only between
  * calls; while any thread is inside rnamsm_forward / _forward_batch / _forward_packed, rnamsm_set_param changes nothing and returns
  * RNAMSM_ERR_INVALID (the one per-forward choice that used to be a knob write, the 16-bit GEMM tile threshold, is thread-local). */

@@ -177,6 +177,12 @@ extern "C" int rnamsm_set_param(const char* name, int value) {
         rnamsm::tuning().ln_fold = value < 0 ? 0 : (value > 3 ? 3 : value);
         return RNAMSM_OK;
     }
+    if (name && !strcmp(name, "seqid_filter_chunk")) {
+        if (value < 64 || value > 512 || value % 64)
+            return rnamsm::fail(RNAMSM_ERR_INVALID, "set_param: seqid_filter_chunk=%d is not a multiple of 64 in [64, 512]", value);
+        rnamsm::tuning().seqid_filter_chunk = value;
+        return RNAMSM_OK;
+    }
     if (name && !strcmp(name, "gemm_splitk")) {
         if (value != 0 && value != 1 && value != 2 && value != 4 && value != 8)
             return rnamsm::fail(RNAMSM_ERR_INVALID, "set_param: gemm_splitk must be 0, 1, 2, 4 or 8");
@@ -215,6 +221,7 @@ extern "C" int rnamsm_get_param(const char* name) {
     if (name && !strcmp(name, "attn16")) return rnamsm::tuning().attn16;
     if (name && !strcmp(name, "ln_fold")) return rnamsm::tuning().ln_fold;
     if (name && !strcmp(name, "greedy_fused")) return rnamsm::tuning().greedy_fused;
+    if (name && !strcmp(name, "seqid_filter_chunk")) return rnamsm::tuning().seqid_filter_chunk;
     if (name && !strcmp(name, "col_small")) return rnamsm::tuning().col_small;
     if (name && !strcmp(name, "col_dma")) return rnamsm::tuning().col_dma;
     if (name && !strcmp(name, "col_fast")) return rnamsm::tuning().col_fast;

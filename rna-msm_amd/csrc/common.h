@@ -95,6 +95,7 @@ struct Tuning {
                                    // epilogues) when R*C >= LN_FOLD_MIN_TOKENS (4096), 3 = for every shape, 2 = every GEMM sums its rows itself (A/B), 0 = separate launches
     int greedy_fused = 1;          // rnamsm_greedy_select: 1 = one launch per step (fused distance / score / argmax) up to 3072 rows, 2 = always, 0 = three launches
     int attn16 = 1;                // 16-bit modes of rnamsm_forward: 1 = attention contractions on the 16-bit matrix cores too, 0 = fp32 attention
+    int seqid_filter_chunk = 256;  // rnamsm_seqid_filter: positions of the order resolved by one block per step of a pass; a multiple of 64 in [64, 512]; every value gives the same indices
 };
 Tuning& tuning();
 // The knobs are process-global A/B instruments, read on the HOST while a driver enqueues its launches.  Writing one while another

@@ -233,6 +233,9 @@ _SIGNATURES = {
     "rnamsm_msa_neff_min_workspace_bytes": (c_size_t, [c_int, c_int]),
     "rnamsm_msa_neff": (c_int, [c_void_p, c_int, c_int, c_int64, c_double, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "rnamsm_msa_coverage": (c_int, [c_void_p, c_int, c_int, c_int64, c_int, c_void_p, c_void_p]),
+    "rnamsm_seqid_filter_workspace_bytes": (c_size_t, [c_int, c_int]),
+    "rnamsm_seqid_filter": (c_int, [c_void_p, c_int, c_int, c_int64, c_int, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p,
+                                    c_void_p, c_void_p, c_size_t, c_void_p]),
     "rnamsm_forward_workspace_bytes": (c_size_t, [POINTER(ModelDims), c_int, c_int, c_int, c_int]),
     "rnamsm_forward": (c_int, [POINTER(ModelDims), POINTER(c_void_p), c_void_p, c_int, c_int, c_void_p, c_size_t,
                                c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int,

@@ -81,6 +81,20 @@ def check_mi_weights(value: str, mi_on: bool = True) -> str:
     return value
 
 
+def check_filter_seqid(min_seqid, max_seqid, step) -> Tuple[int, int, int]:
+    """data.filter_min_seqid / data.filter_max_seqid / data.filter_step (sample_method=seqid-filter); the message names the key."""
+    for key, value in (("filter_min_seqid", min_seqid), ("filter_max_seqid", max_seqid), ("filter_step", step)):
+        if isinstance(value, bool) or not isinstance(value, int):
+            raise ValueError(f"data.{key}={value!r} is not an integer")
+    if min_seqid < 1:
+        raise ValueError(f"data.filter_min_seqid={min_seqid} is below 1")
+    if not 1 <= max_seqid <= 100:
+        raise ValueError(f"data.filter_max_seqid={max_seqid} outside [1, 100]")
+    if step < 1:
+        raise ValueError(f"data.filter_step={step} is below 1")
+    return min_seqid, max_seqid, step
+
+
 @dataclass
 class DataConfig:                       # RNA_MSM_Inference.py:20-32
     device: str = "cuda"
@@ -94,6 +108,17 @@ class DataConfig:                       # RNA_MSM_Inference.py:20-32
     max_tokens: int = 16384
     max_seqs_per_msa: int = 512
     sample_method: str = "hhfilter"
+    # (the name is not checked here: rnamsm.msa.load_msa_tokens refuses an unknown one, and the reference's default, hhfilter, where
+    # an alignment is deeper than max_seqs_per_msa -- that external binary is not part of this project.)
+    # extra (not in the reference): sample_method=seqid-filter, this project's own identity redundancy filter
+    # (rnamsm.msa.seqid_filter; on the device rnamsm_seqid_filter).  It is modelled on what the reference asks of hhfilter
+    # (-id 90 -diff max_seqs_per_msa) and is NOT that binary's selection: it counts identity over the whole alignment, hhfilter's
+    # -diff per window of 50 columns with a threshold schedule of its own.  Passes at filter_min_seqid, + filter_step, ..., up to
+    # filter_max_seqid (per cent) until max_seqs_per_msa rows are kept, then the first max_seqs_per_msa of them.  The keys are read by
+    # that method only; min >= 1, 1 <= max <= 100, step >= 1.
+    filter_min_seqid: int = 20
+    filter_max_seqid: int = 90
+    filter_step: int = 5
     # extra (not in the reference): the small alignments (<= 16384 tokens each; 8192 in bf16) of the id list share launch sets
     # (MSATransformer.forward_ragged).  On by default since round 3: a lone forward of a few hundred tokens costs 2.5 ms on a mostly
     # idle chip; data.batch_small_msas=false restores the strictly one-by-one loop of the reference (RNA_MSM_Inference.py:141-148)
@@ -259,4 +284,5 @@ def parse_overrides(argv: List[str], cfg: Config = None) -> Config:
     check_mi(cfg.data.mi)
     check_mi_gaps(cfg.data.mi_gaps)
     check_mi_weights(cfg.data.mi_weights, cfg.data.mi)
+    check_filter_seqid(cfg.data.filter_min_seqid, cfg.data.filter_max_seqid, cfg.data.filter_step)
     return cfg

@@ -22,7 +22,7 @@ import torch
 
 from . import _lib, contacts, lm, ops, rsa, sharding, ss
 from .alphabet import RNAAlphabet
-from .config import Config, check_invcov, check_long_heads, check_long_msa, check_mi, check_mi_gaps, check_mi_weights, check_msa_stats, check_ss_gemm_dtype
+from .config import Config, check_filter_seqid, check_invcov, check_long_heads, check_long_msa, check_mi, check_mi_gaps, check_mi_weights, check_msa_stats, check_ss_gemm_dtype
 from .model import MSATransformer
 from .msa import load_msa_tokens, msa_invcov_device, msa_mi_device, msa_mi_weighted_device, msa_stats_device
 
@@ -317,6 +317,7 @@ class _Switches(NamedTuple):
     mi_gaps: str                # data.mi_gaps
     mi_weighted: bool           # data.mi_weights=seqid
     seqid_cutoff: float         # data.seqid_cutoff where the configuration has one, else the reference's default
+    filter_seqid: tuple         # data.filter_min_seqid, data.filter_max_seqid, data.filter_step (sample_method=seqid-filter)
     gathering: bool             # gather_to_rank0 with more than one rank
     ss_path: str                # data.ss_model_path
     rsa_dir: str                # data.rsa_model_dir
@@ -356,6 +357,10 @@ def read_switches(cfg: Config, gathering: bool) -> _Switches:
     # data.mi_weights=seqid: the pair is the sequence-weighted one and goes to <id>_wmi.npy / <id>_wmip.npy instead; the same two
     # tensors per item travel the same way
     mi_weighted = check_mi_weights(getattr(cfg.data, "mi_weights", "none"), mi_on) == "seqid"
+    # data.sample_method=seqid-filter: the thresholds of the identity redundancy filter (rnamsm.msa.seqid_filter); the sub-sampling
+    # happens behind on_full, so the statistics and maps of the alignment as read see every row whatever the method
+    filter_seqid = check_filter_seqid(getattr(cfg.data, "filter_min_seqid", 20), getattr(cfg.data, "filter_max_seqid", 90),
+                                      getattr(cfg.data, "filter_step", 5))
     # data.batch_small_msas: small alignments go through ONE launch set per group (forward_ragged: padded into one
     # frame, every MSA scaled by its own depth); a lone forward of a few hundred tokens costs 5.5 ms on a mostly
     # idle chip.  Groups: by shape from the pool (plan_groups); under gather_to_rank0 the RoundGatherer needs this
@@ -372,7 +377,7 @@ def read_switches(cfg: Config, gathering: bool) -> _Switches:
     small_limit = (PACKED_SMALL_TOKENS if exact else PACKED_SMALL_TOKENS_16BIT.get(cfg.model.gemm_dtype, 1024)) if packing else SMALL_MSA_TOKENS
     return _Switches(
         gemm_dtype=cfg.model.gemm_dtype, ss_dtype=ss_dtype, windowing=windowing, window_stride=window_stride, long_heads=long_heads,
-        invcov_on=invcov_on, msa_stats_on=msa_stats_on, mi_on=mi_on, mi_gaps=mi_gaps, mi_weighted=mi_weighted, seqid_cutoff=seqid_cutoff, gathering=gathering, ss_path=getattr(cfg.data, "ss_model_path", ""),
+        invcov_on=invcov_on, msa_stats_on=msa_stats_on, mi_on=mi_on, mi_gaps=mi_gaps, mi_weighted=mi_weighted, seqid_cutoff=seqid_cutoff, filter_seqid=filter_seqid, gathering=gathering, ss_path=getattr(cfg.data, "ss_model_path", ""),
         rsa_dir=getattr(cfg.data, "rsa_model_dir", ""), ss_text=bool(getattr(cfg.data, "ss_prob_text", True)) and not gathering,
         ss_pairs=bool(getattr(cfg.data, "ss_pairs_device", True)) and not gathering,
         rsa_text=bool(getattr(cfg.data, "rsa_text_device", True)) and not gathering, contacts=bool(getattr(cfg.data, "contacts", False)),
@@ -458,7 +463,7 @@ class _Reader:
         torch.cuda.set_device(self.device)
         rna_id = self.ids[idx]
         tokens = load_msa_tokens(self.files[rna_id], self.alphabet, self.cfg.data.max_seqs_per_msa, self.cfg.data.sample_method,
-                                 device=self.device, rng=self.rng,
+                                 device=self.device, rng=self.rng, filter_seqid=self.sw.filter_seqid,
                                  on_full=(lambda full: self.on_full(rna_id, full)) if self.sw.invcov_on or self.sw.msa_stats_on or self.sw.mi_on else None)
         return tokens if self.sw.windowing else crop_tokens(tokens, self.cfg.data.max_seqlen, self.rng)
 

@@ -5,7 +5,9 @@ path.  Row sub-sampling: the reference defaults to the external `hhfilter` binar
 which is not available offline; supported here are `first` (keep the first N rows), the reference's weighted random
 `sample-pretrained` (utils/align.py:150-163; weights on the device, the draw by numpy's generator) and its
 greedy `diversity-max` / `diversity-min` (utils/align.py:128-148), on the HIP device when one is given
-(rnamsm_greedy_select) or on the host -- index-identical to the reference either way.
+(rnamsm_greedy_select) or on the host -- index-identical to the reference either way.  `seqid-filter` is this project's own
+identity redundancy filter (seqid_filter below; rnamsm_seqid_filter on the device, numpy on the host, index-identical): modelled on
+what the reference asks of hhfilter (-id 90 -diff num_seqs), not a reproduction of that binary.
 """
 from __future__ import annotations
 
@@ -16,7 +18,7 @@ import numpy as np
 
 from .alphabet import RNAAlphabet
 
-SAMPLE_METHODS = ("hhfilter", "sample-pretrained", "diversity-max", "diversity-min", "first")
+SAMPLE_METHODS = ("hhfilter", "sample-pretrained", "diversity-max", "diversity-min", "first", "seqid-filter")
 
 
 def read_fasta_records(path_or_text: Union[str, Path], is_text: bool = False) -> List[Tuple[str, str]]:
@@ -229,11 +231,102 @@ def sample_weights(tokens: np.ndarray, num_seqs: int, rng=None, seqid_cutoff: fl
     return np.append(0, np.sort(idx))
 
 
+def check_seqid_filter_args(num_seqs: int, min_seqid: int, max_seqid: int, step: int, prefix: str = "seqid_filter: ") -> None:
+    """The filter's limits (include/rnamsm.h); the message names the value.  prefix: what stands in front of the name (the CLI's keys)."""
+    for name, value in (("num_seqs", num_seqs), ("min_seqid", min_seqid), ("max_seqid", max_seqid), ("step", step)):
+        if isinstance(value, bool) or not isinstance(value, (int, np.integer)):
+            raise ValueError(f"{prefix}{name}={value!r} is not an integer")
+    if num_seqs < 0:
+        raise ValueError(f"{prefix}num_seqs={num_seqs} is negative")
+    if min_seqid < 1:
+        raise ValueError(f"{prefix}min_seqid={min_seqid} is below 1")
+    if not 1 <= max_seqid <= 100:
+        raise ValueError(f"{prefix}max_seqid={max_seqid} outside [1, 100]")
+    if step < 1:
+        raise ValueError(f"{prefix}step={step} is below 1")
+
+
+def seqid_thresholds(num_seqs: int, min_seqid: int = 20, max_seqid: int = 90, step: int = 5) -> List[int]:
+    """The thresholds of the filter's passes: num_seqs > 0: min_seqid, min_seqid + step, ... while below max_seqid, then max_seqid;
+    num_seqs == 0, or min_seqid >= max_seqid: max_seqid alone."""
+    check_seqid_filter_args(num_seqs, min_seqid, max_seqid, step)
+    return (list(range(min_seqid, max_seqid, step)) if num_seqs > 0 else []) + [max_seqid]
+
+
+def seqid_order(body: np.ndarray, gap: int) -> np.ndarray:
+    """The order the filter walks the rows in: row 0, then the others by descending number of residues, ties by ascending index."""
+    nres = (body != gap).sum(1)
+    return np.concatenate([[0], np.argsort(-nres[1:], kind="stable") + 1]).astype(np.int64)
+
+
+def seqid_filter_host(body: np.ndarray, gap: int, num_seqs: int, min_seqid: int = 20, max_seqid: int = 90, step: int = 5,
+                      order=None) -> Tuple[np.ndarray, np.ndarray]:
+    """The identity redundancy filter on the host: body uint8 [N, L] (the alignment's columns, no <cls>) -> (kept row indices
+    ascending int64, kept_at int32 [N]: per row the threshold of the pass that kept it, -1 for a row never kept).  The rule is
+    include/rnamsm.h's (rnamsm_seqid_filter) -- a rule of this project's own, modelled on the reference's `hhfilter -id 90 -diff
+    num_seqs` and not that binary's algorithm -- in integers, vectorised per candidate (one comparison of a row against all rows kept
+    so far): index-identical to the device."""
+    thresholds = seqid_thresholds(num_seqs, min_seqid, max_seqid, step)
+    body = np.ascontiguousarray(body, dtype=np.uint8)
+    N, L = body.shape
+    order = seqid_order(body, gap) if order is None else np.asarray(order, dtype=np.int64)
+    if order.shape != (N,):
+        raise ValueError(f"seqid_filter: expected an order of {N} entries, got {order.shape}")
+    bad = np.flatnonzero((order < 0) | (order >= N))
+    if bad.size:
+        raise ValueError(f"seqid_filter: order[{int(bad[0])}] lies outside [0, {N})")
+    res = body != gap
+    nres = res.sum(1)
+    kept_at = np.full(N, -1, dtype=np.int32)
+    k_body, k_res, nk = np.empty_like(body), np.empty_like(res), 0
+    for t in thresholds:
+        for pos, r in enumerate(order):
+            if kept_at[r] >= 0 or (nres[r] == 0 and pos != 0):
+                continue
+            if nk:
+                m = k_res[:nk] & res[r]
+                both = m.sum(1, dtype=np.int64)
+                same = (m & (k_body[:nk] == body[r])).sum(1, dtype=np.int64)
+                if ((both > 0) & (100 * same >= t * both)).any():
+                    continue
+            k_body[nk], k_res[nk], kept_at[r] = body[r], res[r], t
+            nk += 1
+        if num_seqs > 0 and nk >= num_seqs:
+            break
+    return np.flatnonzero(kept_at >= 0).astype(np.int64), kept_at
+
+
+def seqid_filter(tokens: np.ndarray, gap_idx: int, num_seqs: int, min_seqid: int = 20, max_seqid: int = 90, step: int = 5,
+                 device=None) -> np.ndarray:
+    """Row indices (ascending int64) of the non-redundant rows of an alignment, by the identity redundancy filter: passes at the
+    thresholds min_seqid, min_seqid + step, ..., max_seqid (per cent identity over the columns where both rows have a residue) until
+    num_seqs rows are kept; num_seqs = 0: one pass at max_seqid.  In a pass the rows are walked longest first behind row 0 and a row
+    is kept unless it is that identical to a row already kept.  A rule of this project's own, modelled on the reference's
+    `hhfilter -id 90 -diff num_seqs` (utils/align.py:68-102); it does NOT reproduce that binary (whose -diff counts sequences per
+    window of 50 columns).  The columns are the alignment's (no <cls>, as in msa_weights).  With `device` (a HIP device) it runs
+    there (rnamsm_seqid_filter), else on the host (seqid_filter_host): the same indices either way.  More than num_seqs rows may come
+    back; cutting is the caller's."""
+    body = tokens[:, 1:] if tokens.shape[1] > 1 else tokens
+    if body.size and (int(body.min()) < 0 or int(body.max()) > 255):
+        raise ValueError("seqid_filter: token ids outside [0, 255]")
+    body = np.ascontiguousarray(body.astype(np.uint8))
+    if device is None:
+        return seqid_filter_host(body, int(gap_idx), num_seqs, min_seqid, max_seqid, step)[0]
+    import torch
+    from . import ops
+    check_seqid_filter_args(num_seqs, min_seqid, max_seqid, step)
+    rec = ops.seqid_filter(torch.from_numpy(body).to(device), int(gap_idx), num_seqs, min_seqid, max_seqid, step)
+    return rec.indices.cpu().numpy().astype(np.int64)
+
+
 def load_msa_tokens(path: Union[str, Path], alphabet: RNAAlphabet, max_seqs_per_msa: int = 512,
-                    sample_method: str = "hhfilter", device=None, rng=None, on_full=None) -> np.ndarray:
+                    sample_method: str = "hhfilter", device=None, rng=None, on_full=None, filter_seqid=(20, 90, 5)) -> np.ndarray:
     """.a2m_msa2 file -> int64 tokens [R <= max_seqs, L+1].  With `device` (a HIP device) the sub-sampling arithmetic
-    (greedy selection, sequence weights) runs on the GPU.  `rng` feeds `sample-pretrained` (see sample_weights).  `on_full`: called
-    with the tokens of the alignment as read, every row, before anything is sub-sampled."""
+    (greedy selection, sequence weights, the redundancy filter) runs on the GPU.  `rng` feeds `sample-pretrained` (see
+    sample_weights).  `on_full`: called with the tokens of the alignment as read, every row, before anything is sub-sampled.
+    `seqid-filter`: seqid_filter with num_seqs = max_seqs_per_msa and filter_seqid = (min_seqid, max_seqid, step), then the first
+    max_seqs_per_msa of the kept rows (all of them where fewer are kept) -- this project's stand-in for the reference's hhfilter
+    default, not that binary's selection."""
     if sample_method not in SAMPLE_METHODS:
         raise AssertionError(f"unknown sample_method {sample_method!r}")
     records = read_fasta_records(path)
@@ -251,6 +344,11 @@ def load_msa_tokens(path: Union[str, Path], alphabet: RNAAlphabet, max_seqs_per_
         return tokens[greedy_select(tokens, max_seqs_per_msa, mode)]
     if sample_method == "sample-pretrained":
         return tokens[sample_weights(tokens, max_seqs_per_msa, rng, device=device)]
+    if sample_method == "seqid-filter":
+        lo, hi, step = filter_seqid
+        kept = seqid_filter(tokens, alphabet.tok_to_idx["-"], max_seqs_per_msa, lo, hi, step, device=device)
+        return tokens[kept[:max_seqs_per_msa]]
     raise NotImplementedError(
         f"sample_method={sample_method!r} needs the external hhfilter binary of the reference (utils/align.py:68-102); "
-        "pre-filter the alignment or pass data.sample_method=first | diversity-max | diversity-min | sample-pretrained")
+        "pre-filter the alignment or pass data.sample_method=seqid-filter (this project's identity filter, not hhfilter's "
+        "selection) | first | diversity-max | diversity-min | sample-pretrained")

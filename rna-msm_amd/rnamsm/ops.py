@@ -6,6 +6,7 @@ otherwise -- there is no eager fallback.
 """
 from __future__ import annotations
 
+import ctypes
 import functools
 import math
 from typing import List, NamedTuple, Optional, Sequence, Tuple
@@ -1463,3 +1464,48 @@ def depth_scaling(R: int) -> float:
 def row_scaling(R: int) -> float:
     """RowSelfAttention.align_scaling (modules.py:713-715)."""
     return (HEAD_DIM ** -0.5) / math.sqrt(R)
+
+
+class SeqidFilter(NamedTuple):
+    """What rnamsm_seqid_filter writes, on the device."""
+    indices: torch.Tensor          # int32 [n_kept]: the kept row indices, ascending
+    kept_at: torch.Tensor          # int32 [N]: per row the threshold of the pass that kept it, -1 for a row never kept
+
+
+def seqid_order(msa_u8: torch.Tensor, gap: int) -> torch.Tensor:
+    """The order the filter walks the rows in: row 0, then the others by descending number of residues (bytes other than `gap`),
+    ties by ascending index -- a stable sort, int32 [N] on the operand's device."""
+    nres = (msa_u8 != int(gap)).sum(1)
+    N = msa_u8.shape[0]
+    if N == 1:
+        return torch.zeros(1, dtype=torch.int32, device=msa_u8.device)
+    rest = torch.sort(nres[1:], descending=True, stable=True).indices + 1
+    return torch.cat([torch.zeros(1, dtype=rest.dtype, device=rest.device), rest]).to(torch.int32)
+
+
+@_on_operand_device
+def seqid_filter(msa_u8: torch.Tensor, gap: int, num_seqs: int, min_seqid: int = 20, max_seqid: int = 90, step: int = 5,
+                 order: Optional[torch.Tensor] = None) -> SeqidFilter:
+    """The identity redundancy filter (rnamsm_seqid_filter; include/rnamsm.h states the rule): msa uint8 [N, L] on the device (a view
+    with contiguous rows is read where it lies) -> SeqidFilter.  A rule of this project's own, modelled on the reference's
+    `hhfilter -id 90 -diff num_seqs` and not that binary's algorithm (no per-window count).  num_seqs > 0: passes at min_seqid,
+    min_seqid + step, ..., max_seqid until num_seqs rows are kept; 0: one pass at max_seqid.  order: int32 [N] on the device, the
+    rows in the order they are walked; None = seqid_order's (row 0, then by descending residues).  Cutting to num_seqs rows is the
+    caller's.  N in [1, 2^20], L in [1, 32768]; the call waits for the device (the kept count is read back once per pass)."""
+    msa_u8, N, L, ld = _msa_rows(msa_u8, "seqid_filter")
+    dev = msa_u8.device
+    if order is None:
+        order = seqid_order(msa_u8[:, :L], gap)
+    _dev(order, "order", torch.int32)
+    if order.dim() != 1 or order.shape[0] != N:
+        raise ValueError(f"seqid_filter: expected an order of {N} entries, got {tuple(order.shape)}")
+    order = order.contiguous()
+    lib = _lib.load()
+    ws = _aligned_workspace(lib.rnamsm_seqid_filter_workspace_bytes(N, L), dev)
+    indices = torch.empty(N, dtype=torch.int32, device=dev)
+    kept_at = torch.empty(N, dtype=torch.int32, device=dev)
+    n_kept = ctypes.c_int(0)
+    _lib.check(lib.rnamsm_seqid_filter(msa_u8.data_ptr(), N, L, ld, int(gap), order.data_ptr(), int(num_seqs), int(min_seqid),
+                                       int(max_seqid), int(step), indices.data_ptr(), kept_at.data_ptr(),
+                                       ctypes.addressof(n_kept), ws.data_ptr(), ws.numel(), _stream()))
+    return SeqidFilter(indices[:n_kept.value], kept_at)

@@ -1,0 +1,134 @@
+// Host check of csrc/seqid_words.h, the recoded word form and the per-word pair counts of csrc/seqid_filter.hip, against a byte loop.
+// Built by tests/test_seqid_filter_host.py with g++ -fsanitize=address,undefined and run as a program of its own.
+//   1. the recoding is one-to-one for every gap value, and sends the gap (and nothing else) to the zero byte;
+//   2. every tail length n = 0 .. 8 (and below 0): sq_pack_word reads exactly n bytes of a buffer of exactly that size --
+//      AddressSanitizer sees a read past it -- and the bytes above are gaps;
+//   3. sq_pair and sq_residues on random words over the byte values that break a SWAR mask, for gaps 0, 0x2d, 0x80 and 0xff;
+//   4. rows of every length L = 1 .. 40 in buffers of exactly L bytes and inside wider buffers with garbage past L: both, same and
+//      nres summed over the words against the byte loop;
+//   5. sq_redundant at exact equality and one match fewer, and the threshold lists.
+// Prints "ok <checks>" and exits 0, or the first difference and exits 1.
+#include <stdint.h>
+#include <stdio.h>
+#include <stdlib.h>
+#include <vector>
+
+#include "../../rna-msm_amd/csrc/seqid_words.h"
+
+using namespace rnamsm;
+
+static long checks = 0;
+
+static int fail(const char* what, long a, long b, long c, long d) {
+    printf("FAIL %s: %ld %ld got %ld want %ld\n", what, a, b, c, d);
+    return 1;
+}
+
+static uint32_t state = 2024u;
+static uint32_t next() {
+    state = state * 1664525u + 1013904223u;
+    return state >> 8;
+}
+
+static void count_row(const uint8_t* a, const uint8_t* b, int L, int gap, int* both, int* same, int* nres) {
+    *both = *same = *nres = 0;
+    for (int w = 0; 8 * w < L; ++w) {
+        const uint64_t wa = sq_pack_word(a, 8 * w, L - 8 * w, gap), wb = sq_pack_word(b, 8 * w, L - 8 * w, gap);
+        int bo, sa;
+        sq_pair(wa, wb, &bo, &sa);
+        *both += bo;
+        *same += sa;
+        *nres += sq_residues(wa);
+    }
+}
+
+int main() {
+    const int gaps[4] = {0x00, 0x2d, 0x80, 0xff};
+    // 1. the recoding
+    for (int gap = 0; gap < 256; ++gap) {
+        int seen[256] = {0};
+        for (int b = 0; b < 256; ++b) {
+            const uint8_t r = sq_recode((uint8_t)b, gap);
+            if ((r == 0) != (b == gap)) return fail("recode zero", gap, b, r, b == gap ? 0 : 1);
+            if (seen[r]++) return fail("recode one-to-one", gap, b, r, -1);
+            ++checks;
+        }
+    }
+    // 2. every tail length, exact buffers
+    for (int gi = 0; gi < 4; ++gi)
+        for (int n = -2; n <= 8; ++n)
+            for (int rep = 0; rep < 50; ++rep) {
+                const int len = n < 0 ? 0 : n;
+                std::vector<uint8_t> buf(len);
+                for (int k = 0; k < len; ++k) buf[k] = (uint8_t)next();
+                const uint64_t w = sq_pack_word(buf.data(), 0, n, gaps[gi]);
+                for (int k = 0; k < 8; ++k) {
+                    const uint8_t got = (uint8_t)(w >> (8 * k)), want = k < len ? sq_recode(buf[k], gaps[gi]) : 0;
+                    if (got != want) return fail("tail", n, k, got, want);
+                }
+                int res = 0;
+                for (int k = 0; k < len; ++k) res += buf[k] != gaps[gi];
+                if (sq_residues(w) != res) return fail("tail residues", n, rep, sq_residues(w), res);
+                ++checks;
+            }
+    // 3. random words
+    const uint8_t vals[7] = {0x00, 0x01, 0x7f, 0x80, 0xff, 0x2d, 0x81};
+    for (int gi = 0; gi < 4; ++gi)
+        for (int rep = 0; rep < 200000; ++rep) {
+            uint8_t a[8], b[8];
+            int both = 0, same = 0, ra = 0;
+            for (int k = 0; k < 8; ++k) {
+                a[k] = rep & 1 ? (uint8_t)next() : vals[next() % 7];
+                b[k] = next() % 3 == 0 ? a[k] : (rep & 1 ? (uint8_t)next() : vals[next() % 7]);
+                const bool r = a[k] != gaps[gi] && b[k] != gaps[gi];
+                both += r;
+                same += r && a[k] == b[k];
+                ra += a[k] != gaps[gi];
+            }
+            const uint64_t wa = sq_pack_word(a, 0, 8, gaps[gi]), wb = sq_pack_word(b, 0, 8, gaps[gi]);
+            int bo, sa;
+            sq_pair(wa, wb, &bo, &sa);
+            if (bo != both) return fail("pair both", gi, rep, bo, both);
+            if (sa != same) return fail("pair same", gi, rep, sa, same);
+            if (sq_residues(wa) != ra) return fail("residues", gi, rep, sq_residues(wa), ra);
+            sq_pair(wb, wa, &bo, &sa);
+            if (bo != both || sa != same) return fail("pair symmetric", gi, rep, bo * 16 + sa, both * 16 + same);
+            checks += 4;
+        }
+    // 4. rows of every length
+    for (int gi = 0; gi < 4; ++gi)
+        for (int L = 1; L <= 40; ++L)
+            for (int rep = 0; rep < 100; ++rep) {
+                std::vector<uint8_t> a(L), b(L);
+                int both = 0, same = 0, nres = 0;
+                for (int c = 0; c < L; ++c) {
+                    a[c] = vals[next() % 7];
+                    b[c] = next() % 2 ? a[c] : vals[next() % 7];
+                    const bool r = a[c] != gaps[gi] && b[c] != gaps[gi];
+                    both += r;
+                    same += r && a[c] == b[c];
+                    nres += a[c] != gaps[gi];
+                }
+                int bo, sa, nr;
+                count_row(a.data(), b.data(), L, gaps[gi], &bo, &sa, &nr);
+                if (bo != both || sa != same || nr != nres) return fail("exact rows", L, rep, bo * 10000 + sa * 100 + nr, both * 10000 + same * 100 + nres);
+                std::vector<uint8_t> pa(L + 9, 0xee), pb(L + 9, 0xee);        // guard bytes that are equal residues everywhere
+                for (int c = 0; c < L; ++c) { pa[c] = a[c]; pb[c] = b[c]; }
+                count_row(pa.data(), pb.data(), L, gaps[gi], &bo, &sa, &nr);
+                if (bo != both || sa != same || nr != nres) return fail("padded rows", L, rep, bo * 10000 + sa * 100 + nr, both * 10000 + same * 100 + nres);
+                checks += 2;
+            }
+    // 5. the predicate and the threshold lists
+    if (!sq_redundant(10, 9, 90) || sq_redundant(10, 8, 90) || sq_redundant(0, 0, 1) || !sq_redundant(32768, 32768, 100) ||
+        sq_redundant(32768, 32767, 100) || !sq_redundant(3, 1, 33) || sq_redundant(3, 1, 34))
+        return fail("redundant", 0, 0, 0, 1);
+    int t[100];
+    if (sq_thresholds(512, 20, 90, 5, t) != 15 || t[0] != 20 || t[13] != 85 || t[14] != 90) return fail("thresholds default", 0, 0, t[14], 90);
+    if (sq_thresholds(0, 20, 90, 5, t) != 1 || t[0] != 90) return fail("thresholds num_seqs 0", 0, 0, t[0], 90);
+    if (sq_thresholds(5, 90, 90, 5, t) != 1 || t[0] != 90 || sq_thresholds(5, 95, 50, 5, t) != 1 || t[0] != 50) return fail("thresholds min >= max", 0, 0, t[0], 50);
+    if (sq_thresholds(5, 20, 33, 5, t) != 4 || t[2] != 30 || t[3] != 33) return fail("thresholds off the grid", 0, 0, t[3], 33);
+    if (sq_thresholds(5, 1, 100, 1, t) != 100 || t[99] != 100) return fail("thresholds longest", 0, 0, t[99], 100);
+    checks += 12;
+    printf("ok %ld\n", checks);
+    return 0;
+}
