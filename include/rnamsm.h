@@ -981,6 +981,30 @@ int rnamsm_seqid_filter(const uint8_t* msa, int N, int L, int64_t ld, int gap, c
                         int max_seqid, int step, int32_t* kept_indices, int32_t* kept_at, int* n_kept, void* workspace,
                         size_t workspace_bytes, void* stream);
 
+/* The top-k ranked pairs of an L x L map (contacts, covariance, mutual information: any pair score), selected and ranked on the
+ * device.  x [L, L] with leading dimension ld >= L, float64 (_f64) or float32 (_f32).
+ *   Candidates: the pairs (i, j) with 0 <= i < j < L, j - i >= min_sep and x[i * ld + j] not NaN.  ONLY those elements are read: the
+ *   diagonal, the lower triangle, the band closer than min_sep and the padding beyond column L are never looked at, and symmetry is
+ *   not assumed.
+ *   A pair's value is v = (double)x[i, j] (exact for float32).  -0.0 counts as +0.0; +inf and -inf are ordinary values.
+ *   The order is total: larger v first, then smaller i, then smaller j.
+ * With n = min(k, the number of candidates): pairs[0 .. n) (int32 [k, 2], 0-based i then j) and scores[0 .. n) (float64 [k]) hold the
+ * first n candidates in that order, a zero written as +0.0; *count = n, an int32 on the DEVICE; the rows n .. k are -1, -1 and NaN, so
+ * every output byte is defined.  L in [2, 32768], k in [1, 65536], min_sep in [1, 32768]; min_sep >= L is legal and gives count = 0.
+ * How: values map to unsigned 64-bit keys that are strictly monotone in v (zero canonicalised; negatives with every bit flipped,
+ * the others with the sign bit flipped); the k-th largest key is found by a radix select over 8-bit digits with integer histograms;
+ * records above it are compacted, and of the records equal to it those with the smallest row-major index win (per-block counts, an
+ * exclusive sum in index order); the n selected records are ranked by counting the records that precede each.  Integer atomic adds
+ * are used for counts and slots only; no output bit depends on the order in which they land, and every run gives the same bytes.
+ * workspace: rnamsm_top_pairs_workspace_bytes(L, k) bytes (0 outside the limits of L and k), 256-byte aligned.  Every refusal -- a
+ * limit, ld < L, a null pointer, a workspace that is short or misaligned -- comes before the first launch, names the offending value
+ * (rnamsm_last_error) and touches no output.  Asynchronous: the call waits for nothing and reads nothing back. */
+size_t rnamsm_top_pairs_workspace_bytes(int L, int k);
+int rnamsm_top_pairs_f64(const double* x, int L, int64_t ld, int min_sep, int k, int32_t* pairs, double* scores, int32_t* count,
+                         void* workspace, size_t workspace_bytes, void* stream);
+int rnamsm_top_pairs_f32(const float* x, int L, int64_t ld, int min_sep, int k, int32_t* pairs, double* scores, int32_t* count,
+                         void* workspace, size_t workspace_bytes, void* stream);
+
 /* Whole forward, K0..K10 for one MSA, driven from C++ so that one call enqueues every launch
  * (MSATransformer.forward, model.py:338-416, with repr_layers=[num_layers], need_head_weights=True,
  * lm_head / contact head omitted -- their results are unused by the CLI).

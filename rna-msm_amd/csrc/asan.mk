@@ -26,6 +26,13 @@ $(ASAN_DRV): ../../tests/abi/abi_driver.c $(ASAN_LIB) ../../include/rnamsm.h
 	$(HIPCC) -x c -fsanitize=address,undefined -fno-sanitize-recover=undefined -fno-omit-frame-pointer -O1 -g \
 	    ../../tests/abi/abi_driver.c -x none -o $@ -Lbuild-asan -lrnamsm_hip_asan -Wl,-rpath,'$$ORIGIN'
 
-check-asan: $(ASAN_DRV)
+# the order key of top_pairs.hip (top_pairs_key.h) as a stand-alone host program under the same sanitizers
+KEY_CHECK = build-asan/top_pairs_key_check
+$(KEY_CHECK): ../../tests/native/top_pairs_key_check.cpp top_pairs_key.h
+	@mkdir -p build-asan
+	$(CXX) -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=undefined -fno-omit-frame-pointer $< -o $@
+
+check-asan: $(ASAN_DRV) $(KEY_CHECK)
 	ASAN_OPTIONS=detect_leaks=0:abort_on_error=0 UBSAN_OPTIONS=print_stacktrace=1 ./$(ASAN_DRV)
+	UBSAN_OPTIONS=print_stacktrace=1 ./$(KEY_CHECK)
 

@@ -63,6 +63,8 @@ MI_GAP_MODES = {"pairwise": 0, "state": 1}
 APC_MAX_L = 32768
 # rnamsm_msa_pdist / _neff / _coverage: columns, rows of the matrix form, rows of the other two
 PDIST_MAX_L, PDIST_MAX_N_MATRIX, PDIST_MAX_N = 32768, 16384, 1 << 20
+# rnamsm_top_pairs_f64 / _f32: the widest map, the longest list, the largest separation
+TOP_PAIRS_MAX_L, TOP_PAIRS_MAX_K, TOP_PAIRS_MAX_SEP = 32768, 65536, 32768
 
 
 class ModelDims(ctypes.Structure):
@@ -236,6 +238,9 @@ _SIGNATURES = {
     "rnamsm_seqid_filter_workspace_bytes": (c_size_t, [c_int, c_int]),
     "rnamsm_seqid_filter": (c_int, [c_void_p, c_int, c_int, c_int64, c_int, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p,
                                     c_void_p, c_void_p, c_size_t, c_void_p]),
+    "rnamsm_top_pairs_workspace_bytes": (c_size_t, [c_int, c_int]),
+    "rnamsm_top_pairs_f64": (c_int, [c_void_p, c_int, c_int64, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "rnamsm_top_pairs_f32": (c_int, [c_void_p, c_int, c_int64, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "rnamsm_forward_workspace_bytes": (c_size_t, [POINTER(ModelDims), c_int, c_int, c_int, c_int]),
     "rnamsm_forward": (c_int, [POINTER(ModelDims), POINTER(c_void_p), c_void_p, c_int, c_int, c_void_p, c_size_t,
                                c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int,

@@ -7,7 +7,9 @@ names, keys and defaults.
 from __future__ import annotations
 
 import dataclasses
+import re
 from dataclasses import dataclass, field
+from fractions import Fraction
 from pathlib import Path
 from typing import List, Tuple
 
@@ -79,6 +81,44 @@ def check_mi_weights(value: str, mi_on: bool = True) -> str:
     if value != "none" and not mi_on:
         raise ValueError(f"data.mi_weights={value!r} needs data.mi=true: it reweights the maps that key writes")
     return value
+
+
+def parse_top_pairs_spec(spec):
+    """A ranked-pair list's length as a string -> (count, None) for "N", an integer >= 1, or (None, Fraction x) for "<x>L", x > 0 a
+    plain decimal read exactly (fractions.Fraction of the string: no float arithmetic)."""
+    if not isinstance(spec, str):
+        raise ValueError(f"top_pairs spec {spec!r} is not a string")
+    text = spec.strip()
+    if re.fullmatch(r"[0-9]+", text):
+        if int(text) < 1:
+            raise ValueError(f"top_pairs spec {spec!r}: the count is below 1")
+        return int(text), None
+    m = re.fullmatch(r"([0-9]+(?:\.[0-9]*)?|\.[0-9]+)L", text)
+    if not m:
+        raise ValueError(f"top_pairs spec {spec!r} is neither a positive integer nor a positive decimal multiple of L such as 1.5L")
+    x = Fraction(m.group(1))
+    if x <= 0:
+        raise ValueError(f"top_pairs spec {spec!r}: the multiple of L is not positive")
+    return None, x
+
+
+TOP_PAIRS_MAX_SEP = 32768
+
+
+def check_top_pairs(value, min_sep=1) -> Tuple[str, int]:
+    """data.top_pairs ("" = off, else a spec: "N" or "<x>L") and data.top_pairs_min_sep; the message names the key."""
+    if not isinstance(value, str):
+        raise ValueError(f"data.top_pairs={value!r} is not a string (\"\" = off, a count such as 100, or a multiple of L such as 1.5L)")
+    if value != "":
+        try:
+            parse_top_pairs_spec(value)
+        except ValueError as e:
+            raise ValueError(f"data.top_pairs={value!r}: {e}") from None
+    if isinstance(min_sep, bool) or not isinstance(min_sep, int):
+        raise ValueError(f"data.top_pairs_min_sep={min_sep!r} is not an integer")
+    if not 1 <= min_sep <= TOP_PAIRS_MAX_SEP:
+        raise ValueError(f"data.top_pairs_min_sep={min_sep} outside [1, {TOP_PAIRS_MAX_SEP}]")
+    return value, min_sep
 
 
 def check_filter_seqid(min_seqid, max_seqid, step) -> Tuple[int, int, int]:
@@ -206,6 +246,15 @@ class DataConfig:                       # RNA_MSM_Inference.py:20-32
     # <id>_wmi.npy and <id>_wmip.npy INSTEAD of the unweighted pair.  "seqid" needs data.mi=true; with data.msa_stats on as well the
     # weights are computed once.
     mi_weights: str = "none"
+    # extra (not in the reference's CLI; the first step of its utils/metrics.py): "" = off; else the length of a ranked list of the
+    # strongest pairs, "N" (a count) or "<x>L" (max(1, ceil(x * L)) for the L of the map at hand, x a decimal: 0.5L, 1.5L, 2L).  For
+    # every pair map the run writes for an alignment -- contacts, invcov, mi / mip or wmi / wmip -- <id>_<map>_top.txt appears beside
+    # it: a header line, then `i j score` per pair, 1-based, strongest first, equal scores by i then j, pairs with
+    # j - i >= top_pairs_min_sep only (1 = every pair off the diagonal, the reference's minsep=0), NaN left out.  The lists are
+    # selected and ranked on the device (rnamsm.contacts.top_pairs) from the map where it lies.  A map whose k exceeds 65536 or whose
+    # L is below 2 gets one printed line instead; refused under RNAMSM_GATHER_TO_RANK0=1.
+    top_pairs: str = ""
+    top_pairs_min_sep: int = 1
 
 
 @dataclass
@@ -285,4 +334,5 @@ def parse_overrides(argv: List[str], cfg: Config = None) -> Config:
     check_mi_gaps(cfg.data.mi_gaps)
     check_mi_weights(cfg.data.mi_weights, cfg.data.mi)
     check_filter_seqid(cfg.data.filter_min_seqid, cfg.data.filter_max_seqid, cfg.data.filter_step)
+    check_top_pairs(cfg.data.top_pairs, cfg.data.top_pairs_min_sep)
     return cfg

@@ -8,6 +8,7 @@ lies on the device and turns it into the job that writes `<id>_contacts.npy`.
 """
 from __future__ import annotations
 
+import math
 import os
 from typing import List, NamedTuple, Sequence
 
@@ -15,6 +16,7 @@ import numpy as np
 import torch
 
 from . import _lib, ops
+from .config import parse_top_pairs_spec
 from .ss import long_refusal, plan_chunks
 
 # pixels (sum of L^2) of one packed call: the SS head's budget.  The head's own workspace is 121 floats per position and its
@@ -38,6 +40,35 @@ def predict_many(atps: Sequence[torch.Tensor], weight: torch.Tensor, bias: torch
     for chunk in plan_contact_chunks([a.shape[-1] for a in atps]):
         out += ops.contact_head_packed([atps[i] for i in chunk], weight, bias)
     return out
+
+
+def top_pairs(x, k: int, min_sep: int = 1, device=None):
+    """The top-k ranked pairs of a square pair map (ops.top_pairs; include/rnamsm.h states the rule): x a float32 or float64 [L, L]
+    numpy array (moved to `device`) or a tensor on the HIP device -> (pairs int64 [n, 2], scores float64 [n]) as numpy arrays,
+    trimmed to n = min(k, the number of candidates).  Candidates: i < j, j - i >= min_sep, not NaN; larger score first, then smaller i,
+    then smaller j.  There is no CPU path."""
+    if not isinstance(x, torch.Tensor):
+        if device is None or torch.device(device).type != "cuda":
+            raise _lib.RnamsmError("top_pairs: expected a HIP device for the map (no CPU path exists)")
+        x = torch.from_numpy(np.ascontiguousarray(x)).to(device)
+    rec = ops.top_pairs(x, k, min_sep)
+    n = int(rec.count.item())
+    return rec.pairs[:n].cpu().numpy().astype(np.int64), rec.scores[:n].cpu().numpy()
+
+
+def top_pairs_k(spec, L: int) -> int:
+    """data.top_pairs' spec -> k for a map of L positions: "N" = the integer N >= 1; "<x>L" = max(1, ceil(x * L)) with x > 0 read as an
+    exact decimal fraction (fractions.Fraction of the string, no float arithmetic: 0.1L at L = 30 is 3)."""
+    count, multiple = parse_top_pairs_spec(spec)
+    return count if multiple is None else max(1, math.ceil(multiple * int(L)))
+
+
+def format_top_pairs(pairs, scores, min_sep: int) -> str:
+    """The text of a `<id>_<map>_top.txt`: a header, then `i+1 j+1 repr(float(score))` per ranked pair (at most 65536 short lines,
+    formatted on the host).  A zero of either sign is printed as 0.0, as the device writes it."""
+    lines = [f"# i j score (1-based, j - i >= {int(min_sep)})"]
+    lines += [f"{int(i) + 1} {int(j) + 1} {float(s) + 0.0!r}" for (i, j), s in zip(pairs, scores)]
+    return "\n".join(lines) + "\n"
 
 
 class ContactResult(NamedTuple):

@@ -22,7 +22,7 @@ import torch
 
 from . import _lib, contacts, lm, ops, rsa, sharding, ss
 from .alphabet import RNAAlphabet
-from .config import Config, check_filter_seqid, check_invcov, check_long_heads, check_long_msa, check_mi, check_mi_gaps, check_mi_weights, check_msa_stats, check_ss_gemm_dtype
+from .config import Config, check_filter_seqid, check_invcov, check_long_heads, check_long_msa, check_mi, check_mi_gaps, check_mi_weights, check_msa_stats, check_ss_gemm_dtype, check_top_pairs
 from .model import MSATransformer
 from .msa import load_msa_tokens, msa_invcov_device, msa_mi_device, msa_mi_weighted_device, msa_stats_device
 
@@ -331,6 +331,15 @@ class _Switches(NamedTuple):
     batching: bool              # small alignments share groups at all
     pooled: bool                # ... formed from the pool, by shape, instead of in list order
     small_limit: int            # tokens up to which an alignment waits for company
+    top_pairs: str = ""         # data.top_pairs: "" = off, else the spec of the ranked lists' length
+    top_pairs_min_sep: int = 1  # data.top_pairs_min_sep
+
+
+def refuse_top_pairs_under_gather(top_pairs: str, gathering: bool) -> None:
+    if top_pairs and gathering:
+        raise ValueError(f"data.top_pairs={top_pairs!r} is not available with RNAMSM_GATHER_TO_RANK0=1: the ranked lists are made from the "
+                         f"maps where they lie on the computing rank's device, and the gather carries no such list; run without the "
+                         f"gather (every rank then writes its own files) or without the key")
 
 
 def read_switches(cfg: Config, gathering: bool) -> _Switches:
@@ -361,6 +370,10 @@ def read_switches(cfg: Config, gathering: bool) -> _Switches:
     # happens behind on_full, so the statistics and maps of the alignment as read see every row whatever the method
     filter_seqid = check_filter_seqid(getattr(cfg.data, "filter_min_seqid", 20), getattr(cfg.data, "filter_max_seqid", 90),
                                       getattr(cfg.data, "filter_step", 5))
+    # data.top_pairs: a ranked list of the strongest pairs beside every pair map the run writes, made on the device in the sink; off,
+    # nothing below differs.  Under a gather the maps reach rank 0 as host-staged items and the device text outputs are off: refused
+    top_pairs, top_pairs_min_sep = check_top_pairs(getattr(cfg.data, "top_pairs", ""), getattr(cfg.data, "top_pairs_min_sep", 1))
+    refuse_top_pairs_under_gather(top_pairs, gathering)
     # data.batch_small_msas: small alignments go through ONE launch set per group (forward_ragged: padded into one
     # frame, every MSA scaled by its own depth); a lone forward of a few hundred tokens costs 5.5 ms on a mostly
     # idle chip.  Groups: by shape from the pool (plan_groups); under gather_to_rank0 the RoundGatherer needs this
@@ -382,7 +395,7 @@ def read_switches(cfg: Config, gathering: bool) -> _Switches:
         ss_pairs=bool(getattr(cfg.data, "ss_pairs_device", True)) and not gathering,
         rsa_text=bool(getattr(cfg.data, "rsa_text_device", True)) and not gathering, contacts=bool(getattr(cfg.data, "contacts", False)),
         lm_mode=lm.check_lm_scores(getattr(cfg.data, "lm_scores", "")), exact=exact, packing=packing, batching=batching,
-        pooled=batching and not gathering, small_limit=small_limit)
+        pooled=batching and not gathering, small_limit=small_limit, top_pairs=top_pairs, top_pairs_min_sep=top_pairs_min_sep)
 
 
 def _load_model(cfg: Config, model: Optional[MSATransformer], alphabet, device) -> MSATransformer:
@@ -558,6 +571,29 @@ class _Sink:
     def put_mi(self, rna_id: str, maps: tuple) -> None:
         self.mi_maps[rna_id] = maps
 
+    def top_jobs(self, rna_id: str, maps: list) -> list:
+        """data.top_pairs: maps = [(name, the [L, L] map on the device)] -> one writer job per map: the top-k ranked pairs, selected
+        and ranked on the device from the map where it lies (ops.top_pairs; k from the spec and THIS map's L), written as
+        <id>_<name>_top.txt.  A map with L < 2 or a k beyond the library's limit gets one printed line and no list."""
+        jobs = []
+        for name, t in maps:
+            L = int(t.shape[-1])
+            k = contacts.top_pairs_k(self.sw.top_pairs, L)
+            if L < 2 or k > _lib.TOP_PAIRS_MAX_K:
+                why = f"L={L} is below 2" if L < 2 else f"k={k} exceeds {_lib.TOP_PAIRS_MAX_K}"
+                print(f"{rna_id}: no ranked pair list (data.top_pairs={self.sw.top_pairs}) for its {name} map: {why}")
+                continue
+            rec = ops.top_pairs(t if t.stride(-1) == 1 else t.contiguous(), k, self.sw.top_pairs_min_sep)
+            path = os.path.join(self.save_dir, f"{rna_id}_{name}_top.txt")
+
+            def write(pairs, scores, count, path=path) -> None:
+                n = int(count)
+                with open(path, "w") as f:
+                    f.write(contacts.format_top_pairs(pairs[:n], scores[:n], self.sw.top_pairs_min_sep))
+
+            jobs.append((write, (rec.pairs, rec.scores, rec.count)))
+        return jobs
+
     def deliver(self, idx: int, emb: torch.Tensor, atp: torch.Tensor, after: Optional[torch.cuda.Event], records: list) -> None:
         """records: the alignment's record of every head, None for a head skipped on it."""
         if self.gatherer is None:
@@ -606,6 +642,13 @@ class _Sink:
         if mi is not None:
             names = ("wmi", "wmip") if self.sw.mi_weighted else ("mi", "mip")
             cov_job += [(self.save_dir / f"{rna_id}_{names[0]}.npy", mi[0]), (self.save_dir / f"{rna_id}_{names[1]}.npy", mi[1])]
+        if self.sw.top_pairs:           # the ranked lists, from every pair map of this alignment while it is still on the device
+            maps = [("contacts", r.contacts) for h, r in zip(self.heads, records) if r is not None and isinstance(h, contacts.ContactHead)]
+            maps += [(Path(path).name[len(rna_id) + 1:-len(".npy")], t) for path, t in cov_job if t.dim() == 2]
+            tops = self.top_jobs(rna_id, maps)
+            extra += tops
+            if tops and after is not None:                  # the copies wait for the lists' kernels too
+                after = _record_event()
         if self.writer is not None:
             self.writer.submit([(self.save_dir / f"{rna_id}_atp.npy", atp), (self.save_dir / f"{rna_id}_emb.npy", emb)] + extra + cov_job,
                                lambda r=rna_id: self.written.append(r), after=after)
@@ -853,6 +896,7 @@ def extract_feat(cfg: Config, model: Optional[MSATransformer] = None, gather_to_
     import torch.distributed as dist
     rank = dist.get_rank() if dist.is_initialized() else 0
     world = dist.get_world_size() if dist.is_initialized() else 1
+    refuse_top_pairs_under_gather(getattr(cfg.data, "top_pairs", ""), gather_to_rank0)
     sw = read_switches(cfg, gather_to_rank0 and world > 1)
     device = torch.device(cfg.data.device)
     if device.type != "cuda":

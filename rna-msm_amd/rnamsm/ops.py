@@ -1401,6 +1401,41 @@ def apc(x: torch.Tensor, zero_diagonal: bool = False) -> torch.Tensor:
     return out
 
 
+class TopPairs(NamedTuple):
+    """What rnamsm_top_pairs_f64 / _f32 write, on the device."""
+    pairs: torch.Tensor            # int32 [k, 2]: (i, j) of the ranked pairs, 0-based; -1, -1 from row `count` on
+    scores: torch.Tensor           # float64 [k]: their values; NaN from row `count` on
+    count: torch.Tensor            # int32 scalar: min(k, the number of candidates)
+
+
+@_on_operand_device
+def top_pairs(x: torch.Tensor, k: int, min_sep: int = 1) -> TopPairs:
+    """The top-k ranked pairs of a square map (rnamsm_top_pairs_f64 / _f32; include/rnamsm.h states the rule): x float32 or float64
+    [L, L] on the device, read where it lies (ld = its row stride; a tensor whose last dimension is not contiguous is refused) ->
+    TopPairs.  Candidates are the pairs i < j with j - i >= min_sep whose value is not NaN; larger value first (-0.0 as +0.0), then
+    smaller i, then smaller j.  L in [2, 32768], k in [1, 65536], min_sep in [1, 32768]; the library refuses anything else.
+    Asynchronous: nothing is read back, count stays on the device."""
+    if not isinstance(x, torch.Tensor) or not x.is_cuda:
+        raise _lib.RnamsmError("top_pairs: expected a tensor on the HIP device (no CPU path exists)")
+    if x.dtype not in (torch.float32, torch.float64):
+        raise TypeError(f"top_pairs: expected float32 or float64, got {x.dtype}")
+    if x.dim() != 2 or x.shape[0] != x.shape[1]:
+        raise ValueError(f"top_pairs: expected a square map, got {tuple(x.shape)}")
+    L = x.shape[0]
+    if L > 1 and x.stride(1) != 1:
+        raise ValueError(f"top_pairs: the rows of the map are not contiguous (strides {tuple(x.stride())})")
+    lib = _lib.load()
+    k, min_sep = int(k), int(min_sep)
+    ws = _aligned_workspace(lib.rnamsm_top_pairs_workspace_bytes(L, k), x.device)
+    n_rows = min(max(k, 1), _lib.TOP_PAIRS_MAX_K)           # (a k the library refuses still gets real pointers: its message names k)
+    rec = TopPairs(torch.empty((n_rows, 2), dtype=torch.int32, device=x.device), torch.empty(n_rows, dtype=torch.float64, device=x.device),
+                   torch.empty((), dtype=torch.int32, device=x.device))
+    fn = lib.rnamsm_top_pairs_f64 if x.dtype == torch.float64 else lib.rnamsm_top_pairs_f32
+    _lib.check(fn(x.data_ptr(), L, x.stride(0) if L > 1 else L, min_sep, k, rec.pairs.data_ptr(), rec.scores.data_ptr(),
+                  rec.count.data_ptr(), ws.data_ptr(), ws.numel(), _stream()))
+    return rec
+
+
 @_on_operand_device
 def msa_pdist(msa_u8: torch.Tensor, want: str = "dist"):
     """MSA.pdist (utils/align.py:121-126; rnamsm_msa_pdist): msa uint8 [N, L] on the device -> want="dist": float64 [N, N] =
