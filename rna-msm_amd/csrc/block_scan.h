@@ -1,0 +1,48 @@
+// Two jobs of ONE block of 1024 threads that several files need (device code).
+#pragma once
+#include "common.h"
+
+namespace rnamsm {
+
+// the lowest n in [0, N) with pred(n), or -1 when there is none; the same value in every thread.  The caller's block is 1024 threads.
+template <class Pred>
+__device__ __forceinline__ int block_first_index(int N, Pred pred) {
+    __shared__ int first[1024];
+    int mine = INT32_MAX;
+    for (int n = threadIdx.x; n < N; n += 1024)
+        if (pred(n) && n < mine) mine = n;
+    first[threadIdx.x] = mine;
+    __syncthreads();
+    for (int h = 512; h > 0; h >>= 1) {
+        if ((int)threadIdx.x < h && first[threadIdx.x + h] < first[threadIdx.x]) first[threadIdx.x] = first[threadIdx.x + h];
+        __syncthreads();
+    }
+    return first[0] == INT32_MAX ? -1 : first[0];
+}
+
+// single block: flags -> the ascending list of the indices whose flag is set, 1024 at a time by an inclusive scan
+template <class Flag>
+__global__ __launch_bounds__(1024) void compact_flags_kernel(const Flag* __restrict__ flags, int N, int32_t* __restrict__ out) {
+    __shared__ int base;
+    __shared__ int cnt[1024];
+    if (threadIdx.x == 0) base = 0;
+    __syncthreads();
+    for (int start = 0; start < N; start += 1024) {
+        const int n = start + threadIdx.x;
+        const int f = (n < N && flags[n]) ? 1 : 0;
+        cnt[threadIdx.x] = f;
+        __syncthreads();
+        for (int off = 1; off < 1024; off <<= 1) {                        // inclusive scan
+            const int v = (int)threadIdx.x >= off ? cnt[threadIdx.x - off] : 0;
+            __syncthreads();
+            cnt[threadIdx.x] += v;
+            __syncthreads();
+        }
+        if (f) out[base + cnt[threadIdx.x] - 1] = n;
+        __syncthreads();
+        if (threadIdx.x == 1023) base += cnt[1023];
+        __syncthreads();
+    }
+}
+
+}  // namespace rnamsm

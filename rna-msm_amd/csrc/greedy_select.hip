@@ -17,7 +17,8 @@
 // compares against the row step s-1 picked), so for alignments of a few thousand rows the cost is the per-step latency:
 // there ONE launch per step (greedy_step_kernel: distances, re-reduced means, block argmax, and the grid-wide argmax by
 // whichever block finishes last) replaces three; deeper alignments keep the three kernels (one thread per row).
-#include "common.h"
+#include "block_scan.h"
+#include "msa_words.h"
 
 namespace rnamsm {
 
@@ -125,8 +126,7 @@ __global__ __launch_bounds__(256) void greedy_step_kernel(const uint8_t* __restr
             const uint32_t* a4 = reinterpret_cast<const uint32_t*>(a);
             const uint32_t* b4 = reinterpret_cast<const uint32_t*>(b);
             for (int c = lane; c < L / 4; c += 64) {
-                const uint32_t x = a4[c] ^ b4[c];
-                m += __popc((((x & 0x7f7f7f7fu) + 0x7f7f7f7fu) | x) & 0x80808080u);      // bytes that differ
+                m += __popc(nonzero_bytes32(a4[c] ^ b4[c]));                             // bytes that differ
             }
         } else {
             for (int c = lane; c < L; c += 64) m += a[c] != b[c];
@@ -248,30 +248,6 @@ __global__ __launch_bounds__(1024) void greedy_pick_kernel(const double* __restr
     }
 }
 
-// single block: taken flags -> ascending index list (indices = sorted(indices), utils/align.py:146)
-__global__ __launch_bounds__(1024) void greedy_compact_kernel(const uint8_t* __restrict__ taken, int N, int* out) {
-    __shared__ int base;
-    __shared__ int cnt[1024];
-    if (threadIdx.x == 0) base = 0;
-    __syncthreads();
-    for (int start = 0; start < N; start += 1024) {
-        const int n = start + threadIdx.x;
-        const int f = (n < N && taken[n]) ? 1 : 0;
-        cnt[threadIdx.x] = f;
-        __syncthreads();
-        for (int off = 1; off < 1024; off <<= 1) {                        // inclusive scan
-            const int v = (int)threadIdx.x >= off ? cnt[threadIdx.x - off] : 0;
-            __syncthreads();
-            cnt[threadIdx.x] += v;
-            __syncthreads();
-        }
-        if (f) out[base + cnt[threadIdx.x] - 1] = n;
-        __syncthreads();
-        if (threadIdx.x == 1023) base += cnt[1023];
-        __syncthreads();
-    }
-}
-
 __global__ void greedy_init_kernel(double* lut, int L, uint8_t* taken, int* chosen, int N, unsigned* counter) {
     const int n = blockIdx.x * blockDim.x + threadIdx.x;
     if (n == 0 && counter) *counter = 0u;
@@ -381,7 +357,8 @@ extern "C" int rnamsm_greedy_select(const uint8_t* msa, int N, int L, int num_se
             hipLaunchKernelGGL(greedy_pick_kernel, dim3(1), dim3(1024), 0, s, score, N, chosen, step, taken);
         }
     }
-    hipLaunchKernelGGL(greedy_compact_kernel, dim3(1), dim3(1024), 0, s, taken, N, out_indices);
+    // taken flags -> ascending index list (indices = sorted(indices), utils/align.py:146)
+    hipLaunchKernelGGL(compact_flags_kernel<uint8_t>, dim3(1), dim3(1024), 0, s, taken, N, out_indices);
     RNAMSM_CHECK_LAUNCH("greedy_select");
     return RNAMSM_OK;
 }

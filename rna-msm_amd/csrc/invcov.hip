@@ -14,16 +14,15 @@
 //   marginals  n_a(i) = sum_w popcount(P[w][i*K + a])                                    invcov_marginals_kernel
 //   counts     n_ab(i,j) = sum_w popcount(P[w][i*K+a] & P[w][j*K+b]), int32, a band of columns i at a time    invcov_count_kernel
 //   norm       the block in fp64, one-sided Jacobi, the upper triangle mirrored         invcov_norm_kernel
-// The count kernel sees the planes as a bit matrix of R = L*K rows and computes R x R popcount inner products like a GEMM: a
-// block of 256 threads owns 64 x 64 of them (64 / K alignment columns each way: the tile is counted in (column, symbol) rows, so any
-// K in 1..16 runs the same code), a thread 4 x 4 in 16 int32 registers; 16 words of the 64 + 64 rows are staged in LDS (2 x 8 KB,
-// word-major, so both the global reads and the LDS reads are contiguous 16-byte vectors).  Each sum is over one thread's words in
-// ascending order in integers: no atomics, the same bits on every run.  Tiles wholly below the diagonal are skipped unless the
-// caller asked for the counts.
+// The count kernel sees the planes as a bit matrix of R = L*K rows and computes R x R popcount inner products by word_tile.h's tile
+// loop, 16 words per step (2 x 8 KB of LDS): a block owns 64 x 64 of them (64 / K alignment columns each way: the tile is counted in
+// (column, symbol) rows, so any K in 1..16 runs the same code).  Tiles wholly below the diagonal are skipped unless the caller asked
+// for the counts.
 //
 // Mutual information (rnamsm_msa_mi) runs the same stage 1 and replaces the norm by mi_pair_kernel, a per-pair fp64 sum over the
 // integer table; its corrected map is apc.hip's rnamsm_apc_f64 of the map with a zero diagonal.
 #include "invcov_stage1.h"
+#include "word_tile.h"
 
 namespace rnamsm {
 
@@ -109,33 +108,7 @@ __global__ __launch_bounds__(256) void invcov_count_kernel(const uint64_t* __res
     }
     const int ty = threadIdx.x >> 4, tx = threadIdx.x & 15;
     int c[4][4];
-#pragma unroll
-    for (int x = 0; x < 4; ++x)
-#pragma unroll
-        for (int y = 0; y < 4; ++y) c[x][y] = 0;
-
-    for (int w0 = 0; w0 < Wp; w0 += IC_WK) {
-        // 16 words x 64 rows per operand = 512 vectors of two rows; the rows of one word are contiguous in P
-#pragma unroll
-        for (int v = threadIdx.x; v < IC_WK * IC_TILE / 2; v += 256) {
-            const int w = v >> 5, p = (v & 31) * 2;
-            const uint64_t* base = P + (int64_t)(w0 + w) * Rp;
-            *reinterpret_cast<uint4*>(&sA[w][p]) = *reinterpret_cast<const uint4*>(base + rb + p);
-            *reinterpret_cast<uint4*>(&sB[w][p]) = *reinterpret_cast<const uint4*>(base + cb + p);
-        }
-        __syncthreads();
-#pragma unroll
-        for (int w = 0; w < IC_WK; ++w) {
-            uint64_t a[4], b[4];
-#pragma unroll
-            for (int x = 0; x < 4; ++x) { a[x] = sA[w][ty * 4 + x]; b[x] = sB[w][tx * 4 + x]; }
-#pragma unroll
-            for (int x = 0; x < 4; ++x)
-#pragma unroll
-                for (int y = 0; y < 4; ++y) c[x][y] += __popcll(a[x] & b[y]);
-        }
-        __syncthreads();
-    }
+    word_tile_loop<IC_WK, false, AndPopcountOp>(P, Wp, Rp, rb, cb, nullptr, sA, sB, c);
 #pragma unroll
     for (int x = 0; x < 4; ++x) {
         const int64_t r = rb + ty * 4 + x;

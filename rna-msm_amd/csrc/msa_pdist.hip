@@ -6,13 +6,12 @@
 // Neff = the weights' sum.
 //
 // Data flow (all on the caller's stream; every buffer in the caller's workspace):
-//   pack    P[w][i] = the bytes of columns 8w .. 8w + 7 of row i as one 64-bit word (msa_pdist_words.h: the bytes as they are, zero
-//           past L), word-major; rows padded with zero words to a multiple of 64, words to a multiple of 8      pdist_pack_kernel
-//   pairs   m(i, j) = sum_w nonzero_bytes(P[w][i] ^ P[w][j]) like a GEMM: a block of 256 threads owns 64 x 64 pairs, a thread 4 x 4
-//           of them in 16 int32 registers; 8 words of the 64 + 64 rows are staged in LDS per step (2 x 4 KB, word-major, so the global
-//           reads and the LDS reads are contiguous 16-byte vectors).  Only tiles on or above the diagonal run.  Every sum is over one
-//           thread's words in ascending order in integers: no atomics, no scratch, the same bits on every run.  pdist_pair_kernel
-//   the loop has two epilogues (a template parameter):
+//   pack    P[w][i] = the bytes of columns 8w .. 8w + 7 of row i as one 64-bit word (msa_words.h with gap = 0: the bytes as they
+//           are, zero past L), word-major; rows padded with zero words to a multiple of 64, words to a multiple of 8
+//                                                                                                  word_tile.h: words_pack_kernel
+//   pairs   m(i, j) = sum_w nonzero_bytes(P[w][i] ^ P[w][j]) by word_tile.h's tile loop, 8 words per step (2 x 4 KB of LDS).  Only
+//           tiles on or above the diagonal run.                                                               pdist_pair_kernel
+//   the kernel has two epilogues (a template parameter):
 //   matrix       the tile goes through LDS and is written twice, as it is and transposed: rows of 64 consecutive elements either
 //                way, and the lower triangle is a copy of the upper -- exactly symmetric, the diagonal exactly 0 (x ^ x = 0)
 //   neighbours   the tile is thresholded; its row sums are the hits of its 64 rows against its column block, its column sums the
@@ -26,12 +25,11 @@
 //           0.0, then the 1024 sums are folded in halves (s[t] += s[t + 512], then + 256, ..., + 1)         pdist_neff_kernel
 //   coverage[c] = (double)#{rows with msa[r][c] != gap} / (double)N: 64 columns x 16 row lanes a block, integer counts, the 16
 //           lanes' counts added in LDS, one division                                                         msa_coverage_kernel
-#include "common.h"
-#include "msa_pdist_words.h"
+#include "word_tile.h"
 
 namespace rnamsm {
 
-constexpr int PD_TILE = 64;        // rows of a pair tile, each way
+constexpr int PD_TILE = WT_TILE;   // rows of a pair tile, each way
 constexpr int PD_WK = 8;           // words staged per step
 constexpr int PD_PITCH = PD_TILE + 1;
 constexpr int PD_MAX_L = 32768;
@@ -39,27 +37,21 @@ constexpr int PD_MAX_N_MATRIX = 16384;
 constexpr int PD_MAX_N = 1 << 20;
 constexpr size_t PD_PARTIAL_BYTES = (size_t)1 << 28;       // the partial table of the default workspace: at most 256 MB
 
-// one thread per (row, word), the words of a row on neighbouring threads
-__global__ __launch_bounds__(256) void pdist_pack_kernel(const uint8_t* __restrict__ msa, int N, int L, int64_t ld, int Wp, int64_t Np,
-                                                         uint64_t* __restrict__ P) {
+// P[w][p] = the recoded word (msa_words.h: pack_word) of columns 8w .. 8w + 7 of row order[p] -- of row p without an order; gap = 0:
+// the bytes as they are.  A position past N, or an order entry outside [0, N), packs as a row of zero words and reads nothing.  One
+// thread per (position, word), the words of a position on neighbouring threads.
+__global__ __launch_bounds__(256) void words_pack_kernel(const uint8_t* __restrict__ msa, int N, int L, int64_t ld, int gap,
+                                                         const int32_t* __restrict__ order, int Wp, int64_t Np, uint64_t* __restrict__ P) {
     const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (idx >= Np * Wp) return;
-    const int64_t row = idx / Wp;
-    const int w = (int)(idx - row * Wp);
-    P[(int64_t)w * Np + row] = row < N ? pd_pack_word(msa + row * ld, 8 * w, L - 8 * w) : 0ull;
+    const int64_t pos = idx / Wp;
+    const int w = (int)(idx - pos * Wp);
+    int64_t row = -1;
+    if (pos < N) row = order ? (int64_t)order[pos] : pos;
+    P[(int64_t)w * Np + pos] = (row >= 0 && row < N) ? pack_word(msa + row * ld, 8 * w, L - 8 * w, gap) : 0ull;
 }
-
-// acc + the set bits of mask in ONE instruction (v_bcnt_u32_b32 adds its second operand).  Written out because the compiler, left to
-// itself, counts into fresh registers and adds afterwards: one more instruction per dword, and 256 live temporaries per step.
-__device__ __forceinline__ int pd_count_add(uint32_t mask, int acc) {
-    int out;
-    asm("v_bcnt_u32_b32 %0, %1, %2" : "=v"(out) : "v"(mask), "v"(acc));
-    return out;
-}
-// c + pd_mismatches(a, b)
-__device__ __forceinline__ int pd_mismatches_add(uint64_t a, uint64_t b, int c) {
-    const uint64_t x = a ^ b;
-    return pd_count_add(pd_nonzero_bytes32((uint32_t)(x >> 32)), pd_count_add(pd_nonzero_bytes32((uint32_t)x), c));
+void words_pack(const uint8_t* msa, int N, int L, int64_t ld, int gap, const int32_t* order, int Wp, int64_t Np, uint64_t* P, hipStream_t s) {
+    hipLaunchKernelGGL(words_pack_kernel, dim3((unsigned)((Np * Wp + 255) / 256)), dim3(256), 0, s, msa, N, L, ld, gap, order, Wp, Np, P);
 }
 
 // MODE 0: the matrix (counts and / or dist, [N, N]).  MODE 1: the neighbour partials of the band of row blocks b0 .. b0 + nb - 1:
@@ -81,29 +73,7 @@ __global__ __launch_bounds__(256) void pdist_pair_kernel(const uint64_t* __restr
     const int64_t rb = (int64_t)bi * PD_TILE, cb = (int64_t)bj * PD_TILE;
     const int ty = threadIdx.x >> 4, tx = threadIdx.x & 15;
     int c[4][4];
-#pragma unroll
-    for (int x = 0; x < 4; ++x)
-#pragma unroll
-        for (int y = 0; y < 4; ++y) c[x][y] = 0;
-
-    const int sw = threadIdx.x >> 5, sp = (threadIdx.x & 31) * 2;       // this thread's vector of a panel: word sw, rows sp, sp + 1
-    for (int w0 = 0; w0 < Wp; w0 += PD_WK) {
-        const uint64_t* base = P + (int64_t)(w0 + sw) * Np;
-        *reinterpret_cast<uint4*>(&sA[sw][sp]) = *reinterpret_cast<const uint4*>(base + rb + sp);
-        *reinterpret_cast<uint4*>(&sB[sw][sp]) = *reinterpret_cast<const uint4*>(base + cb + sp);
-        __syncthreads();
-#pragma unroll
-        for (int w = 0; w < PD_WK; ++w) {
-            uint64_t a[4], b[4];
-#pragma unroll
-            for (int x = 0; x < 4; ++x) { a[x] = sA[w][ty * 4 + x]; b[x] = sB[w][tx * 4 + x]; }
-#pragma unroll
-            for (int x = 0; x < 4; ++x)
-#pragma unroll
-                for (int y = 0; y < 4; ++y) c[x][y] = pd_mismatches_add(a[x], b[y], c[x][y]);
-        }
-        __syncthreads();
-    }
+    word_tile_loop<PD_WK, false, MismatchOp>(P, Wp, Np, rb, cb, nullptr, sA, sB, c);
 
     const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
     if (MODE == 0) {
@@ -220,9 +190,10 @@ struct PdistWs {
 };
 static PdistWs pdist_ws(int N, int L) {
     PdistWs w;
-    w.T = (N + PD_TILE - 1) / PD_TILE;
-    w.Np = (int64_t)w.T * PD_TILE;
-    w.Wp = ((L + 7) / 8 + PD_WK - 1) / PD_WK * PD_WK;
+    const WordDims d = word_dims(N, L, PD_WK);
+    w.Np = d.Np;
+    w.Wp = d.Wp;
+    w.T = (int)(d.Np / PD_TILE);
     w.pack = 0;
     w.acc = (size_t)w.Wp * (size_t)w.Np * 8;                  // (a multiple of 256: Np * 8 is one of 512)
     w.partial = w.fixed = w.acc + (size_t)w.Np * 4;
@@ -230,11 +201,6 @@ static PdistWs pdist_ws(int N, int L) {
     return w;
 }
 static bool pdist_shape_ok(int N, int L, int max_n) { return N >= 1 && N <= max_n && L >= 1 && L <= PD_MAX_L; }
-
-static void pdist_pack(const uint8_t* msa, int N, int L, int64_t ld, const PdistWs& w, uint64_t* P, hipStream_t s) {
-    const int64_t total = w.Np * w.Wp;
-    hipLaunchKernelGGL(pdist_pack_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, msa, N, L, ld, w.Wp, w.Np, P);
-}
 
 }  // namespace rnamsm
 
@@ -259,7 +225,7 @@ extern "C" int rnamsm_msa_pdist(const uint8_t* msa, int N, int L, int64_t ld, in
                      "msa_pdist: counts / dist misaligned");
     hipStream_t s = static_cast<hipStream_t>(stream);
     uint64_t* P = reinterpret_cast<uint64_t*>(workspace);
-    pdist_pack(msa, N, L, ld, w, P, s);
+    words_pack(msa, N, L, ld, 0, nullptr, w.Wp, w.Np, P, s);
     hipLaunchKernelGGL(pdist_pair_kernel<0>, dim3(w.T, w.T), dim3(256), 0, s, P, w.Wp, w.Np, N, L, 0, w.T, counts, dist, 0.0,
                        (int32_t*)nullptr, (int32_t*)nullptr);
     RNAMSM_CHECK_LAUNCH("msa_pdist");
@@ -304,7 +270,7 @@ extern "C" int rnamsm_msa_neff(const uint8_t* msa, int N, int L, int64_t ld, dou
     const int band = room > (size_t)w.T ? w.T : (int)room;
     int32_t* pr = reinterpret_cast<int32_t*>(ws + w.partial);
     int32_t* pc = pr + (int64_t)band * w.Np;                   // pr: T x (band * 64) slots = band * Np
-    pdist_pack(msa, N, L, ld, w, P, s);
+    words_pack(msa, N, L, ld, 0, nullptr, w.Wp, w.Np, P, s);
     for (int b0 = 0; b0 < w.T; b0 += band) {
         const int nb = b0 + band < w.T ? band : w.T - b0;
         hipLaunchKernelGGL(pdist_pair_kernel<1>, dim3(w.T - b0, nb), dim3(256), 0, s, P, w.Wp, w.Np, N, L, b0, nb, (int32_t*)nullptr,

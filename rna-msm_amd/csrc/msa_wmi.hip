@@ -30,6 +30,7 @@
 // n = 4g .. 4g + 3, g ascending from an accumulator of 0.0; within a group the instruction's own order of its four products.  Rows
 // whose bit is clear add an exact 0.0.  c(i,a; j,b) and c(j,b; i,a) add the same values in the same order: equal bit for bit.
 // Tiles wholly below the diagonal are skipped unless the caller asked for the counts.
+#include "block_scan.h"
 #include "invcov_stage1.h"
 
 namespace rnamsm {
@@ -44,19 +45,8 @@ static_assert(IC_WK % WM_WORDS == 0, "the planes' word padding covers whole step
 
 // one block of 1024: the lowest row whose weight is NaN, +-inf, zero or negative; -1 when there is none
 __global__ __launch_bounds__(1024) void wmi_check_kernel(const double* __restrict__ w, int N, int32_t* __restrict__ verdict) {
-    __shared__ int first[1024];
-    int mine = INT32_MAX;
-    for (int n = threadIdx.x; n < N; n += 1024) {
-        const double v = w[n];
-        if (!(v > 0.0 && v < INFINITY) && n < mine) mine = n;           // (NaN fails both comparisons)
-    }
-    first[threadIdx.x] = mine;
-    __syncthreads();
-    for (int h = 512; h > 0; h >>= 1) {
-        if ((int)threadIdx.x < h && first[threadIdx.x + h] < first[threadIdx.x]) first[threadIdx.x] = first[threadIdx.x + h];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) *verdict = first[0] == INT32_MAX ? -1 : first[0];
+    const int first = block_first_index(N, [&](int n) { return !(w[n] > 0.0 && w[n] < INFINITY); });      // (NaN fails both comparisons)
+    if (threadIdx.x == 0) *verdict = first;
 }
 
 // Q[w][i*S + a] from P[w][i*K + a]; one thread per (word, column, state).  S == K + 1: state K is the word's rows without a symbol.

@@ -4,7 +4,7 @@
 //
 // The rule, all in integers.  Per pair of rows, both = the columns where neither has the gap, same = those of them
 // where the bytes are equal, nres(i) = both(i, i).  Row k is REDUNDANT to row j at threshold t iff both > 0 and 100 * same >= t * both.
-// The rows are walked in `order`, one pass per threshold (seqid_words.h: sq_thresholds): a row not kept yet is kept iff it is
+// The rows are walked in `order`, one pass per threshold (msa_words.h: sq_thresholds): a row not kept yet is kept iff it is
 // redundant to no kept row -- of an earlier pass, or earlier in this one; a row without residues is never kept unless it is the first
 // of the order, which always is.  The walk stops after the first pass that leaves num_seqs rows kept (num_seqs > 0), or after the
 // last threshold.
@@ -12,19 +12,17 @@
 // Data flow (all on the caller's stream, every buffer in the caller's workspace).  Everything past the pack works on POSITIONS of
 // the order, not on row indices: position p holds row order[p], so a chunk of the walk is a run of consecutive positions.
 //   check    the lowest position whose order entry lies outside [0, N), or -1: one block, one slot          seqid_order_check_kernel
-//   pack     P[w][p] = the recoded bytes of columns 8w .. 8w + 7 of row order[p] as a 64-bit word (seqid_words.h), word-major, the
+//   pack     P[w][p] = the recoded bytes of columns 8w .. 8w + 7 of row order[p] as a 64-bit word (msa_words.h), word-major, the
 //            positions padded to a multiple of 64 and the words to a multiple of 8 with zero words; an entry outside [0, N) packs
-//            as a row of gaps and reads nothing                                                              seqid_pack_kernel
+//            as a row of gaps and reads nothing                                                 word_tile.h: words_pack_kernel
 //   nres     per position, from its words; kept_at = -1; the kept count = 0                                  seqid_nres_kernel
 //   then, per pass at threshold t and per chunk of `chunk` positions, two launches ordered by the stream:
 //   cand     a block owns 64 positions of the chunk.  A CANDIDATE is a position not kept yet with residues (or position 0).  The
 //            block walks the kept list 64 at a time -- the kept count is read from device memory, so it holds what earlier chunks of
-//            this pass kept -- and accumulates both and same of its 64 x 64 pairs like pdist_pair_kernel accumulates m: 256 threads,
-//            a 4 x 4 register tile per thread, two int32 each, 8 words of the 64 + 64 rows staged in LDS per step.  The kept rows'
-//            words are GATHERED through the kept list (8-byte reads; no second copy of the rows).  Each pair is thresholded, a
-//            candidate redundant to any kept row is rejected; a block whose 64 positions are all rejected or no candidates stops
-//            walking.  rej[p] = 1 for a rejected position or one that is no candidate, else 0: one slot per position, written
-//            once a launch                                                                                   seqid_cand_kernel
+//            this pass kept -- and accumulates both and same of its 64 x 64 pairs by word_tile.h's tile loop, 8 words per step, the
+//            kept rows' words GATHERED through the kept list.  Each pair is thresholded, a candidate redundant to any kept row is
+//            rejected; a block whose 64 positions are all rejected or no candidates stops walking.  rej[p] = 1 for a rejected
+//            position or one that is no candidate, else 0: one slot per position, written once a launch      seqid_cand_kernel
 //   resolve  one block per chunk.  The chunk's survivors (rej = 0) as bit masks; the predicate of every pair of the chunk whose
 //            64 x 64 tile has survivors on both sides, on or above the diagonal, by the same tile loop, as a bit matrix in LDS
 //            (chunk x chunk bits).  Then ONE WAVE walks the chunk in order: the lowest survivor still alive is kept -- appended
@@ -34,14 +32,14 @@
 //   a pass nothing is read back.  A chunk's kept rows are exactly those the walk would keep row by row: a survivor is redundant to
 //   no row kept before the chunk (cand) and to no row kept earlier in the chunk (resolve), so ANY chunk size gives the same list.
 //   finish   the kept positions -> row flags and kept_at per row (each kept row written once), then the flags -> ascending
-//            indices by a block-wide scan                                        seqid_scatter_kernel, seqid_compact_kernel
+//            indices by a block-wide scan                          seqid_scatter_kernel, block_scan.h: compact_flags_kernel
 // No atomics anywhere; integer sums in a fixed order; the same indices on every run.
-#include "common.h"
-#include "seqid_words.h"
+#include "block_scan.h"
+#include "word_tile.h"
 
 namespace rnamsm {
 
-constexpr int SQ_TILE = 64;          // positions of a pair tile, each way
+constexpr int SQ_TILE = WT_TILE;     // positions of a pair tile, each way
 constexpr int SQ_WK = 8;             // words staged per step
 constexpr int SQ_MAX_L = 32768;
 constexpr int SQ_MAX_N = 1 << 20;
@@ -50,32 +48,8 @@ constexpr int SQ_MAX_TILES = SQ_MAX_CHUNK / SQ_TILE;
 
 // meta[0] = the kept count, meta[1] = the lowest position with an order entry outside [0, N), or -1
 __global__ __launch_bounds__(1024) void seqid_order_check_kernel(const int32_t* __restrict__ order, int N, int32_t* __restrict__ meta) {
-    __shared__ int s[1024];
-    int bad = 0x7fffffff;
-    if (order)
-        for (int p = threadIdx.x; p < N; p += 1024) {
-            const int r = order[p];
-            if ((r < 0 || r >= N) && p < bad) bad = p;
-        }
-    s[threadIdx.x] = bad;
-    __syncthreads();
-    for (int off = 512; off > 0; off >>= 1) {
-        if ((int)threadIdx.x < off && s[threadIdx.x + off] < s[threadIdx.x]) s[threadIdx.x] = s[threadIdx.x + off];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) meta[1] = s[0] == 0x7fffffff ? -1 : s[0];
-}
-
-// one thread per (position, word), the words of a position on neighbouring threads
-__global__ __launch_bounds__(256) void seqid_pack_kernel(const uint8_t* __restrict__ msa, int N, int L, int64_t ld, int gap,
-                                                         const int32_t* __restrict__ order, int Wp, int64_t Np, uint64_t* __restrict__ P) {
-    const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (idx >= Np * Wp) return;
-    const int64_t pos = idx / Wp;
-    const int w = (int)(idx - pos * Wp);
-    int64_t row = -1;
-    if (pos < N) row = order ? (int64_t)order[pos] : pos;
-    P[(int64_t)w * Np + pos] = (row >= 0 && row < N) ? sq_pack_word(msa + row * ld, 8 * w, L - 8 * w, gap) : 0ull;
+    const int bad = block_first_index(order ? N : 0, [&](int p) { return order[p] < 0 || order[p] >= N; });
+    if (threadIdx.x == 0) meta[1] = bad;
 }
 
 // one thread per (padded) position
@@ -88,62 +62,6 @@ __global__ __launch_bounds__(256) void seqid_nres_kernel(const uint64_t* __restr
     for (int w = 0; w < Wp; ++w) n += sq_residues(P[(int64_t)w * Np + p]);
     nres[p] = n;
     kept_at[p] = -1;
-}
-
-// acc + the set bits of mask in one instruction (msa_pdist.hip: pd_count_add)
-__device__ __forceinline__ int sq_count_add(uint32_t mask, int acc) {
-    int out;
-    asm("v_bcnt_u32_b32 %0, %1, %2" : "=v"(out) : "v"(mask), "v"(acc));
-    return out;
-}
-
-// The tile loop both kernels share: both and same of 64 x 64 pairs over all Wp words.  Side A is the 64 consecutive positions from
-// `ra`; side B is the 64 consecutive positions from `rb` (idxB == nullptr) or the positions idxB[0 .. 63] (LDS; -1 = no row: zero
-// words, so both = 0 and the pair is never redundant).  Thread (ty, tx) = (threadIdx.x / 16, % 16) owns the pairs
-// (ty * 4 + x, tx * 4 + y).  Ends with a barrier: the panels are free again.
-__device__ __forceinline__ void sq_tile_counts(const uint64_t* __restrict__ P, int Wp, int64_t Np, int64_t ra, int64_t rb, const int* idxB,
-                                               uint64_t (*sA)[SQ_TILE], uint64_t (*sB)[SQ_TILE], int (&both)[4][4], int (&same)[4][4]) {
-    const int ty = threadIdx.x >> 4, tx = threadIdx.x & 15;
-#pragma unroll
-    for (int x = 0; x < 4; ++x)
-#pragma unroll
-        for (int y = 0; y < 4; ++y) both[x][y] = same[x][y] = 0;
-    const int sw = threadIdx.x >> 5, sp = (threadIdx.x & 31) * 2;       // this thread's vector of a panel: word sw, rows sp, sp + 1
-    int64_t g0 = 0, g1 = 0;
-    if (idxB) { g0 = idxB[sp]; g1 = idxB[sp + 1]; }
-    for (int w0 = 0; w0 < Wp; w0 += SQ_WK) {
-        const uint64_t* base = P + (int64_t)(w0 + sw) * Np;
-        *reinterpret_cast<uint4*>(&sA[sw][sp]) = *reinterpret_cast<const uint4*>(base + ra + sp);
-        if (idxB) {
-            sB[sw][sp] = g0 >= 0 ? base[g0] : 0ull;
-            sB[sw][sp + 1] = g1 >= 0 ? base[g1] : 0ull;
-        } else {
-            *reinterpret_cast<uint4*>(&sB[sw][sp]) = *reinterpret_cast<const uint4*>(base + rb + sp);
-        }
-        __syncthreads();
-#pragma unroll
-        for (int w = 0; w < SQ_WK; ++w) {
-            uint64_t a[4], b[4];
-            uint32_t al[4], ah[4], bl[4], bh[4];
-#pragma unroll
-            for (int x = 0; x < 4; ++x) {
-                a[x] = sA[w][ty * 4 + x];
-                b[x] = sB[w][tx * 4 + x];
-                al[x] = sq_residues_lo(a[x]); ah[x] = sq_residues_hi(a[x]);
-                bl[x] = sq_residues_lo(b[x]); bh[x] = sq_residues_hi(b[x]);
-            }
-#pragma unroll
-            for (int x = 0; x < 4; ++x)
-#pragma unroll
-                for (int y = 0; y < 4; ++y) {
-                    const uint64_t d = a[x] ^ b[y];
-                    const uint32_t ml = al[x] & bl[y], mh = ah[x] & bh[y];
-                    both[x][y] = sq_count_add(mh, sq_count_add(ml, both[x][y]));
-                    same[x][y] = sq_count_add(mh & ~sq_residues_hi(d), sq_count_add(ml & ~sq_residues_lo(d), same[x][y]));
-                }
-        }
-        __syncthreads();
-    }
 }
 
 // grid = the 64-position tiles of the chunk that starts at position c0
@@ -170,13 +88,13 @@ __global__ __launch_bounds__(256) void seqid_cand_kernel(const uint64_t* __restr
         if (__ballot(s_rej[lane] != 0) == ~0ull) break;
         if (threadIdx.x < SQ_TILE) s_idx[threadIdx.x] = k0 + (int)threadIdx.x < nk ? kept_pos[k0 + threadIdx.x] : -1;
         __syncthreads();
-        int both[4][4], same[4][4];
-        sq_tile_counts(P, Wp, Np, ra, 0, s_idx, sA, sB, both, same);
+        ResiduePairOp::Acc c[4][4];
+        word_tile_loop<SQ_WK, true, ResiduePairOp>(P, Wp, Np, ra, 0, s_idx, sA, sB, c);
 #pragma unroll
         for (int x = 0; x < 4; ++x) {
             bool hit = false;
 #pragma unroll
-            for (int y = 0; y < 4; ++y) hit = hit || sq_redundant(both[x][y], same[x][y], t);
+            for (int y = 0; y < 4; ++y) hit = hit || sq_redundant(c[x][y].both, c[x][y].same, t);
             if (hit) s_rej[ty * 4 + x] = 1;          // several threads may store the same 1
         }
         __syncthreads();
@@ -207,13 +125,13 @@ __global__ __launch_bounds__(256) void seqid_resolve_kernel(const uint64_t* __re
         if (!s_surv[ti]) continue;
         for (int tj = ti; tj < tiles; ++tj) {
             if (!s_surv[tj]) continue;
-            int both[4][4], same[4][4];
-            sq_tile_counts(P, Wp, Np, c0 + (int64_t)ti * SQ_TILE, c0 + (int64_t)tj * SQ_TILE, nullptr, sA, sB, both, same);
+            ResiduePairOp::Acc c[4][4];
+            word_tile_loop<SQ_WK, false, ResiduePairOp>(P, Wp, Np, c0 + (int64_t)ti * SQ_TILE, c0 + (int64_t)tj * SQ_TILE, nullptr, sA, sB, c);
 #pragma unroll
             for (int x = 0; x < 4; ++x) {
                 uint32_t nib = 0;
 #pragma unroll
-                for (int y = 0; y < 4; ++y) nib |= sq_redundant(both[x][y], same[x][y], t) ? 1u << y : 0u;
+                for (int y = 0; y < 4; ++y) nib |= sq_redundant(c[x][y].both, c[x][y].same, t) ? 1u << y : 0u;
                 // the 16 threads of a row (neighbouring lanes) OR their nibbles into one 64-bit word, as two halves
                 uint32_t lo = tx < 8 ? nib << (4 * tx) : 0u, hi = tx >= 8 ? nib << (4 * (tx - 8)) : 0u;
 #pragma unroll
@@ -270,30 +188,6 @@ __global__ __launch_bounds__(256) void seqid_scatter_kernel(int nk, const int32_
     flags[r] = 1;
     if (kept_at_out) kept_at_out[r] = kept_at[p];
 }
-// single block: row flags -> ascending index list (greedy_compact_kernel's scan)
-__global__ __launch_bounds__(1024) void seqid_compact_kernel(const int32_t* __restrict__ flags, int N, int32_t* __restrict__ out) {
-    __shared__ int base;
-    __shared__ int cnt[1024];
-    if (threadIdx.x == 0) base = 0;
-    __syncthreads();
-    for (int start = 0; start < N; start += 1024) {
-        const int n = start + threadIdx.x;
-        const int f = (n < N && flags[n]) ? 1 : 0;
-        cnt[threadIdx.x] = f;
-        __syncthreads();
-        for (int off = 1; off < 1024; off <<= 1) {                        // inclusive scan
-            const int v = (int)threadIdx.x >= off ? cnt[threadIdx.x - off] : 0;
-            __syncthreads();
-            cnt[threadIdx.x] += v;
-            __syncthreads();
-        }
-        if (f) out[base + cnt[threadIdx.x] - 1] = n;
-        __syncthreads();
-        if (threadIdx.x == 1023) base += cnt[1023];
-        __syncthreads();
-    }
-}
-
 struct SeqidWs {
     size_t pack, nres, kept_at, kept_pos, rej, meta, total;      // offsets, each a multiple of 256
     int Wp;
@@ -301,8 +195,9 @@ struct SeqidWs {
 };
 static SeqidWs seqid_ws(int N, int L) {
     SeqidWs w;
-    w.Np = ((int64_t)N + SQ_TILE - 1) / SQ_TILE * SQ_TILE;
-    w.Wp = ((L + 7) / 8 + SQ_WK - 1) / SQ_WK * SQ_WK;
+    const WordDims d = word_dims(N, L, SQ_WK);
+    w.Np = d.Np;
+    w.Wp = d.Wp;
     const size_t ints = (size_t)w.Np * 4;                         // (a multiple of 256: Np is one of 64)
     w.pack = 0;
     w.nres = (size_t)w.Wp * (size_t)w.Np * 8;
@@ -355,8 +250,7 @@ extern "C" int rnamsm_seqid_filter(const uint8_t* msa, int N, int L, int64_t ld,
     const int chunk = tuning().seqid_filter_chunk;
 
     hipLaunchKernelGGL(seqid_order_check_kernel, dim3(1), dim3(1024), 0, s, order, N, meta);
-    const int64_t total = w.Np * w.Wp;
-    hipLaunchKernelGGL(seqid_pack_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, msa, N, L, ld, gap, order, w.Wp, w.Np, P);
+    words_pack(msa, N, L, ld, gap, order, w.Wp, w.Np, P, s);
     hipLaunchKernelGGL(seqid_nres_kernel, dim3((unsigned)((w.Np + 255) / 256)), dim3(256), 0, s, P, w.Wp, w.Np, nres, at, meta);
     RNAMSM_CHECK_LAUNCH("seqid_filter");
     int host_meta[2] = {0, -1};
@@ -378,7 +272,7 @@ extern "C" int rnamsm_seqid_filter(const uint8_t* msa, int N, int L, int64_t ld,
     const int nk = host_meta[0];
     hipLaunchKernelGGL(seqid_clear_kernel, dim3((N + 255) / 256), dim3(256), 0, s, N, rej, kept_at);
     hipLaunchKernelGGL(seqid_scatter_kernel, dim3((nk + 255) / 256), dim3(256), 0, s, nk, kept_pos, at, order, rej, kept_at);
-    hipLaunchKernelGGL(seqid_compact_kernel, dim3(1), dim3(1024), 0, s, rej, N, kept_indices);
+    hipLaunchKernelGGL(compact_flags_kernel<int32_t>, dim3(1), dim3(1024), 0, s, rej, N, kept_indices);
     RNAMSM_CHECK_LAUNCH("seqid_filter");
     const hipError_t e = hipStreamSynchronize(s);
     if (e != hipSuccess) return fail(RNAMSM_ERR_HIP, "seqid_filter: waiting for the stream: %s", hipGetErrorString(e));

@@ -52,4 +52,4 @@ def alignment(N: int, L: int, seed: int) -> np.ndarray:
 # every N of {1, 2, 63, 64, 65, 129, 200} (a lone row, tile seams, a ragged last tile, more than one tile each way) and every L of
 # {1, 7, 8, 9, 63, 64, 65, 513} (word seams, the masked tail, more than one staged step) at least twice
 SHAPES = [(1, 1), (1, 64), (2, 7), (2, 513), (63, 8), (63, 65), (64, 9), (64, 63), (65, 1), (65, 64), (129, 7), (129, 513), (200, 8),
-          (200, 9), (200, 63), (200, 65)]
+          (200, 9), (200, 63), (200, 65), (65, 7), (65, 63), (65, 65)]

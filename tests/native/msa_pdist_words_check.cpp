@@ -1,17 +1,19 @@
-// Host check of csrc/msa_pdist_words.h, the word form and the per-word mismatch count of csrc/msa_pdist.hip, against a byte loop.
+// Host check of csrc/msa_words.h with gap = 0, the word form and the per-word mismatch count of csrc/msa_pdist.hip, against a byte loop.
 // Built by tests/test_msa_stats_host.py with g++ -fsanitize=address,undefined and run as a program of its own.
 //   1. every one of the 65 536 pairs of byte values in every one of the eight lanes of a word, the other lanes equal (count 0 or 1)
 //      and the other lanes all different (count 7 or 8);
 //   2. rows of every length L = 1 .. 40 (every L mod 8, more than one word) in buffers of exactly L bytes -- AddressSanitizer
 //      sees a read past a row -- packed and counted against the byte loop, over the byte values that break a SWAR mask;
-//   3. the same rows inside a wider buffer whose bytes past L differ: the tail counts nothing.
+//   3. the same rows inside a wider buffer whose bytes past L differ: the tail counts nothing;
+//   4. every tail length n = 0 .. 8 (and below 0): pack_word with gap = 0 is the bytes as they are, zeros above them, from a buffer
+//      of exactly n bytes.
 // Prints "ok <checks>" and exits 0, or the first difference and exits 1.
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <vector>
 
-#include "../../rna-msm_amd/csrc/msa_pdist_words.h"
+#include "../../rna-msm_amd/csrc/msa_words.h"
 
 using namespace rnamsm;
 
@@ -24,7 +26,7 @@ static int fail(const char* what, long a, long b, long c, long d) {
 
 static int count_row(const uint8_t* a, const uint8_t* b, int L) {
     int m = 0;
-    for (int w = 0; 8 * w < L; ++w) m += pd_mismatches(pd_pack_word(a, 8 * w, L - 8 * w), pd_pack_word(b, 8 * w, L - 8 * w));
+    for (int w = 0; 8 * w < L; ++w) m += pd_mismatches(pack_word(a, 8 * w, L - 8 * w, 0), pack_word(b, 8 * w, L - 8 * w, 0));
     return m;
 }
 
@@ -67,9 +69,21 @@ int main() {
             if (got != want) return fail("padded rows", L, rep, got, want);
             checks += 2;
         }
-    // a tail of no bytes is the zero word
-    const uint8_t one[1] = {0xff};
-    if (pd_pack_word(one, 0, 0) != 0 || pd_pack_word(one, 0, -3) != 0) return fail("empty tail", 0, 0, 1, 0);
+    // 4. gap = 0 packs the bytes as they are: every tail length, exact buffers, every byte value in every lane
+    for (int n = -3; n <= 8; ++n)
+        for (int rep = 0; rep < 256; ++rep) {
+            const int len = n < 0 ? 0 : n;
+            std::vector<uint8_t> buf(len);
+            uint64_t want = 0;
+            for (int k = 0; k < len; ++k) {
+                state = state * 1664525u + 1013904223u;
+                buf[k] = k == rep % 8 ? (uint8_t)rep : (uint8_t)(state >> 16);
+                want |= (uint64_t)buf[k] << (8 * k);
+            }
+            const uint64_t got = pack_word(buf.data(), 0, n, 0);
+            if (got != want) return fail("gap 0 tail", n, rep, (long)got, (long)want);
+            ++checks;
+        }
     printf("ok %ld\n", checks);
     return 0;
 }

@@ -1,7 +1,7 @@
-// Host check of csrc/seqid_words.h, the recoded word form and the per-word pair counts of csrc/seqid_filter.hip, against a byte loop.
+// Host check of csrc/msa_words.h, the recoded word form and the per-word pair counts of csrc/seqid_filter.hip, against a byte loop.
 // Built by tests/test_seqid_filter_host.py with g++ -fsanitize=address,undefined and run as a program of its own.
 //   1. the recoding is one-to-one for every gap value, and sends the gap (and nothing else) to the zero byte;
-//   2. every tail length n = 0 .. 8 (and below 0): sq_pack_word reads exactly n bytes of a buffer of exactly that size --
+//   2. every tail length n = 0 .. 8 (and below 0): pack_word reads exactly n bytes of a buffer of exactly that size --
 //      AddressSanitizer sees a read past it -- and the bytes above are gaps;
 //   3. sq_pair and sq_residues on random words over the byte values that break a SWAR mask, for gaps 0, 0x2d, 0x80 and 0xff;
 //   4. rows of every length L = 1 .. 40 in buffers of exactly L bytes and inside wider buffers with garbage past L: both, same and
@@ -13,7 +13,7 @@
 #include <stdlib.h>
 #include <vector>
 
-#include "../../rna-msm_amd/csrc/seqid_words.h"
+#include "../../rna-msm_amd/csrc/msa_words.h"
 
 using namespace rnamsm;
 
@@ -33,7 +33,7 @@ static uint32_t next() {
 static void count_row(const uint8_t* a, const uint8_t* b, int L, int gap, int* both, int* same, int* nres) {
     *both = *same = *nres = 0;
     for (int w = 0; 8 * w < L; ++w) {
-        const uint64_t wa = sq_pack_word(a, 8 * w, L - 8 * w, gap), wb = sq_pack_word(b, 8 * w, L - 8 * w, gap);
+        const uint64_t wa = pack_word(a, 8 * w, L - 8 * w, gap), wb = pack_word(b, 8 * w, L - 8 * w, gap);
         int bo, sa;
         sq_pair(wa, wb, &bo, &sa);
         *both += bo;
@@ -48,7 +48,7 @@ int main() {
     for (int gap = 0; gap < 256; ++gap) {
         int seen[256] = {0};
         for (int b = 0; b < 256; ++b) {
-            const uint8_t r = sq_recode((uint8_t)b, gap);
+            const uint8_t r = recode((uint8_t)b, gap);
             if ((r == 0) != (b == gap)) return fail("recode zero", gap, b, r, b == gap ? 0 : 1);
             if (seen[r]++) return fail("recode one-to-one", gap, b, r, -1);
             ++checks;
@@ -61,9 +61,9 @@ int main() {
                 const int len = n < 0 ? 0 : n;
                 std::vector<uint8_t> buf(len);
                 for (int k = 0; k < len; ++k) buf[k] = (uint8_t)next();
-                const uint64_t w = sq_pack_word(buf.data(), 0, n, gaps[gi]);
+                const uint64_t w = pack_word(buf.data(), 0, n, gaps[gi]);
                 for (int k = 0; k < 8; ++k) {
-                    const uint8_t got = (uint8_t)(w >> (8 * k)), want = k < len ? sq_recode(buf[k], gaps[gi]) : 0;
+                    const uint8_t got = (uint8_t)(w >> (8 * k)), want = k < len ? recode(buf[k], gaps[gi]) : 0;
                     if (got != want) return fail("tail", n, k, got, want);
                 }
                 int res = 0;
@@ -85,7 +85,7 @@ int main() {
                 same += r && a[k] == b[k];
                 ra += a[k] != gaps[gi];
             }
-            const uint64_t wa = sq_pack_word(a, 0, 8, gaps[gi]), wb = sq_pack_word(b, 0, 8, gaps[gi]);
+            const uint64_t wa = pack_word(a, 0, 8, gaps[gi]), wb = pack_word(b, 0, 8, gaps[gi]);
             int bo, sa;
             sq_pair(wa, wb, &bo, &sa);
             if (bo != both) return fail("pair both", gi, rep, bo, both);

@@ -68,6 +68,16 @@ def test_counts_equal_numpys_integer_counts(device_results, name):
     assert np.array_equal(counts, want), name
 
 
+@pytest.mark.parametrize("N", [65, 1023, 1024, 1025])
+def test_counts_on_both_sides_of_a_step_of_sixteen_words(N):
+    """The count kernel stages 16 words = 1024 alignment rows per step: one step short by a row, one step exactly, one step and a
+    row; N = 65 is one word and a row.  rnamsm_msa_mi counts through the same launch."""
+    t = T.random_alignment(np.random.RandomState(N), N, 5, 4, gaps=0.15)
+    _, counts, syms = ops.msa_invcov(torch.from_numpy(t).to(DEV), T.GAP, want_counts=True)
+    assert np.array_equal(syms.cpu().numpy(), T.symbols(t).astype(np.int32))
+    assert np.array_equal(counts.cpu().numpy(), T.pair_counts(t))
+
+
 @pytest.mark.parametrize("name", CASES)
 def test_map_against_the_fp64_truth(device_results, yard, name):
     t = T.cases()[name]

@@ -110,7 +110,7 @@ def test_identical_rows_give_zero_and_rows_that_differ_everywhere_give_one():
 
 
 # ---- neighbours, weights, Neff ------------------------------------------------------------------------------------------------
-NEFF_SHAPES = [(1, 64), (2, 7), (63, 65), (64, 9), (65, 1), (129, 513), (200, 63), (200, 65)]
+NEFF_SHAPES = [(1, 64), (2, 7), (63, 65), (64, 9), (65, 1), (65, 7), (65, 63), (65, 64), (65, 65), (129, 513), (200, 63), (200, 65)]
 
 
 def _cutoffs(a):

@@ -67,7 +67,7 @@ def planted(N, L, seed):
     return a
 
 
-@pytest.mark.parametrize("L", [1, 7, 8, 9, 64, 65, 100])
+@pytest.mark.parametrize("L", [1, 7, 8, 9, 63, 64, 65, 100])
 @pytest.mark.parametrize("N", [1, 2, 3, 63, 64, 65, 130, 257])
 def test_shapes(N, L):
     a = planted(N, L, 7 * N + L)
@@ -78,6 +78,23 @@ def test_shapes(N, L):
         assert len(counts) == 5 and all(x < y for x, y in zip(counts, counts[1:])) and counts[0] > 1 and counts[-1] < N, passes
     same_as_truth(a, GAP, 0, memo=memo)
     same_as_truth(a, GAP, max(1, N // 4), memo=memo)
+
+
+@pytest.mark.parametrize("L", [1, 7, 63, 64, 65])
+def test_the_second_pass_gathers_a_second_block_of_kept_rows(L):
+    """130 rows: 100 mutually dissimilar ones (120 symbols; at L = 1 a hundred different bytes), then 30 copies of rows 5, 8, .., 92,
+    every second copy with a seventh of its columns changed where L > 1.  The pass at 50 keeps the hundred; the pass at 90 then
+    gathers them as a block of 64 and a block of 36 padded to 64, and keeps the changed copies only."""
+    rng = np.random.RandomState(900 + L)
+    a = np.empty((130, L), dtype=np.uint8)
+    a[:100] = 20 + (rng.permutation(120)[:100, None] if L == 1 else rng.randint(0, 120, size=(100, L)))
+    for k in range(30):
+        a[100 + k] = a[5 + 3 * k]
+        if k % 2 and L > 1:
+            a[100 + k, :(L + 6) // 7] = 200 + k
+    kept, at, passes = same_as_truth(a, 255, 130, 50, 90, 40)      # (no row has a gap: the default order is the rows as given)
+    assert [t for t, _ in passes] == [50, 90] and 64 < passes[0][1] < 128 and 64 < len(kept) < 128, passes
+    assert passes[0][1] == 100 and len(kept) == (100 if L == 1 else 115)
 
 
 def chains(N, places, L=16, t=75):

@@ -1,6 +1,6 @@
 """Alignment statistics (rnamsm_msa_pdist, rnamsm_msa_neff, rnamsm_msa_coverage; data.msa_stats) without a GPU: the symbols in the
 header, the binding and the built library's export list; the size functions at and outside the limits; every refusal the entry points
-make before anything is enqueued (on fabricated aligned addresses that are never dereferenced); csrc/msa_pdist_words.h -- the word form
+make before anything is enqueued (on fabricated aligned addresses that are never dereferenced); csrc/msa_words.h -- the word form
 and the per-word mismatch count -- compiled into a stand-alone program (tests/native/msa_pdist_words_check.cpp) with g++ and
 AddressSanitizer + UBSan; the key in the configuration; and the numpy restatement (tests/msa_stats_truth.py) against the reference's
 own MSA class (tests/golden/msa_stats_reference_2drb64.npz, made by tests/golden/make_golden_msa_stats.py) and against scipy."""
@@ -178,7 +178,7 @@ def test_sink_writes_the_two_vectors_it_was_left(tmp_path):
 @pytest.fixture(scope="module")
 def words_program(tmp_path_factory):
     cxx = shutil.which("g++")
-    assert cxx, "g++ is needed to build the host check of msa_pdist_words.h"
+    assert cxx, "g++ is needed to build the host check of msa_words.h"
     exe = str(tmp_path_factory.mktemp("msa_pdist_words") / "msa_pdist_words_check")
     subprocess.run([cxx, "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
                     os.path.join(ROOT, "tests", "native", "msa_pdist_words_check.cpp"), "-o", exe], check=True)

@@ -2,7 +2,7 @@
 host implementation against the plain-loop restatement (tests/seqid_filter_truth.py), indices and kept_at, on random alignments, the
 64-row 2DRB_1 excerpt and the full 1176-row alignment (tests/golden/tokens_2DRB_1_full.npz holds all of its rows); the restatement
 against the recorded figures on 2DRB_1; the threshold lists; the reader's cut; the keys; every refusal the entry point makes before
-anything is enqueued (on fabricated aligned addresses that are never dereferenced); csrc/seqid_words.h compiled into a stand-alone
+anything is enqueued (on fabricated aligned addresses that are never dereferenced); csrc/msa_words.h compiled into a stand-alone
 program (tests/native/seqid_words_check.cpp) with g++ and AddressSanitizer + UBSan."""
 import os
 import re
@@ -253,7 +253,7 @@ def test_the_keys_in_the_configuration():
 @pytest.fixture(scope="module")
 def words_program(tmp_path_factory):
     cxx = shutil.which("g++")
-    assert cxx, "g++ is needed to build the host check of seqid_words.h"
+    assert cxx, "g++ is needed to build the host check of msa_words.h"
     exe = str(tmp_path_factory.mktemp("seqid_words") / "seqid_words_check")
     subprocess.run([cxx, "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
                     os.path.join(ROOT, "tests", "native", "seqid_words_check.cpp"), "-o", exe], check=True)
