@@ -32,7 +32,14 @@ $(KEY_CHECK): ../../tests/native/top_pairs_key_check.cpp top_pairs_key.h
 	@mkdir -p build-asan
 	$(CXX) -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=undefined -fno-omit-frame-pointer $< -o $@
 
-check-asan: $(ASAN_DRV) $(KEY_CHECK)
+# the window plan of stitch.hip (stitch_plan.h) the same way: brute force up to the shipped width and the length limit
+PLAN_CHECK = build-asan/stitch_plan_check
+$(PLAN_CHECK): ../../tests/native/stitch_plan_check.cpp stitch_plan.h
+	@mkdir -p build-asan
+	$(CXX) -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=undefined -fno-omit-frame-pointer $< -o $@
+
+check-asan: $(ASAN_DRV) $(KEY_CHECK) $(PLAN_CHECK)
 	ASAN_OPTIONS=detect_leaks=0:abort_on_error=0 UBSAN_OPTIONS=print_stacktrace=1 ./$(ASAN_DRV)
 	UBSAN_OPTIONS=print_stacktrace=1 ./$(KEY_CHECK)
+	UBSAN_OPTIONS=print_stacktrace=1 ./$(PLAN_CHECK)
 

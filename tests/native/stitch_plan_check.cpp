@@ -1,9 +1,12 @@
 // Host check of rna-msm_amd/csrc/stitch_plan.h, the header the device stitcher computes its window plan with.
 //   stitch_plan_check                 every plan of W <= 24 (all admissible strides, L up to 3 W + 5) against a brute-force
 //                                     restatement: starts, window count, the windows that contain a column, the weights' ranges;
-//                                     then a few hand-computed plans.  Prints "plans ok"; exit 1 with a message otherwise.
+//                                     then a few hand-computed plans; then the same brute force at the shipped width (W = 1023,
+//                                     L up to 4096) and at the length limit RNAMSM_STITCH_MAX_L = 2^19 (windows of 2^18 columns, and
+//                                     1024 windows of 1023, there on the columns near both ends and every 97th in between).
+//                                     Prints "plans ok"; exit 1 with a message otherwise.
 //   stitch_plan_check L W stride      prints the starts, then every window's weights as fp32 bit patterns (hex), one per line.
-// Built by tests/test_windows_host.py with -fsanitize=address,undefined.
+// Built by tests/test_windows_host.py and by `make check-asan` with -fsanitize=address,undefined.
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -18,7 +21,8 @@ static int fail(const char* what, int L, int W, int stride, int at) {
     return 1;
 }
 
-static int check(int L, int W, int stride) {
+// sampled: the columns within 2 W of either end and every 97th in between (the plan is periodic in between); else every column.
+static int check(int L, int W, int stride, bool sampled = false) {
     if (!stitch_plan_ok(L, W, stride)) return fail("refused", L, W, stride, 0);
     const StitchPlan pl = stitch_plan(L, W, stride);
     int n = 1;
@@ -31,6 +35,7 @@ static int check(int L, int W, int stride) {
         if (k && st[k] <= st[k - 1]) return fail("starts ascend", L, W, stride, k);
     }
     for (int p = 0; p < L; ++p) {
+        if (sampled && p >= 2 * W && p < L - 2 * W && p % 97) continue;
         int lo, hi, blo = -1, bhi = -1, cnt = 0;
         stitch_cover(pl, p, lo, hi);
         for (int k = 0; k < n; ++k)
@@ -93,6 +98,27 @@ int main(int argc, char** argv) {
     {
         const StitchPlan pl = stitch_plan(3000, 1023, 512);
         if (pl.n != 5 || stitch_start(pl, 3) != 1536 || stitch_start(pl, 4) != 1977) return fail("hand: 3000", 3000, 1023, 512, pl.n);
+    }
+    // the shipped width up to RNAMSM_LONG_MAX_L, and the length limit of the stitcher
+    {
+        const int strides[3] = {512, 700, 1023}, lengths[4] = {1024, 1535, 2047, 4096};
+        for (int s = 0; s < 3; ++s)
+            for (int l = 0; l < 4; ++l, ++plans)
+                if (check(lengths[l], 1023, strides[s])) return 1;
+        const int LMAX = 1 << 19;
+        if (check(LMAX, (1 << 18) + 1, (1 << 17) + 1) || check(LMAX - 3, 300001, 150001)) return 1;
+        if (stitch_plan(LMAX, 1023, 512).n != 1024 || check(LMAX, 1023, 512, true)) return 1;
+        plans += 3;
+        const StitchPlan pl = stitch_plan(LMAX, (1 << 18) + 1, (1 << 17) + 1);        // starts 0, 2^17 + 1, 2^18 - 1; ramp 2^17
+        if (pl.n != 3 || stitch_start(pl, 1) != 131073 || stitch_start(pl, 2) != 262143 || pl.ramp != 131072)
+            return fail("hand: 2^19", LMAX, pl.W, pl.stride, pl.n);
+        // column 2^18 lies in all three; in window 1 (local 131071) left 131072, right 131074 -> 1; in window 2 (local 1) left 2 -> 2^-16
+        int lo, hi;
+        stitch_cover(pl, 1 << 18, lo, hi);
+        if (lo != 0 || hi != 2) return fail("hand: cover of 2^18", LMAX, pl.W, pl.stride, lo * 10 + hi);
+        if (stitch_weight(pl, 0, 1 << 18) != 1.0f / 131072.0f || stitch_weight(pl, 1, 131071) != 1.0f ||
+            stitch_weight(pl, 2, 1) != 2.0f / 131072.0f)
+            return fail("hand: weights at 2^18", LMAX, pl.W, pl.stride, 1 << 18);
     }
     std::printf("%ld plans ok\n", plans);
     return 0;

@@ -1,6 +1,8 @@
 """MSATransformer.forward_windows on synthetic weights, exact mode: an alignment wider than max_seqlen comes out as the numpy fp32
 stitch (tests/windows_truth.py) of the lone forwards of its windows, bit for bit; a singly covered region carries that window's
-own bits; the batched and the one-by-one route agree bit for bit; an alignment that fits is the lone forward itself."""
+own bits; the batched and the one-by-one route agree bit for bit; an alignment that fits is the lone forward itself.  A padded
+alignment is the stitch of its windows' forwards under the one mask decision forward_windows takes for all of them, on both routes;
+in a 16-bit mode the one-by-one route is the fp32 stitch of that mode's own lone forwards."""
 import numpy as np
 import pytest
 import torch
@@ -14,6 +16,7 @@ DEV = "cuda:0"
 # (embed_dim, heads, layers, max_seqlen, R, L)
 SMALL = (128, 2, 4, 33, 5, 70)            # (8 maps: a batch member stays 16-byte aligned at C = 33) W = 32, default stride 16: starts 0, 16, 32, 38 -- three-fold coverage at the right end
 FULL = (768, 12, 10, 17, 3, 40)           # the shipped width and depth: W = 16, stride 8: starts 0, 8, 16, 24
+WIDE = (128, 2, 4, 129, 3, 300)           # W = 128, default stride 64: starts 0, 64, 128, 172 -- the stitched atp is two 256-column tiles wide, three-fold coverage at the right end
 
 
 def _model(D, H, NL, max_seqlen):
@@ -30,7 +33,7 @@ def _tokens(R, L, seed):
     return torch.from_numpy(np.concatenate([np.full((R, 1), synthetic.CLS_IDX), body], 1).astype(np.int64)).to(DEV)
 
 
-@pytest.fixture(scope="module", params=[SMALL, FULL], ids=["d128", "d768"])
+@pytest.fixture(scope="module", params=[SMALL, FULL, WIDE], ids=["d128", "d768", "wide"])
 def case(request):
     """The model, the tokens, the lone forwards of the windows (computed once, never changed) and their numpy stitch."""
     D, H, NL, max_seqlen, R, L = request.param
@@ -116,3 +119,65 @@ def test_an_alignment_that_fits_is_the_lone_forward(case):
     assert got["emb"].cpu().numpy().tobytes() == ref["emb"].cpu().numpy().tobytes()
     assert got["atp"].cpu().numpy().tobytes() == ref["atp"].cpu().numpy().tobytes()
     assert windows.default_stride(W) == stride
+
+
+def _stitch_of_lone_forwards(model, toks, W, stride, has_padding=None):
+    """The numpy stitch of checked_forward_one(window, has_padding, need_repr=False) over the plan's windows -> (emb, atp) on the host."""
+    L = toks.shape[1] - 1
+    lone = []
+    for s in T.starts(L, W, stride):
+        out = model.checked_forward_one(torch.cat([toks[:, :1], toks[:, 1 + s:1 + s + W]], 1), has_padding, need_repr=False)
+        lone.append((out["emb"].cpu().numpy(), out["atp"].cpu().numpy()))
+    return T.stitch_rows([e for e, _ in lone], L, W, stride), T.stitch_pairs([a for _, a in lone], L, W, stride)
+
+
+# (the case, then the body column at which a <pad> tail starts in row 1 and in row 2)
+@pytest.mark.parametrize("params,tail1,tail2", [(SMALL, 34, 38), (WIDE, 150, 172)], ids=["d128", "wide"])
+def test_a_padded_alignment_is_the_stitch_of_its_windows_under_one_mask_decision(params, tail1, tail2, monkeypatch):
+    """Two rows end in <pad>: one tail starts inside the overlap of windows 1 and 2, so that window 0 holds no <pad> at all and
+    still runs with the masks on; the other starts where the last window starts and fills that row of it."""
+    D, H, NL, max_seqlen, R, L = params
+    model = _model(D, H, NL, max_seqlen)
+    W = max_seqlen - 1
+    stride = windows.default_stride(W)
+    st = T.starts(L, W, stride)
+    assert st[2] <= tail1 < st[1] + W and tail1 < st[3] and tail2 == st[-1]
+    toks = _tokens(R, L, seed=L + 1)
+    pad = model.vocab.pad_idx
+    assert pad == synthetic.PAD_IDX
+    toks[1, 1 + tail1:] = pad
+    toks[2, 1 + tail2:] = pad
+    assert not (toks[:, :1 + st[0] + W] == pad).any() and (toks[2, 1 + st[-1]:] == pad).all()
+    want_emb, want_atp = _stitch_of_lone_forwards(model, toks, W, stride, has_padding=True)
+    assert np.isfinite(want_emb).all() and np.isfinite(want_atp).all()
+    calls = {"batch": 0}
+    batch = model.checked_forward_batch
+    monkeypatch.setattr(model, "checked_forward_batch", lambda *a, **k: (calls.__setitem__("batch", calls["batch"] + 1), batch(*a, **k))[1])
+    batched = _host(model.forward_windows(toks))
+    assert calls == {"batch": 1}                                               # the padded alignment did take the batched route
+    single = _host(model.forward_windows(toks, batched=False))
+    assert calls == {"batch": 1}
+    for emb, atp in (batched, single):
+        assert emb.tobytes() == want_emb.tobytes() and atp.tobytes() == want_atp.tobytes()
+
+
+@pytest.mark.parametrize("mode", ["f16x3", "bf16"])
+def test_the_one_by_one_route_in_a_16bit_mode_is_the_fp32_stitch_of_that_mode_s_lone_forwards(mode):
+    """The stitch is fp32 whatever produced the windows.  (The batched route is not held to it in these modes: equal bits of the two
+    routes are promised for exact mode only.)"""
+    D, H, NL, max_seqlen, R, L = SMALL
+    model = _model(D, H, NL, max_seqlen)
+    W = max_seqlen - 1
+    stride = windows.default_stride(W)
+    toks = _tokens(R, L, seed=L)
+    exact = _host(model.forward_windows(toks, batched=False))
+    try:
+        model.gemm_dtype = mode
+        assert model.layers[3].column_self_attention.layer.gemm_dtype == mode
+        want_emb, want_atp = _stitch_of_lone_forwards(model, toks, W, stride)
+        emb, atp = _host(model.forward_windows(toks, batched=False))
+    finally:
+        model.gemm_dtype = "f32"
+    assert np.isfinite(emb).all() and np.isfinite(atp).all()
+    assert emb.tobytes() == want_emb.tobytes() and atp.tobytes() == want_atp.tobytes()
+    assert emb.tobytes() != exact[0].tobytes()                                 # the mode did run: these are not the exact path's bits

@@ -86,6 +86,21 @@ def test_weights():
             assert (u[cover[s:s + W] == 1] == 1).all(), (L, W, stride, k)
 
 
+def test_the_vectorised_weights_of_the_truth_are_its_loop_byte_for_byte():
+    """windows_truth.weights works on whole arrays so that the GPU tests can afford windows of 2^18 columns; weights_loop is the
+    definition it restates.  Every (W, stride) of this file's plans, every position of the window in the plan, and the shipped
+    width."""
+    count = 0
+    for W, stride in ([(W, s) for W in range(1, 71) for s in range((W + 1) // 2, W + 1)]
+                      + [(1023, 512), (1023, 700), (1023, 1022), (1023, 1023), (4097, 2049)]):
+        for first, last in ((True, False), (False, False), (False, True), (True, True)):
+            u = T.weights(W, stride, first, last)
+            assert u.dtype == np.float32 and u.shape == (W,)
+            assert u.tobytes() == T.weights_loop(W, stride, first, last).tobytes(), (W, stride, first, last)
+            count += 1
+    assert count > 5000
+
+
 def test_numpy_stitch_on_hand_computed_cases():
     # W = 2, stride = 1, L = 3: windows at 0 and 1, ramp 1 -> every weight is 1; column 1 is the plain mean of both windows
     xs = [np.array([[1.0], [3.0]], np.float32), np.array([[5.0], [7.0]], np.float32)]
@@ -152,8 +167,8 @@ def test_the_new_symbols_are_declared_bound_and_exported():
 
 
 def test_stitch_plan_header_under_sanitizers(tmp_path):
-    """stitch_plan.h on the host: every plan of W <= 24 against a brute-force restatement inside the program, and a few
-    hand-computed plans and weights given on the command line."""
+    """stitch_plan.h on the host: every plan of W <= 24, the shipped width up to L = 4096 and the plans at the length limit 2^19
+    against a brute-force restatement inside the program, and a few hand-computed plans and weights given on the command line."""
     cxx = shutil.which("g++")
     assert cxx, "g++ is needed to build the host check of stitch_plan.h"
     exe = str(tmp_path / "stitch_plan_check")
@@ -163,7 +178,8 @@ def test_stitch_plan_header_under_sanitizers(tmp_path):
     assert res.returncode == 0, (res.stdout[-2000:], res.stderr[-2000:])
     assert "plans ok" in res.stdout
     # the weights the program prints for (L, W, stride) are the numpy model's bits
-    for L, W, stride in ((70, 32, 16), (13, 5, 3), (200, 33, 17)):
+    for L, W, stride in ((70, 32, 16), (13, 5, 3), (200, 33, 17), (2100, 1023, 512), (1535, 1023, 700),
+                         (1 << 19, (1 << 18) + 1, (1 << 17) + 1), ((1 << 19) - 3, 300001, 150001)):
         res = subprocess.run([exe, str(L), str(W), str(stride)], capture_output=True, text=True)
         assert res.returncode == 0, res.stderr[-2000:]
         lines = res.stdout.split()

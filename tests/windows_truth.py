@@ -14,8 +14,8 @@ def starts(L, W, stride):
     return [k * stride for k in range(n - 1)] + [L - W]
 
 
-def weights(W, stride, first, last):
-    """u(i), i in [0, W), float32."""
+def weights_loop(W, stride, first, last):
+    """u(i), i in [0, W), float32: the definition, one column at a time."""
     ramp = W - stride
     if ramp == 0:
         return np.ones(W, dtype=F)
@@ -25,6 +25,21 @@ def weights(W, stride, first, last):
         right = ramp if last else W - i
         u[i] = F(min(left, right, ramp)) / F(ramp)
     return u
+
+
+def weights(W, stride, first, last):
+    """u(i), i in [0, W), float32: weights_loop on whole arrays (a window of 2^18 columns takes the loop seconds) -- the same
+    integers, converted to float32 exactly (ramp <= W < 2^24) and divided once; tests/test_windows_host.py holds the two equal."""
+    ramp = W - stride
+    if ramp == 0:
+        return np.ones(W, dtype=F)
+    i = np.arange(W, dtype=np.int64)
+    m = np.full(W, ramp, dtype=np.int64)
+    if not first:
+        m = np.minimum(m, i + 1)
+    if not last:
+        m = np.minimum(m, W - i)
+    return m.astype(F) / F(ramp)
 
 
 def _accumulate(num, den, seen, term, w):
