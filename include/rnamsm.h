@@ -1005,6 +1005,53 @@ int rnamsm_top_pairs_f64(const double* x, int L, int64_t ld, int min_sep, int k,
 int rnamsm_top_pairs_f32(const float* x, int L, int64_t ld, int min_sep, int k, int32_t* pairs, double* scores, int32_t* count,
                          void* workspace, size_t workspace_bytes, void* stream);
 
+/* A pair map against a target structure, counted on the device: the reference's rna_compute_precisions (the threshold sweep) and
+ * compute_precisions (precision among the top-ranked pairs), utils/metrics.py, as exact integer counts.  Shared by both calls:
+ *   x [L, L] with leading dimension ld >= L, float64 (_f64) or float32 (_f32); target int8 [L, L] with leading dimension ld_t >= L;
+ *   L in [2, 32768].  min_sep in [1, 32768] is the least j - i, as in rnamsm_top_pairs_*; min_sep >= L is legal and leaves no
+ *   candidate.  The Python wrappers named after the reference translate: the sweep's `minsep` is min_sep - 1 (its mask is
+ *   triu(minsep + 1)), compute_precisions' `minsep` is min_sep.
+ *   ONLY candidate elements of x and target are read: never the diagonal, the lower triangle, the band closer than min_sep or the
+ *   padding beyond column L.  A pair's value is v = (double)x[i, j] (exact for float32).
+ * rnamsm_pair_sweep_*: skip uint8 [L] on the device or NULL; a position with a non-zero byte drops its whole row and column (the
+ *   reference's missing_nt_index).  thresholds float64 [T] on the device, T in [1, 4096], strictly ascending and finite: that is the
+ *   caller's contract (the Python wrapper checks it before the upload; the device does not).
+ *   Candidates: the pairs i < j with j - i >= min_sep where neither i nor j is skipped.  A candidate is POSITIVE iff
+ *   target[i, j] != 0.  Its bin is the number of thresholds with v >= thresholds[t]: NaN gives 0, as np.greater_equal does; +inf and
+ *   -inf are ordinary values.  counts int64 [4, T], the rows tp, fp, tn, fn: tp[t] = the positives with bin > t, fp[t] = the negatives
+ *   with bin > t, fn[t] = P - tp[t], tn[t] = N - fp[t] (P, N = all positives, all negatives).  The counts add over a dataset.
+ *   How: a block streams row pieces with the thresholds and a histogram of 2 * (T + 1) bins in LDS (a binary search of at most 12
+ *   steps per value, equal bins added once per wave), adds one 64-bit integer per used bin into a global table, and one block takes
+ *   the suffix sums.  workspace: rnamsm_pair_sweep_workspace_bytes(T) bytes (0 outside the limits of T), 256-byte aligned.
+ * rnamsm_pair_precision_*: Candidates: the pairs i < j with j - i >= min_sep, j - i < max_sep when max_sep > 0 (0 = no upper limit),
+ *   target[i, j] >= 0 (a negative target is invalid, as in the reference) and x[i, j] not NaN.  They are ranked by the rule of
+ *   rnamsm_top_pairs_*: larger v first, then smaller i, then smaller j.  n = min(k, the number of candidates), k in [1, 65536].
+ *   cuts int32 [ncuts] on the device, ascending, each in [1, k] (the caller's contract; a cut is read as min(max(cut, 0), n)),
+ *   ncuts in [1, 64].  hits int32 [ncuts]: hits[c] = the number of the first min(cuts[c], n) ranked pairs whose target is > 0.
+ *   *count = n, an int32 on the DEVICE.  pairs (int32 [k, 2]) and scores (float64 [k]) are optional (NULL = not wanted) and defined as
+ *   in rnamsm_top_pairs_*.  With fewer than k candidates the list ends at n and the rest count as misses (the reference ranks its
+ *   -inf-filled pairs there and sums their targets).
+ *   How: a copy of the candidate band with NaN at the excluded pairs goes through rnamsm_top_pairs_* unchanged; one block gathers the
+ *   target at the n listed pairs, scans it and reads the sums at the cuts.  workspace:
+ *   rnamsm_pair_precision_workspace_bytes(L, k, elem_bytes) bytes with elem_bytes = 8 (_f64) or 4 (_f32) (0 outside the limits),
+ *   256-byte aligned; it holds the L x L copy.
+ * Integer atomic adds are used for counts only; no output bit depends on the order in which they land, and every run gives the same
+ * bytes.  Every refusal -- a limit, ld < L, ld_t < L, a null pointer, a workspace that is short or misaligned -- comes before the
+ * first launch, names the offending value (rnamsm_last_error) and touches no output.  Asynchronous: the calls wait for nothing and
+ * read nothing back. */
+size_t rnamsm_pair_sweep_workspace_bytes(int T);
+int rnamsm_pair_sweep_f64(const double* x, int L, int64_t ld, const int8_t* target, int64_t ld_t, const uint8_t* skip, int min_sep,
+                          const double* thresholds, int T, int64_t* counts, void* workspace, size_t workspace_bytes, void* stream);
+int rnamsm_pair_sweep_f32(const float* x, int L, int64_t ld, const int8_t* target, int64_t ld_t, const uint8_t* skip, int min_sep,
+                          const double* thresholds, int T, int64_t* counts, void* workspace, size_t workspace_bytes, void* stream);
+size_t rnamsm_pair_precision_workspace_bytes(int L, int k, int elem_bytes);
+int rnamsm_pair_precision_f64(const double* x, int L, int64_t ld, const int8_t* target, int64_t ld_t, int min_sep, int max_sep, int k,
+                              const int32_t* cuts, int ncuts, int32_t* hits, int32_t* count, int32_t* pairs, double* scores,
+                              void* workspace, size_t workspace_bytes, void* stream);
+int rnamsm_pair_precision_f32(const float* x, int L, int64_t ld, const int8_t* target, int64_t ld_t, int min_sep, int max_sep, int k,
+                              const int32_t* cuts, int ncuts, int32_t* hits, int32_t* count, int32_t* pairs, double* scores,
+                              void* workspace, size_t workspace_bytes, void* stream);
+
 /* Whole forward, K0..K10 for one MSA, driven from C++ so that one call enqueues every launch
  * (MSATransformer.forward, model.py:338-416, with repr_layers=[num_layers], need_head_weights=True,
  * lm_head / contact head omitted -- their results are unused by the CLI).

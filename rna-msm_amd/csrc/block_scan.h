@@ -1,4 +1,4 @@
-// Two jobs of ONE block of 1024 threads that several files need (device code).
+// Three jobs of ONE block of 1024 threads that several files need (device code).
 #pragma once
 #include "common.h"
 
@@ -18,6 +18,24 @@ __device__ __forceinline__ int block_first_index(int N, Pred pred) {
         __syncthreads();
     }
     return first[0] == INT32_MAX ? -1 : first[0];
+}
+
+// the inclusive sums of one value per thread over the block's 1024 threads (thread t gets v[0] + ... + v[t]); s: 1024 values of LDS
+// that are free again when the call returns
+template <class V>
+__device__ __forceinline__ V block_inclusive_sum(V v, V* s) {
+    const int t = threadIdx.x;
+    s[t] = v;
+    __syncthreads();
+    for (int off = 1; off < 1024; off <<= 1) {
+        const V w = t >= off ? s[t - off] : (V)0;
+        __syncthreads();
+        s[t] += w;
+        __syncthreads();
+    }
+    const V r = s[t];
+    __syncthreads();
+    return r;
 }
 
 // single block: flags -> the ascending list of the indices whose flag is set, 1024 at a time by an inclusive scan

@@ -65,6 +65,8 @@ APC_MAX_L = 32768
 PDIST_MAX_L, PDIST_MAX_N_MATRIX, PDIST_MAX_N = 32768, 16384, 1 << 20
 # rnamsm_top_pairs_f64 / _f32: the widest map, the longest list, the largest separation
 TOP_PAIRS_MAX_L, TOP_PAIRS_MAX_K, TOP_PAIRS_MAX_SEP = 32768, 65536, 32768
+# rnamsm_pair_sweep_* / rnamsm_pair_precision_*: the longest threshold table, the most cuts (L, k and min_sep as top_pairs)
+PAIR_SWEEP_MAX_T, PAIR_PRECISION_MAX_CUTS = 4096, 64
 
 
 class ModelDims(ctypes.Structure):
@@ -241,6 +243,12 @@ _SIGNATURES = {
     "rnamsm_top_pairs_workspace_bytes": (c_size_t, [c_int, c_int]),
     "rnamsm_top_pairs_f64": (c_int, [c_void_p, c_int, c_int64, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "rnamsm_top_pairs_f32": (c_int, [c_void_p, c_int, c_int64, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "rnamsm_pair_sweep_workspace_bytes": (c_size_t, [c_int]),
+    "rnamsm_pair_sweep_f64": (c_int, [c_void_p, c_int, c_int64, c_void_p, c_int64, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "rnamsm_pair_sweep_f32": (c_int, [c_void_p, c_int, c_int64, c_void_p, c_int64, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "rnamsm_pair_precision_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "rnamsm_pair_precision_f64": (c_int, [c_void_p, c_int, c_int64, c_void_p, c_int64, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "rnamsm_pair_precision_f32": (c_int, [c_void_p, c_int, c_int64, c_void_p, c_int64, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "rnamsm_forward_workspace_bytes": (c_size_t, [POINTER(ModelDims), c_int, c_int, c_int, c_int]),
     "rnamsm_forward": (c_int, [POINTER(ModelDims), POINTER(c_void_p), c_void_p, c_int, c_int, c_void_p, c_size_t,
                                c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int,

@@ -121,6 +121,18 @@ def check_top_pairs(value, min_sep=1) -> Tuple[str, int]:
     return value, min_sep
 
 
+def check_target_dir(value, min_sep=1) -> Tuple[str, int]:
+    """data.target_dir ("" = off, else a directory of known structures) and data.target_min_sep; the message names the key.  Whether
+    the directory exists is looked at when the run starts, not here."""
+    if not isinstance(value, str):
+        raise ValueError(f"data.target_dir={value!r} is not a string (\"\" = off, else a directory of <id>.bpseq / .ct / .npy targets)")
+    if isinstance(min_sep, bool) or not isinstance(min_sep, int):
+        raise ValueError(f"data.target_min_sep={min_sep!r} is not an integer")
+    if not 1 <= min_sep <= TOP_PAIRS_MAX_SEP:
+        raise ValueError(f"data.target_min_sep={min_sep} outside [1, {TOP_PAIRS_MAX_SEP}]")
+    return value, min_sep
+
+
 def check_filter_seqid(min_seqid, max_seqid, step) -> Tuple[int, int, int]:
     """data.filter_min_seqid / data.filter_max_seqid / data.filter_step (sample_method=seqid-filter); the message names the key."""
     for key, value in (("filter_min_seqid", min_seqid), ("filter_max_seqid", max_seqid), ("filter_step", step)):
@@ -255,6 +267,16 @@ class DataConfig:                       # RNA_MSM_Inference.py:20-32
     # L is below 2 gets one printed line instead; refused under RNAMSM_GATHER_TO_RANK0=1.
     top_pairs: str = ""
     top_pairs_min_sep: int = 1
+    # extra (not in the reference's CLI; its utils/metrics.py rna_compute_precisions and compute_precisions): "" = off; else a
+    # directory that holds the known structure of an alignment as <id>.bpseq, <id>.ct or <id>.npy (an integer [L, L] array; looked for
+    # in that order).  <id>_metrics.json then appears beside the alignment's files: the threshold sweep (tp / fp / tn / fn at the 1001
+    # thresholds and F1, PR, PR1, AUC) of the SS probability map, the decoded structure's precision / recall / F1, and P@L, P@L2, P@L5
+    # and their AUC (k = L) for contacts and every other pair map the run writes -- counted on the device (rnamsm.ops.pair_sweep,
+    # pair_precision) from the maps where they lie, pairs with j - i >= target_min_sep only.  metrics_summary.json at the end of the
+    # list carries the summed sweep counts, their scores and the mean of each precision.  A missing target, a length mismatch or
+    # L < 10 prints one line and leaves that entry out; refused under RNAMSM_GATHER_TO_RANK0=1.
+    target_dir: str = ""
+    target_min_sep: int = 1
 
 
 @dataclass
@@ -335,4 +357,5 @@ def parse_overrides(argv: List[str], cfg: Config = None) -> Config:
     check_mi_weights(cfg.data.mi_weights, cfg.data.mi)
     check_filter_seqid(cfg.data.filter_min_seqid, cfg.data.filter_max_seqid, cfg.data.filter_step)
     check_top_pairs(cfg.data.top_pairs, cfg.data.top_pairs_min_sep)
+    check_target_dir(cfg.data.target_dir, cfg.data.target_min_sep)
     return cfg

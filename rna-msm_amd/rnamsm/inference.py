@@ -8,6 +8,7 @@ to rank 0 over RCCL first (`gather_to_rank0=True`).
 """
 from __future__ import annotations
 
+import json
 import math
 import os
 import queue
@@ -20,9 +21,9 @@ from typing import Dict, List, NamedTuple, Optional
 import numpy as np
 import torch
 
-from . import _lib, contacts, lm, ops, rsa, sharding, ss
+from . import _lib, contacts, lm, metrics, ops, rsa, sharding, ss
 from .alphabet import RNAAlphabet
-from .config import Config, check_filter_seqid, check_invcov, check_long_heads, check_long_msa, check_mi, check_mi_gaps, check_mi_weights, check_msa_stats, check_ss_gemm_dtype, check_top_pairs
+from .config import Config, check_filter_seqid, check_invcov, check_long_heads, check_long_msa, check_mi, check_mi_gaps, check_mi_weights, check_msa_stats, check_ss_gemm_dtype, check_target_dir, check_top_pairs
 from .model import MSATransformer
 from .msa import load_msa_tokens, msa_invcov_device, msa_mi_device, msa_mi_weighted_device, msa_stats_device
 
@@ -333,12 +334,21 @@ class _Switches(NamedTuple):
     small_limit: int            # tokens up to which an alignment waits for company
     top_pairs: str = ""         # data.top_pairs: "" = off, else the spec of the ranked lists' length
     top_pairs_min_sep: int = 1  # data.top_pairs_min_sep
+    target_dir: str = ""        # data.target_dir: "" = off, else the directory of the known structures
+    target_min_sep: int = 1     # data.target_min_sep
 
 
 def refuse_top_pairs_under_gather(top_pairs: str, gathering: bool) -> None:
     if top_pairs and gathering:
         raise ValueError(f"data.top_pairs={top_pairs!r} is not available with RNAMSM_GATHER_TO_RANK0=1: the ranked lists are made from the "
                          f"maps where they lie on the computing rank's device, and the gather carries no such list; run without the "
+                         f"gather (every rank then writes its own files) or without the key")
+
+
+def refuse_target_dir_under_gather(target_dir: str, gathering: bool) -> None:
+    if target_dir and gathering:
+        raise ValueError(f"data.target_dir={target_dir!r} is not available with RNAMSM_GATHER_TO_RANK0=1: the counts are made from the "
+                         f"maps where they lie on the computing rank's device, and the gather carries no such record; run without the "
                          f"gather (every rank then writes its own files) or without the key")
 
 
@@ -374,6 +384,9 @@ def read_switches(cfg: Config, gathering: bool) -> _Switches:
     # nothing below differs.  Under a gather the maps reach rank 0 as host-staged items and the device text outputs are off: refused
     top_pairs, top_pairs_min_sep = check_top_pairs(getattr(cfg.data, "top_pairs", ""), getattr(cfg.data, "top_pairs_min_sep", 1))
     refuse_top_pairs_under_gather(top_pairs, gathering)
+    # data.target_dir: the accuracy of every map against a known structure, counted on the device in the sink; off, nothing differs
+    target_dir, target_min_sep = check_target_dir(getattr(cfg.data, "target_dir", ""), getattr(cfg.data, "target_min_sep", 1))
+    refuse_target_dir_under_gather(target_dir, gathering)
     # data.batch_small_msas: small alignments go through ONE launch set per group (forward_ragged: padded into one
     # frame, every MSA scaled by its own depth); a lone forward of a few hundred tokens costs 5.5 ms on a mostly
     # idle chip.  Groups: by shape from the pool (plan_groups); under gather_to_rank0 the RoundGatherer needs this
@@ -395,7 +408,8 @@ def read_switches(cfg: Config, gathering: bool) -> _Switches:
         ss_pairs=bool(getattr(cfg.data, "ss_pairs_device", True)) and not gathering,
         rsa_text=bool(getattr(cfg.data, "rsa_text_device", True)) and not gathering, contacts=bool(getattr(cfg.data, "contacts", False)),
         lm_mode=lm.check_lm_scores(getattr(cfg.data, "lm_scores", "")), exact=exact, packing=packing, batching=batching,
-        pooled=batching and not gathering, small_limit=small_limit, top_pairs=top_pairs, top_pairs_min_sep=top_pairs_min_sep)
+        pooled=batching and not gathering, small_limit=small_limit, top_pairs=top_pairs, top_pairs_min_sep=top_pairs_min_sep,
+        target_dir=target_dir, target_min_sep=target_min_sep)
 
 
 def _load_model(cfg: Config, model: Optional[MSATransformer], alphabet, device) -> MSATransformer:
@@ -554,6 +568,9 @@ class _Sink:
         self.invcov_maps: Dict[str, torch.Tensor] = {}      # id -> the map on the device, from the reader until the alignment is delivered
         self.msa_stats: Dict[str, tuple] = {}               # id -> (weights, coverage) on the device, likewise (data.msa_stats)
         self.mi_maps: Dict[str, tuple] = {}                 # id -> (mi, mip) on the device, likewise (data.mi)
+        self.device = device
+        self.metric_entries: Dict[str, dict] = {}           # id -> what <id>_metrics.json holds (data.target_dir), for the summary
+        self.sweep_table = None                             # the sweep's 1001 thresholds on the device, checked and uploaded once
         self.writer = _AsyncNpyWriter(device) if async_io and (not sw.gathering or rank == 0) else None
         # gather_to_rank0: outputs travel to rank 0 one ROUND (one MSA per rank) at a time, round k's RCCL transfers
         # overlapping round k+1's forward, and are handed to the writer as they arrive -- at most one round is resident
@@ -593,6 +610,92 @@ class _Sink:
 
             jobs.append((write, (rec.pairs, rec.scores, rec.count)))
         return jobs
+
+    def metrics_job(self, rna_id: str, records, maps: list) -> list:
+        """data.target_dir: the accuracy of this alignment's maps against <target_dir>/<id>.bpseq | .ct | .npy, counted on the device
+        from the maps where they lie (ops.pair_sweep for the SS probabilities, ops.pair_precision with k = L for every map of
+        `maps` = [(name, [L, L] map)]) -> one writer job, <id>_metrics.json, or none.  A missing target, a target of another length
+        or L < 10 prints one line that names the reason; that map (or the whole alignment) gets no entry."""
+        path = metrics.find_target(self.sw.target_dir, rna_id)
+        if path is None:
+            print(f"{rna_id}: no metrics (data.target_dir={self.sw.target_dir}): no {rna_id}.bpseq, .ct or .npy there")
+            return []
+        min_sep, targets = self.sw.target_min_sep, {}
+
+        def target_for(L: int, what: str):
+            """(the target on the device, the partner vector on the host) at this length, or None behind one printed line"""
+            if L not in targets:
+                try:
+                    if L < 10:
+                        raise ValueError(f"L={L} is below 10")
+                    if L > _lib.TOP_PAIRS_MAX_L:
+                        raise ValueError(f"L={L} exceeds {_lib.TOP_PAIRS_MAX_L}")
+                    t, partner = metrics.read_target(path, L)
+                    targets[L] = (torch.from_numpy(t).to(self.device), partner)
+                except (ValueError, OSError) as e:
+                    targets[L] = str(e)
+            if isinstance(targets[L], str):
+                print(f"{rna_id}: no metrics (data.target_dir) for its {what}: {targets[L]}")
+                return None
+            return targets[L]
+
+        tensors, layout, partner_true = [], [], None        # layout: (kind, name, L, how many tensors, host extras)
+        for h, r in zip(self.heads, records):
+            if r is None or not isinstance(h, ss.SSHead) or r.probs is None:
+                continue
+            L = int(r.probs.shape[-1])
+            got = target_for(L, "SS probability map")
+            if got is None:
+                continue
+            if self.sweep_table is None:
+                self.sweep_table = ops.sweep_table(metrics.sweep_thresholds(), self.device)
+            probs = r.probs if r.probs.stride(-1) == 1 else r.probs.contiguous()
+            tensors.append(ops.pair_sweep(probs, got[0], self.sweep_table, min_sep))
+            layout.append(("sweep", "ss", L, 1, None))
+            if r.structure is not None:
+                tensors.append(r.structure[0])
+                layout.append(("structure", "ss", L, 1, got[1]))
+        for name, t in maps:
+            L = int(t.shape[-1])
+            got = target_for(L, f"{name} map")
+            if got is None:
+                continue
+            cuts = metrics.precision_cuts(L)
+            rec = ops.pair_precision(t if t.stride(-1) == 1 else t.contiguous(), got[0], L, cuts, min_sep)
+            tensors += [rec.hits, rec.count]
+            layout.append(("precision", name, L, 2, cuts))
+        if not layout:
+            return []
+        out = os.path.join(self.save_dir, f"{rna_id}_metrics.json")
+
+        def write(*host) -> None:
+            host, entry = list(host), {"id": rna_id, "target": os.path.basename(path), "min_sep": min_sep}
+            for kind, name, L, n, extra in layout:
+                got, host = host[:n], host[n:]
+                if kind == "sweep":
+                    entry.setdefault("ss", {"L": L})["sweep"] = metrics.sweep_entry(got[0])
+                elif kind == "structure":
+                    entry.setdefault("ss", {"L": L})["structure"] = metrics.structure_scores(got[0], extra)
+                else:
+                    entry.setdefault("precision", {})[name] = metrics.precision_entry(got[0], int(got[1]), extra, L)
+            with open(out, "w") as f:
+                json.dump(entry, f, indent=1)
+                f.write("\n")
+            self.metric_entries[rna_id] = entry
+
+        return [(write, tuple(tensors))]
+
+    def write_metrics_summary(self, rank: int, world: int) -> None:
+        """data.target_dir, at the end of the list: metrics_summary.json (per rank where several ranks write) -- the summed sweep counts,
+        sweep_scores of the sum, and the mean of each precision over the alignments that had one, in list order."""
+        if not self.sw.target_dir:
+            return
+        position = {rna_id: n for n, rna_id in enumerate(self.ids)}
+        entries = [self.metric_entries[i] for i in sorted(self.metric_entries, key=position.__getitem__)]
+        name = "metrics_summary.json" if world == 1 else f"metrics_summary_rank{rank}.json"
+        with open(os.path.join(self.save_dir, name), "w") as f:
+            json.dump(metrics.summary(entries), f, indent=1)
+            f.write("\n")
 
     def deliver(self, idx: int, emb: torch.Tensor, atp: torch.Tensor, after: Optional[torch.cuda.Event], records: list) -> None:
         """records: the alignment's record of every head, None for a head skipped on it."""
@@ -642,12 +745,14 @@ class _Sink:
         if mi is not None:
             names = ("wmi", "wmip") if self.sw.mi_weighted else ("mi", "mip")
             cov_job += [(self.save_dir / f"{rna_id}_{names[0]}.npy", mi[0]), (self.save_dir / f"{rna_id}_{names[1]}.npy", mi[1])]
-        if self.sw.top_pairs:           # the ranked lists, from every pair map of this alignment while it is still on the device
+        if self.sw.top_pairs or self.sw.target_dir:         # every pair map of this alignment, while it is still on the device
             maps = [("contacts", r.contacts) for h, r in zip(self.heads, records) if r is not None and isinstance(h, contacts.ContactHead)]
             maps += [(Path(path).name[len(rna_id) + 1:-len(".npy")], t) for path, t in cov_job if t.dim() == 2]
-            tops = self.top_jobs(rna_id, maps)
-            extra += tops
-            if tops and after is not None:                  # the copies wait for the lists' kernels too
+            made = self.top_jobs(rna_id, maps) if self.sw.top_pairs else []           # the ranked lists
+            if self.sw.target_dir:                          # the accuracy against the known structure
+                made += self.metrics_job(rna_id, records, maps)
+            extra += made
+            if made and after is not None:                  # the copies wait for these kernels too
                 after = _record_event()
         if self.writer is not None:
             self.writer.submit([(self.save_dir / f"{rna_id}_atp.npy", atp), (self.save_dir / f"{rna_id}_emb.npy", emb)] + extra + cov_job,
@@ -897,6 +1002,7 @@ def extract_feat(cfg: Config, model: Optional[MSATransformer] = None, gather_to_
     rank = dist.get_rank() if dist.is_initialized() else 0
     world = dist.get_world_size() if dist.is_initialized() else 1
     refuse_top_pairs_under_gather(getattr(cfg.data, "top_pairs", ""), gather_to_rank0)
+    refuse_target_dir_under_gather(getattr(cfg.data, "target_dir", ""), gather_to_rank0)
     sw = read_switches(cfg, gather_to_rank0 and world > 1)
     device = torch.device(cfg.data.device)
     if device.type != "cuda":
@@ -933,6 +1039,7 @@ def extract_feat(cfg: Config, model: Optional[MSATransformer] = None, gather_to_
         if reader is not None:
             reader.shutdown(wait=True)
         sink.close()
+    sink.write_metrics_summary(rank, world)
     if rank == 0:
         print(f"Done! Generated files are saved at {save_dir}")
     return sink.written_in_list_order()

@@ -11,6 +11,7 @@ import functools
 import math
 from typing import List, NamedTuple, Optional, Sequence, Tuple
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -1434,6 +1435,131 @@ def top_pairs(x: torch.Tensor, k: int, min_sep: int = 1) -> TopPairs:
     _lib.check(fn(x.data_ptr(), L, x.stride(0) if L > 1 else L, min_sep, k, rec.pairs.data_ptr(), rec.scores.data_ptr(),
                   rec.count.data_ptr(), ws.data_ptr(), ws.numel(), _stream()))
     return rec
+
+
+def _pair_map_and_target(x, target, what: str):
+    """The operand checks pair_sweep and pair_precision share -> (L, ld, ld_t)."""
+    if not isinstance(x, torch.Tensor) or not x.is_cuda or not isinstance(target, torch.Tensor) or not target.is_cuda:
+        raise _lib.RnamsmError(f"{what}: expected the map and the target on the HIP device (no CPU path exists)")
+    if x.dtype not in (torch.float32, torch.float64):
+        raise TypeError(f"{what}: expected a float32 or float64 map, got {x.dtype}")
+    if target.dtype != torch.int8:
+        raise TypeError(f"{what}: expected an int8 target, got {target.dtype}")
+    if x.dim() != 2 or x.shape[0] != x.shape[1]:
+        raise ValueError(f"{what}: expected a square map, got {tuple(x.shape)}")
+    if tuple(target.shape) != tuple(x.shape):
+        raise ValueError(f"{what}: the target is {tuple(target.shape)}, the map {tuple(x.shape)}")
+    if target.device != x.device:
+        raise ValueError(f"{what}: the target is on {target.device}, the map on {x.device}")
+    L = x.shape[0]
+    if L > 1 and x.stride(1) != 1:
+        raise ValueError(f"{what}: the rows of the map are not contiguous (strides {tuple(x.stride())})")
+    if L > 1 and target.stride(1) != 1:
+        raise ValueError(f"{what}: the rows of the target are not contiguous (strides {tuple(target.stride())})")
+    return L, (x.stride(0) if L > 1 else L), (target.stride(0) if L > 1 else L)
+
+
+def _checked_thresholds(thresholds) -> "np.ndarray":
+    th = thresholds.detach().cpu().numpy() if isinstance(thresholds, torch.Tensor) else thresholds
+    th = np.ascontiguousarray(np.asarray(th, dtype=np.float64))
+    if th.ndim != 1:
+        raise ValueError(f"pair_sweep: expected a vector of thresholds, got shape {th.shape}")
+    if not np.isfinite(th).all():
+        raise ValueError(f"pair_sweep: threshold {int(np.flatnonzero(~np.isfinite(th))[0])} is not finite")
+    if th.size > 1 and not (th[1:] > th[:-1]).all():
+        at = int(np.flatnonzero(~(th[1:] > th[:-1]))[0]) + 1
+        raise ValueError(f"pair_sweep: the thresholds are not strictly ascending at index {at} ({th[at - 1]!r}, then {th[at]!r})")
+    return th
+
+
+class SweepTable(NamedTuple):
+    """A threshold table that has been checked (finite, strictly ascending) and lies on the device: float64 [T]."""
+    values: torch.Tensor
+
+
+def sweep_table(thresholds, device) -> SweepTable:
+    """Checks the thresholds once, on the host, and uploads them: pair_sweep takes the result as it is, so a caller that sweeps many
+    maps with one table (the CLI's 1001 values) pays the check and the copy once and its calls read nothing back."""
+    return SweepTable(torch.from_numpy(_checked_thresholds(thresholds)).to(device))
+
+
+@_on_operand_device
+def pair_sweep(x: torch.Tensor, target: torch.Tensor, thresholds, min_sep: int = 1, skip: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The threshold sweep of a pair map against a target (rnamsm_pair_sweep_f64 / _f32; include/rnamsm.h states the rule): x float32
+    or float64 [L, L] and target int8 [L, L] on the device, read where they lie (a last dimension that is not contiguous is refused);
+    thresholds: a SweepTable (sweep_table: checked and uploaded once; the call is then asynchronous and reads nothing back), or T
+    values, strictly ascending and finite, that are checked here on the host before the upload (a device tensor is copied back for
+    that check: build a SweepTable instead); T in [1, 4096]; skip: uint8 or bool [L] on the device, non-zero = the position's row and
+    column are left out -> int64 [4, T] on the device, the rows tp, fp, tn, fn.  Candidates are the pairs i < j with
+    j - i >= min_sep; a candidate is positive iff its target is not 0."""
+    L, ld, ld_t = _pair_map_and_target(x, target, "pair_sweep")
+    dev = x.device
+    if isinstance(thresholds, SweepTable):
+        th_dev = thresholds.values
+        if th_dev.device != dev:
+            raise ValueError(f"pair_sweep: the threshold table is on {th_dev.device}, the map on {dev}")
+    else:
+        th_dev = torch.from_numpy(_checked_thresholds(thresholds)).to(dev)
+    T = int(th_dev.numel())
+    skip_ptr = None
+    if skip is not None:
+        if not isinstance(skip, torch.Tensor) or not skip.is_cuda or skip.dtype not in (torch.uint8, torch.bool):
+            raise TypeError("pair_sweep: expected skip as a uint8 or bool tensor on the HIP device")
+        if tuple(skip.shape) != (L,):
+            raise ValueError(f"pair_sweep: skip is {tuple(skip.shape)}, expected ({L},)")
+        skip = skip.contiguous()
+        skip_ptr = skip.data_ptr()
+    lib = _lib.load()
+    ws = _aligned_workspace(lib.rnamsm_pair_sweep_workspace_bytes(T), dev)
+    counts = torch.empty((4, max(min(T, _lib.PAIR_SWEEP_MAX_T), 1)), dtype=torch.int64, device=dev)
+    fn = lib.rnamsm_pair_sweep_f64 if x.dtype == torch.float64 else lib.rnamsm_pair_sweep_f32
+    _lib.check(fn(x.data_ptr(), L, ld, target.data_ptr(), ld_t, skip_ptr, int(min_sep), th_dev.data_ptr(), T, counts.data_ptr(),
+                  ws.data_ptr(), ws.numel(), _stream()))
+    return counts
+
+
+class PairPrecision(NamedTuple):
+    """What rnamsm_pair_precision_f64 / _f32 count, on the device."""
+    hits: torch.Tensor             # int32 [ncuts]: the pairs with a target > 0 among the first min(cuts[c], count) ranked pairs
+    count: torch.Tensor            # int32 scalar: min(k, the number of candidates)
+
+
+@_on_operand_device
+def pair_precision(x: torch.Tensor, target: torch.Tensor, k: int, cuts, min_sep: int, max_sep: int = 0,
+                   want_pairs: bool = False):
+    """The hits among the top-ranked pairs of a map (rnamsm_pair_precision_f64 / _f32; include/rnamsm.h states the rule): x float32
+    or float64 [L, L] and target int8 [L, L] on the device, read where they lie (a last dimension that is not contiguous is refused).
+    Candidates: i < j, j - i >= min_sep, j - i < max_sep when max_sep > 0, target >= 0, value not NaN; ranked as ops.top_pairs
+    ranks.  cuts: ascending integers in [1, k], at most 64 (checked here; a device int32 tensor is checked too, by one copy to the
+    host) -> PairPrecision(hits, count); with want_pairs=True -> (PairPrecision, TopPairs), the ranked list beside the counts."""
+    L, ld, ld_t = _pair_map_and_target(x, target, "pair_precision")
+    k, min_sep, max_sep = int(k), int(min_sep), int(max_sep)
+    c = cuts.detach().cpu().numpy() if isinstance(cuts, torch.Tensor) else np.asarray(cuts)
+    if c.ndim != 1 or not np.issubdtype(c.dtype, np.integer):
+        raise ValueError(f"pair_precision: expected a vector of integer cuts, got shape {c.shape} of {c.dtype}")
+    c = c.astype(np.int64)
+    if c.size and (c.min() < 1 or c.max() > k):
+        raise ValueError(f"pair_precision: cut {int(c[(c < 1) | (c > k)][0])} outside [1, k={k}]")
+    if c.size > 1 and (c[1:] < c[:-1]).any():
+        raise ValueError("pair_precision: the cuts are not ascending")
+    dev = x.device
+    cuts_dev = torch.from_numpy(c.astype(np.int32)).to(dev)
+    ncuts = int(c.size)
+    lib = _lib.load()
+    ws = _aligned_workspace(lib.rnamsm_pair_precision_workspace_bytes(L, k, x.element_size()), dev)
+    hits = torch.empty(max(min(ncuts, _lib.PAIR_PRECISION_MAX_CUTS), 1), dtype=torch.int32, device=dev)
+    count = torch.empty((), dtype=torch.int32, device=dev)
+    pairs = scores = None
+    if want_pairs:
+        n_rows = min(max(k, 1), _lib.TOP_PAIRS_MAX_K)
+        pairs = torch.empty((n_rows, 2), dtype=torch.int32, device=dev)
+        scores = torch.empty(n_rows, dtype=torch.float64, device=dev)
+    fn = lib.rnamsm_pair_precision_f64 if x.dtype == torch.float64 else lib.rnamsm_pair_precision_f32
+    _lib.check(fn(x.data_ptr(), L, ld, target.data_ptr(), ld_t, min_sep, max_sep, k, cuts_dev.data_ptr(), ncuts, hits.data_ptr(),
+                  count.data_ptr(), pairs.data_ptr() if want_pairs else None, scores.data_ptr() if want_pairs else None, ws.data_ptr(),
+                  ws.numel(), _stream()))
+    rec = PairPrecision(hits, count)
+    return (rec, TopPairs(pairs, scores, count)) if want_pairs else rec
 
 
 @_on_operand_device
