@@ -658,6 +658,66 @@ int rnamsm_ss_struct_text_long_bytes(int L, size_t* ct_bytes, size_t* bpseq_byte
 int rnamsm_ss_pairs_long(const float* probs, const uint8_t* letters, int L, int32_t* partner, int32_t* counts, uint8_t* ct,
                          uint8_t* bpseq, void* workspace, size_t workspace_bytes, void* stream);
 
+/* f4 nested -- the pseudoknot-free structure of greatest expected accuracy, decoded from the [L, L] probabilities on the device
+ * (csrc/ss_nested.h: the arithmetic below in a plain C++ header that g++ and hipcc both compile; csrc/ss_nested.hip: the kernels).
+ * rnamsm_ss_pairs keeps every pair above 0.516 and removes multiplets base by base, so two crossing helices both survive; this
+ * decoding finds the NESTED matching that maximises the summed pair probability in excess of a threshold (a Nussinov-style
+ * max-plus dynamic programme, O(L^3)).  Everything is exact integer arithmetic: the result is specified bit for bit.
+ *   inputs    probs [L, L] fp32: only the strict upper triangle is read; theta, fp32 in [0, 1) (the reference's 0.516f by
+ *             default); min_loop in [0, RNAMSM_SS_NESTED_MAX_LOOP] (3 by default)
+ *   allowed   (i, j), i < j, iff j - i > min_loop and probs[i, j] > theta, compared in fp32.  NaN and -inf are never allowed; +inf
+ *             and values above 1 are allowed and count as 1.0
+ *   weights   Q(x) = floor(min(x, 1) * 2^18), exact in fp32 (a scaling by a power of two);
+ *             w(i, j) = max(1, Q(probs[i, j]) - Q(theta)) for an allowed pair, an int32.  At most L / 2 = 2048 pairs of weight
+ *             <= 2^18: every sum is below 2^29; "not allowed" is -2^30, and one such value plus any sum stays inside int32
+ *   table     N(i, j) = 0 for j <= i (and N(i, i - 1) = 0); for i < j
+ *             N(i, j) = max(N(i, j-1), max over k in [i, j - min_loop - 1] with (k, j) allowed of N(i, k-1) + w(k, j) + N(k+1, j-1));
+ *             the score is N(0, L-1)
+ *   traceback canonical, so the structure is unique: from (0, L-1) with an explicit stack; at (i, j), j > i: if N(i, j) == N(i, j-1)
+ *             go to (i, j-1) (j unpaired is preferred), else take the SMALLEST k that attains N(i, j), record the pair (k, j) and
+ *             continue in (i, k-1) and (k+1, j-1)
+ * Outputs:
+ *   partner int32 [L]      0 = unpaired, else the partner's 1-based index, as rnamsm_ss_pairs writes it
+ *   counts  int32 [5]      {pairs, bytes written to ct, bytes written to bpseq, fallback, score}; a score of -1 (no valid score is
+ *                          negative) says that the traceback did not end on the tables it was given: the structure is then partial
+ *   ct, bpseq              the bodies of `<name>.nested.ct` / `<name>.nested.bpseq`: rnamsm_ss_pairs' lines, bounds (32 L and 12 L
+ *                          bytes) and fallback word (a letter of 0 or >= 128 sets counts[3] = 1: the bodies are then unspecified)
+ *   dbn     uint8 [L]      '(' at the lower base of a pair, ')' at the upper one, '.' elsewhere
+ * workspace: rnamsm_ss_nested_workspace_bytes(B, Ls) bytes (B = 1 and &L for the lone call), 16-byte aligned, caller-owned (nothing
+ * is allocated inside): per member the int32 tables N and M(k, j) = w(k, j) + N(k+1, j-1), [Lp, Lp] each with Lp = L rounded up
+ * to 64 (8 Lp^2 bytes: 134 MB at the limit).  The size is 0 for B outside [1, RNAMSM_SS_MAX_BATCH], a null Ls or an L outside
+ * [1, RNAMSM_LONG_MAX_L].  Its contents on entry do not matter.
+ * One entry point with one limit, L in [1, RNAMSM_LONG_MAX_L]: ceil(L / 64) fill launches (one per diagonal of 64 x 64 cell tiles)
+ * and one traceback launch of one workgroup per member.  Packed: B members of unlike L, 32 per launch set (the descriptors travel
+ * as kernel arguments; items is a HOST array, free to go after the call); the member is a grid dimension, so a set costs the
+ * launches of its largest member.  A member's outputs are byte-identical to the lone call's, whatever its company; the members'
+ * outputs must not overlap.
+ * Refused (RNAMSM_ERR_INVALID) before anything is enqueued, rnamsm_last_error naming the argument or the member at fault: L, B,
+ * theta (also NaN) or min_loop out of range, a null pointer, probs / partner / counts not 4-byte aligned, a workspace that is not
+ * 16-byte aligned or too short.
+ * No atomics: the same inputs give the same bytes on every run.
+ * rnamsm_ss_nested_phases is rnamsm_ss_nested_packed with the two stages selectable, for measurement (tools/ss_nested_timing.py):
+ * phases = 1 the fill alone (no output is written), 2 the traceback alone, on a workspace that a fill with the same arguments has
+ * written, 3 both.  Its refusals are the packed call's, and phases outside [1, 3]. */
+#define RNAMSM_SS_NESTED_MAX_LOOP 32
+typedef struct {                 /* one structure of the batch */
+    const float*   probs;        /* device [L, L] */
+    const uint8_t* letters;      /* device [L] */
+    int32_t        L;            /* 1 .. RNAMSM_LONG_MAX_L */
+    int32_t*       partner;      /* device [L] */
+    int32_t*       counts;       /* device [5] */
+    uint8_t*       ct;           /* device, 32 L bytes */
+    uint8_t*       bpseq;        /* device, 12 L bytes */
+    uint8_t*       dbn;          /* device, L bytes */
+} rnamsm_ss_nested_item;
+size_t rnamsm_ss_nested_workspace_bytes(int B, const int* Ls);
+int rnamsm_ss_nested(const float* probs, const uint8_t* letters, int L, float theta, int min_loop, int32_t* partner, int32_t* counts,
+                     uint8_t* ct, uint8_t* bpseq, uint8_t* dbn, void* workspace, size_t workspace_bytes, void* stream);
+int rnamsm_ss_nested_packed(const rnamsm_ss_nested_item* items, int B, float theta, int min_loop, void* workspace,
+                            size_t workspace_bytes, void* stream);
+int rnamsm_ss_nested_phases(const rnamsm_ss_nested_item* items, int B, float theta, int min_loop, void* workspace,
+                            size_t workspace_bytes, int phases, void* stream);
+
 /* f5 -- RNA-MSM RSA (relative solvent accessibility) predictor (_downstream_tasks/RSA: predict.py, model/_0811/model_entry.py
  * FrameModel(Cin, 1, planes 64, depth 1, BatchNorm1d)) for an ensemble of n_models members in one set of four launches, exact fp32:
  *   x[c, p]  = (onehot(code[p])[c] - mu_oh[c]) / std_oh[c]  (c < 4, only with use_onehot),

@@ -35,6 +35,8 @@ SS_MAX_L = 1024
 SS_MAX_BATCH = 1024
 SS_TEXT_RECORD = 25                # bytes of one element of the .prob text: "%.18e" and its separator
 SS_CT_LINE_MAX, SS_BPSEQ_LINE_MAX = 32, 12      # rnamsm_ss_struct_text_bytes: bytes of the longest .ct / .bpseq line at L = 1024
+# rnamsm_ss_nested / _packed: the longest hairpin loop that may be asked for, and the defaults of the two parameters
+SS_NESTED_MAX_LOOP, SS_NESTED_THETA, SS_NESTED_MIN_LOOP = 32, 0.516, 3
 
 # index tables of rnamsm_rsa_head's weight-pointer array (include/rnamsm.h): four statistics, then 26 packed entries per member
 W_RSA_GLOBAL = ("mu_emb", "std_emb", "mu_oh", "std_oh")
@@ -90,6 +92,12 @@ class SsPairsItem(ctypes.Structure):
     """rnamsm_ss_pairs_item: one structure of an rnamsm_ss_pairs_packed batch (device pointers as integers)."""
     _fields_ = [("probs", c_void_p), ("letters", c_void_p), ("L", ctypes.c_int32), ("partner", c_void_p), ("counts", c_void_p),
                 ("ct", c_void_p), ("bpseq", c_void_p)]
+
+
+class SsNestedItem(ctypes.Structure):
+    """rnamsm_ss_nested_item: one structure of an rnamsm_ss_nested_packed batch (device pointers as integers)."""
+    _fields_ = [("probs", c_void_p), ("letters", c_void_p), ("L", ctypes.c_int32), ("partner", c_void_p), ("counts", c_void_p),
+                ("ct", c_void_p), ("bpseq", c_void_p), ("dbn", c_void_p)]
 
 
 class RsaItem(ctypes.Structure):
@@ -202,6 +210,11 @@ _SIGNATURES = {
                                     c_void_p]),
     "rnamsm_ss_prob_text_long_bytes": (c_size_t, [c_int]),
     "rnamsm_ss_prob_text_long": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
+    "rnamsm_ss_nested_workspace_bytes": (c_size_t, [c_int, POINTER(c_int)]),
+    "rnamsm_ss_nested": (c_int, [c_void_p, c_void_p, c_int, c_float, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                 c_size_t, c_void_p]),
+    "rnamsm_ss_nested_packed": (c_int, [POINTER(SsNestedItem), c_int, c_float, c_int, c_void_p, c_size_t, c_void_p]),
+    "rnamsm_ss_nested_phases": (c_int, [POINTER(SsNestedItem), c_int, c_float, c_int, c_void_p, c_size_t, c_int, c_void_p]),
     "rnamsm_ss_pairs_long_workspace_bytes": (c_size_t, [c_int]),
     "rnamsm_ss_struct_text_long_bytes": (c_int, [c_int, POINTER(c_size_t), POINTER(c_size_t)]),
     "rnamsm_ss_pairs_long": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),

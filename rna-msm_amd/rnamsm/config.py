@@ -26,6 +26,20 @@ def check_ss_gemm_dtype(value: str) -> str:
     return value
 
 
+def check_ss_nested(value, threshold, min_loop, ss_model_path: str) -> bool:
+    """data.ss_nested / data.ss_nested_threshold / data.ss_nested_min_loop (rnamsm_ss_nested's ranges)."""
+    from ._lib import SS_NESTED_MAX_LOOP
+    if not isinstance(value, bool):
+        raise ValueError(f"data.ss_nested={value!r} is not one of false, true")
+    if isinstance(threshold, bool) or not isinstance(threshold, (int, float)) or not 0.0 <= float(threshold) < 1.0:
+        raise ValueError(f"data.ss_nested_threshold={threshold!r} is not a number in [0, 1)")
+    if isinstance(min_loop, bool) or not isinstance(min_loop, int) or not 0 <= min_loop <= SS_NESTED_MAX_LOOP:
+        raise ValueError(f"data.ss_nested_min_loop={min_loop!r} is not an integer in [0, {SS_NESTED_MAX_LOOP}]")
+    if value and not ss_model_path:
+        raise ValueError("data.ss_nested=true needs data.ss_model_path: the nested structure is decoded from the SS head's probabilities")
+    return value
+
+
 def check_lm_scores(value: str) -> str:
     if value not in LM_SCORES_MODES:
         raise ValueError(f"data.lm_scores={value!r} is not one of {', '.join(repr(m) for m in LM_SCORES_MODES)}")
@@ -199,6 +213,12 @@ class DataConfig:                       # RNA_MSM_Inference.py:20-32
     # with the SS head on: the arithmetic of its convolutions -- f32 (exact, default) | bf16 (rnamsm_ss_head16: bf16 operands on
     # the matrix cores; accumulation, residual image and LayerNorm stay fp32).  Its own key: it does NOT follow model.gemm_dtype.
     ss_gemm_dtype: str = "f32"
+    # with the SS head on: also decode the NESTED (pseudoknot-free) structure of greatest summed pair probability above
+    # ss_nested_threshold, hairpin loops of at least ss_nested_min_loop bases, on the device (rnamsm_ss_nested), and write
+    # SS_result/<id>.dbn (dot-bracket), <id>.nested.ct and <id>.nested.bpseq beside the reference's files, which stay as they are
+    ss_nested: bool = False
+    ss_nested_threshold: float = 0.516
+    ss_nested_min_loop: int = 3
     # extra (not in the reference): "" = off; else an RSA model directory of the reference (_downstream_tasks/RSA/models/OH+RNA-MSM_Emb:
     # model_pcc_*.pt and the statistic_dict*.pickle files): the solvent-accessibility ensemble (rnamsm.rsa) then runs on every
     # alignment's embedding where it lies on the device, and RSA_result/<id>_<k>/<id>.txt, RSA_result/<id>_ensemble/<id>.txt are
@@ -347,6 +367,7 @@ def parse_overrides(argv: List[str], cfg: Config = None) -> Config:
             raise KeyError(f"unknown key {key!r} in group {group!r}")
         setattr(node, key, _coerce(value, getattr(node, key)))
     check_ss_gemm_dtype(cfg.data.ss_gemm_dtype)
+    check_ss_nested(cfg.data.ss_nested, cfg.data.ss_nested_threshold, cfg.data.ss_nested_min_loop, cfg.data.ss_model_path)
     check_lm_scores(cfg.data.lm_scores)
     check_long_msa(cfg.data.long_msa)
     check_long_heads(cfg.data.long_heads)

@@ -23,7 +23,7 @@ import torch
 
 from . import _lib, contacts, lm, metrics, ops, rsa, sharding, ss
 from .alphabet import RNAAlphabet
-from .config import Config, check_filter_seqid, check_invcov, check_long_heads, check_long_msa, check_mi, check_mi_gaps, check_mi_weights, check_msa_stats, check_ss_gemm_dtype, check_target_dir, check_top_pairs
+from .config import Config, check_filter_seqid, check_invcov, check_long_heads, check_long_msa, check_mi, check_mi_gaps, check_mi_weights, check_msa_stats, check_ss_gemm_dtype, check_ss_nested, check_target_dir, check_top_pairs
 from .model import MSATransformer
 from .msa import load_msa_tokens, msa_invcov_device, msa_mi_device, msa_mi_weighted_device, msa_stats_device
 
@@ -336,6 +336,7 @@ class _Switches(NamedTuple):
     top_pairs_min_sep: int = 1  # data.top_pairs_min_sep
     target_dir: str = ""        # data.target_dir: "" = off, else the directory of the known structures
     target_min_sep: int = 1     # data.target_min_sep
+    ss_nested: Optional[tuple] = None      # data.ss_nested: None = off, else (data.ss_nested_threshold, data.ss_nested_min_loop)
 
 
 def refuse_top_pairs_under_gather(top_pairs: str, gathering: bool) -> None:
@@ -350,6 +351,13 @@ def refuse_target_dir_under_gather(target_dir: str, gathering: bool) -> None:
         raise ValueError(f"data.target_dir={target_dir!r} is not available with RNAMSM_GATHER_TO_RANK0=1: the counts are made from the "
                          f"maps where they lie on the computing rank's device, and the gather carries no such record; run without the "
                          f"gather (every rank then writes its own files) or without the key")
+
+
+def refuse_ss_nested_under_gather(on: bool, gathering: bool) -> None:
+    if on and gathering:
+        raise ValueError("data.ss_nested=true is not available with RNAMSM_GATHER_TO_RANK0=1: the nested structure is decoded from the "
+                         "probabilities where they lie on the computing rank's device, and the gather carries no such record; run "
+                         "without the gather (every rank then writes its own files) or without the key")
 
 
 def read_switches(cfg: Config, gathering: bool) -> _Switches:
@@ -387,6 +395,10 @@ def read_switches(cfg: Config, gathering: bool) -> _Switches:
     # data.target_dir: the accuracy of every map against a known structure, counted on the device in the sink; off, nothing differs
     target_dir, target_min_sep = check_target_dir(getattr(cfg.data, "target_dir", ""), getattr(cfg.data, "target_min_sep", 1))
     refuse_target_dir_under_gather(target_dir, gathering)
+    # data.ss_nested: the nested structure of every alignment the SS head runs on, decoded on the device behind it; off, nothing differs
+    nested_theta, nested_loop = getattr(cfg.data, "ss_nested_threshold", 0.516), getattr(cfg.data, "ss_nested_min_loop", 3)
+    nested_on = check_ss_nested(getattr(cfg.data, "ss_nested", False), nested_theta, nested_loop, getattr(cfg.data, "ss_model_path", ""))
+    refuse_ss_nested_under_gather(nested_on, gathering)
     # data.batch_small_msas: small alignments go through ONE launch set per group (forward_ragged: padded into one
     # frame, every MSA scaled by its own depth); a lone forward of a few hundred tokens costs 5.5 ms on a mostly
     # idle chip.  Groups: by shape from the pool (plan_groups); under gather_to_rank0 the RoundGatherer needs this
@@ -409,7 +421,7 @@ def read_switches(cfg: Config, gathering: bool) -> _Switches:
         rsa_text=bool(getattr(cfg.data, "rsa_text_device", True)) and not gathering, contacts=bool(getattr(cfg.data, "contacts", False)),
         lm_mode=lm.check_lm_scores(getattr(cfg.data, "lm_scores", "")), exact=exact, packing=packing, batching=batching,
         pooled=batching and not gathering, small_limit=small_limit, top_pairs=top_pairs, top_pairs_min_sep=top_pairs_min_sep,
-        target_dir=target_dir, target_min_sep=target_min_sep)
+        target_dir=target_dir, target_min_sep=target_min_sep, ss_nested=(float(nested_theta), int(nested_loop)) if nested_on else None)
 
 
 def _load_model(cfg: Config, model: Optional[MSATransformer], alphabet, device) -> MSATransformer:
@@ -444,7 +456,7 @@ def _load_heads(sw: _Switches, model: MSATransformer, alphabet, device, rank: in
             print(f"SS head arithmetic: {sw.ss_dtype} (data.ss_gemm_dtype; independent of model.gemm_dtype={sw.gemm_dtype})")
         predictor = ss.load_predictor(sw.ss_path, device)
         predictor.gemm_dtype = sw.ss_dtype
-        heads.append(ss.SSHead(predictor, alphabet, base_lut, device, text_on=sw.ss_text, pairs_on=sw.ss_pairs))
+        heads.append(ss.SSHead(predictor, alphabet, base_lut, device, text_on=sw.ss_text, pairs_on=sw.ss_pairs, nested=sw.ss_nested))
     if sw.rsa_dir:      # (the reference program's seed; every alignment's draws are taken as its writer job is made, in delivery order)
         heads.append(rsa.RSAHead(rsa.load_ensemble(sw.rsa_dir, device), alphabet, base_lut, random.Random(2022),
                                  text_on=sw.rsa_text, device=device))
@@ -655,6 +667,9 @@ class _Sink:
             if r.structure is not None:
                 tensors.append(r.structure[0])
                 layout.append(("structure", "ss", L, 1, got[1]))
+            if r.nested is not None:                        # data.ss_nested: the nested structure against the same target
+                tensors.append(r.nested[0])
+                layout.append(("nested", "ss_nested", L, 1, got[1]))
         for name, t in maps:
             L = int(t.shape[-1])
             got = target_for(L, f"{name} map")
@@ -676,6 +691,8 @@ class _Sink:
                     entry.setdefault("ss", {"L": L})["sweep"] = metrics.sweep_entry(got[0])
                 elif kind == "structure":
                     entry.setdefault("ss", {"L": L})["structure"] = metrics.structure_scores(got[0], extra)
+                elif kind == "nested":
+                    entry["ss_nested"] = {"L": L, **metrics.structure_scores(got[0], extra)}
                 else:
                     entry.setdefault("precision", {})[name] = metrics.precision_entry(got[0], int(got[1]), extra, L)
             with open(out, "w") as f:

@@ -216,4 +216,12 @@ def summary(entries) -> Dict[str, object]:
             per_map.setdefault(name, []).append(rec)
     out["precision"] = {name: {"alignments": len(recs), **{n: float(np.mean(np.array([r[n] for r in recs], dtype=np.float64))) for n in PRECISION_NAMES}}
                         for name, recs in per_map.items()}
+    nested = [e["ss_nested"] for e in entries if "ss_nested" in e]       # data.ss_nested: absent, the summary is what it was
+    if nested:
+        def mean(name):          # over the alignments where the ratio exists (0 / 0 is NaN there); NaN where it exists nowhere
+            vals = np.array([r[name] for r in nested], dtype=np.float64)
+            vals = vals[~np.isnan(vals)]
+            return float(vals.mean()) if vals.size else float("nan")
+
+        out["ss_nested"] = {"alignments": len(nested), **{n: mean(n) for n in ("precision", "recall", "F1")}}
     return out

@@ -906,6 +906,80 @@ def _ss_pairs_run(route: Optional[_Route], probs, letters):
     return outs
 
 
+def _ss_nested_params(fn: str, theta: float, min_loop: int) -> Tuple[float, int]:
+    theta = float(theta)
+    if not 0.0 <= theta < 1.0:                                  # NaN fails both
+        raise ValueError(f"{fn}: theta = {theta} outside [0, 1)")
+    if int(min_loop) != min_loop or not 0 <= min_loop <= _lib.SS_NESTED_MAX_LOOP:
+        raise ValueError(f"{fn}: min_loop = {min_loop} outside [0, {_lib.SS_NESTED_MAX_LOOP}]")
+    return theta, int(min_loop)
+
+
+@_on_operand_device
+def ss_nested(probs: torch.Tensor, letters: torch.Tensor, theta: float = _lib.SS_NESTED_THETA, min_loop: int = _lib.SS_NESTED_MIN_LOOP):
+    """The nested structure of greatest summed probability above theta, decoded on the device (rnamsm_ss_nested: include/rnamsm.h
+    states the arithmetic); probs [L, L] fp32, L up to LONG_MAX_L, letters uint8 [L] -> (partner int32 [L]; counts int32 [5]: pairs,
+    bytes of the .ct body, bytes of the .bpseq body, fallback, score; the .ct body uint8 [32 L]; the .bpseq body uint8 [12 L]; the
+    dot-bracket line uint8 [L]).  The bodies are read as ss_pairs' are."""
+    return _ss_nested_run("ss_nested", [probs], [letters], theta, min_loop, True)[0]
+
+
+@_on_operand_device
+def ss_nested_packed(probs: Sequence[torch.Tensor], letters: Sequence[torch.Tensor], theta: float = _lib.SS_NESTED_THETA,
+                     min_loop: int = _lib.SS_NESTED_MIN_LOOP):
+    """ss_nested of every (probs[b], letters[b]) in one call (rnamsm_ss_nested_packed: the member is a grid dimension, so the call
+    costs the launches of its largest member) -> a list of ss_nested's tuples, each byte-identical to the lone call's.  One
+    allocation per output kind and one workspace (8 Lp^2 bytes per member, Lp = L rounded up to 64) per call: the returned tensors
+    are views."""
+    return _ss_nested_run("ss_nested_packed", probs, letters, theta, min_loop, False)
+
+
+def _ss_nested_run(fn: str, probs, letters, theta, min_loop, lone: bool, phase_events: Optional[list] = None):
+    theta, min_loop = _ss_nested_params(fn, theta, min_loop)
+    rule = functools.partial(_ss_pairs_operands, max_L=_lib.LONG_MAX_L)
+    members, device = _members(fn, rule, _lib.SS_MAX_BATCH, None, ("matrices", "letter rows", "structures"),
+                               {"probs": probs, "letters": letters}, checked=2, lone=lone)
+    if not members:
+        return []
+    B, Ls = len(members), [L for _, _, L in members]
+    lib = _lib.load()
+    ws = torch.empty(lib.rnamsm_ss_nested_workspace_bytes(B, (_lib.c_int * B)(*Ls)), dtype=torch.uint8, device=device)
+    outs = list(zip(_carved(Ls, device, torch.int32), _carved([5] * B, device, torch.int32),
+                    _carved([_lib.SS_CT_LINE_MAX * L for L in Ls], device, torch.uint8),
+                    _carved([_lib.SS_BPSEQ_LINE_MAX * L for L in Ls], device, torch.uint8), _carved(Ls, device, torch.uint8)))
+    args = [(p.data_ptr(), l.data_ptr(), L, *(t.data_ptr() for t in o)) for (p, l, L), o in zip(members, outs)]
+    if lone:
+        p, l, L, *o = args[0]
+        _lib.check(lib.rnamsm_ss_nested(p, l, L, theta, min_loop, *o, ws.data_ptr(), ws.numel(), _stream()))
+        return outs
+    items = (_lib.SsNestedItem * B)(*(_lib.SsNestedItem(*a) for a in args))
+    if phase_events is not None:          # the same launches in the same order, with an event recorded around each stage
+        for phases in (1, 2):
+            phase_events.append(_record_event())
+            _lib.check(lib.rnamsm_ss_nested_phases(items, B, theta, min_loop, ws.data_ptr(), ws.numel(), phases, _stream()))
+        phase_events.append(_record_event())
+        return outs
+    _lib.check(lib.rnamsm_ss_nested_packed(items, B, theta, min_loop, ws.data_ptr(), ws.numel(), _stream()))
+    return outs
+
+
+def _record_event() -> torch.cuda.Event:
+    e = torch.cuda.Event(enable_timing=True)
+    e.record()
+    return e
+
+
+@_on_operand_device
+def ss_nested_phase_times(probs: Sequence[torch.Tensor], letters: Sequence[torch.Tensor], theta: float = _lib.SS_NESTED_THETA,
+                          min_loop: int = _lib.SS_NESTED_MIN_LOOP):
+    """ss_nested_packed with the fill and the traceback enqueued by two calls (rnamsm_ss_nested_phases) and an event around each, for
+    tools/ss_nested_timing.py -> (ss_nested_packed's results, fill ms, traceback ms).  Synchronises the device."""
+    events: list = []
+    outs = _ss_nested_run("ss_nested_phase_times", probs, letters, theta, min_loop, False, events)
+    torch.cuda.synchronize()
+    return outs, events[0].elapsed_time(events[1]), events[1].elapsed_time(events[2])
+
+
 def _rsa_operands(fn: str, emb: torch.Tensor, bc: torch.Tensor, name: str, bc_name: str):
     """The operand rules of one alignment, for rsa_head and for every member of rsa_head_packed: -> (emb, row stride, base_codes,
     L) as the library reads them (an embedding whose rows are not contiguous, overlap or do not start at a 16-byte boundary is

@@ -245,6 +245,13 @@ class SSPredictor(nn.Module):
         probs = self.predict(atp, seq)
         return (probs,) + structure(probs, _letters_for(seq, letters, probs.device))
 
+    def predict_nested(self, atp: torch.Tensor, seq, letters=None, theta: float = _lib.SS_NESTED_THETA,
+                       min_loop: int = _lib.SS_NESTED_MIN_LOOP):
+        """predict() and nested_structure() of its result -> (probs, partner, counts [5], ct body, bpseq body, dbn), all on the
+        device.  letters: as for predict_structure."""
+        probs = self.predict(atp, seq)
+        return (probs,) + tuple(nested_structure(probs, _letters_for(seq, letters, probs.device), theta, min_loop))
+
     def predict_structure_many(self, atps: Sequence[torch.Tensor], seqs: Sequence, letters: Optional[Sequence] = None):
         """predict_many() and structure_many() of its results -> a list of predict_structure()'s tuples, each the lone call's."""
         seqs = list(seqs)
@@ -325,6 +332,111 @@ def structure_long(probs: torch.Tensor, letters: torch.Tensor):
     return ops.ss_pairs_long(probs, letters)
 
 
+def nested_structure(probs: torch.Tensor, letters: torch.Tensor, theta: float = _lib.SS_NESTED_THETA,
+                     min_loop: int = _lib.SS_NESTED_MIN_LOOP):
+    """The NESTED structure of the [L, L] probabilities `probs` on the HIP device, L up to LONG_MAX_L (rnamsm_ss_nested): the
+    pseudoknot-free matching that maximises the summed pair probability in excess of theta, hairpin loops of at least min_loop
+    bases -> (partner int32 [L]; counts int32 [5]: pairs, bytes of the `.ct` body, bytes of the `.bpseq` body, fallback, score;
+    ct body uint8 [32 L]; bpseq body uint8 [12 L]; the dot-bracket line uint8 [L]).  Exact integer arithmetic, stated in
+    include/rnamsm.h and, in NumPy, by nested_structure_host: the same bytes for the same inputs, always.  Device only."""
+    return ops.ss_nested(probs, letters, theta, min_loop)
+
+
+def nested_structure_many(probs: Sequence[torch.Tensor], letters: Sequence[torch.Tensor], theta: float = _lib.SS_NESTED_THETA,
+                          min_loop: int = _lib.SS_NESTED_MIN_LOOP):
+    """nested_structure() of every (probs[b], letters[b]) in as few calls as the batch limit allows; each result is the lone call's."""
+    probs, letters = list(probs), list(letters)
+    if len(probs) != len(letters):
+        raise ValueError(f"nested_structure_many: {len(probs)} matrices for {len(letters)} letter rows")
+    out = []
+    for i in range(0, len(probs), _lib.SS_MAX_BATCH):
+        out += ops.ss_nested_packed(probs[i:i + _lib.SS_MAX_BATCH], letters[i:i + _lib.SS_MAX_BATCH], theta, min_loop)
+    return out
+
+
+def nested_structure_host(prob: np.ndarray, theta: float = _lib.SS_NESTED_THETA, min_loop: int = _lib.SS_NESTED_MIN_LOOP):
+    """The contract of rnamsm_ss_nested in NumPy, for documentation and tools -> (partner int32 [L], score, dot-bracket str).  Written
+    cell by cell for reading, O(L^3) steps of interpreted Python: seconds at L = 100, not usable much beyond L = 200.  Not a fallback
+    of nested_structure(), which runs on the device or not at all."""
+    p = np.asarray(prob, dtype=np.float32)
+    L = p.shape[0]
+    if p.shape != (L, L) or not 0.0 <= float(theta) < 1.0 or not 0 <= int(min_loop) <= _lib.SS_NESTED_MAX_LOOP:
+        raise ValueError("nested_structure_host: an [L, L] matrix, theta in [0, 1) and min_loop in [0, 32] are needed")
+    neg, th = -(1 << 30), np.float32(theta)
+    w = np.full((L, L), neg, dtype=np.int64)
+    q_theta = int(float(th) * 262144.0)
+    for i in range(L):
+        for j in range(i + min_loop + 1, L):
+            if p[i, j] > th:                                       # float32 compare; NaN and -inf fail it
+                w[i, j] = max(1, int(min(float(p[i, j]), 1.0) * 262144.0) - q_theta)
+    N = np.zeros((L + 1, L + 1), dtype=np.int64)                   # N[i + 1, j + 1] = N(i, j): row / column 0 hold N(i, i - 1) = 0
+    n = lambda i, j: int(N[i + 1, j + 1]) if j >= i else 0         # noqa: E731
+    for j in range(L):
+        for i in range(j - 1, -1, -1):
+            best = n(i, j - 1)
+            for k in range(i, j - min_loop):
+                if w[k, j] > neg:
+                    best = max(best, n(i, k - 1) + int(w[k, j]) + n(k + 1, j - 1))
+            N[i + 1, j + 1] = best
+    partner, stack = np.zeros(L, dtype=np.int32), [(0, L - 1)]
+    while stack:
+        i, j = stack.pop()
+        if j <= i:
+            continue
+        if n(i, j) == n(i, j - 1):
+            stack.append((i, j - 1))
+            continue
+        k = next(k for k in range(i, j - min_loop) if w[k, j] > neg and n(i, k - 1) + int(w[k, j]) + n(k + 1, j - 1) == n(i, j))
+        partner[k], partner[j] = j + 1, k + 1
+        stack += [(i, k - 1), (k + 1, j - 1)]
+    return partner, n(0, L - 1), dbn_from_partner(partner)
+
+
+def dbn_from_partner(partner) -> str:
+    """The dot-bracket line of a NESTED partner vector: '(' at the lower base of a pair, ')' at the upper one, '.' elsewhere."""
+    return "".join("." if p == 0 else "(" if p > b + 1 else ")" for b, p in enumerate(np.asarray(partner).reshape(-1)))
+
+
+def write_dbn(name: str, seq: str, dbn, output_dir: Union[str, Path]) -> str:
+    """`<output_dir>/SS_result/<name>.dbn`: three lines -- `>name`, the sequence's letters as `.bpseq` prints them, the brackets
+    (a str, bytes or a uint8 array of len(seq)).  Returns the path."""
+    if not isinstance(dbn, str):
+        dbn = bytes(dbn if isinstance(dbn, (bytes, bytearray)) else np.ascontiguousarray(dbn, dtype=np.uint8)).decode("ascii")
+    if len(dbn) != len(seq) or set(dbn) - set("()."):
+        raise ValueError(f"write_dbn: a dot-bracket line of {len(dbn)} characters ({''.join(sorted(set(dbn)))!r}) for a sequence of length {len(seq)}")
+    out = os.path.join(str(output_dir), "SS_result")
+    os.makedirs(out, exist_ok=True)
+    path = os.path.join(out, name + ".dbn")
+    with open(path, "w", encoding="utf-8", newline="\n") as f:
+        f.write(f">{name}\n{seq}\n{dbn}\n")
+    return path
+
+
+def write_nested_files(seq: str, name: str, output_dir: Union[str, Path], partner, counts, ct_body, bpseq_body, dbn) -> str:
+    """The files of the nested structure, from nested_structure()'s results on the host: `<output_dir>/SS_result/<name>.dbn`,
+    `<name>.nested.ct` and `<name>.nested.bpseq` -- the headers of `.ct` / `.bpseq`, the bodies as the device wrote them; with
+    counts[3] set (a letter that is no single ASCII byte) or a name outside ASCII the two tables are formatted on the host from the
+    partner vector, as write_ss_files does.  Returns the `.dbn` path."""
+    L = len(seq)
+    partner, counts = np.asarray(partner).reshape(-1).astype(int), np.asarray(counts).reshape(-1)
+    if partner.shape[0] != L or counts.shape[0] != 5:
+        raise ValueError(f"write_nested_files: a partner vector of {partner.shape[0]} entries and {counts.shape[0]} counts for a "
+                         f"sequence of length {L}")
+    path = write_dbn(name, seq, dbn_from_partner(partner) if int(counts[3]) else dbn, output_dir)
+    out = os.path.dirname(path)
+    if int(counts[3]) or not name.isascii():
+        _tables_on_host(out, name, seq, partner, stem=name + ".nested")
+        return path
+    bodies = []
+    for body, n in ((ct_body, int(counts[1])), (bpseq_body, int(counts[2]))):
+        body = memoryview(body if isinstance(body, (bytes, bytearray)) else np.ascontiguousarray(body, dtype=np.uint8))
+        if not 0 < n <= body.nbytes:
+            raise ValueError(f"write_nested_files: a body of {body.nbytes} bytes for a count of {n}")
+        bodies.append(body[:n])
+    _tables_from_bodies(out, name, L, bodies[0], bodies[1], stem=name + ".nested")
+    return path
+
+
 def pairs_from_partner(partner) -> List[Tuple[int, int]]:
     """The list secondary_structure returns -- pairs (i, j), i < j, 0-based, sorted -- from a partner vector (0 = unpaired, else the
     partner's 1-based index)."""
@@ -364,25 +476,27 @@ def secondary_structure(prob: np.ndarray) -> List[Tuple[int, int]]:
     return _multiplet_free(pairs, prob)
 
 
-def _tables_on_host(out: str, name: str, seq: str, partner: np.ndarray) -> None:
-    """`<out>/<name>.ct` and `.bpseq` as the reference builds them: string tables through np.savetxt."""
+def _tables_on_host(out: str, name: str, seq: str, partner: np.ndarray, stem: Optional[str] = None) -> None:
+    """`<out>/<name>.ct` and `.bpseq` as the reference builds them: string tables through np.savetxt.  stem: the files' name where
+    it is not the one the headers carry (`<name>.nested`)."""
+    stem = name if stem is None else stem
     L = len(seq)
     idx = np.arange(1, L + 1)
     bases = np.array(list(seq))
     fmt_int = lambda a: np.char.mod("%d", a)          # noqa: E731
     ct = np.vstack((fmt_int(idx), bases, fmt_int(idx - 1), fmt_int(np.append(idx[1:], [0])), fmt_int(partner),
                     fmt_int(idx))).T
-    np.savetxt(os.path.join(out, name + ".ct"), ct, delimiter="\t\t", fmt="%s",
+    np.savetxt(os.path.join(out, stem + ".ct"), ct, delimiter="\t\t", fmt="%s",
                header=f"{L}\t\t{name}\t\tRNAMSM_SS output\n", comments="")
     bp = np.vstack((fmt_int(idx), bases, fmt_int(partner))).T
-    np.savetxt(os.path.join(out, name + ".bpseq"), bp, delimiter=" ", fmt="%s", header="#" + name, comments="")
+    np.savetxt(os.path.join(out, stem + ".bpseq"), bp, delimiter=" ", fmt="%s", header="#" + name, comments="")
 
 
-def _tables_from_bodies(out: str, name: str, L: int, ct_body, bpseq_body) -> None:
+def _tables_from_bodies(out: str, name: str, L: int, ct_body, bpseq_body, stem: Optional[str] = None) -> None:
     """The same two files from device-made bodies: the header line and one binary write each.  np.savetxt ends the header with a
     newline of its own: the .ct header, which ends in one already, is followed by an empty line."""
     for ext, head, body in ((".ct", f"{L}\t\t{name}\t\tRNAMSM_SS output\n\n", ct_body), (".bpseq", f"#{name}\n", bpseq_body)):
-        with open(os.path.join(out, name + ext), "wb") as f:
+        with open(os.path.join(out, (name if stem is None else stem) + ext), "wb") as f:
             f.write(head.encode("ascii"))
             f.write(body)
 
@@ -463,6 +577,7 @@ class SSResult(NamedTuple):
     tokens: torch.Tensor                          # [L] the query's tokens
     text: Optional[tuple] = None                  # prob_text(probs): (text, fallback word); None where the formatter is off
     structure: Optional[tuple] = None             # structure(probs, letters): (partner, counts, ct body, bpseq body); None where off
+    nested: Optional[tuple] = None                # nested_structure(probs, letters): (partner, counts [5], ct body, bpseq body, dbn)
 
 
 class SSHead:
@@ -471,12 +586,15 @@ class SSHead:
     (data.ss_pairs_device: the pairs are decoded and the bodies of `.ct` / `.bpseq` written there)."""
 
     def __init__(self, model: Optional[SSPredictor], alphabet, base_lut: Optional[torch.Tensor], device, text_on: bool = True,
-                 pairs_on: bool = True):
+                 pairs_on: bool = True, nested: Optional[Tuple[float, int]] = None):
+        """nested: (theta, min_loop) of data.ss_nested (the nested structure is decoded on the device behind the head and travels in
+        the record's last field), or None.  It never goes through a gather: flatten() / unflatten() do not carry it."""
         self.model, self.base_lut, self.text_on, self.pairs_on = model, base_lut, bool(text_on), bool(pairs_on)
+        self.nested = None if nested is None else (float(nested[0]), int(nested[1]))
         self.all_toks = list(alphabet.all_toks)
         # a token that is no single ASCII character is 0: that structure's tables come from the host
         self.letters_lut = torch.tensor([ord(t) if len(t) == 1 and ord(t) < 128 else 0 for t in self.all_toks],
-                                        dtype=torch.uint8).to(device) if self.pairs_on else None
+                                        dtype=torch.uint8).to(device) if self.pairs_on or self.nested else None
         self.n_tensors = 2 + 2 * self.text_on + 4 * self.pairs_on
 
     # ------------------------------------------------------------------ records
@@ -485,7 +603,8 @@ class SSHead:
                                 else (self.model.predict, prob_text, structure))
         probs = predict(atp, self.base_lut[tokens])
         return SSResult(probs, tokens, tuple(text(probs)) if self.text_on else None,
-                        tuple(pairs(probs, self.letters_lut[tokens])) if self.pairs_on else None)
+                        tuple(pairs(probs, self.letters_lut[tokens])) if self.pairs_on else None,
+                        tuple(nested_structure(probs, self.letters_lut[tokens], *self.nested)) if self.nested else None)
 
     def one(self, emb: torch.Tensor, atp: torch.Tensor, tokens: torch.Tensor) -> SSResult:
         """A lone alignment through the lone ops; atp is read where it lies (emb is not read: the heads share one signature).  The
@@ -511,8 +630,10 @@ class SSHead:
         probs = self.model.predict_many(atps, [self.base_lut[t] for t in tokens])
         texts = prob_text_many(probs) if self.text_on else [None] * len(probs)
         structs = structure_many(probs, [self.letters_lut[t] for t in tokens]) if self.pairs_on else [None] * len(probs)
-        return [SSResult(p, t, None if tx is None else tuple(tx), None if st is None else tuple(st))
-                for p, t, tx, st in zip(probs, tokens, texts, structs)]
+        nests = (nested_structure_many(probs, [self.letters_lut[t] for t in tokens], *self.nested) if self.nested
+                 else [None] * len(probs))
+        return [SSResult(p, t, None if tx is None else tuple(tx), None if st is None else tuple(st), None if ne is None else tuple(ne))
+                for p, t, tx, st, ne in zip(probs, tokens, texts, structs, nests)]
 
     # ------------------------------------------------------------------ the gather's flat lists
     def flatten(self, rec: SSResult) -> list:
@@ -537,7 +658,7 @@ class SSHead:
         bodies, as far as the record has them, then the probabilities -- unless it has both a text and a structure: then they stay where
         they are, and write() fetches them (fetch_probs; default: from rec.probs) only for a map whose text could not be formatted (a
         NaN-poisoned one)."""
-        probs, has_text, has_structure = rec.probs, rec.text is not None, rec.structure is not None
+        probs, has_text, has_structure, has_nested = rec.probs, rec.text is not None, rec.structure is not None, rec.nested is not None
         lazy = has_text and has_structure
         if fetch_probs is None:         # holds the probabilities alone: the job's other tensors are released once their copies have run
             fetch_probs = lambda: probs.cpu().numpy()      # noqa: E731  (behind the writer's event: the head has run)
@@ -548,11 +669,14 @@ class SSHead:
                 kw.update(prob_text=made.pop(0), fallback=int(made.pop(0)[0]))
             if has_structure:
                 kw.update(partner=made.pop(0), counts=made.pop(0), ct_body=made.pop(0), bpseq_body=made.pop(0))
+            nested = [made.pop(0) for _ in range(5)] if has_nested else None
             if lazy:
                 prob = fetch_probs() if kw["fallback"] else None
             else:
                 prob = made.pop(0)
             assert not made
             write_ss_files(prob, self.letters(tokens), name, output_dir, **kw)
+            if nested is not None:          # the reference's three files stay as they are: .dbn, .nested.ct, .nested.bpseq beside them
+                write_nested_files(self.letters(tokens), name, output_dir, *nested)
 
-        return write, (rec.tokens, *(rec.text or ()), *(rec.structure or ()), *(() if lazy else (probs,)))
+        return write, (rec.tokens, *(rec.text or ()), *(rec.structure or ()), *(rec.nested or ()), *(() if lazy else (probs,)))
