@@ -1,8 +1,38 @@
-// Three jobs of ONE block of 1024 threads that several files need (device code).
+// Jobs of ONE block that several files need (device code): three for a block of 1024 threads, and the wave-shuffle prefix sum of
+// the text writers (struct_text.h, rsa_text.hip) for a block of any whole number of waves.
 #pragma once
+#include <type_traits>
+
 #include "common.h"
 
 namespace rnamsm {
+
+// The sum of v over the threads below the calling one; total: the sum over the whole block, the same in every thread.  V: uint32_t
+// or uint64_t (unsigned: several fields may share the word as long as no field's sum overflows into the next).  The block is
+// blockDim.x threads, a multiple of 64 and at most 1024; wave_sums: blockDim.x / 64 words of LDS.  One barrier inside, between the
+// write and the reads of wave_sums: the caller may write those words again only behind its own next barrier.
+template <class V>
+__device__ __forceinline__ V block_exclusive_sum(V v, V* wave_sums, V& total) {
+    static_assert(sizeof(V) == 4 || sizeof(V) == 8, "a 32-bit or a 64-bit word");
+    using Shfl = typename std::conditional<sizeof(V) == 8, unsigned long long, unsigned int>::type;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
+    V incl = v;
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+        const V up = (V)__shfl_up((Shfl)incl, off, 64);
+        if (lane >= off) incl += up;
+    }
+    if (lane == 63) wave_sums[wave] = incl;
+    __syncthreads();
+    V before = 0;
+    total = 0;
+    for (int w = 0; w < nw; ++w) {
+        const V s = wave_sums[w];
+        if (w < wave) before += s;
+        total += s;
+    }
+    return before + incl - v;
+}
 
 // the lowest n in [0, N) with pred(n), or -1 when there is none; the same value in every thread.  The caller's block is 1024 threads.
 template <class Pred>

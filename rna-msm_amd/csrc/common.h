@@ -453,8 +453,10 @@ struct PackedMsa {           // 64 bytes
 static_assert(sizeof(PackedMsa) == 64, "PackedMsa layout");
 
 // ---- descriptor tables of the batched stages (PackedMsa here, SsMember in ss_head.hip, RsaMember in rsa_head.hip): one upload, one
-// search.  The descriptors travel host -> device as kernel arguments, 32 (2 KB) per launch, on the caller's stream: no host buffer
-// has to outlive the call.
+// search.  The descriptors travel host -> device as kernel arguments, 32 per launch, on the caller's stream: no host buffer has to
+// outlive the call.  A launch carries at most 4096 bytes of kernel arguments: a chunk may take 3584 of them (descriptors of up to
+// 112 bytes), which leaves 512 to the kernel's other arguments and the hidden ones the compiler appends.
+constexpr size_t MEMBER_CHUNK_MAX_BYTES = 3584;
 template <class T>
 struct MemberChunk { T m[32]; };
 template <class T>
@@ -465,7 +467,7 @@ __global__ void members_kernel(MemberChunk<T> chunk, int n, T* __restrict__ dev)
 // sums can live in the caller's lambda.  The unused entries of the last chunk repeat its entry 0.
 template <class T, class Fill>
 MemberChunk<T> member_chunk(int b0, int B, Fill& fill, int& n) {
-    static_assert(sizeof(T) == 64, "descriptor layout");
+    static_assert(sizeof(MemberChunk<T>) <= MEMBER_CHUNK_MAX_BYTES, "a chunk fits the kernel-argument budget");
     MemberChunk<T> chunk;
     n = B - b0 < 32 ? B - b0 : 32;
     for (int i = 0; i < 32; ++i) chunk.m[i] = i < n ? fill(b0 + i) : chunk.m[0];

@@ -2,8 +2,8 @@
 // write_rsa_files (rnamsm/rsa.py), byte for byte: the float64 arithmetic and the lines are rsa_text.h's.
 // One workgroup per (alignment, table), 256 threads, a thread per position and as many passes of 256 positions as L needs.  The
 // lines have unlike lengths (1 to 4 index digits, 4 to 6 ASA characters): within a pass a block prefix scan of the lengths gives
-// every thread its offset (wave shuffles, then the four wave totals through LDS), a running base carries over from pass to pass, and
-// the thread writes its bytes itself.
+// every thread its offset (block_scan.h: block_exclusive_sum), a running base carries over from pass to pass, and the thread writes
+// its bytes itself.
 // The ensemble table's workgroup recomputes the K products from the members' values: no workgroup reads what another wrote, and
 // one launch does everything.  It reads every value and every letter of the alignment, so it alone decides the two flag words and
 // writes each once (plain stores, no atomics, nothing to zero first).
@@ -11,6 +11,7 @@
 // fits its bound (and no zero is made up); the fallback word says that the bodies are not to be used.
 // The lone entry point and the packed one run the same kernel: the descriptors travel as kernel arguments, 32 per launch
 // (common.h: MemberChunk, member_chunk); workgroup b serves table b % (K + 1) of the chunk's member b / (K + 1).
+#include "block_scan.h"
 #include "common.h"
 #include "rsa_text.h"
 
@@ -38,11 +39,11 @@ struct RsaTextMember {       // 64 bytes
 static_assert(sizeof(RsaTextMember) == 64, "RsaTextMember layout");
 
 __global__ __launch_bounds__(RT_THREADS) void rsa_text_kernel(const MemberChunk<RsaTextMember> chunk, int K) {
-    __shared__ uint32_t wave_total[RT_THREADS / 64];
+    __shared__ uint32_t scan[RT_THREADS / 64];
     const int tables = K + 1;
     const RsaTextMember m = chunk.m[blockIdx.x / tables];
     const int f = blockIdx.x % tables, L = m.L;
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    const int t = threadIdx.x;
     const bool ensemble = f == K;
     uint8_t* body = m.text + (size_t)f * rsatext::LINE_BYTES * L;
     const uint32_t* rsa_bits = reinterpret_cast<const uint32_t*>(m.rsa);
@@ -84,24 +85,11 @@ __global__ __launch_bounds__(RT_THREADS) void rsa_text_kernel(const MemberChunk<
             ln = rsatext::line_of(asa, rsa);
             len = (uint32_t)rsatext::line_len(p + 1, ln);
         }
-        uint32_t incl = len;
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) {
-            const uint32_t up = __shfl_up(incl, off, 64);
-            if (lane >= off) incl += up;
-        }
-        if (lane == 63) wave_total[wave] = incl;
-        __syncthreads();
-        uint32_t before = 0, total = 0;
-#pragma unroll
-        for (int w = 0; w < RT_THREADS / 64; ++w) {
-            const uint32_t s = wave_total[w];
-            if (w < wave) before += s;
-            total += s;
-        }
-        if (p < L) rsatext::put_line(body + (base + before + incl - len), p + 1, letter, ln);      // base + ... + len <= LINE_BYTES L
+        uint32_t total;
+        const uint32_t before = block_exclusive_sum(len, scan, total);
+        if (p < L) rsatext::put_line(body + (base + before), p + 1, letter, ln);      // base + before + len <= LINE_BYTES L
         base += total;
-        __syncthreads();                                      // wave_total is written again in the next pass
+        __syncthreads();                                      // the scan's words are written again in the next pass
     }
     if (t == 0) m.counts[f] = (int32_t)base;
     if (ensemble) {                                           // block-uniform

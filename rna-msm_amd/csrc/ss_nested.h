@@ -18,7 +18,7 @@
 #pragma once
 #include <stdint.h>
 
-#include "ss_pairs.h"
+#include "struct_text.h"
 
 namespace ssnested {
 
@@ -27,6 +27,7 @@ namespace ssnested {
 constexpr int MAX_L = 4096, MAX_LOOP = 32, TILE = 64;
 constexpr int32_t NEG = -(1 << 30);          // "not allowed": NEG + NEG = INT32_MIN and NEG + any sum (< 2^29) stay inside int32
 constexpr float DEFAULT_THETA = 0.516f;
+static_assert(MAX_L <= sspairs::LONG_MAX_L, "the lines' limit");
 
 SSN_HD inline int tiles(int L) { return (L + TILE - 1) / TILE; }
 SSN_HD inline int padded(int L) { return tiles(L) * TILE; }
@@ -189,17 +190,13 @@ inline bool trace_serial(const int32_t* N, const int32_t* M, int L, int min_loop
         }
     }
     if (sp > 0) return false;
-    counts[0] = counts[1] = counts[2] = counts[3] = 0;
+    const auto at = [&](int b) { return partner[b]; };          // the kernel's tail with one "thread" that owns every base
+    bool bad = false;
+    const uint64_t total = sspairs::measure_lines(0, L, L, at, letters, &bad);
+    sspairs::put_lines(0, L, L, at, letters, 0, ct, bpseq);
+    sspairs::put_counts(counts, total, bad);
     counts[4] = N[(size_t)Lp * 0 + L - 1];
-    for (int b = 0; b < L; ++b) {
-        counts[0] += partner[b] > b + 1;
-        counts[3] |= sspairs::letter_needs_host(letters[b]);
-        sspairs::put_ct_line(ct + counts[1], b + 1, letters[b], L, partner[b]);
-        sspairs::put_bpseq_line(bpseq + counts[2], b + 1, letters[b], partner[b]);
-        counts[1] += sspairs::ct_line_len(b + 1, L, partner[b]);
-        counts[2] += sspairs::bpseq_line_len(b + 1, partner[b]);
-        dbn[b] = dbn_char(b, partner[b]);
-    }
+    for (int b = 0; b < L; ++b) dbn[b] = dbn_char(b, partner[b]);
     return true;
 }
 #endif

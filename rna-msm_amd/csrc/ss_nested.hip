@@ -7,8 +7,11 @@
 //                 read of the loop is conflict-free -- and folds two k per v_max3_i32
 //   inner phase   127 anti-diagonal steps in LDS, four threads per cell sharing its walk over k, one barrier per step
 // The traceback: one workgroup of 1024 threads per member, an explicit stack in LDS, at most L + 1 intervals, each resolved by two
-// block-wide reductions; then the partner vector, the dot-bracket line and the .ct / .bpseq bodies (a 64-bit scan of line lengths
-// over threads that own ceil(L / 1024) consecutive bases each).  No atomics anywhere: the same bytes on every run.
+// block-wide reductions; then the partner vector and the dot-bracket line, and the tail every decoder shares for the .ct / .bpseq
+// bodies (struct_text.h: emit_struct_text, over threads that own ceil(L / 1024) consecutive bases each, their partners in LDS).
+// No atomics anywhere: the same bytes on every run.
+// The lone entry point and the packed one run the same kernels: the descriptors travel as kernel arguments, 32 per launch
+// (common.h: MemberChunk, member_chunk).
 #include "common.h"
 #include "ss_nested.h"
 
@@ -32,9 +35,9 @@ struct NestedMember {
     uint8_t* dbn;            // [L]
     int32_t L, pad_;
 };
-struct NestedChunk { NestedMember m[32]; };
 
-__global__ __launch_bounds__(FILL_THREADS) void ss_nested_fill_kernel(const NestedChunk chunk, int d, ssnested::Params q) {
+__global__ __launch_bounds__(FILL_THREADS) void ss_nested_fill_kernel(const MemberChunk<NestedMember> chunk, int d,
+                                                                      ssnested::Params q) {
     __shared__ TileMem mem;
     const NestedMember mb = chunk.m[blockIdx.y];
     const int L = mb.L, T = ssnested::tiles(L), Lp = T * TILE;
@@ -124,16 +127,16 @@ __device__ __forceinline__ int block_extreme(int v, int* red) {
     return r;
 }
 
-__global__ __launch_bounds__(TRACE_THREADS) void ss_nested_trace_kernel(const NestedChunk chunk, int min_loop) {
+__global__ __launch_bounds__(TRACE_THREADS) void ss_nested_trace_kernel(const MemberChunk<NestedMember> chunk, int min_loop) {
     __shared__ int32_t partner[ssnested::MAX_L];
     __shared__ int32_t stack[ssnested::MAX_L + 4];           // (i, j) pairs: never more than L / 2 + 1 intervals wait
     __shared__ int red[TRACE_WAVES];
-    __shared__ uint64_t wave_total[TRACE_WAVES];
+    __shared__ uint64_t scan[TRACE_WAVES];
     const NestedMember mb = chunk.m[blockIdx.x];
     const int L = mb.L, Lp = ssnested::padded(L);
     const int32_t* __restrict__ N = mb.N;
     const int32_t* __restrict__ M = mb.N + (size_t)Lp * Lp;
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    const int t = threadIdx.x;
 
     for (int b = t; b < L; b += TRACE_THREADS) partner[b] = 0;
     if (t == 0) {
@@ -177,48 +180,15 @@ __global__ __launch_bounds__(TRACE_THREADS) void ss_nested_trace_kernel(const Ne
     }
     __syncthreads();
 
-    // thread t owns bases [t * per, t * per + per): its lines are contiguous
-    const int per = (L + TRACE_THREADS - 1) / TRACE_THREADS, b0 = t * per, b1 = min(L, b0 + per);
-    uint64_t len = 0;                                        // .ct bytes | .bpseq bytes << 24 | pairs << 48
-    bool bad = false;
+    const int b0 = sspairs::first_base(t, L, TRACE_THREADS), b1 = sspairs::end_base(t, L, TRACE_THREADS);
     for (int b = b0; b < b1; ++b) {
         const int p = partner[b];
         mb.partner[b] = p;
         mb.dbn[b] = ssnested::dbn_char(b, p);
-        bad |= sspairs::letter_needs_host(mb.letters[b]);
-        len += (uint64_t)sspairs::ct_line_len(b + 1, L, p) | (uint64_t)sspairs::bpseq_line_len(b + 1, p) << 24 |
-               (uint64_t)(p > b + 1) << 48;
     }
-    const int any_bad = __syncthreads_or(bad);
-    uint64_t incl = len;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const uint64_t up = (uint64_t)__shfl_up((unsigned long long)incl, off, 64);
-        if (lane >= off) incl += up;
-    }
-    if (lane == 63) wave_total[wave] = incl;
-    __syncthreads();
-    uint64_t before = 0, total = 0;
-    for (int w = 0; w < TRACE_WAVES; ++w) {
-        const uint64_t s = wave_total[w];
-        if (w < wave) before += s;
-        total += s;
-    }
-    uint64_t at = before + incl - len;
-    for (int b = b0; b < b1; ++b) {
-        const int p = partner[b];
-        const uint8_t letter = mb.letters[b];
-        sspairs::put_ct_line(mb.ct + (at & 0xffffffu), b + 1, letter, L, p);
-        sspairs::put_bpseq_line(mb.bpseq + ((at >> 24) & 0xffffffu), b + 1, letter, p);
-        at += (uint64_t)sspairs::ct_line_len(b + 1, L, p) | (uint64_t)sspairs::bpseq_line_len(b + 1, p) << 24;
-    }
-    if (t == 0) {
-        mb.counts[0] = (int32_t)(total >> 48);
-        mb.counts[1] = (int32_t)(total & 0xffffffu);
-        mb.counts[2] = (int32_t)((total >> 24) & 0xffffffu);
-        mb.counts[3] = any_bad ? 1 : 0;
+    emit_struct_text(L, b0, b1, [&](int b) { return partner[b]; }, mb.letters, mb.ct, mb.bpseq, mb.counts, scan);
+    if (t == 0)
         mb.counts[4] = (failed || sp > 0) ? -1 : N[L - 1];   // -1: the traceback did not end (an inconsistent table); never a valid score
-    }
 }
 
 size_t tables_bytes(int L) {
@@ -238,33 +208,24 @@ int ss_nested_run(const char* who, bool lone, const rnamsm_ss_nested_item* items
     for (int b = 0; b < B; ++b) {
         const rnamsm_ss_nested_item& it = items[b];
         if (!lone) snprintf(where, sizeof(where), "member %d: ", b);
-        RNAMSM_CHECK_ARG(it.L >= 1 && it.L <= RNAMSM_LONG_MAX_L, "%s: %sL=%d outside [1, %d]", who, where, it.L, RNAMSM_LONG_MAX_L);
-        RNAMSM_CHECK_ARG(it.probs && it.letters && it.partner && it.counts && it.ct && it.bpseq && it.dbn, "%s: %snull pointer", who,
-                         where);
-        RNAMSM_CHECK_ARG(((uintptr_t)it.probs & 3u) == 0 && ((uintptr_t)it.partner & 3u) == 0 && ((uintptr_t)it.counts & 3u) == 0,
-                         "%s: %sprobs, partner or counts is not 4-byte aligned", who, where);
+        const rnamsm_ss_pairs_item six = {it.probs, it.letters, it.L, it.partner, it.counts, it.ct, it.bpseq};
+        if (int rc = check_struct_item(who, where, RNAMSM_LONG_MAX_L, six, &it.dbn)) return rc;
         need += tables_bytes(it.L);
     }
-    RNAMSM_CHECK_ARG(workspace, "%s: null pointer (workspace)", who);
-    RNAMSM_CHECK_ARG(aligned16(workspace), "%s: workspace is not 16-byte aligned", who);
-    RNAMSM_CHECK_ARG(workspace_bytes >= need, "%s: workspace of %zu bytes, %zu needed", who, workspace_bytes, need);
+    if (int rc = check_struct_workspace(who, workspace, workspace_bytes, need)) return rc;
     const ssnested::Params q = ssnested::params(theta, min_loop);
     size_t off = 0;
     for (int b0 = 0; b0 < B; b0 += 32) {
-        const int n = B - b0 < 32 ? B - b0 : 32;
-        NestedChunk chunk;
-        int max_T = 1;
-        for (int i = 0; i < 32; ++i) {
-            if (i >= n) {
-                chunk.m[i] = chunk.m[0];
-                continue;
-            }
-            const rnamsm_ss_nested_item& it = items[b0 + i];
-            chunk.m[i] = NestedMember{it.probs, it.letters, reinterpret_cast<int32_t*>(static_cast<uint8_t*>(workspace) + off),
-                                      it.partner, it.counts, it.ct, it.bpseq, it.dbn, it.L, 0};
+        int n, max_T = 1;
+        auto fill = [&](int b) {
+            const rnamsm_ss_nested_item& it = items[b];
+            NestedMember m = {it.probs, it.letters, reinterpret_cast<int32_t*>(static_cast<uint8_t*>(workspace) + off),
+                              it.partner, it.counts, it.ct, it.bpseq, it.dbn, it.L, 0};
             off += tables_bytes(it.L);
             if (ssnested::tiles(it.L) > max_T) max_T = ssnested::tiles(it.L);
-        }
+            return m;
+        };
+        const MemberChunk<NestedMember> chunk = member_chunk<NestedMember>(b0, B, fill, n);
         for (int d = 0; d < max_T && (phases & 1); ++d) {
             hipLaunchKernelGGL(ss_nested_fill_kernel, dim3((unsigned)(max_T - d), (unsigned)n), dim3(FILL_THREADS), 0, s, chunk, d, q);
             RNAMSM_CHECK_LAUNCH("ss_nested_fill");

@@ -1,12 +1,12 @@
 // RNA-MSM-SS: the predicted structure on the device -- the [L, L] probabilities of the head become the partner vector and the
-// bodies of `<name>.ct` / `<name>.bpseq` (ss_pairs.h: the decoding as a graph process, and the lines), so that nothing of size L^2
-// has to reach the host for them.
+// bodies of `<name>.ct` / `<name>.bpseq` (ss_pairs.h: the decoding as a graph process; struct_text.h: the lines), so that nothing of
+// size L^2 has to reach the host for them.
 // One workgroup per structure, one thread per base (L <= 1024 = the workgroup limit: no grid-wide synchronisation).  The adjacency
 // bit matrix (L x ceil(L / 64) words, 128 KB at L = 1024) lies in the caller's workspace: one code path for every L, no dynamic LDS
 // to configure per device, and a member's rows stay in L2.  Building it: a wave per row, a lane per partner, one __ballot per 64
 // partners.  A round: thread b marks (LDS), a block-wide "any mark" ends the loop, then thread b clears its own row -- a thread
 // writes its own row and its own mark only: no atomics, the same bits on every run.
-// The lines have variable width: a block prefix scan of the lengths gives every thread its offsets, and it writes its bytes itself.
+// The kernel ends in the tail every decoder shares (struct_text.h: emit_struct_text), with thread b's partner in a register.
 // The lone entry point and the packed one run the same kernel: the descriptors travel as kernel arguments, 32 per launch
 // (common.h: MemberChunk, member_chunk); a block's member is its index in the chunk, and the lone call is a chunk of one.
 #include "common.h"
@@ -30,8 +30,7 @@ struct SsPairsMember {       // 64 bytes
 static_assert(sizeof(SsPairsMember) == 64, "SsPairsMember layout");
 
 __global__ __launch_bounds__(1024) void ss_pairs_kernel(const MemberChunk<SsPairsMember> chunk) {
-    __shared__ int32_t mark[sspairs::MAX_L];
-    __shared__ uint32_t wave_total[16];
+    __shared__ alignas(8) int32_t mark[sspairs::MAX_L];      // and, behind the rounds, the scan's 16 words
     const SsPairsMember m = chunk.m[blockIdx.x];
     const int L = m.L, W = sspairs::words(L);
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6, nw = blockDim.x >> 6;      // blockDim: a multiple of 64, >= L
@@ -52,49 +51,16 @@ __global__ __launch_bounds__(1024) void ss_pairs_kernel(const MemberChunk<SsPair
         __syncthreads();
     }
 
-    int partner = 0, ct_len = 0, bp_len = 0;
-    uint8_t letter = 0;
-    bool bad = false;
-    if (t < L) {
+    const int b0 = sspairs::first_base(t, L, blockDim.x), b1 = sspairs::end_base(t, L, blockDim.x);      // base t, or none
+    int partner = 0;
+    if (b0 < b1) {
         partner = sspairs::partner_of(row, W);
         m.partner[t] = partner;
-        letter = m.letters[t];
-        bad = sspairs::letter_needs_host(letter);
-        ct_len = sspairs::ct_line_len(t + 1, L, partner);
-        bp_len = sspairs::bpseq_line_len(t + 1, partner);
     }
-    const int n_pairs = __syncthreads_count(partner > t + 1);
-    const int any_bad = __syncthreads_or(bad);
-    // both lengths in one word: ct <= 32 L < 2^16 in the low half, bpseq <= 12 L in the high half
-    const uint32_t len = (uint32_t)ct_len | (uint32_t)bp_len << 16;
-    uint32_t incl = len;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const uint32_t up = __shfl_up(incl, off, 64);
-        if (lane >= off) incl += up;
-    }
-    if (lane == 63) wave_total[wave] = incl;
-    __syncthreads();
-    uint32_t before = 0, total = 0;
-    for (int w = 0; w < nw; ++w) {
-        const uint32_t s = wave_total[w];
-        if (w < wave) before += s;
-        total += s;
-    }
-    const uint32_t at = before + incl - len;
-    if (t < L) {
-        sspairs::put_ct_line(m.ct + (at & 0xffffu), t + 1, letter, L, partner);
-        sspairs::put_bpseq_line(m.bpseq + (at >> 16), t + 1, letter, partner);
-    }
-    if (t == 0) {
-        m.counts[0] = n_pairs;
-        m.counts[1] = (int32_t)(total & 0xffffu);
-        m.counts[2] = (int32_t)(total >> 16);
-        m.counts[3] = any_bad ? 1 : 0;
-    }
+    // mark is free: nobody reads it after the barrier that ended the rounds, and the scan writes behind another one
+    emit_struct_text(L, b0, b1, [partner](int) { return partner; }, m.letters, m.ct, m.bpseq, m.counts,
+                     reinterpret_cast<uint64_t*>(mark));
 }
-
-size_t adj_bytes(int L) { return ((size_t)L * sspairs::words(L) * 8 + 255) & ~(size_t)255; }
 
 // Every refusal, then the launches.  who: the entry point's name; lone: the one item is the call's own arguments, not "member 0".
 int ss_pairs_run(const char* who, bool lone, const rnamsm_ss_pairs_item* items, int B, void* workspace, size_t workspace_bytes,
@@ -102,17 +68,11 @@ int ss_pairs_run(const char* who, bool lone, const rnamsm_ss_pairs_item* items, 
     char where[32] = "";
     size_t need = 0;
     for (int b = 0; b < B; ++b) {
-        const rnamsm_ss_pairs_item& it = items[b];
         if (!lone) snprintf(where, sizeof(where), "member %d: ", b);
-        RNAMSM_CHECK_ARG(it.L >= 1 && it.L <= RNAMSM_SS_MAX_L, "%s: %sL=%d outside [1, %d]", who, where, it.L, RNAMSM_SS_MAX_L);
-        RNAMSM_CHECK_ARG(it.probs && it.letters && it.partner && it.counts && it.ct && it.bpseq, "%s: %snull pointer", who, where);
-        RNAMSM_CHECK_ARG(((uintptr_t)it.probs & 3u) == 0 && ((uintptr_t)it.partner & 3u) == 0 && ((uintptr_t)it.counts & 3u) == 0,
-                         "%s: %sprobs, partner or counts is not 4-byte aligned", who, where);
-        need += adj_bytes(it.L);
+        if (int rc = check_struct_item(who, where, RNAMSM_SS_MAX_L, items[b])) return rc;
+        need += sspairs::adj_bytes(items[b].L);
     }
-    RNAMSM_CHECK_ARG(workspace, "%s: null pointer (workspace)", who);
-    RNAMSM_CHECK_ARG(aligned16(workspace), "%s: workspace is not 16-byte aligned", who);
-    RNAMSM_CHECK_ARG(workspace_bytes >= need, "%s: workspace of %zu bytes, %zu needed", who, workspace_bytes, need);
+    if (int rc = check_struct_workspace(who, workspace, workspace_bytes, need)) return rc;
     size_t off = 0;
     for (int b0 = 0; b0 < B; b0 += 32) {
         int n, max_L = 1;
@@ -120,7 +80,7 @@ int ss_pairs_run(const char* who, bool lone, const rnamsm_ss_pairs_item* items, 
             const rnamsm_ss_pairs_item& it = items[b];
             SsPairsMember m = {it.probs, it.letters, reinterpret_cast<uint64_t*>(static_cast<uint8_t*>(workspace) + off),
                                it.partner, it.counts, it.ct, it.bpseq, it.L, 0};
-            off += adj_bytes(it.L);
+            off += sspairs::adj_bytes(it.L);
             if (it.L > max_L) max_L = it.L;
             return m;
         };
@@ -141,17 +101,13 @@ extern "C" size_t rnamsm_ss_pairs_workspace_bytes(int B, const int* Ls) {
     size_t n = 0;
     for (int b = 0; b < B; ++b) {
         if (Ls[b] < 1 || Ls[b] > RNAMSM_SS_MAX_L) return 0;
-        n += adj_bytes(Ls[b]);
+        n += sspairs::adj_bytes(Ls[b]);
     }
     return n;
 }
 
 extern "C" int rnamsm_ss_struct_text_bytes(int L, size_t* ct_bytes, size_t* bpseq_bytes) {
-    RNAMSM_CHECK_ARG(L >= 1 && L <= RNAMSM_SS_MAX_L, "ss_struct_text_bytes: L=%d outside [1, %d]", L, RNAMSM_SS_MAX_L);
-    RNAMSM_CHECK_ARG(ct_bytes && bpseq_bytes, "ss_struct_text_bytes: null pointer");
-    *ct_bytes = (size_t)sspairs::CT_LINE_MAX * L;
-    *bpseq_bytes = (size_t)sspairs::BPSEQ_LINE_MAX * L;
-    return RNAMSM_OK;
+    return struct_text_bytes("ss_struct_text_bytes", RNAMSM_SS_MAX_L, L, ct_bytes, bpseq_bytes);
 }
 
 extern "C" int rnamsm_ss_pairs(const float* probs, const uint8_t* letters, int L, int32_t* partner, int32_t* counts, uint8_t* ct,

@@ -881,6 +881,18 @@ _SS_PAIRS = _Route("ss_pairs", _lib.SS_MAX_L)
 _SS_PAIRS_LONG = _Route("ss_pairs_long", _lib.LONG_MAX_L)
 
 
+def _ss_struct_outputs(members, device, n_counts: int, dbn: bool = False):
+    """One allocation per output kind of a structure decoder -- partner [L], counts [n_counts], the .ct body [32 L], the .bpseq body
+    [12 L] and, with dbn, the dot-bracket line [L] -> (a tuple of views per member, the arguments (probs, letters, L, *outputs) per
+    member as the library takes them)."""
+    Ls = [L for _, _, L in members]
+    kinds = [_carved(Ls, device, torch.int32), _carved([n_counts] * len(Ls), device, torch.int32),
+             _carved([_lib.SS_CT_LINE_MAX * L for L in Ls], device, torch.uint8),
+             _carved([_lib.SS_BPSEQ_LINE_MAX * L for L in Ls], device, torch.uint8)] + ([_carved(Ls, device, torch.uint8)] if dbn else [])
+    outs = list(zip(*kinds))
+    return outs, [(p.data_ptr(), l.data_ptr(), L, *(t.data_ptr() for t in o)) for (p, l, L), o in zip(members, outs)]
+
+
 def _ss_pairs_run(route: Optional[_Route], probs, letters):
     """route: the lone call's; None: the packed call."""
     fn = route.fn if route else "ss_pairs_packed"
@@ -894,10 +906,7 @@ def _ss_pairs_run(route: Optional[_Route], probs, letters):
     nbytes = (lib.rnamsm_ss_pairs_long_workspace_bytes(Ls[0]) if route and route.long
               else lib.rnamsm_ss_pairs_workspace_bytes(B, (_lib.c_int * B)(*Ls)))
     ws = torch.empty(nbytes, dtype=torch.uint8, device=device)
-    outs = list(zip(_carved(Ls, device, torch.int32), _carved([4] * B, device, torch.int32),
-                    _carved([_lib.SS_CT_LINE_MAX * L for L in Ls], device, torch.uint8),
-                    _carved([_lib.SS_BPSEQ_LINE_MAX * L for L in Ls], device, torch.uint8)))
-    args = [(p.data_ptr(), l.data_ptr(), L, *(t.data_ptr() for t in o)) for (p, l, L), o in zip(members, outs)]
+    outs, args = _ss_struct_outputs(members, device, 4)
     if route:
         _lib.check(getattr(lib, route.entry)(*args[0], ws.data_ptr(), ws.numel(), _stream()))
         return outs
@@ -944,10 +953,7 @@ def _ss_nested_run(fn: str, probs, letters, theta, min_loop, lone: bool, phase_e
     B, Ls = len(members), [L for _, _, L in members]
     lib = _lib.load()
     ws = torch.empty(lib.rnamsm_ss_nested_workspace_bytes(B, (_lib.c_int * B)(*Ls)), dtype=torch.uint8, device=device)
-    outs = list(zip(_carved(Ls, device, torch.int32), _carved([5] * B, device, torch.int32),
-                    _carved([_lib.SS_CT_LINE_MAX * L for L in Ls], device, torch.uint8),
-                    _carved([_lib.SS_BPSEQ_LINE_MAX * L for L in Ls], device, torch.uint8), _carved(Ls, device, torch.uint8)))
-    args = [(p.data_ptr(), l.data_ptr(), L, *(t.data_ptr() for t in o)) for (p, l, L), o in zip(members, outs)]
+    outs, args = _ss_struct_outputs(members, device, 5, dbn=True)
     if lone:
         p, l, L, *o = args[0]
         _lib.check(lib.rnamsm_ss_nested(p, l, L, theta, min_loop, *o, ws.data_ptr(), ws.numel(), _stream()))

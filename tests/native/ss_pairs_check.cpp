@@ -59,18 +59,13 @@ int main(int argc, char** argv) {
         }
         if (rounds > (L > 2 ? L - 2 : 0)) return 4;
         std::vector<uint8_t> ct((size_t)CT_LINE_MAX * L), bp((size_t)BPSEQ_LINE_MAX * L);
-        int32_t counts[4] = {0, 0, 0, 0};
-        for (int b = 0; b < L; ++b) {
-            partner[b] = partner_of(&adj[(size_t)b * W], W);
-            counts[0] += partner[b] > b + 1;
-            counts[3] |= letter_needs_host(letters[b]);
-        }
-        for (int b = 0; b < L; ++b) {              // the offsets of the kernel's prefix scan
-            put_ct_line(ct.data() + counts[1], b + 1, letters[b], L, partner[b]);
-            put_bpseq_line(bp.data() + counts[2], b + 1, letters[b], partner[b]);
-            counts[1] += ct_line_len(b + 1, L, partner[b]);
-            counts[2] += bpseq_line_len(b + 1, partner[b]);
-        }
+        for (int b = 0; b < L; ++b) partner[b] = partner_of(&adj[(size_t)b * W], W);
+        const auto at = [&](int b) { return partner[b]; };          // the kernel's tail with one "thread" that owns every base
+        int32_t counts[4];
+        bool bad = false;
+        const uint64_t total = measure_lines(0, L, L, at, letters.data(), &bad);
+        put_lines(0, L, L, at, letters.data(), 0, ct.data(), bp.data());
+        put_counts(counts, total, bad);
         fwrite(partner.data(), 4, L, out);
         fwrite(counts, 4, 4, out);
         fwrite(ct.data(), 1, counts[1], out);

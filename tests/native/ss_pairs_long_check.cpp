@@ -1,6 +1,6 @@
 // Host check of csrc/ss_pairs_long.h (tests/test_long_heads_host.py builds it with g++ -fsanitize=address,undefined): the long
-// kernel's per-thread round logic and its line scan, run serially over the LONG_THREADS "threads" of its one workgroup, on heap
-// buffers of exactly the documented sizes.
+// kernel's per-thread round logic and the line scan of struct_text.h, run serially over the LONG_THREADS "threads" of its one
+// workgroup, on heap buffers of exactly the documented sizes.
 //   ss_pairs_long_check IN OUT     IN: records of { int32 L; uint8 letters[L]; float probs[L * L] }, L <= LONG_MAX_L
 //                                  OUT: per record { int32 partner[L]; int32 counts[4]; ct bytes; bpseq bytes }
 #include <stdint.h>
@@ -26,8 +26,9 @@ int main(int argc, char** argv) {
         // every base has exactly one owner, and the owners' runs tile [0, L) in thread order
         int next = 0;
         for (int t = 0; t < LONG_THREADS; ++t) {
-            if (first_base(t, L) != next || end_base(t, L) < next || end_base(t, L) - next > bases_per_thread(L)) return 5;
-            next = end_base(t, L);
+            const int b0 = first_base(t, L, LONG_THREADS), b1 = end_base(t, L, LONG_THREADS);
+            if (b0 != next || b1 < next || b1 - next > bases_per_thread(L, LONG_THREADS)) return 5;
+            next = b1;
         }
         if (next != L) return 5;
         std::vector<uint64_t> adj((size_t)L * W, ~0ull);          // the workspace's contents on entry do not matter
@@ -48,7 +49,11 @@ int main(int argc, char** argv) {
         if (rounds > (L > 2 ? L - 2 : 0)) return 4;
         std::vector<uint64_t> len(LONG_THREADS);
         bool bad = false;
-        for (int t = 0; t < LONG_THREADS; ++t) len[t] = thread_measure(adj.data(), W, t, L, letters.data(), partner.data(), &bad);
+        const auto at = [&](int b) { return partner[b]; };
+        for (int t = 0; t < LONG_THREADS; ++t) {
+            thread_partners(adj.data(), W, t, L, partner.data());
+            len[t] = measure_lines(first_base(t, L, LONG_THREADS), end_base(t, L, LONG_THREADS), L, at, letters.data(), &bad);
+        }
         uint64_t total = 0;
         for (int t = 0; t < LONG_THREADS; ++t) total += len[t];
         // the bodies: exactly the bytes the counts announce -- a line put at a wrong offset is a heap overflow or a gap
@@ -56,10 +61,11 @@ int main(int argc, char** argv) {
         if (ct.size() > (size_t)CT_LINE_MAX * L || bp.size() > (size_t)BPSEQ_LINE_MAX * L) return 3;
         uint64_t before = 0;                                      // the scan over threads
         for (int t = 0; t < LONG_THREADS; ++t) {
-            thread_put_lines(t, L, letters.data(), partner.data(), before, ct.data(), bp.data());
+            put_lines(first_base(t, L, LONG_THREADS), end_base(t, L, LONG_THREADS), L, at, letters.data(), before, ct.data(), bp.data());
             before += len[t];
         }
-        const int32_t counts[4] = {pairs_of(total), ct_of(total), bpseq_of(total), bad ? 1 : 0};
+        int32_t counts[4];
+        put_counts(counts, total, bad);
         fwrite(partner.data(), 4, L, out);
         fwrite(counts, 4, 4, out);
         fwrite(ct.data(), 1, ct.size(), out);
